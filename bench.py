@@ -2,7 +2,12 @@
 """Headline benchmark: pseudo-label scenes/sec on synthetic ScanNet-shaped scenes (150k points /
 1.5k segments), SegModel.forward in ins_infer mode through the C ABI.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the pseudo-label mIoU of the
+timed steps); nothing else runs on the GPU.  `--full` adds every other leg listed below (repeat regions, roofline, CPU baseline,
+parity checks, label files, extras, comm probe).  `--dump-outputs DIR` writes what the last timed step returned as .npy files
+(`dump_outputs`), so that two builds can be compared output for output on the same seeded scenes.
 
 N > 1 without a launcher: this process starts `torch.distributed.run` with N ranks itself (before it
 touches the GPU) and relays rank 0's JSON line; under torchrun (RANK / WORLD_SIZE set) it is one rank.
@@ -16,7 +21,8 @@ region covers everything SegModel.forward does for a scene (all kernels, the ser
 of the 14 label vectors and metrics) except writing the label files (reported separately as
 `with_label_files_scenes_per_s`, through the asynchronous native writer pool).
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job scenes/s, plus
+Prints ONE JSON line on rank 0: value = whole-job scenes/s, plus with --full
+  repeat_values - further timed regions of K steps, back to back (--repeats);
   roofline     - the dominant MFMA kernel, k_edgeconv<S2X>: the 16-bit MFMA work the launch EXECUTES
                   / the duration of the batched launch with ONE engine group on the
                  GPU ("solo batched", HIP events on the group's stream, measured in this process after the
@@ -28,7 +34,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-j
   parity_check - after the timed region, label digests of EVERY scene of the last batch against the same
                  scenes through a single default-stream pipeline;
   extra        - strong_1201 (BASELINE configs[3] at W = 1), latency (configs[1] / configs[4]: one scene alone),
-                 the ScanNet-shaped profile, the training step.
+                 the ScanNet-shaped profile, the training step;
+  with_label_files_scenes_per_s, comm.
+The --no-* / --repeats / --parity-scenes / --extra-* options below trim these legs; without --full none of them runs.
 """
 from __future__ import annotations
 
@@ -88,7 +96,11 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=80, help="timed steps (80 x 64 scenes: a timed region of > 2 s)")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps each: `value` is the FIRST (the contract's K steps), "
+    ap.add_argument("--full", action="store_true", help="run every leg besides the headline timed region (repeat regions, roofline, CPU baseline, "
+                                                         "parity checks, label files, extras, comm probe); a plain run only times --steps steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step returned (label samples, metric tensors, "
+                                                                       "cluster traces; rank 0) as float32 / float64 .npy files under DIR")
+    ap.add_argument("--repeats", type=int, default=3, help="--full: timed regions of --steps steps each: `value` is the FIRST (the contract's K steps), "
                                                             "the others are reported as repeat_values (run-to-run spread)")
     ap.add_argument("--warmup", type=int, default=10, help="untimed steps in front of the timed region (clocks and caches settle over the first ~0.2 s)")
     ap.add_argument("--batch", type=int, default=64, help="distinct scenes per GPU per step (BASELINE.json configs[2]: 64)")
@@ -272,6 +284,67 @@ def digest_of_digests(results) -> str:
     return h.hexdigest()
 
 
+DUMP_SEED = 20261016
+DUMP_POINTS = 8192              # sampled vertices per scene: 64 scenes x 14 vectors x 8192 x 4 B = 29 MB
+DUMP_BYTES = 48 << 20           # cap on the sample for larger batches (the files stay well under 64 MB)
+
+
+def dump_outputs(out_dir: str, results) -> dict:
+    """`--dump-outputs`: what a caller of the timed path received for the scenes of the last timed batch, as .npy files --
+    labels_sample [B, nvec, k] f32: every label vector at the same k vertices, drawn per scene from a fixed seed;
+    labels_sample_index [B, k] f64: those vertices; labels_sum [B, nvec] f64: each FULL vector's sum (no entry goes unchecked);
+    iou_sem / iou_ins [B, 2, 40] f32, acc [B, 4] f32, trace [B, 5] f32: the metric tensors and the cluster trace.
+    Reads the results at once: their label buffers are a ring that later submits overwrite."""
+    B, nvec = len(results), results[0].n_vectors
+    k = min([DUMP_POINTS, DUMP_BYTES // (B * (4 * nvec + 8))] + [r.labels.shape[1] for r in results])
+    rng = np.random.default_rng(DUMP_SEED)
+    sample = np.empty((B, nvec, k), np.float32)
+    index = np.empty((B, k), np.float64)
+    sums = np.empty((B, nvec), np.float64)
+    for b, r in enumerate(results):
+        lab = r.labels[:nvec]
+        idx = np.sort(rng.choice(lab.shape[1], k, replace=False))
+        sample[b], index[b] = lab[:, idx], idx
+        sums[b] = lab.sum(axis=1, dtype=np.int64)
+    arrays = {"labels_sample": sample, "labels_sample_index": index, "labels_sum": sums,
+              "iou_sem": np.stack([r.iou_sem[0] for r in results]).astype(np.float32),
+              "iou_ins": np.stack([r.iou_ins[0] for r in results]).astype(np.float32),
+              "acc": np.stack([r.acc for r in results]).astype(np.float32),
+              "trace": np.array([r.trace for r in results], dtype=np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def headline(args, world, value, elapsed, vec, scenes_per_gpu, engine_profile, numa_info, trace0, gen_s) -> dict:
+    """The keys of the result line that a plain run prints (--full adds its legs' keys to them); `vec` = the all-reduced accumulators."""
+    I_s, U_s = vec[:40], vec[40:80]
+    I_i, U_i = vec[80:120], vec[120:160]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        miou_sem = float(np.nanmean(I_s / U_s)) if np.any(U_s > 0) else float("nan")
+        miou_ins = float(np.nanmean(I_i / U_i)) if np.any(U_i > 0) else float("nan")
+    if args.scenes_total > 0:
+        workload = (f"{args.scenes_total} distinct synthetic scenes sharded i mod {world} over {world} GPU(s), one pass per step in batches of "
+                    f"{args.batch}, {args.points} pts / {args.segments} segs each (BASELINE.json configs[3])")
+    else:
+        workload = (f"{args.batch} distinct synthetic scenes per GPU per step, {args.points} pts / {args.segments} segs each "
+                    f"(BASELINE.json configs[2]; configs[1] = the same scene shape, single scene)")
+    return {
+        "metric": "pseudo-label scenes/sec (150k pts, 1.5k segs)", "value": round(value, 3), "unit": "scenes/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "strong" if args.scenes_total > 0 else "weak", "vs_baseline": None, "dtype": DTYPE,
+        "data": "synthetic", "full": args.full,
+        "config": {"workload": workload, "mode": "ins_infer", "scenes_per_step_per_gpu": scenes_per_gpu, "scenes_in_flight": args.groups * args.per_group,
+                   "engine": f"{args.groups} groups x {args.per_group} scenes per batched launch",
+                   "seg_profile": args.seg_profile, "weights": "tests/golden/weights_g2.npz", "parallelism": f"scene-parallel x{world}"},
+        "timed_region_s": round(elapsed, 3),
+        "pseudo_label_mIoU": {"semantic": round(miou_sem, 4), "instance": round(miou_ins, 4), "scenes": int(vec[164])},
+        "engine_profile": engine_profile, "numa": numa_info,
+        "cluster_trace_scene0": trace0, "scene_generation_s": round(gen_s, 1),
+    }
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
@@ -293,7 +366,7 @@ def main(argv=None):
     # ---- synthetic input, generated in worker processes BEFORE this process initialises the GPU ----
     t_gen = time.time()
     cores = os.cpu_count() or 1
-    extras_on = not (args.no_extras or world > 1 or args.seg_profile != "voronoi" or args.scenes_total > 0)
+    extras_on = args.full and not (args.no_extras or world > 1 or args.seg_profile != "voronoi" or args.scenes_total > 0)
     n_strong = max(0, args.extra_strong) if extras_on else 0
     workers = args.gen_workers or max(1, min(64 if n_strong else 16, cores // (2 * max(world, 1)) or 1))
     cache = args.scene_cache
@@ -416,11 +489,25 @@ def main(argv=None):
     mean_ms = runner.mean_stage_ms()
     scenes_per_step = args.scenes_total if args.scenes_total > 0 else world * args.batch
     value = scenes_per_step * args.steps / elapsed
-    # labels of the last timed batch, digested before anything else is submitted (their buffers are a ring)
+    # labels of the last timed batch, dumped and digested before anything else is submitted (their buffers are a ring)
     last_batch = batches[-1]
+    batch_trace0 = list(last_results[0].trace)
+    dumped = dump_outputs(args.dump_outputs, last_results) if (args.dump_outputs and rank == 0) else None
+    vec = reduce_accumulators(np.concatenate([acc["iou_sem"], acc["iou_ins"], acc["acc"], [acc["n"]]]), world, args.backend, dev)
+    line = headline(args, world, value, elapsed, vec, len(scenes), engine_profile, numa_info, batch_trace0, gen_s)
+    if dumped is not None:
+        line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if not args.full:
+        if rank == 0:
+            os.write(result_fd, (json.dumps(line) + "\n").encode())
+        runner.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     n_par = min(args.parity_scenes, len(last_batch))
     batch_digests = [label_digest(last_results[i]) for i in range(n_par)]
-    batch_trace0 = list(last_results[0].trace)
     repeat_values = [round(value, 3)]
     for _ in range(max(0, args.repeats - 1)):                   # run-to-run spread; `value` stays the first region
         el, _ = timed(args.steps, None)
@@ -433,7 +520,6 @@ def main(argv=None):
         run_batches(batches, max(2, args.steps // 8))
         mean_ms = runner.mean_stage_ms()
         runner.set_timing(0)
-    vec = reduce_accumulators(np.concatenate([acc["iou_sem"], acc["iou_ins"], acc["acc"], [acc["n"]]]), world, args.backend, dev)
     # What the collective layer saw.  With ranks (a process group exists since start-up) every rank takes part here.  At N = 1 the probe has to
     # BUILD (and remove) a communicator; it runs LAST there, behind every measured leg, so that no leg's number can depend on it (a precaution:
     # an A / B of the timed region with a communicator built up front showed no difference).
@@ -808,26 +894,7 @@ def main(argv=None):
 
         if comm is None:
             comm = comm_probe(world, args.backend, dev)               # N = 1: behind every measured leg (see above)
-        I_s, U_s = vec[:40], vec[40:80]
-        I_i, U_i = vec[80:120], vec[120:160]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            miou_sem = float(np.nanmean(I_s / U_s)) if np.any(U_s > 0) else float("nan")
-            miou_ins = float(np.nanmean(I_i / U_i)) if np.any(U_i > 0) else float("nan")
-        if args.scenes_total > 0:
-            workload = (f"{args.scenes_total} distinct synthetic scenes sharded i mod {world} over {world} GPU(s), one pass per step in batches of "
-                        f"{args.batch}, {args.points} pts / {args.segments} segs each (BASELINE.json configs[3])")
-        else:
-            workload = (f"{args.batch} distinct synthetic scenes per GPU per step, {args.points} pts / {args.segments} segs each "
-                        f"(BASELINE.json configs[2]; configs[1] = the same scene shape, single scene)")
-        out = {
-            "metric": "pseudo-label scenes/sec (150k pts, 1.5k segs)", "value": round(value, 3), "unit": "scenes/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "strong" if args.scenes_total > 0 else "weak", "vs_baseline": None, "dtype": DTYPE,
-            "data": "synthetic",
-            "config": {"workload": workload, "mode": "ins_infer", "scenes_per_step_per_gpu": len(scenes), "scenes_in_flight": args.groups * args.per_group,
-                       "engine": f"{args.groups} groups x {args.per_group} scenes per batched launch",
-                       "seg_profile": args.seg_profile, "weights": "tests/golden/weights_g2.npz", "parallelism": f"scene-parallel x{world}"},
-            "timed_region_s": round(elapsed, 3),
+        out = dict(line, **{
             "repeat_values": {"scenes_per_s": repeat_values, "min": min(repeat_values), "median": float(np.median(repeat_values)),
                               "what": f"{len(repeat_values)} timed regions of {args.steps} steps each, back to back; `value` is the first"},
             "roofline": roofline, "cpu_baseline": cpu, "comm": comm,
@@ -836,11 +903,8 @@ def main(argv=None):
                              "what": "sha256 over the 14 label vectors + metric tensors + cluster trace of every checked scene of the last timed batch "
                                      "== the same scenes through one default-stream pipeline (and the extra legs' own checks)"},
             "with_label_files_scenes_per_s": with_files or None,
-            "pseudo_label_mIoU": {"semantic": round(miou_sem, 4), "instance": round(miou_ins, 4), "scenes": int(vec[164])},
             "extra": extras or None,
-            "engine_profile": engine_profile, "numa": numa_info,
-            "cluster_trace_scene0": batch_trace0, "scene_generation_s": round(gen_s, 1),
-        }
+        })
         os.write(result_fd, (json.dumps(out) + "\n").encode())
         if not parity_all:
             print("bench.py: PARITY FAILURE -- the concurrent path's labels differ from the single-pipeline path", file=sys.stderr)

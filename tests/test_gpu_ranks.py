@@ -149,7 +149,7 @@ def test_bench_strong_scaling_two_ranks_on_one_gpu():
     own parity checks green -- the bench's rank logic on the hardware a test box has."""
     import json
     import subprocess
-    common = ["--scenes-total", "1201", "--points", "3000", "--segments", "30", "--steps", "2", "--warmup", "1", "--repeats", "1",
+    common = ["--full", "--scenes-total", "1201", "--points", "3000", "--segments", "30", "--steps", "2", "--warmup", "1", "--repeats", "1",
               "--no-cpu-baseline", "--no-files", "--no-extras", "--batch", "64", "--parity-scenes", "8", "--backend", "gloo", "--groups", "4"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
@@ -271,7 +271,7 @@ def test_bench_eight_ranks_on_one_gpu_and_the_comm_field():
     communicator made for the probe."""
     import json
     import subprocess
-    common = ["--scenes-total", "97", "--points", "3000", "--segments", "30", "--steps", "2", "--warmup", "1", "--repeats", "1",
+    common = ["--full", "--scenes-total", "97", "--points", "3000", "--segments", "30", "--steps", "2", "--warmup", "1", "--repeats", "1",
               "--no-cpu-baseline", "--no-files", "--no-extras", "--batch", "8", "--parity-scenes", "4", "--groups", "2", "--per-group", "4"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
@@ -329,7 +329,7 @@ def test_configs3_full_size_1201_scenes_over_eight_ranks(tmp_path):
     import json
     import subprocess
     cache = str(tmp_path / "scenes")
-    common = ["--scenes-total", "1201", "--steps", "1", "--warmup", "0", "--repeats", "1", "--no-cpu-baseline", "--no-files", "--no-extras", "--batch", "64",
+    common = ["--full", "--scenes-total", "1201", "--steps", "1", "--warmup", "0", "--repeats", "1", "--no-cpu-baseline", "--no-files", "--no-extras", "--batch", "64",
               "--parity-scenes", "8", "--no-oos", "--scene-cache", cache]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "gloo", "--gen-workers", "48"] + common, capture_output=True, text=True, timeout=1500,

@@ -27,7 +27,6 @@ for k in marker_api_stats kernel_stats; do cp gpurun_out/${TAG}_ranges_${k}.csv 
 [ -f gpurun_out/r06_ec_lever.txt ] && cp gpurun_out/r06_ec_lever.txt profiles/${TAG}_edgeconv_bn2_lever.txt
 # exits non-zero (and says why) when a summary averages launches of different sizes: the run goes on, the files say checks.ok = false
 python3 tools/summarise_profiles.py $TAG | tail -30
-timeout 1200 python3 bench.py --scene-cache $SG_SCENE_CACHE > gpurun_out/bench_line.json 2> gpurun_out/bench_line.err
-cp gpurun_out/bench_line.json profiles/${TAG}_bench.json
+timeout 1200 python3 bench.py --full --scene-cache $SG_SCENE_CACHE > profiles/${TAG}_bench.json
 mkdir -p gpurun_out/profiles_$TAG && cp profiles/${TAG}_* gpurun_out/profiles_$TAG/
-tail -c 600 gpurun_out/bench_line.json
+tail -c 600 profiles/${TAG}_bench.json

@@ -7,10 +7,10 @@ mkdir -p gpurun_out
 timeout 600 python3 bench.py --generate-only --no-extras --seg-profile scannet --scene-cache $SG_SCENE_CACHE
 timeout 600 python3 bench.py --generate-only --no-extras --scene-cache $SG_SCENE_CACHE
 for G in 10 14 18; do
-  timeout 600 python3 bench.py --steps 30 --warmup 5 --repeats 2 --no-cpu-baseline --no-files --no-extras --groups $G --seg-profile scannet --scene-cache $SG_SCENE_CACHE > gpurun_out/p2_scannet_g$G.json 2> gpurun_out/p2_scannet_g$G.err
-  python3 -c "import json;d=json.load(open('gpurun_out/p2_scannet_g$G.json'));print('scannet groups',$G,d['value'],d['repeat_values']['scenes_per_s'],d['engine_profile'])"
+  timeout 600 python3 bench.py --full --steps 30 --warmup 5 --repeats 2 --no-cpu-baseline --no-files --no-extras --groups $G --seg-profile scannet --scene-cache $SG_SCENE_CACHE | \
+    python3 -c "import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('scannet groups',$G,d['value'],d['repeat_values']['scenes_per_s'],d['engine_profile'])"
 done
 for G in 10 14; do
-  timeout 600 python3 bench.py --steps 30 --warmup 5 --repeats 2 --no-cpu-baseline --no-files --no-extras --groups $G --scene-cache $SG_SCENE_CACHE > gpurun_out/p2_voronoi_g$G.json 2> gpurun_out/p2_voronoi_g$G.err
-  python3 -c "import json;d=json.load(open('gpurun_out/p2_voronoi_g$G.json'));print('voronoi groups',$G,d['value'],d['repeat_values']['scenes_per_s'],d['engine_profile'])"
+  timeout 600 python3 bench.py --full --steps 30 --warmup 5 --repeats 2 --no-cpu-baseline --no-files --no-extras --groups $G --scene-cache $SG_SCENE_CACHE | \
+    python3 -c "import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('voronoi groups',$G,d['value'],d['repeat_values']['scenes_per_s'],d['engine_profile'])"
 done

@@ -20,6 +20,6 @@ for k, v in sorted(agg.items()): print("walk", sys.argv[2], sys.argv[3], k, "per
 PY
     rm -rf $R/gpurun_out/p5_raw
   done
-  timeout 600 python3 bench.py --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-files --no-extras --scene-cache $SG_SCENE_CACHE > gpurun_out/p5_bench_$M.json 2> gpurun_out/p5_bench_$M.err
-  python3 -c "import json;d=json.load(open('gpurun_out/p5_bench_$M.json'));print('walk $M bench',d['repeat_values']['scenes_per_s'])"
+  timeout 600 python3 bench.py --full --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-files --no-extras --scene-cache $SG_SCENE_CACHE | \
+    python3 -c "import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('walk $M bench',d['repeat_values']['scenes_per_s'])"
 done

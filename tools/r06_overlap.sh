@@ -12,7 +12,7 @@ python3 bench.py --generate-only --no-extras --scene-cache $SG_SCENE_CACHE 2>&1 
 if [ -x build_micro/cu_mask_probe ]; then timeout 60 build_micro/cu_mask_probe | tee -a $OUT; fi
 run() {
   name=$1; shift
-  env "$@" timeout 300 python3 bench.py --steps ${SG_STEPS:-40} --repeats 2 --warmup 6 --no-cpu-baseline --no-files --no-extras --no-oos --parity-scenes 8 --scene-cache $SG_SCENE_CACHE 2> gpurun_out/r06_overlap_$name.err | python3 -c "
+  env "$@" timeout 300 python3 bench.py --full --steps ${SG_STEPS:-40} --repeats 2 --warmup 6 --no-cpu-baseline --no-files --no-extras --no-oos --parity-scenes 8 --scene-cache $SG_SCENE_CACHE 2> ${OUT%.txt}_$name.err | python3 -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1])
