@@ -417,7 +417,7 @@ typedef struct sg_result {        /* HOST outputs                               
     int32_t trace[5];               /* cluster counts of layers 1..5                                     */
     int32_t stalled;                /* 1 if a pass-2 sweep was cut short (SG_ESTALL condition)           */
     int32_t used_fallback;          /* 1 if the FPS-1024 fallback of model.py:479-494 ran                */
-    int32_t* h_tables;              /* optional [14,S] int32 (NULL = not wanted): the label tables the vectors are looked up in,
+    int32_t* h_tables;              /* optional [14,S] int32 (NULL = not wanted; sg_pipeline_forward, the engine and the trainer fill it): the label tables the vectors are looked up in,
                                        h_labels[t][v] = s >= 0 ? h_tables[t][s] : -1 with s = h_seg_of_vertex[v] (sg_expand_labels) */
 } sg_result;
 
@@ -566,9 +566,53 @@ int  sg_writer_submit_scene_tables(sg_writer* w, const char* out_dir, const int3
                                    int nvec, int formats, long long tag);
 /* h_out[t][v] = (s >= 0 && s < S) ? h_tables[t][s] : -1, s = h_seg_of_vertex[v]: what k_export computes on the device (model.py:525-605) */
 int  sg_expand_labels(const int32_t* h_tables, int nvec, int S, const int32_t* h_seg_of_vertex, int V, int32_t* h_out);
+/* The same scene written as ONE compact file, <out_dir>/pseudo_labels.sgl (sg_write_sgl), instead of per-vector files; tables and
+ * seg_of_vertex are copied (tag and flush semantics as sg_writer_submit_scene_tables). */
+int  sg_writer_submit_scene_sgl(sg_writer* w, const char* out_dir, const int32_t* h_tables, int S, const int32_t* h_seg_of_vertex, int V,
+                                int nvec, long long tag);
 int  sg_writer_wait_tag(sg_writer* w, long long tag);
 int  sg_writer_flush(sg_writer* w);
 void sg_writer_destroy(sg_writer* w);
+
+/* =============================================================================================
+ * Compact pseudo-label file `pseudo_labels.sgl` (one per export directory, results/<exp>/<scene>/<stage>/): the label tables and the
+ * over-segment of every raw vertex, from which every label vector is a look-up (sg_expand_labels).  All fields little-endian:
+ *   header, 48 bytes:  char magic[8] = "SGLABEL\0" | u32 version (SG_SGL_VERSION) | u32 nvec (14 ins_infer / train, 6 sem_infer) | u32 S |
+ *                      u32 V | u32 sov_width (2 when S < 65535, else 4) | u32 0 | u64 payload_bytes (= nvec*S*4 + V*sov_width) |
+ *                      u32 CRC-32 of the payload (IEEE 802.3 polynomial, zlib.crc32) | u32 0
+ *   payload:           int32 tables [nvec,S] (rows in layer_1.seg ... final.sem order) | seg_of_vertex [V]: uint16 with 0xFFFF = -1
+ *                      (sov_width 2) or int32 (sov_width 4)
+ * sg_write_sgl writes atomically (a temporary name in the same directory, then renameat over `path`).  The readers treat the file as
+ * untrusted: magic, version, every size (64-bit, overflow-checked) against the file's length, the CRC and every seg_of_vertex entry
+ * (-1 or < S) are checked; any mismatch is SG_EINVAL.  sg_read_sgl_header: h_info[5] = {version, nvec, S, V, sov_width} (CRC not
+ * checked).  sg_read_sgl: h_tables [nvec*S], h_seg_of_vertex [V] widened to int32; capacities in elements.
+ * ============================================================================================= */
+#define SG_SGL_VERSION 1
+#define SG_SGL_HEADER_BYTES 48
+int sg_write_sgl(const char* path, const int32_t* h_tables, int nvec, int S, const int32_t* h_seg_of_vertex, int V);
+int sg_read_sgl_header(const char* path, int* h_info);
+int sg_read_sgl(const char* path, int32_t* h_tables, long long tables_capacity, int32_t* h_seg_of_vertex, long long V_capacity);
+
+/* The label vectors on the device from the compact form (csrc/kernels_sgl.hip): d_out[t][v] = tables[t][s] (s = seg_of_vertex[v] in
+ * [0,S)) or -1, t < nvec, as int32 (out_elem_bytes 4) or int64 (8).  d_seg_of_vertex is uint16 with 0xFFFF = -1 (sov_width 2) or int32
+ * (4).  The tables are staged in LDS when nvec*S*4 <= 128 KiB.  Enqueue only.
+ * _batch: B scenes in one launch (scene = grid.y); d_desc DEVICE [B,5] int64 = {table offset (elements of d_tables), S, seg_of_vertex
+ * offset (entries), V, output offset (elements)}: scene b's row t starts at d_out + out_off + t*V.  max_V / max_S bound the batch. */
+int sg_expand_labels_device(const int32_t* d_tables, int nvec, int S, const void* d_seg_of_vertex, int sov_width, int V, void* d_out,
+                            int out_elem_bytes, void* stream);
+int sg_expand_labels_device_batch(int B, const long long* d_desc, int max_V, int max_S, const int32_t* d_tables, int nvec,
+                                  const void* d_seg_of_vertex, int sov_width, void* d_out, int out_elem_bytes, void* stream);
+
+/* evaluate (model.py:608-655) of `nlayers` layers of B scenes from their tables, one pass over each scene's vertices: gt[v] and
+ * seg_of_vertex[v] are read once and every layer's (ins, sem) prediction is a look-up in its table rows h_layer_rows[2l], [2l+1].  Counts
+ * as k_eval_counts (integers: bitwise reproducible), ratios on the host as sg_evaluate forms them, so every float equals sg_evaluate's
+ * on the expanded vectors.  h_desc HOST [B,6] int64 = {table offset, S, seg_of_vertex offset, V, gt offset (vertices of d_gt [*,2]
+ * int32), max_ins (> every predicted instance id of the scene's layers)}.  Outputs [B, nlayers] x {80, 80, 4}.  SYNCHRONISES the stream.
+ * d_ws needs sg_eval_tables_ws_bytes(B, nlayers, h_desc). */
+size_t sg_eval_tables_ws_bytes(int B, int nlayers, const long long* h_desc);
+int sg_eval_tables(int B, const long long* h_desc, const int32_t* d_tables, int nvec, const void* d_seg_of_vertex, int sov_width,
+                   const int32_t* d_gt, int nlayers, const int* h_layer_rows, float* h_iou_sem, float* h_iou_ins, float* h_acc,
+                   void* d_ws, size_t ws_bytes, void* stream);
 
 /* =============================================================================================
  * Raw scan -> hot-path inputs (reference seggroup/dataset/scannet/util.py).  The compute parts

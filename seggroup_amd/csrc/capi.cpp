@@ -270,7 +270,8 @@ int write_vector_files(int dfd, const char* name, const int32_t* vec, int V, int
 struct sg_writer {
     // a scene (dir + nvec vectors of V values at `base`, stride V; not owned) or one owned vector (`own`, full path without extension in dir)
     // ... or a scene as tables: `own` = [nvec * S] tables followed by [V] seg_of_vertex, S > 0
-    struct Job { std::string dir; const int32_t* base = nullptr; int V = 0, nvec = 0, formats = 0, S = 0; long long tag = 0; std::vector<int32_t> own; };
+    // ... or the same written as <dir>/pseudo_labels.sgl (sgl)
+    struct Job { std::string dir; const int32_t* base = nullptr; int V = 0, nvec = 0, formats = 0, S = 0; long long tag = 0; std::vector<int32_t> own; bool sgl = false; };
     std::mutex mu;
     std::condition_variable cv_job, cv_idle;
     std::deque<Job> q;
@@ -297,7 +298,10 @@ struct sg_writer {
             }
             cv_idle.notify_all();
             int rc = 0;
-            if (j.S > 0) {
+            if (j.sgl) {
+                const int32_t* tab = j.own.data();
+                rc = sg_write_sgl((j.dir + "/pseudo_labels.sgl").c_str(), tab, j.nvec, j.S, tab + (size_t)j.nvec * j.S, j.V);
+            } else if (j.S > 0) {
                 // tables + seg_of_vertex: expand one vector at a time into this thread's buffer, then format / write it like any other
                 const int dfd = open(j.dir.c_str(), O_RDONLY | O_DIRECTORY | O_CLOEXEC);
                 if (dfd < 0) rc = sg::fail(SG_EINVAL, "label writer: cannot open directory %s: %s", j.dir.c_str(), strerror(errno));
@@ -372,6 +376,20 @@ int sg_writer_submit_scene_tables(sg_writer* w, const char* out_dir, const int32
     sg_writer::Job j;
     j.dir = out_dir; j.V = V; j.nvec = nvec; j.formats = formats; j.S = S;
     j.tag = -1;                                                  // owns its data: nothing of the caller's to wait for
+    (void)tag;
+    j.own.resize((size_t)nvec * S + (size_t)V);
+    std::memcpy(j.own.data(), h_tables, (size_t)nvec * S * 4);
+    if (V > 0) std::memcpy(j.own.data() + (size_t)nvec * S, h_seg_of_vertex, (size_t)V * 4);
+    return w->push(std::move(j));
+}
+
+int sg_writer_submit_scene_sgl(sg_writer* w, const char* out_dir, const int32_t* h_tables, int S, const int32_t* h_seg_of_vertex, int V, int nvec,
+                               long long tag) {
+    if (!w || !out_dir || !h_tables || S <= 0 || (V > 0 && !h_seg_of_vertex) || V < 0 || nvec < 1 || nvec > SG_NUM_LABEL_VECTORS)
+        return sg::fail(SG_EINVAL, "sg_writer_submit_scene_sgl: bad arguments");
+    sg_writer::Job j;
+    j.dir = out_dir; j.V = V; j.nvec = nvec; j.S = S; j.sgl = true;
+    j.tag = -1;                                                  // owns its data, as sg_writer_submit_scene_tables
     (void)tag;
     j.own.resize((size_t)nvec * S + (size_t)V);
     std::memcpy(j.own.data(), h_tables, (size_t)nvec * S * 4);

@@ -673,7 +673,7 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
 
     // ---------------- export + evaluate (model.py:525-655) -------------------------------------------
     pl->mark(-1);
-    (void)n_tables;
+    if (out->h_tables) std::memcpy(out->h_tables, tab, (size_t)n_tables * S * 4);     // optional: the tables the vectors are looked up in (.sgl)
     PL_CHECK(flush_exports(true));                         // whatever is left (at least the final rows)
     PL_HIP(hipStreamWaitEvent(st, pl->ev_side, 0));        // the metric kernels read the LAST exported rows on the device
     pl->mark(17);

@@ -192,6 +192,14 @@ SIGNATURES = {
     "sg_writer_submit_scene": (_I, [vp, C.c_char_p, vp, _I, _I, _I, C.c_longlong]),
     "sg_writer_submit_scene_tables": (_I, [vp, C.c_char_p, vp, _I, vp, _I, _I, _I, C.c_longlong]),
     "sg_expand_labels": (_I, [vp, _I, _I, vp, _I, vp]),
+    "sg_writer_submit_scene_sgl": (_I, [vp, C.c_char_p, vp, _I, vp, _I, _I, C.c_longlong]),
+    "sg_write_sgl": (_I, [C.c_char_p, vp, _I, _I, vp, _I]),
+    "sg_read_sgl_header": (_I, [C.c_char_p, vp]),
+    "sg_read_sgl": (_I, [C.c_char_p, vp, C.c_longlong, vp, C.c_longlong]),
+    "sg_expand_labels_device": (_I, [vp, _I, _I, vp, _I, _I, vp, _I, vp]),
+    "sg_expand_labels_device_batch": (_I, [_I, vp, _I, _I, vp, _I, vp, _I, vp, _I, vp]),
+    "sg_eval_tables_ws_bytes": (_Z, [_I, _I, vp]),
+    "sg_eval_tables": (_I, [_I, vp, vp, _I, vp, _I, vp, _I, vp, vp, vp, vp, vp, _Z, vp]),
     "sg_pack_build": (_I, [vp, C.c_char_p, C.c_char_p]),
     "sg_pack_build_many": (_I, [vp, vp, vp, _I, _I, vp]),
     "sg_writer_wait_tag": (_I, [vp, C.c_longlong]),

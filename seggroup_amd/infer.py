@@ -51,7 +51,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--root', type=str, default='.', help='directory holding dataset/, checkpoints/, results/ (default: CWD)')
     p.add_argument('--sampler', choices=['shard', 'reference'], default='shard',
                    help="scene->rank assignment: 'shard' = i mod W (no padding); 'reference' = DistributedSampler order")
-    p.add_argument('--out-format', type=str, default='txt,npy', help='comma list of txt,npy')
+    p.add_argument('--out-format', type=str, default='txt,npy',
+                   help='comma list of txt,npy,sgl (sgl: one compact pseudo_labels.sgl per scene, seggroup_amd/pseudo_labels.py; '
+                        'python -m seggroup_amd.expand writes the per-vector files from it)')
     p.add_argument('--world-size', type=int, default=0, help='processes to spawn (default: one per visible GPU)')
     p.add_argument('--backend', type=str, default='nccl', help='torch.distributed backend (nccl = RCCL on ROCm)')
     p.add_argument('--numa', type=str, default='auto', choices=['auto', 'off'],
@@ -374,7 +376,10 @@ def _run_packed(rank, world, args, model, scene_list, mine, acc, io, dev):
     # Round 6, with 32 scenes in flight (same sweeps): `.npy` 6 / 8 writer threads 1,860-1,910 / 1,920-1,950 scenes/s; `.txt` + `.npy` 8 / 12 / 16 threads 1,470-1,510 /
     # 1,650-1,670 / 1,520-1,600.  The count no longer follows -j (the reference's loader processes): it is what the formats need, inside the rank's share of the host
     cpus = (len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 8)) // max(world, 1)
-    writer = AsyncLabelWriter(threads=int(os.environ.get('SG_WRITER_THREADS', '0')) or max(2, min(12 if 'txt' in formats else 8, max(cpus - 6, 2))))
+    # `.sgl` alone: ~0.38 MB per scene and no formatting -- two threads keep up
+    per_vector = 'txt' in formats or 'npy' in formats
+    writer = AsyncLabelWriter(threads=int(os.environ.get('SG_WRITER_THREADS', '0')) or
+                              (max(2, min(12 if 'txt' in formats else 8, max(cpus - 6, 2))) if per_vector else 2))
     runner, done, stalled = None, 0, []
     w = model.export_weights()
     tickets = []
@@ -460,6 +465,10 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.sem_infer == args.ins_infer:
         print("Please choose either '--sem_infer' or '--ins_infer'")       # infer.py:214-216
+        raise SystemExit(1)
+    bad = [f for f in args.out_format.split(',') if f not in ('txt', 'npy', 'sgl')]
+    if bad:
+        print('--out-format: a comma list of txt, npy, sgl (got %r)' % args.out_format)
         raise SystemExit(1)
     if args.synthetic > 0:                                                 # before the first HIP call: the generator pool spawns processes
         if 'RANK' in os.environ and int(os.environ.get('WORLD_SIZE', '1')) > 1:

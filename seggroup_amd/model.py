@@ -142,6 +142,25 @@ class SceneResult:
     def label_dict(self) -> Dict[str, np.ndarray]:
         return {hip.LABEL_NAMES[i]: self.labels[i] for i in range(self.n_vectors)}
 
+    def compact(self):
+        """(tables [n_vectors, S] int32, seg_of_vertex [V] int32): what a `.sgl` file holds.  Raises ValueError when the forward was not
+        asked for its tables (sg_result.h_tables) or the scene carries no seg_of_vertex."""
+        if self._sov is None and getattr(self, "sov_scene", None) is not None:
+            self._sov = scene_seg_of_vertex(self.sov_scene)        # derived on first use (the trainer's results)
+        if self.tables is None or self._sov is None:
+            raise ValueError("this result has no label tables / seg_of_vertex: the .sgl format needs a forward made with its tables "
+                             "(Engine.submit / SegModel with 'sgl' in the formats)")
+        if self._owner is not None and self._owner.released:
+            raise RuntimeError("SceneResult.compact: the scene's loader slot was released (call .detach() before LoadedScene.release())")
+        return np.ascontiguousarray(self.tables[:self.n_vectors], dtype=np.int32), np.ascontiguousarray(self._sov, dtype=np.int32)
+
+
+def scene_seg_of_vertex(sc) -> Optional[np.ndarray]:
+    """The scene's seg_of_vertex: a loader scene's host array, or what a DeviceScene derives (`DeviceScene.seg_of_vertex`)."""
+    if getattr(sc, "h_seg_of_vertex", None) is not None:
+        return sc.h_seg_of_vertex
+    return getattr(sc, "seg_of_vertex", None)
+
 
 class Pipeline:
     """Owns one `sg_pipeline` (one in-flight scene on one HIP stream) and its pinned output buffer."""
@@ -164,8 +183,14 @@ class Pipeline:
     def fits(self, sc: DeviceScene) -> bool:
         return sc.N <= self.caps[0] and sc.S <= self.caps[1] and sc.E0 <= self.caps[2] and sc.V <= self.caps[3]
 
-    def forward(self, sc: DeviceScene, mode: int = hip.MODE_INS_INFER, debug: Optional[hip.Debug] = None, want_feat5: bool = False) -> SceneResult:
+    def forward(self, sc: DeviceScene, mode: int = hip.MODE_INS_INFER, debug: Optional[hip.Debug] = None, want_feat5: bool = False,
+                want_tables: bool = False) -> SceneResult:
+        """want_tables: also return the label tables (result.tables, result.compact(): what a `.sgl` file holds)."""
         res = hip.Result()
+        tabs = None
+        if want_tables:
+            tabs = np.empty((hip.NUM_LABEL_VECTORS, sc.S), dtype=np.int32)
+            res.h_tables = tabs.ctypes.data
         # A pinned block of exactly this scene's [14, V] per forward, handed to the result as it is: torch's caching host allocator returns the
         # block of an earlier, dropped result (no hipHostMalloc in steady state), and nothing is copied -- the private copy this replaced was
         # 8.4 MB per 150k-point scene (0.2 ms of a 2.2 ms forward; 0.85 ms at 500k points).  A result stays valid for as long as it is held.
@@ -186,7 +211,8 @@ class Pipeline:
         nvec = 14 if mode == hip.MODE_INS_INFER else 6
         # the C side packs the vectors at stride V of THIS scene (include/seggroup_hip.h, sg_result.h_labels)
         lab = lab_t.numpy()[:, :sc.V]                              # a view: the array keeps the pinned tensor alive
-        out = SceneResult(lab, nvec, res)
+        out = SceneResult(lab, nvec, res, tables=None if tabs is None else tabs[:nvec],
+                          seg_of_vertex=scene_seg_of_vertex(sc) if tabs is not None else None)
         if feat5 is not None:
             n5 = int(debug.n5)
             out.feat5, out.ins5, out.sem5 = feat5[:n5].copy(), ins5[:n5].copy(), sem5[:n5].copy()
@@ -302,7 +328,8 @@ class Engine:
         c_scenes = (hip.Scene * n)(*[s.c_struct for s in scenes])
         c_res = (hip.Result * n)()
         tabs = None
-        if self.compact:
+        want_sgl = writer is not None and out_dirs is not None and "sgl" in formats
+        if self.compact or want_sgl:                      # .sgl files are written from the tables in both label-transfer modes
             tabs = [np.empty((hip.NUM_LABEL_VECTORS, s.S), dtype=np.int32) for s in scenes]
         for i in range(n):
             c_res[i].h_labels = buf[i].data_ptr() if buf is not None else None
@@ -313,8 +340,11 @@ class Engine:
             for d_ in out_dirs:
                 os.makedirs(d_, exist_ok=True)
             c_dirs = (C.c_char_p * n)(*[d_.encode() for d_ in out_dirs])
-            wh = writer.handle
             fm = (1 if "txt" in formats else 0) | (2 if "npy" in formats else 0)
+            if fm:
+                wh = writer.handle
+            else:                                         # .sgl only: the engine's threads write nothing, wait() submits the files
+                c_dirs = None
         with torch.cuda.device(self.device):
             tid = self.lib.sg_engine_submit(self.handle, c_scenes, n, mode, c_res, wh, c_dirs, fm)
         hip.check(tid)
@@ -322,6 +352,7 @@ class Engine:
             self._slot_writer[slot] = (writer, tid)
         t = Ticket(tid, list(scenes), c_scenes, c_res, c_dirs, buf, mode)
         t.tables = tabs
+        t.sgl = (writer, list(out_dirs)) if want_sgl else None
         return t
 
     def _release_slot(self, slot: int) -> None:
@@ -355,11 +386,20 @@ class Engine:
         lab = t.labels.numpy() if t.labels is not None else None
         nv = hip.NUM_LABEL_VECTORS                  # scene i's vectors are packed at stride V_i inside its slot
         out = []
+        sgl = getattr(t, "sgl", None)
         for i, s in enumerate(t.scenes):
-            if getattr(t, "tables", None) is not None and s.h_seg_of_vertex is not None:
+            if self.compact and getattr(t, "tables", None) is not None and s.h_seg_of_vertex is not None:
                 out.append(SceneResult(None, nvec, t.c_res[i], tables=t.tables[i][:nvec], seg_of_vertex=s.h_seg_of_vertex, owner=s))
             else:
-                out.append(SceneResult(lab[i].reshape(-1)[:nv * s.V].reshape(nv, s.V), nvec, t.c_res[i]))
+                sov = None
+                if getattr(t, "tables", None) is not None:
+                    sov = scene_seg_of_vertex(s)
+                out.append(SceneResult(lab[i].reshape(-1)[:nv * s.V].reshape(nv, s.V), nvec, t.c_res[i],
+                                       tables=None if sov is None else t.tables[i][:nvec], seg_of_vertex=sov))
+            if sgl is not None:                           # tables + seg_of_vertex are copied by the call: the loader slot may go after this
+                tab, sov = out[-1].compact()
+                hip.check(self.lib.sg_writer_submit_scene_sgl(sgl[0].handle, sgl[1][i].encode(), tab.ctypes.data, tab.shape[1], sov.ctypes.data,
+                                                              sov.shape[0], nvec, int(t.id)))
         return out
 
     def run(self, scenes: List[DeviceScene], mode: int = hip.MODE_INS_INFER, writer: "Optional[AsyncLabelWriter]" = None,
@@ -445,9 +485,14 @@ class AsyncLabelWriter:
             raise hip.SgError(hip.SG_EINVAL, self.lib.sg_last_error().decode())
 
     def submit(self, output_root: str, result: "SceneResult", formats=("txt", "npy")) -> None:
+        """formats: any of "txt", "npy" (one file per label vector) and "sgl" (<output_root>/pseudo_labels.sgl from result.compact())."""
         os.makedirs(output_root, exist_ok=True)
+        if "sgl" in formats:
+            tab, sov = result.compact()
+            hip.check(self.lib.sg_writer_submit_scene_sgl(self.handle, output_root.encode(), tab.ctypes.data, tab.shape[1], sov.ctypes.data,
+                                                          sov.shape[0], tab.shape[0], -1))
         fm = (1 if "txt" in formats else 0) | (2 if "npy" in formats else 0)
-        for i in range(result.n_vectors):
+        for i in range(result.n_vectors if fm else 0):
             vec = np.ascontiguousarray(result.labels[i])
             hip.check(self.lib.sg_writer_submit(self.handle, os.path.join(output_root, hip.LABEL_NAMES[i]).encode(), vec.ctypes.data,
                                                 vec.shape[0], fm))
@@ -473,7 +518,12 @@ def write_label_files(output_root: str, result: SceneResult, formats=("txt", "np
     lib = hip.lib()
     os.makedirs(output_root, exist_ok=True)
     written = []
-    for i in range(result.n_vectors):
+    if "sgl" in formats:                                  # the compact file (include/seggroup_hip.h, sg_write_sgl)
+        tab, sov = result.compact()
+        path = os.path.join(output_root, "pseudo_labels.sgl")
+        hip.check(lib.sg_write_sgl(path.encode(), tab.ctypes.data, tab.shape[0], tab.shape[1], sov.ctypes.data, sov.shape[0]))
+        written.append(path)
+    for i in range(result.n_vectors if ("txt" in formats or "npy" in formats) else 0):
         vec = np.ascontiguousarray(result.labels[i])
         base = os.path.join(output_root, hip.LABEL_NAMES[i])
         if "txt" in formats:
@@ -595,7 +645,7 @@ class SegModel(nn.Module):
         """Hot path on a staged scene.  Returns the SceneResult; writes the label files if `write`."""
         with self._lock:
             if self.sem_infer or self.ins_infer:
-                res = self.pipeline_for(sc).forward(sc, self.mode())
+                res = self.pipeline_for(sc).forward(sc, self.mode(), want_tables=write and "sgl" in self.out_formats)
             else:                                            # train mode: the same forward, recorded for the backward (csrc/trainer.cpp)
                 res = self.trainer_for(sc).forward(sc)
             if write:

@@ -106,6 +106,16 @@ class DeviceScene:
     def c_struct(self) -> hip.Scene:
         return self._c
 
+    @property
+    def seg_of_vertex(self) -> np.ndarray:
+        """[V] int32: the over-segment of every raw vertex (-1 where it maps to no point): the host array when the scene has one,
+        else derived once from the device arrays (seg_of_point[unmap[v]])."""
+        if self.h_seg_of_vertex is not None:
+            return self.h_seg_of_vertex
+        if getattr(self, "_sov_derived", None) is None:       # (h_seg_of_vertex stays None: it says what the C struct carries)
+            self._sov_derived = seg_of_vertex(self.d_seg_of_point.cpu().numpy(), self.d_unmap.cpu().numpy())
+        return self._sov_derived
+
     @classmethod
     def from_synthetic(cls, sc, device="cuda") -> "DeviceScene":
         return cls(sc.data, sc.weak_label, sc.seg, sc.adj, sc.unmap, sc.gt, device=device, name=sc.name)

@@ -43,7 +43,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('-v', '--visualize', action='store_true', help='Visualize results (ignored).')
     # additions of this build
     p.add_argument('--root', type=str, default='.', help='directory holding dataset/, checkpoints/, results/ (default: CWD)')
-    p.add_argument('--out-format', type=str, default='txt,npy', help='comma list of txt,npy; empty = no pseudo-label files while training')
+    p.add_argument('--out-format', type=str, default='txt,npy', help='comma list of txt,npy,sgl; empty = no pseudo-label files while training')
     p.add_argument('--world-size', type=int, default=0, help='processes to spawn (default: one per visible GPU)')
     p.add_argument('--backend', type=str, default='nccl', help='torch.distributed backend (nccl = RCCL on ROCm)')
     p.add_argument('--port', type=int, default=23456, help='rendezvous port on 127.0.0.1 (reference: 23456)')

@@ -124,12 +124,16 @@ class Trainer:
         """SegModel.forward up to the classifier with the current parameters (pseudo labels + metrics as in ins_infer)."""
         res = hip.Result()
         res.h_labels = self.labels.data_ptr()
+        tabs = np.empty((hip.NUM_LABEL_VECTORS, sc.S), dtype=np.int32)        # the label tables too (84 KB at 1.5k segments): `.sgl` output
+        res.h_tables = tabs.ctypes.data
         c5, k = C.c_int(), C.c_int()
         with torch.cuda.device(self.device):
             hip.check(self.lib.sg_trainer_forward(self.handle, C.byref(sc.c_struct), C.byref(res), C.byref(c5), C.byref(k)))
         self.C5, self.K = c5.value, k.value
         lab = self.labels.numpy().reshape(-1)[:hip.NUM_LABEL_VECTORS * sc.V].reshape(hip.NUM_LABEL_VECTORS, sc.V).copy()
-        return SceneResult(lab, 14, res)
+        out = SceneResult(lab, 14, res, tables=tabs, seg_of_vertex=sc.h_seg_of_vertex)
+        out.sov_scene = sc                               # a scene without a host seg_of_vertex derives it only if a .sgl file is asked for
+        return out
 
     def dropout_mask(self, keep="random") -> Optional[torch.Tensor]:
         """Dropout(p=0.5) keep mask [K,128] scaled by 2: "random" from this trainer's generator, "pinned" = the counter-based mask

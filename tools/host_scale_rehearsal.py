@@ -105,7 +105,10 @@ def _rank(rank, world, cfg, barrier, q):
                 np.copyto(buf, src)                                           # stands in for the DMA write of the label vectors
                 hip.check(lib.sg_writer_submit_scene(Wr, d, buf.ctypes.data, V, 14, fm, tag))
             else:
-                hip.check(lib.sg_writer_submit_scene_tables(Wr, d, tables.ctypes.data, S, sc.h_seg_of_vertex, sc.V, 14, fm, tag))
+                if "sgl" in cfg["formats"]:                                  # the compact file: tables + seg_of_vertex, no formatting
+                    hip.check(lib.sg_writer_submit_scene_sgl(Wr, d, tables.ctypes.data, S, sc.h_seg_of_vertex, sc.V, 14, tag))
+                if fm:
+                    hip.check(lib.sg_writer_submit_scene_tables(Wr, d, tables.ctypes.data, S, sc.h_seg_of_vertex, sc.V, 14, fm, tag))
         waits["writer"] += time.perf_counter() - ta
         for s_ in slots:
             hip.check(lib.sg_loader_release(L, s_))
@@ -129,6 +132,7 @@ def main():
     ap.add_argument("--numa", default="auto", choices=["auto", "off"])
     ap.add_argument("--results-base", default="", help="where the label files go (default: beside the packs, i.e. --base)")
     ap.add_argument("--out", default="")
+    ap.add_argument("--legs", default="", help="comma list of leg names to run (default: all), e.g. 'npy, tables;sgl, tables' separated by ';'")
     a = ap.parse_args()
     from seggroup_amd import cache, synthetic
     root = tempfile.mkdtemp(prefix="sg_rehearsal_", dir=a.base)
@@ -142,9 +146,13 @@ def main():
             cache.write_pack(p, sc.name, cache.stage_arrays(sc.data, sc.weak_label, sc.seg, sc.adj, sc.unmap, sc.gt))
             paths.append(p)
         ctx = mp.get_context("spawn")
-        for leg, formats, full, lt, wt, only in (("npy, tables", "npy", False, 6, 6, ""), ("txt+npy, tables", "txt,npy", False, 8, 8, ""),
+        for leg, formats, full, lt, wt, only in (("npy, tables", "npy", False, 6, 6, ""), ("sgl, tables", "sgl", False, 6, 2, ""),
+                                                 ("writer only, sgl, tables (one batch of scenes reused)", "sgl", False, 6, 2, "writer"),
+                                                 ("txt+npy, tables", "txt,npy", False, 8, 8, ""),
                                                  ("npy, full label vectors", "npy", True, 6, 6, ""), ("loader only (no files written)", "npy", False, 6, 6, "loader"),
                                                  ("writer only, npy, tables (one batch of scenes reused)", "npy", False, 6, 6, "writer")):
+            if a.legs and leg not in a.legs.split(";"):
+                continue
             rows = {}
             for W in [int(x) for x in a.ranks.split(",")]:
                 cfg = {"paths": paths, "scenes": a.scenes, "rate": a.rate, "batch": a.batch, "formats": formats, "full_labels": full, "loader_threads": lt,

@@ -21,7 +21,7 @@ def main():
     ap.add_argument("--scenes", type=int, default=16)
     ap.add_argument("--points", type=int, default=150000)
     ap.add_argument("--segments", type=int, default=1000)
-    ap.add_argument("--out-format", default="txt,npy", help="label file formats; several sets separated by ';' share one tree (e.g. 'npy;txt,npy')")
+    ap.add_argument("--out-format", default="txt,npy", help="label file formats (txt, npy, sgl); several sets separated by ';' share one tree (e.g. 'sgl;npy;txt,npy')")
     ap.add_argument("--base", default="/tmp", help="where the input tree and the results live (/dev/shm = tmpfs)")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--inflight", type=int, default=0, help="0 = the driver's own default")
