@@ -437,6 +437,8 @@ typedef struct sg_debug {         /* optional taps for stage-level parity tests 
     int32_t* h_sem5;                /* HOST [S] weak semantic label of every final cluster                */
     int32_t  n5;                    /* final clusters written                                             */
     void*    tape;                  /* library-internal (sg_trainer): the training step's record of this forward; NULL otherwise */
+    float*   d_cat[2];              /* DEVICE [C2,192] / [C3,256] cluster features in front of each GCN: the previous layer's
+                                       features grouped (max) | the EdgeConv point features' max per cluster, after its BN + LReLU */
 } sg_debug;
 
 sg_pipeline* sg_pipeline_create(int max_points, int max_segments, int max_edges, int max_vertices,
@@ -467,8 +469,14 @@ int sg_batch_forward(sg_pipeline* const* pipes, int npipes, const sg_scene* scen
  * time from a job queue and advance them in lock-step: every kernel is launched ONCE per phase for all scenes of the
  * group (csrc/engine_ctx.h), with one host->device copy, one device->host copy and one stream synchronisation per
  * phase; the serial grouping of a group's scenes runs on its thread while the other groups' kernels occupy the GPU.
- * groups x scenes_per_group scenes are in flight.  Results are bit-identical to sg_pipeline_forward (same kernel
- * bodies; tests/test_gpu_scene.py).
+ * groups x scenes_per_group scenes are in flight.  Labels, metrics, traces, kNN tables and adjacency lists are bit-identical
+ * to sg_pipeline_forward (same kernel bodies; tests/test_gpu_scene.py, tests/test_gpu_engine_taps.py).  So are the float
+ * stages (MLP1 features, cluster features, GCN outputs, decision distances) as long as every scene's EdgeConv tile groups
+ * (ceil(N / 128)) fit in the launch's per-scene grid, 2 x CUs / scenes in the super-step: each group is then one workgroup's
+ * row of BatchNorm partial sums in both paths.  A larger scene in a group of several is walked by fewer workgroups than in
+ * sg_pipeline_forward and its fp64 partials are summed in another association: a fold value may then round to a neighbouring
+ * float, and the scene's float stages may differ from the single-scene ones in the last bits (the tests bound this by 1e-5;
+ * observed: none, at 150k and 2^20 points beside other scenes).
  *
  * sg_engine_submit enqueues `count` scenes and returns a ticket at once (the arrays must stay valid until the ticket
  * has been waited for; results[i].h_labels as for sg_batch_forward); sg_engine_wait blocks until every scene of the
@@ -482,6 +490,12 @@ void sg_engine_destroy(sg_engine* e);
 int sg_engine_submit(sg_engine* e, const sg_scene* scenes, int count, int mode, sg_result* results,
                      struct sg_writer* writer, const char* const* out_dirs, int formats);
 int sg_engine_wait(sg_engine* e, int ticket);
+/* sg_engine_submit with stage taps (a test hook): dbg (may be NULL) holds `count` pointers, dbg[i] (may be NULL) receives scene i's
+ * taps in the sg_debug layouts: d_samples1, d_feat1, d_knn / d_members, d_cat, h_gcn, h_dist, h_adj / n_adj.  The engine has no
+ * per-point features: d_pointfeat, the train-mode tail (h_feat5, h_ins5, h_sem5, n5) and tape are left untouched (tape must be NULL).
+ * A tapped group copies the taps behind each phase and waits for them; without taps the launches are those of sg_engine_submit. */
+int sg_engine_submit_debug(sg_engine* e, const sg_scene* scenes, int count, int mode, sg_result* results, sg_debug* const* dbg,
+                           struct sg_writer* writer, const char* const* out_dirs, int formats);
 /* 0 = no stage timing (default), 1 | 2 = HIP events around the stages of every batched launch.  Returns the previous level. */
 int sg_engine_set_timing(sg_engine* e, int level);
 /* 0 (default): every scene's 14 label vectors are copied to results[i].h_labels (8.4 MB per 150k-vertex scene).  1 = compact: the

@@ -18,7 +18,11 @@
 //
 // The engine owns G groups (one persistent host thread + one HIP stream each) that pull scenes from a job queue:
 // sg_engine_submit() returns at once, so a driver can queue the next batch before the previous one has drained.
-// Kernel bodies are shared with the single-scene path, so results are bit-identical to sg_pipeline_forward (tested).
+// Kernel bodies are shared with the single-scene path, so labels, kNN tables and adjacency lists are bit-identical to sg_pipeline_forward, and so
+// are the float stages unless a scene has more EdgeConv tile groups than the launch gives it workgroups (b_edgeconv): then its BatchNorm partial
+// sums are added in another association than in the single-scene launch and may differ in the last bits (include/seggroup_hip.h;
+// tests/test_gpu_engine_taps.py).
+// sg_engine_submit_debug fills sg_debug taps behind each phase (a test hook: without taps nothing is copied and nothing waits).
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -85,6 +89,7 @@ struct Job {
     int id = 0;
     const sg_scene* scenes = nullptr;
     sg_result* results = nullptr;
+    sg_debug* const* dbg = nullptr;            // sg_engine_submit_debug: one optional tap set per scene
     int count = 0, mode = 0;
     sg_writer* writer = nullptr;
     const char* const* out_dirs = nullptr;
@@ -99,6 +104,7 @@ struct Run {
     sg_pipeline* pl = nullptr;
     const sg_scene* sc = nullptr;
     sg_result* out = nullptr;
+    sg_debug* dbg = nullptr;                   // stage taps (sg_engine_submit_debug), usually none
     const char* out_dir = nullptr;
     sg_partition* part = nullptr;
     int max_ins = 1, max_seg = 0, cap1 = 0, out_rows = 0;
@@ -411,6 +417,19 @@ int sg_engine::Group::phase_p0(Run* runs_, int n, int mode) {
     mark(3);
     rg.next("P0.sync");
     EG_CHECK(outbox_and_sync());
+    {
+        // stage taps: the samples and MLP1's features, copied and waited for before the next phase can touch the slot
+        bool tapped = false;
+        for (int i = 0; i < n; ++i) {
+            const sg_debug* dg = runs_[i].dbg;
+            if (!dg) continue;
+            const size_t S = (size_t)runs_[i].sc->S;
+            if (dg->d_samples1) EG_HIP(hipMemcpyAsync(dg->d_samples1, runs_[i].pl->samples.p, S * 64 * 6 * 4, hipMemcpyDeviceToDevice, stream));
+            if (dg->d_feat1) EG_HIP(hipMemcpyAsync(dg->d_feat1, runs_[i].pl->feat1.p, S * 128 * 4, hipMemcpyDeviceToDevice, stream));
+            tapped = true;
+        }
+        if (tapped) EG_HIP(timed_sync(stream));
+    }
     rg.next("P0.host_grouping");
 
     // ---- host: layer 1 tables, structural grouping, layer 2 tables ----
@@ -476,6 +495,11 @@ int sg_engine::Group::phase_p0(Run* runs_, int n, int mode) {
             r.adj.assign(r.o_adj1, r.o_adj1 + 2 * (size_t)E1);
         }
         r.E = E1;
+        if (r.dbg) {
+            if (r.dbg->h_adj[0]) std::copy(r.adj.begin(), r.adj.end(), r.dbg->h_adj[0]);
+            if (r.dbg->h_dist[0]) std::copy(h_dist, h_dist + E1, r.dbg->h_dist[0]);
+            r.dbg->n_adj[0] = E1;
+        }
         if (mode == SG_MODE_INS_INFER) r.seg_sums.assign(r.o_seg_sums, r.o_seg_sums + (size_t)S * 3);
         freeze_layer(r.part, S, r.Lcur);                          // layer 1: every segment its own cluster
         r.out->trace[0] = r.Lcur.C;
@@ -483,6 +507,10 @@ int sg_engine::Group::phase_p0(Run* runs_, int n, int mode) {
         EG_CHECK(regroup(r, h_dist, mode == SG_MODE_SEM_INFER ? 3.0f : 6.0f));
         r.out->trace[1] = r.Lnew.C;
         EG_CHECK(tables_for(r, 3, true));                         // layer_2.*
+        if (r.dbg) {
+            if (r.dbg->h_adj[1]) std::copy(r.adj.begin(), r.adj.end(), r.dbg->h_adj[1]);
+            r.dbg->n_adj[1] = r.E;
+        }
         r.feat_prev = r.pl->feat1.p; r.feat_prev_stride = 128; r.feat_prev_dim = 128;
     }
     return SG_OK;
@@ -699,6 +727,22 @@ int sg_engine::Group::phase_layer(Run* runs_, int n, int layer) {
     mark(sb + 5);
     rg.next(layer == 0 ? "L2.sync" : "L3.sync");
     EG_CHECK(outbox_and_sync());
+    {
+        // stage taps: the layer's kNN table + member order, the cluster features in front of the GCN (featA) and its output (featB)
+        bool tapped = false;
+        for (int i = 0; i < n; ++i) {
+            const Run& r = runs_[i];
+            const sg_debug* dg = r.dbg;
+            if (!dg) continue;
+            const size_t N = (size_t)r.sc->N, cat = (size_t)r.Lnew.C * (r.feat_prev_dim + 64);
+            if (dg->d_knn[layer]) EG_HIP(hipMemcpyAsync(dg->d_knn[layer], r.pl->knn.p, N * 20 * 4, hipMemcpyDeviceToDevice, stream));
+            if (dg->d_members[layer]) EG_HIP(hipMemcpyAsync(dg->d_members[layer], r.pl->members.p, N * 4, hipMemcpyDeviceToDevice, stream));
+            if (dg->d_cat[layer]) EG_HIP(hipMemcpyAsync(dg->d_cat[layer], r.pl->featA.p, cat * 4, hipMemcpyDeviceToDevice, stream));
+            if (dg->h_gcn[layer]) EG_HIP(hipMemcpyAsync(dg->h_gcn[layer], r.pl->featB.p, cat * 4, hipMemcpyDeviceToHost, stream));
+            tapped = true;
+        }
+        if (tapped) EG_HIP(timed_sync(stream));
+    }
     rg.next(layer == 0 ? "L2.host_grouping" : "L3.host_grouping");
 
     // ---- host: grouping on the GCN features (model.py:802-815 / 843-856) ----
@@ -749,10 +793,18 @@ int sg_engine::Group::phase_layer(Run* runs_, int n, int layer) {
             }
         }
 #endif
+        if (r.dbg && r.dbg->h_dist[1 + layer]) {
+            const float* d = r.dist_in_outbox ? r.o_dist : r.pl->h_dist.p;
+            std::copy(d, d + r.E, r.dbg->h_dist[1 + layer]);
+        }
         r.Lcur = r.Lnew;
         EG_CHECK(regroup(r, r.dist_in_outbox ? r.o_dist : r.pl->h_dist.p, 2.0f));
         r.out->trace[2 + layer] = r.Lnew.C;
         EG_CHECK(tables_for(r, 6 + 3 * layer, true));             // layer_3.* / layer_4.*
+        if (r.dbg) {
+            if (r.dbg->h_adj[2 + layer]) std::copy(r.adj.begin(), r.adj.end(), r.dbg->h_adj[2 + layer]);
+            r.dbg->n_adj[2 + layer] = r.E;
+        }
         // next layer: previous features = this GCN output (featB); its concat goes to featA again and its GCN output back
         // into featB -- safe, the stream runs the group max (featB -> featA) before the GCN writes featB
         r.feat_prev = r.pl->featB.p; r.feat_prev_stride = Dcat; r.feat_prev_dim = Dcat;
@@ -965,6 +1017,7 @@ void sg_engine::Group::loop() {
             Run& r = runs[i];
             r.sc = &job->scenes[first + i];
             r.out = &job->results[first + i];
+            r.dbg = job->dbg ? job->dbg[first + i] : nullptr;
             r.out_dir = job->out_dirs ? job->out_dirs[first + i] : nullptr;
         }
         int rc = SG_OK;
@@ -1154,12 +1207,14 @@ sg_engine* sg_engine_create(int maxN, int maxS, int maxE, int maxV, const sg_wei
     return e.release();
 }
 
-int sg_engine_submit(sg_engine* e, const sg_scene* scenes, int count, int mode, sg_result* results, sg_writer* writer,
-                     const char* const* out_dirs, int formats) {
+int sg_engine_submit_debug(sg_engine* e, const sg_scene* scenes, int count, int mode, sg_result* results, sg_debug* const* dbg,
+                           sg_writer* writer, const char* const* out_dirs, int formats) {
     if (!e || count < 0 || (count > 0 && (!scenes || !results))) return sg::fail(SG_EINVAL, "sg_engine_submit: bad arguments");
     SG_REQUIRE(mode == SG_MODE_INS_INFER || mode == SG_MODE_SEM_INFER, "sg_engine_submit: bad mode %d", mode);
+    for (int i = 0; dbg && i < count; ++i)
+        SG_REQUIRE(!dbg[i] || !dbg[i]->tape, "sg_engine_submit_debug: the engine records no training tape (scene %d)", i);
     auto job = std::make_shared<Job>();
-    job->scenes = scenes; job->results = results; job->count = count; job->mode = mode;
+    job->scenes = scenes; job->results = results; job->dbg = dbg; job->count = count; job->mode = mode;
     job->writer = (writer && out_dirs) ? writer : nullptr; job->out_dirs = out_dirs; job->formats = formats;
     int id;
     {
@@ -1169,6 +1224,11 @@ int sg_engine_submit(sg_engine* e, const sg_scene* scenes, int count, int mode, 
     }
     e->cv_work.notify_all();
     return id;
+}
+
+int sg_engine_submit(sg_engine* e, const sg_scene* scenes, int count, int mode, sg_result* results, sg_writer* writer,
+                     const char* const* out_dirs, int formats) {
+    return sg_engine_submit_debug(e, scenes, count, mode, results, nullptr, writer, out_dirs, formats);
 }
 
 int sg_engine_wait(sg_engine* e, int ticket) {

@@ -546,6 +546,7 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
                 if (dbg->d_pointfeat[layer]) PL_CHECK(sg::edgeconv_apply(pl->pf.p, N, affine[0], affine[1], dbg->d_pointfeat[layer], stv));
                 if (dbg->d_knn[layer]) PL_HIP(hipMemcpyAsync(dbg->d_knn[layer], pl->knn.p, (size_t)N * 20 * 4, hipMemcpyDeviceToDevice, st));
                 if (dbg->d_members[layer]) PL_HIP(hipMemcpyAsync(dbg->d_members[layer], pl->members.p, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+                if (dbg->d_cat[layer]) PL_HIP(hipMemcpyAsync(dbg->d_cat[layer], cat, (size_t)C * Dcat * 4, hipMemcpyDeviceToDevice, st));
             }
             if (tape) {
                 sg_tape::Layer& TL = tape->layer[layer];

@@ -59,7 +59,7 @@ class Classifier(C.Structure):
 class Debug(C.Structure):
     _fields_ = [("d_samples1", vp), ("d_feat1", vp), ("d_pointfeat", vp * 2), ("d_knn", vp * 2), ("d_members", vp * 2),
                 ("h_gcn", vp * 2), ("h_dist", vp * 3), ("h_adj", vp * 4), ("n_adj", C.c_int32 * 4),
-                ("h_feat5", vp), ("h_ins5", vp), ("h_sem5", vp), ("n5", C.c_int32), ("tape", vp)]
+                ("h_feat5", vp), ("h_ins5", vp), ("h_sem5", vp), ("n5", C.c_int32), ("tape", vp), ("d_cat", vp * 2)]
 
 
 # name -> (restype, argtypes); every symbol declared in include/seggroup_hip.h
@@ -167,6 +167,7 @@ SIGNATURES = {
     "sg_engine_create": (vp, [_I, _I, _I, _I, vp, _I, _I]),
     "sg_engine_destroy": (None, [vp]),
     "sg_engine_submit": (_I, [vp, vp, _I, _I, vp, vp, vp, _I]),
+    "sg_engine_submit_debug": (_I, [vp, vp, _I, _I, vp, vp, vp, vp, _I]),
     "sg_engine_wait": (_I, [vp, _I]),
     "sg_engine_set_timing": (_I, [vp, _I]),
     "sg_engine_set_label_transfer": (_I, [vp, _I]),

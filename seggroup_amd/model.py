@@ -300,10 +300,14 @@ class Engine:
         return sc.N <= self.caps[0] and sc.S <= self.caps[1] and sc.E0 <= self.caps[2] and sc.V <= self.caps[3]
 
     def submit(self, scenes: List[DeviceScene], mode: int = hip.MODE_INS_INFER, writer: "Optional[AsyncLabelWriter]" = None,
-               out_dirs: Optional[List[str]] = None, formats=("txt", "npy")) -> Ticket:
+               out_dirs: Optional[List[str]] = None, formats=("txt", "npy"), debug: "Optional[List[Optional[hip.Debug]]]" = None) -> Ticket:
+        """debug (a test hook): one hip.Debug or None per scene; the engine fills the stage taps it can (sg_engine_submit_debug).  The
+        Debug objects and the buffers they point at must stay alive until `wait()` has returned."""
         n = len(scenes)
         if any(not self.fits(s) for s in scenes):
             raise ValueError("Engine.submit: a scene exceeds the capacities this engine was created with")
+        if debug is not None and len(debug) != n:
+            raise ValueError("Engine.submit: debug needs one entry (hip.Debug or None) per scene")
         slot = self._turn
         self._turn = (self._turn + 1) % self.ring
         self._release_slot(slot)                          # the writer pool reads the label vectors in place (sg_writer_submit_scene)
@@ -345,13 +349,19 @@ class Engine:
                 wh = writer.handle
             else:                                         # .sgl only: the engine's threads write nothing, wait() submits the files
                 c_dirs = None
+        c_dbg = None
         with torch.cuda.device(self.device):
-            tid = self.lib.sg_engine_submit(self.handle, c_scenes, n, mode, c_res, wh, c_dirs, fm)
+            if debug is None:
+                tid = self.lib.sg_engine_submit(self.handle, c_scenes, n, mode, c_res, wh, c_dirs, fm)
+            else:
+                c_dbg = (C.c_void_p * n)(*[C.addressof(d) if d is not None else None for d in debug])
+                tid = self.lib.sg_engine_submit_debug(self.handle, c_scenes, n, mode, c_res, c_dbg, wh, c_dirs, fm)
         hip.check(tid)
         if wh is not None:
             self._slot_writer[slot] = (writer, tid)
         t = Ticket(tid, list(scenes), c_scenes, c_res, c_dirs, buf, mode)
         t.tables = tabs
+        t.debug = (c_dbg, list(debug)) if debug is not None else None      # alive until the ticket is
         t.sgl = (writer, list(out_dirs)) if want_sgl else None
         return t
 
@@ -403,10 +413,10 @@ class Engine:
         return out
 
     def run(self, scenes: List[DeviceScene], mode: int = hip.MODE_INS_INFER, writer: "Optional[AsyncLabelWriter]" = None,
-            out_dirs: Optional[List[str]] = None, formats=("txt", "npy")) -> List[SceneResult]:
+            out_dirs: Optional[List[str]] = None, formats=("txt", "npy"), debug: "Optional[List[Optional[hip.Debug]]]" = None) -> List[SceneResult]:
         """Forward every scene; with `writer` + `out_dirs` the native threads also hand each scene's label vectors to
         the writer pool (files appear asynchronously: call writer.flush())."""
-        return self.wait(self.submit(scenes, mode, writer, out_dirs, formats))
+        return self.wait(self.submit(scenes, mode, writer, out_dirs, formats, debug=debug))
 
     def set_knn_variant(self, variant: int) -> int:
         return self.lib.sg_engine_set_knn_variant(self.handle, int(variant))

@@ -511,6 +511,75 @@ def test_gcn_forward(env):
         assert np.abs(out.cpu().numpy() - ref).max() < 1e-5
 
 
+def _gcn_graph(S, hubs, seed):
+    """Random sparse cluster graph (~3 edges per row) on the first four fifths of the S rows, plus every hub row joined to exactly
+    `degree` distinct non-hub rows; the last fifth has no edges but those of the hubs."""
+    rng = np.random.default_rng(seed)
+    hub_rows = [r for r, _ in hubs]
+    other = np.setdiff1d(np.arange(S), hub_rows)
+    live = other[other < S - S // 5]
+    pairs = [rng.choice(live, (3 * live.size, 2))] if live.size > 1 else []
+    for row, deg in hubs:
+        pairs.append(np.stack([np.full(deg, row), rng.choice(other, size=deg, replace=False)], 1))
+    if not pairs:
+        return np.zeros((0, 2), np.int32)
+    p = np.unique(np.sort(np.concatenate(pairs), axis=1), axis=0)
+    return p[p[:, 0] != p[:, 1]].astype(np.int32)
+
+
+GCN_EDGE_CASES = [  # (S, D, hub rows (row, degree), seed)
+    (600, 192, [(3, 300), (9, 256), (17, 257)], 11),          # unstaged rows (> kDegCap = 256), the staged path at its cap, one past it
+    (600, 256, [(5, 300), (8, 256), (13, 257)], 12),
+    (17, 192, [], 14),
+    (1, 256, [], 15),                                          # S = 1: E = 0
+    (40, 192, [], 16),                                         # E forced to 0 below
+    (4000, 192, [(1234, 300)], 17),
+    (4000, 256, [], 18),
+    (333, 64, [(2, 280)], 19),                                 # D outside {192, 256}: the VALU k_gcn_fc
+    (333, 100, [(7, 257), (8, 256)], 20),
+    (129, 100, [], 21),
+]
+
+
+@pytest.mark.parametrize("S,D,hubs,seed", GCN_EDGE_CASES, ids=[f"S{c[0]}-D{c[1]}-hub{max([h[1] for h in c[2]], default=0)}-{c[3]}" for c in GCN_EDGE_CASES])
+def test_gcn_forward_edge_cases(env, S, D, hubs, seed):
+    """sg_gcn_forward against the float64 oracle where test_gcn_forward does not go: rows of more than kDegCap = 256 edges (the
+    aggregate's unstaged path), exactly 256 and 257, rows without edges, E = 0, S = 1 / 17 / 4,000 and D outside {192, 256}."""
+    lib, torch, hip = env
+    from oracle import cpu_ref as O
+    rng = np.random.default_rng(seed)
+    adj = _gcn_graph(S, hubs, seed) if seed != 16 else np.zeros((0, 2), np.int32)
+    E = adj.shape[0]
+    deg = np.bincount(adj.reshape(-1), minlength=S)
+    for row, d in hubs:
+        assert deg[row] == d, (row, deg[row], d)
+    if S >= 5:
+        assert (deg == 0).any()                                   # rows without edges take part
+    x = rng.normal(size=(S, D)).astype(np.float32)
+    Wfc = (rng.uniform(-1, 1, (D, D)) / np.sqrt(D)).astype(np.float32)
+    ref = O.gcn_forward(x, adj, Wfc, alpha=0.125)
+    rowptr = np.zeros(S + 1, np.int32)
+    np.add.at(rowptr, adj[:, 0] + 1, 1)
+    np.add.at(rowptr, adj[:, 1] + 1, 1)
+    np.cumsum(rowptr, out=rowptr)
+    fill = rowptr[:-1].copy()
+    col = np.zeros(max(2 * E, 1), np.int32)
+    eid = np.zeros(max(2 * E, 1), np.int32)
+    for e, (a, b) in enumerate(adj):
+        col[fill[a]] = b; eid[fill[a]] = e; fill[a] += 1
+        col[fill[b]] = a; eid[fill[b]] = e; fill[b] += 1
+    out = torch.full((S, D), float("nan"), device="cuda:0")
+    ws = _ws(torch, lib.sg_gcn_ws_bytes(S, D, E))
+    adj_d = _up(torch, adj if E else np.zeros((1, 2), np.int32))
+    hip.check(lib.sg_gcn_forward(_up(torch, x).data_ptr(), S, D, adj_d.data_ptr(), E, _up(torch, rowptr).data_ptr(),
+                                 _up(torch, col).data_ptr(), _up(torch, eid).data_ptr(), _up(torch, Wfc).data_ptr(),
+                                 C.c_float(0.125), out.data_ptr(), ws.data_ptr(), ws.numel(), None))
+    got = out.cpu().numpy()
+    assert np.isfinite(got).all()
+    err = np.abs(got - ref).max()
+    assert err < 1e-5, f"max |HIP - oracle| = {err:.3g}"
+
+
 def test_export_and_evaluate(env, golden_index):
     lib, torch, hip = env
     from oracle import cpu_ref as O
