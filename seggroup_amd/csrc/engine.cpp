@@ -18,7 +18,8 @@
 //
 // The engine owns G groups (one persistent host thread + one HIP stream each) that pull scenes from a job queue:
 // sg_engine_submit() returns at once, so a driver can queue the next batch before the previous one has drained.
-// Kernel bodies are shared with the single-scene path, so labels, kNN tables and adjacency lists are bit-identical to sg_pipeline_forward, and so
+// Kernel bodies and the host grouping (scene_host.cpp) are shared with the single-scene path, so labels, kNN tables and adjacency lists are
+// bit-identical to sg_pipeline_forward, and so
 // are the float stages unless a scene has more EdgeConv tile groups than the launch gives it workgroups (b_edgeconv): then its BatchNorm partial
 // sums are added in another association than in the single-scene launch and may differ in the last bits (include/seggroup_hip.h;
 // tests/test_gpu_engine_taps.py).
@@ -36,6 +37,7 @@
 
 #include "engine_ctx.h"
 #include "pipeline_priv.h"
+#include "scene_host.h"
 
 namespace {
 
@@ -106,17 +108,11 @@ struct Run {
     sg_result* out = nullptr;
     sg_debug* dbg = nullptr;                   // stage taps (sg_engine_submit_debug), usually none
     const char* out_dir = nullptr;
-    sg_partition* part = nullptr;
-    int max_ins = 1, max_seg = 0, cap1 = 0, out_rows = 0;
+    SceneGrouping g;                           // the scene's host grouping; its label tables live in pl->h_tables
+    int cap1 = 0, out_rows = 0;
     std::vector<int32_t> lay_big;
-    int E = 0;
-    std::vector<int32_t> adj, adj_next;
-    std::vector<uint8_t> connected, keep;
-    LayerDesc Lcur, Lnew;
     const float* feat_prev = nullptr;
     int feat_prev_stride = 128, feat_prev_dim = 128;
-    int n_tables = 6, ins_row = 4, sem_row = 5;
-    std::vector<int32_t> tab;                  // [14,S] export tables
     SlotCtx ctx;                               // master copy; written into the params arena before every phase
     // host views of this phase's outbox
     int32_t* o_count = nullptr;
@@ -270,29 +266,6 @@ void debug_reset() { std::lock_guard<std::mutex> g(g_dbg_mu); g_dbg_samples.clea
 inline void debug_reset() {}
 #endif
 
-int tables_for(Run& r, int first_row, bool with_seg) {
-    const int S = r.sc->S;
-    int32_t* a = r.tab.data() + (size_t)first_row * S;
-    return sg_partition_export_tables(r.part, with_seg ? a : nullptr, with_seg ? a + S : a, with_seg ? a + 2 * (size_t)S : a + S);
-}
-
-// group + re-index + contract (model.py:218-258, 291-302, 759-768): new layer in Lnew, contracted adjacency in adj
-int regroup(Run& r, const float* h_dist, float th) {
-    r.connected.assign(std::max(r.E, 1), 0);
-    int rc = sg_partition_group_nearby(r.part, r.Lcur.root.data(), r.Lcur.C, h_dist, r.adj.data(), r.E, th, r.connected.data());
-    if (rc == SG_ESTALL) { r.out->stalled = 1; rc = SG_OK; sg::err_buf()[0] = 0; }
-    if (rc < 0) return rc;
-    r.keep.resize(r.connected.size());
-    for (size_t i = 0; i < r.connected.size(); ++i) r.keep[i] = !r.connected[i];
-    r.adj_next.resize(2 * (size_t)std::max(r.E, 1));
-    const int En = sg_partition_contract(r.part, r.Lcur.root.data(), r.adj.data(), r.E, r.keep.data(), r.adj_next.data());
-    if (En < 0) return En;
-    freeze_layer(r.part, r.sc->S, r.Lnew);
-    r.adj.assign(r.adj_next.begin(), r.adj_next.begin() + 2 * (size_t)En);
-    r.E = En;
-    return SG_OK;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -311,18 +284,12 @@ int sg_engine::Group::phase_p0(Run* runs_, int n, int mode) {
         sg_pipeline* pl = r.pl;
         const sg_scene* sc = r.sc;
         const int N = sc->N, S = sc->S;
-        r.out->stalled = 0; r.out->used_fallback = 0;
-        for (int k = 0; k < 5; ++k) r.out->trace[k] = 0;
-        r.part = sg_partition_create(S, sc->h_seg_first, sc->h_seg_size, sc->h_seg_ins, sc->h_seg_sem);
-        if (!r.part) return SG_EINVAL;
-        r.max_ins = 1; r.max_seg = 0;
-        for (int s = 0; s < S; ++s) { r.max_ins = std::max(r.max_ins, sc->h_seg_ins[s] + 2); r.max_seg = std::max(r.max_seg, sc->h_seg_size[s]); }
-        if (r.max_ins > pl->maxS + 2)
-            return sg::fail(SG_EUNSUP, "weak instance ids up to %d exceed the engine's metric workspace (max_segments + 2)", r.max_ins - 2);
-        r.tab.resize((size_t)SG_NUM_LABEL_VECTORS * S);
+        r.g.begin(sc, mode, pl->h_tables.p, r.out, r.dbg);
+        EG_CHECK(r.g.create_partition());
+        if (r.g.max_ins > pl->maxS + 2)
+            return sg::fail(SG_EUNSUP, "weak instance ids up to %d exceed the engine's metric workspace (max_segments + 2)", r.g.max_ins - 2);
         r.cap1 = (int)(pl->adj1.n / 2);
         r.out_rows = std::min(r.cap1, 8 * S + 64);
-        r.n_tables = 6; r.ins_row = 4; r.sem_row = 5;
 
         SlotCtx& c = r.ctx;
         std::memset(&c, 0, sizeof c);
@@ -371,7 +338,7 @@ int sg_engine::Group::phase_p0(Run* runs_, int n, int mode) {
         c.dist = pl->dist.p; c.dist_copy = c.dist1_out; c.dist_copy_rows = r.out_rows;
         c.labels = pl->labels.p;
         bd.max_N = std::max(bd.max_N, N); bd.max_S = std::max(bd.max_S, S); bd.max_E0 = std::max(bd.max_E0, sc->E0); bd.max_V = std::max(bd.max_V, sc->V);
-        bd.max_bits_blocks = std::max(bd.max_bits_blocks, c.bits_blocks); bd.max_seg = std::max(bd.max_seg, r.max_seg);
+        bd.max_bits_blocks = std::max(bd.max_bits_blocks, c.bits_blocks); bd.max_seg = std::max(bd.max_seg, r.g.max_seg);
         bd.max_E = std::max(bd.max_E, r.out_rows);
     }
     if (!par.ok || !box.ok) return sg::fail(SG_ENOMEM, "engine: phase P0 exceeds the group's parameter / outbox arena");
@@ -449,7 +416,7 @@ int sg_engine::Group::phase_p0(Run* runs_, int n, int mode) {
                 float* d_ref = nullptr; void* d_wsr = nullptr;
                 if (hipMalloc((void**)&d_ref, smp.size() * 4) == hipSuccess && hipMalloc(&d_wsr, (size_t)r.sc->N * 16) == hipSuccess &&
                     sg::fps_sample_hint(r.sc->d_data, r.sc->N, 6, r.sc->d_seg_points, r.sc->d_seg_off, S, 64, 6, 1, d_ref, nullptr, d_wsr, (size_t)r.sc->N * 16,
-                                        (void*)stream, r.max_seg) == SG_OK) {
+                                        (void*)stream, r.g.max_seg) == SG_OK) {
                     std::vector<float> ref(smp.size());
                     (void)fetch(ref.data(), d_ref, ref.size() * 4);
                     for (int sg_ = 0; sg_ < S; ++sg_)
@@ -482,6 +449,7 @@ int sg_engine::Group::phase_p0(Run* runs_, int n, int mode) {
                          (unsigned long long)dev_digest(r.pl->adj1.p, (size_t)std::min(E1, r.cap1) * 8), (unsigned long long)dev_digest(r.pl->dist.p, (size_t)std::min(E1, r.cap1) * 4));
 #endif
         if (E1 > r.cap1) return sg::fail(SG_ENOMEM, "adjacency capacity exceeded (%d > %d)", E1, r.cap1);
+        const int32_t* h_adj = r.o_adj1;
         const float* h_dist = r.o_dist;
         if (E1 > r.out_rows) {                                    // rare: denser than the outbox assumes -- fetch the full arrays
             // into the pipeline's PINNED landing buffers (sized for the adjacency capacity): a pageable destination makes the copy a
@@ -489,28 +457,12 @@ int sg_engine::Group::phase_p0(Run* runs_, int n, int mode) {
             EG_HIP(hipMemcpyAsync(r.pl->h_adj.p, r.pl->adj1.p, (size_t)E1 * 8, hipMemcpyDeviceToHost, stream));
             EG_HIP(hipMemcpyAsync(r.pl->h_dist.p, r.pl->dist.p, (size_t)E1 * 4, hipMemcpyDeviceToHost, stream));
             EG_HIP(timed_sync(stream));
-            r.adj.assign(r.pl->h_adj.p, r.pl->h_adj.p + 2 * (size_t)E1);
+            h_adj = r.pl->h_adj.p;
             h_dist = r.pl->h_dist.p;
-        } else {
-            r.adj.assign(r.o_adj1, r.o_adj1 + 2 * (size_t)E1);
-        }
-        r.E = E1;
-        if (r.dbg) {
-            if (r.dbg->h_adj[0]) std::copy(r.adj.begin(), r.adj.end(), r.dbg->h_adj[0]);
-            if (r.dbg->h_dist[0]) std::copy(h_dist, h_dist + E1, r.dbg->h_dist[0]);
-            r.dbg->n_adj[0] = E1;
         }
         if (mode == SG_MODE_INS_INFER) r.seg_sums.assign(r.o_seg_sums, r.o_seg_sums + (size_t)S * 3);
-        freeze_layer(r.part, S, r.Lcur);                          // layer 1: every segment its own cluster
-        r.out->trace[0] = r.Lcur.C;
-        EG_CHECK(tables_for(r, 0, true));                         // layer_1.{seg,ins,sem}
-        EG_CHECK(regroup(r, h_dist, mode == SG_MODE_SEM_INFER ? 3.0f : 6.0f));
-        r.out->trace[1] = r.Lnew.C;
-        EG_CHECK(tables_for(r, 3, true));                         // layer_2.*
-        if (r.dbg) {
-            if (r.dbg->h_adj[1]) std::copy(r.adj.begin(), r.adj.end(), r.dbg->h_adj[1]);
-            r.dbg->n_adj[1] = r.E;
-        }
+        EG_CHECK(r.g.layer1());
+        EG_CHECK(r.g.structural(h_adj, h_dist, E1));
         r.feat_prev = r.pl->feat1.p; r.feat_prev_stride = 128; r.feat_prev_dim = 128;
     }
     return SG_OK;
@@ -533,13 +485,19 @@ int sg_engine::Group::phase_layer(Run* runs_, int n, int layer) {
         Run& r = runs_[i];
         sg_pipeline* pl = r.pl;
         const sg_scene* sc = r.sc;
-        const int N = sc->N, S = sc->S, C = r.Lnew.C, E = r.E, Dcat = r.feat_prev_dim + 64;
-        const LayerDesc& Ln = r.Lnew;
-        const LayerDesc& Lc = r.Lcur;
+        const int N = sc->N, S = sc->S, C = r.g.Lnew.C, E = r.g.E, Dcat = r.feat_prev_dim + 64;
+        const LayerDesc& Ln = r.g.Lnew;
+        const LayerDesc& Lc = r.g.Lcur;
         SlotCtx& c = r.ctx;
-        auto put = [&](const int32_t* v, size_t count) -> const int32_t* {
+        auto take = [&](size_t count, const int32_t** dev) {         // host view of `count` words of the parameter block, device address in *dev
             int32_t* d = nullptr;
             int32_t* h = par.take<int32_t>(std::max<size_t>(count, 1), &d);
+            *dev = d;
+            return h;
+        };
+        auto put = [&](const int32_t* v, size_t count) -> const int32_t* {
+            const int32_t* d = nullptr;
+            int32_t* h = take(count, &d);
             if (h && count) std::memcpy(h, v, count * 4);
             return d;
         };
@@ -574,82 +532,37 @@ int sg_engine::Group::phase_layer(Run* runs_, int n, int layer) {
         {
             std::vector<int32_t>& big = r.lay_big;                // a block lays out kLayoutPiece rows: list the rest of larger segments
             big.clear();
-            if (r.max_seg > sg::kLayoutPiece)
+            if (r.g.max_seg > sg::kLayoutPiece)
                 for (int k = 0; k < S; ++k)
                     for (int r0 = sg::kLayoutPiece; r0 < sc->h_seg_size[Ln.order[k]]; r0 += sg::kLayoutPiece) { big.push_back(k); big.push_back(r0); }
             c.lay_big = put(big.data(), big.size()); c.lay_nbig = (int)(big.size() / 2);
             bd.max_lay_big = std::max(bd.max_lay_big, c.lay_nbig);
         }
         c.seg_chunk_off = put(r.chunk_off.data(), (size_t)S + 1);
-        tmp.resize(S);
-        for (int k = 0; k < S; ++k) tmp[k] = Ln.cl_of_seg[Ln.order[k]];
-        c.cl = put(tmp.data(), S);
+        if (int32_t* h = take(S, &c.cl)) fill_cl_of_order(Ln, h);
         c.cl_pt_off = put(Ln.cl_pt_off.data(), C + 1); c.cl_seg_off = put(Ln.cl_seg_off.data(), C + 1);
-        // layer 3 may start from layer 2's table: former clusters of <= 20 points have no kNN list (-1)
-        if (layer == 1) {
-            for (int sg = 0; sg < S; ++sg) {
-                const int pc = Lc.cl_of_seg[sg];
-                tmp[sg] = Lc.cl_pt_off[pc + 1] - Lc.cl_pt_off[pc] > 20 ? pc : -1;
-            }
-            c.seg_prevcl = put(tmp.data(), S);
-        } else c.seg_prevcl = nullptr;
-        // cluster centroids (combine_centralized_pointcloud, model.py:429-436) from the per-segment coordinate sums
+        c.seg_prevcl = nullptr;                                   // (only the seeded layer-3 kNN reads it)
+        if (layer == 1)
+            if (int32_t* h = take(S, &c.seg_prevcl)) fill_seg_prevcl(Lc, h);
         {
             float* d_m = nullptr;
             float* m = par.take<float>(3 * (size_t)std::max(C, 1), &d_m);
-            if (m)
-                for (int cc = 0; cc < C; ++cc) {
-                    double sx = 0.0, sy = 0.0, sz = 0.0;
-                    for (int k = Ln.cl_seg_off[cc]; k < Ln.cl_seg_off[cc + 1]; ++k) {
-                        const double* q = r.seg_sums.data() + 3 * (size_t)Ln.order[k];
-                        sx += q[0]; sy += q[1]; sz += q[2];
-                    }
-                    const double cnt = (double)(Ln.cl_pt_off[cc + 1] - Ln.cl_pt_off[cc]);
-                    m[3 * cc] = (float)(sx / cnt); m[3 * cc + 1] = (float)(sy / cnt); m[3 * cc + 2] = (float)(sz / cnt);
-                }
+            if (m) fill_cl_mean(Ln, r.seg_sums.data(), m);
             c.cl_mean = d_m;
         }
-        // parents: old clusters (Lcur numbering) absorbed by each new cluster, in old order (model.py:766-768)
-        {
-            int32_t *d_goff = nullptr, *d_gidx = nullptr;
-            int32_t* goff = par.take<int32_t>((size_t)C + 1, &d_goff);
-            int32_t* gidx = par.take<int32_t>(std::max(Lc.C, 1), &d_gidx);
-            if (goff && gidx) {
-                std::fill(goff, goff + C + 1, 0);
-                for (int j = 0; j < Lc.C; ++j) ++goff[Ln.cl_of_seg[Lc.root[j]] + 1];
-                for (int cc = 0; cc < C; ++cc) goff[cc + 1] += goff[cc];
-                tmp.assign(goff, goff + C);
-                for (int j = 0; j < Lc.C; ++j) gidx[tmp[Ln.cl_of_seg[Lc.root[j]]]++] = j;
-            }
-            c.goff = d_goff; c.gidx = d_gidx;
-        }
-        // adjacency + symmetric CSR of the cluster graph
-        c.g_adj = put(r.adj.data(), 2 * (size_t)E);
-        {
-            int32_t *d_rp = nullptr, *d_col = nullptr, *d_eid = nullptr;
-            int32_t* rowptr = par.take<int32_t>((size_t)C + 1, &d_rp);
-            int32_t* col = par.take<int32_t>(std::max<size_t>(2 * (size_t)E, 1), &d_col);
-            int32_t* eid = par.take<int32_t>(std::max<size_t>(2 * (size_t)E, 1), &d_eid);
-            if (rowptr && col && eid) {
-                std::fill(rowptr, rowptr + C + 1, 0);
-                for (int e = 0; e < E; ++e) { ++rowptr[r.adj[2 * e] + 1]; ++rowptr[r.adj[2 * e + 1] + 1]; }
-                for (int cc = 0; cc < C; ++cc) rowptr[cc + 1] += rowptr[cc];
-                tmp.assign(rowptr, rowptr + C);
-                for (int e = 0; e < E; ++e) {
-                    const int a = r.adj[2 * e], b = r.adj[2 * e + 1];
-                    col[tmp[a]] = b; eid[tmp[a]++] = e;
-                    col[tmp[b]] = a; eid[tmp[b]++] = e;
-                }
-            }
-            c.rowptr = d_rp; c.col = d_col; c.eid = d_eid;
-        }
+        int32_t* goff = take((size_t)C + 1, &c.goff);
+        int32_t* gidx = take(Lc.C, &c.gidx);
+        if (goff && gidx) fill_parents(Lc, Ln, goff, gidx);
+        c.g_adj = put(r.g.adj.data(), 2 * (size_t)E);
+        int32_t* rowptr = take((size_t)C + 1, &c.rowptr);
+        int32_t* col = take(2 * (size_t)E, &c.col);
+        int32_t* eid = take(2 * (size_t)E, &c.eid);
+        if (rowptr && col && eid) fill_csr(r.g.adj.data(), E, C, rowptr, col, eid);
         c.E = E; c.C = C; c.Dcat = Dcat;
         c.members = pl->members.p; c.pos_of_point = pl->pos_of_point.p; c.point_rec = layer == 1 ? reinterpret_cast<float4*>(pl->point_rec.p) : nullptr;   /* only the seeded (layer-3) kNN reads the records */ c.cluster_of_pos = pl->cluster_of_pos.p; c.slot_of_pos = pl->slot_of_pos.p; c.seed_id = pl->seed_id.p;
         c.x9m = pl->x9m.p; c.sxyzw = reinterpret_cast<float4*>(pl->xyzw.p); c.smpos = pl->smpos.p;
         c.gm_rows = r.feat_prev; c.gm_stride = r.feat_prev_stride; c.gm_D = r.feat_prev_dim; c.cat = pl->featA.p;
-        // point 0 is the first member of segment 0; its member-order position is that segment's dst
-        c.pos0 = 0;
-        for (int k = 0; k < S; ++k) if (Ln.order[k] == 0) { c.pos0 = Ln.dst[k]; break; }
+        c.pos0 = pos_of_point0(Ln);
         c.knn = pl->knn.p; c.knn_seed = pl->knn_seed.p;
         const float* W = pl->w.p;
         if (layer == 0) { c.ec_w1 = W + pl->o_m2w; c.ec_g1 = W + pl->o_m2g; c.ec_b1 = W + pl->o_m2b; c.ec_w2 = nullptr; c.ec_g2 = nullptr; c.ec_b2 = nullptr; }
@@ -721,7 +634,7 @@ int sg_engine::Group::phase_layer(Run* runs_, int n, int layer) {
     for (int i = 0; i < n; ++i) {
         Run& r = runs_[i];
         if (!r.dist_in_outbox) {
-            EG_HIP(hipMemcpyAsync(r.pl->h_dist.p, r.pl->dist.p, (size_t)r.E * 4, hipMemcpyDeviceToHost, stream));     // pinned (see above)
+            EG_HIP(hipMemcpyAsync(r.pl->h_dist.p, r.pl->dist.p, (size_t)r.g.E * 4, hipMemcpyDeviceToHost, stream));     // pinned (see above)
         }
     }
     mark(sb + 5);
@@ -734,7 +647,7 @@ int sg_engine::Group::phase_layer(Run* runs_, int n, int layer) {
             const Run& r = runs_[i];
             const sg_debug* dg = r.dbg;
             if (!dg) continue;
-            const size_t N = (size_t)r.sc->N, cat = (size_t)r.Lnew.C * (r.feat_prev_dim + 64);
+            const size_t N = (size_t)r.sc->N, cat = (size_t)r.g.Lnew.C * (r.feat_prev_dim + 64);
             if (dg->d_knn[layer]) EG_HIP(hipMemcpyAsync(dg->d_knn[layer], r.pl->knn.p, N * 20 * 4, hipMemcpyDeviceToDevice, stream));
             if (dg->d_members[layer]) EG_HIP(hipMemcpyAsync(dg->d_members[layer], r.pl->members.p, N * 4, hipMemcpyDeviceToDevice, stream));
             if (dg->d_cat[layer]) EG_HIP(hipMemcpyAsync(dg->d_cat[layer], r.pl->featA.p, cat * 4, hipMemcpyDeviceToDevice, stream));
@@ -752,12 +665,12 @@ int sg_engine::Group::phase_layer(Run* runs_, int n, int layer) {
 #ifdef SG_ENGINE_DEBUG
         if (g_hash) tl_hash_stream = stream;
         if (g_hash)
-            std::fprintf(stderr, "SGHASH %p L%d C=%d E=%d knn=%016llx x9m=%016llx fold=%016llx cat=%016llx gcn=%016llx dist=%016llx\n", (const void*)r.sc->d_data, layer, r.Lnew.C, r.E,
+            std::fprintf(stderr, "SGHASH %p L%d C=%d E=%d knn=%016llx x9m=%016llx fold=%016llx cat=%016llx gcn=%016llx dist=%016llx\n", (const void*)r.sc->d_data, layer, r.g.Lnew.C, r.g.E,
                          (unsigned long long)dev_digest(r.pl->knn.p, (size_t)r.sc->N * 20 * 4), (unsigned long long)dev_digest(r.pl->x9m.p, (size_t)r.sc->N * 12 * 4),
                          (unsigned long long)(layer == 0 ? dev_digest(r.ctx.ec_w1f, 64 * 4) ^ (dev_digest(r.ctx.ec_sh1, 64 * 4) << 1)      /* MLP2: |a| [64] and the shifts [64] only */
                                                                  : dev_digest(r.ctx.ec_w1f, (size_t)((r.ctx.ec_scale + 4) - r.ctx.ec_w1f) * 4)),
-                         (unsigned long long)dev_digest(r.pl->featA.p, (size_t)r.Lnew.C * Dcat * 4), (unsigned long long)dev_digest(r.pl->featB.p, (size_t)r.Lnew.C * Dcat * 4),
-                         (unsigned long long)dev_digest(r.dist_in_outbox ? (const void*)r.ctx.dist : (const void*)r.pl->dist.p, (size_t)r.E * 4));
+                         (unsigned long long)dev_digest(r.pl->featA.p, (size_t)r.g.Lnew.C * Dcat * 4), (unsigned long long)dev_digest(r.pl->featB.p, (size_t)r.g.Lnew.C * Dcat * 4),
+                         (unsigned long long)dev_digest(r.dist_in_outbox ? (const void*)r.ctx.dist : (const void*)r.pl->dist.p, (size_t)r.g.E * 4));
         if (g_hash) {
             // the first table seen for (scene, layer) is kept; later ones are compared row by row
             const int N = r.sc->N;
@@ -780,8 +693,8 @@ int sg_engine::Group::phase_layer(Run* runs_, int n, int layer) {
                     if (std::memcmp(&knn[(size_t)q * 20], &it->second[(size_t)q * 20], 80) == 0) continue;
                     ++rows;
                     if (shown++ >= 3) continue;
-                    const int cc = cop[q], n = r.Lnew.cl_pt_off[cc + 1] - r.Lnew.cl_pt_off[cc];
-                    std::fprintf(stderr, "SGROW %p L%d row %d cluster %d (%d points, from %d) seed id %d\n   now  :", (const void*)r.sc->d_data, layer, q, cc, n, r.Lnew.cl_pt_off[cc], sid[q]);
+                    const int cc = cop[q], n = r.g.Lnew.cl_pt_off[cc + 1] - r.g.Lnew.cl_pt_off[cc];
+                    std::fprintf(stderr, "SGROW %p L%d row %d cluster %d (%d points, from %d) seed id %d\n   now  :", (const void*)r.sc->d_data, layer, q, cc, n, r.g.Lnew.cl_pt_off[cc], sid[q]);
                     for (int j = 0; j < 20; ++j) std::fprintf(stderr, " %d", knn[(size_t)q * 20 + j]);
                     std::fprintf(stderr, "\n   first:");
                     for (int j = 0; j < 20; ++j) std::fprintf(stderr, " %d", it->second[(size_t)q * 20 + j]);
@@ -793,18 +706,7 @@ int sg_engine::Group::phase_layer(Run* runs_, int n, int layer) {
             }
         }
 #endif
-        if (r.dbg && r.dbg->h_dist[1 + layer]) {
-            const float* d = r.dist_in_outbox ? r.o_dist : r.pl->h_dist.p;
-            std::copy(d, d + r.E, r.dbg->h_dist[1 + layer]);
-        }
-        r.Lcur = r.Lnew;
-        EG_CHECK(regroup(r, r.dist_in_outbox ? r.o_dist : r.pl->h_dist.p, 2.0f));
-        r.out->trace[2 + layer] = r.Lnew.C;
-        EG_CHECK(tables_for(r, 6 + 3 * layer, true));             // layer_3.* / layer_4.*
-        if (r.dbg) {
-            if (r.dbg->h_adj[2 + layer]) std::copy(r.adj.begin(), r.adj.end(), r.dbg->h_adj[2 + layer]);
-            r.dbg->n_adj[2 + layer] = r.E;
-        }
+        EG_CHECK(r.g.semantic(layer, r.dist_in_outbox ? r.o_dist : r.pl->h_dist.p));
         // next layer: previous features = this GCN output (featB); its concat goes to featA again and its GCN output back
         // into featB -- safe, the stream runs the group max (featB -> featA) before the GCN writes featB
         r.feat_prev = r.pl->featB.p; r.feat_prev_stride = Dcat; r.feat_prev_dim = Dcat;
@@ -821,53 +723,13 @@ int sg_engine::Group::phase_end(Run* runs_, int n, int mode) {
     if (mode == SG_MODE_INS_INFER) {
         for (int i = 0; i < n; ++i) {
             Run& r = runs_[i];
-            sg_pipeline* pl = r.pl;
-            const sg_scene* sc = r.sc;
-            const int S = sc->S, D4 = 256;
-            // Feat_4 = max over absorbed rows of the gcn_3 output (outbox copy), adj_4 = current adj
-            std::vector<float> feat4((size_t)r.Lnew.C * D4, -INFINITY);
-            for (int j = 0; j < r.Lcur.C; ++j) {
-                float* dstp = &feat4[(size_t)r.Lnew.cl_of_seg[r.Lcur.root[j]] * D4];
-                const float* src = r.o_feat + (size_t)j * D4;
-                for (int k = 0; k < D4; ++k) dstp[k] = std::max(dstp[k], src[k]);
-            }
-            std::vector<int32_t> root5(r.Lnew.root.begin(), r.Lnew.root.begin() + r.Lnew.C);
-            root5.resize(S);
-            int C5 = r.Lnew.C, E5 = r.E;
-            r.adj.resize(2 * (size_t)std::max(r.E, 1));
-            const int need_fallback = sg_partition_group_unlabeled(r.part, root5.data(), &C5, feat4.data(), D4, r.adj.data(), &E5);
-            if (need_fallback < 0) return need_fallback;
-            if (need_fallback) {
-                // FPS-1024 over the current clusters (model.py:479), XYZ only, no transform: this scene alone, on the group's stream
-                LayerDesc L5;
-                freeze_layer(r.part, S, L5);
-                std::vector<int32_t> cl_of_order(S);
-                for (int k = 0; k < S; ++k) cl_of_order[k] = L5.cl_of_seg[L5.order[k]];
-                size_t cur = 0;
-                auto put = [&](const std::vector<int32_t>& v, size_t count) {
-                    const size_t at = cur;
-                    std::copy(v.begin(), v.begin() + count, pl->h_desc.p + at);
-                    cur += (count + 3) / 4 * 4;
-                    return at;
-                };
-                const size_t o_order = put(L5.order, S), o_dst = put(L5.dst, S), o_cl = put(cl_of_order, S), o_off = put(L5.cl_pt_off, L5.C + 1);
-                EG_HIP(hipMemcpyAsync(pl->desc.p, pl->h_desc.p, cur * 4, hipMemcpyHostToDevice, stream));
-                const int32_t* dd = pl->desc.p;
-                EG_CHECK(sg_gather_members(sc->d_seg_points, sc->d_seg_off, S, dd + o_order, dd + o_dst, dd + o_cl, pl->members.p, nullptr, nullptr,
-                                           nullptr, (void*)stream));
-                int max_cl = 0;
-                for (int cc = 0; cc < L5.C; ++cc) max_cl = std::max(max_cl, L5.cl_pt_off[cc + 1] - L5.cl_pt_off[cc]);
-                EG_CHECK(pl->need_fallback_buffers());
-                EG_CHECK(sg::fps_sample_hint(sc->d_data, sc->N, 6, pl->members.p, dd + o_off, L5.C, 1024, 3, 0, pl->samples_big.p, nullptr,
-                                             pl->ws_fps.p, pl->ws_fps.n, (void*)stream, max_cl));
-                EG_HIP(hipMemcpyAsync(pl->h_samples.p, pl->samples_big.p, (size_t)L5.C * 1024 * 3 * 4, hipMemcpyDeviceToHost, stream));
+            int rc = r.g.final_clustering(r.o_feat);
+            if (rc == 1) {                                        // the FPS-1024 fallback: this scene alone, on the group's stream
+                EG_CHECK(fallback_fps1024(r.pl, r.sc, r.g.L5, stream));
                 EG_HIP(timed_sync(stream));
-                EG_CHECK(sg_partition_unlabeled_fallback(r.part, L5.root.data(), L5.C, pl->h_samples.p, 1024));
-                r.out->used_fallback = 1;
+                rc = r.g.final_fallback(r.pl->h_samples.p);
             }
-            r.out->trace[4] = sg_partition_num_clusters(r.part);
-            EG_CHECK(tables_for(r, 12, false));                   // final.{ins,sem}
-            r.n_tables = 14; r.ins_row = 12; r.sem_row = 13;
+            EG_CHECK(rc);
         }
     }
     par.reset(); box.reset();
@@ -880,11 +742,12 @@ int sg_engine::Group::phase_end(Run* runs_, int n, int mode) {
         const int S = r.sc->S;
         SlotCtx& c = r.ctx;
         int32_t* d_tab = nullptr;
-        int32_t* tab = par.take<int32_t>((size_t)r.n_tables * S, &d_tab);
-        if (tab) std::memcpy(tab, r.tab.data(), (size_t)r.n_tables * S * 4);
-        c.tables = d_tab; c.n_tables = r.n_tables; c.labels = r.pl->labels.p; c.sem_row = r.sem_row; c.ins_row = r.ins_row; c.max_ins = r.max_ins;
-        r.o_cnt = box.take<uint32_t>(128 + 5 * (size_t)r.max_ins, &c.cnt);
-        bd.max_V = std::max(bd.max_V, r.sc->V); bd.max_ins = std::max(bd.max_ins, r.max_ins);
+        const SceneGrouping& g = r.g;
+        int32_t* tab = par.take<int32_t>((size_t)g.n_tables() * S, &d_tab);
+        if (tab) std::memcpy(tab, g.tab, (size_t)g.n_tables() * S * 4);
+        c.tables = d_tab; c.n_tables = g.n_tables(); c.labels = r.pl->labels.p; c.sem_row = g.sem_row(); c.ins_row = g.ins_row(); c.max_ins = g.max_ins;
+        r.o_cnt = box.take<uint32_t>(128 + 5 * (size_t)g.max_ins, &c.cnt);
+        bd.max_V = std::max(bd.max_V, r.sc->V); bd.max_ins = std::max(bd.max_ins, g.max_ins);
     }
     if (!par.ok || !box.ok) return sg::fail(SG_ENOMEM, "engine: the export phase exceeds the group's parameter / outbox arena");
     for (int i = 0; i < n; ++i) h_ctx[i] = runs_[i].ctx;
@@ -906,10 +769,10 @@ int sg_engine::Group::phase_end(Run* runs_, int n, int mode) {
             // The label vectors (8.4 MB per 150k-vertex scene).  hipMemcpyAsync moves them with a blit KERNEL on this ROCm -- waves on the CUs waiting for
             // PCIe, 6-7 % of the engine's throughput (sdma.cpp) -- so by default they go over the copy engines instead, behind the stream's sync below
             // (SG_ENGINE_LABEL_COPY=hip restores the stream copy; it is also the fallback when the HSA path is not there or refuses a pointer)
-            if (label_sdma) { sd_dst.push_back(r.out->h_labels); sd_src.push_back(r.pl->labels.p); sd_bytes.push_back((size_t)r.n_tables * r.sc->V * 4); }
-            else EG_HIP(hipMemcpyAsync(r.out->h_labels, r.pl->labels.p, (size_t)r.n_tables * r.sc->V * 4, hipMemcpyDeviceToHost, stream));
+            if (label_sdma) { sd_dst.push_back(r.out->h_labels); sd_src.push_back(r.pl->labels.p); sd_bytes.push_back((size_t)r.g.n_tables() * r.sc->V * 4); }
+            else EG_HIP(hipMemcpyAsync(r.out->h_labels, r.pl->labels.p, (size_t)r.g.n_tables() * r.sc->V * 4, hipMemcpyDeviceToHost, stream));
         }
-        if (r.out->h_tables) std::memcpy(r.out->h_tables, r.tab.data(), (size_t)r.n_tables * r.sc->S * 4);
+        if (r.out->h_tables) std::memcpy(r.out->h_tables, r.g.tab, (size_t)r.g.n_tables() * r.sc->S * 4);
     }
     mark(18);
     rg.next("END.sync");
@@ -926,7 +789,7 @@ int sg_engine::Group::phase_end(Run* runs_, int n, int mode) {
     }
     for (int i = 0; i < n; ++i) {
         Run& r = runs_[i];
-        sg::eval_finish(r.o_cnt, r.max_ins, r.out->iou_sem, r.out->iou_ins, r.out->acc);
+        sg::eval_finish(r.o_cnt, r.g.max_ins, r.out->iou_sem, r.out->iou_ins, r.out->acc);
     }
     return SG_OK;
 }
@@ -965,14 +828,10 @@ int sg_engine::Group::superstep(Run* r, int n, int mode, sg_writer* writer, int 
         for (int i = 0; i < n && rc >= 0; ++i) {
             if (!r[i].out_dir) continue;
             if (eng->label_compact && r[i].sc->h_seg_of_vertex)     // tables + seg_of_vertex, copied: the worker expands while it formats
-                rc = sg_writer_submit_scene_tables(writer, r[i].out_dir, r[i].tab.data(), r[i].sc->S, r[i].sc->h_seg_of_vertex, r[i].sc->V, nvec, formats, tag);
+                rc = sg_writer_submit_scene_tables(writer, r[i].out_dir, r[i].g.tab, r[i].sc->S, r[i].sc->h_seg_of_vertex, r[i].sc->V, nvec, formats, tag);
             else   // by reference: the vectors stay in the caller's buffer, which the caller reuses only behind sg_writer_wait_tag(ticket)
                 rc = sg_writer_submit_scene(writer, r[i].out_dir, r[i].out->h_labels, r[i].sc->V, nvec, formats, tag);
         }
-    }
-    for (int i = 0; i < n; ++i) {
-        if (r[i].part) sg_partition_destroy(r[i].part);
-        r[i].part = nullptr;
     }
     if (rc < 0) {
         // an aborted phase may leave set bits in the contraction bitmaps (they are only cleared by k_emit_pairs): restore the

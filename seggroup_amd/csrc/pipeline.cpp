@@ -1,8 +1,8 @@
 // SegModel.forward (reference seggroup/model.py:684-897) for one scene on one HIP stream.
 //
 // The reference alternates device math with serial, order-dependent Python bookkeeping; here the
-// bookkeeping is the host grouping engine (grouping.cpp, segment-level, microseconds) and every
-// per-point / per-edge computation is a kernel.  Per scene the host blocks on the stream only where
+// bookkeeping is the host grouping (scene_host.cpp over grouping.cpp, segment-level, microseconds; shared with the
+// scene engine) and every per-point / per-edge computation is a kernel.  Per scene the host blocks on the stream only where
 // the serial grouping needs distances: after MLP1, after each of the two semantic layers, optionally
 // after the FPS-1024 fallback, and at the end (3-5 synchronisations).  Several pipelines on distinct
 // streams (one per in-flight scene) overlap their host phases with each other's kernels.
@@ -17,6 +17,7 @@
 #include <string>
 
 #include "pipeline_priv.h"
+#include "scene_host.h"
 
 namespace {
 
@@ -25,7 +26,7 @@ using namespace sgp;
 // SG_HOST_PROFILE=1: wall time of sg_pipeline_forward split into 'blocked in hipStreamSynchronize' and the rest (host work +
 // launches), printed per sg_batch_forward call -- a development aid
 std::atomic<long long> g_prof_total_ns{0}, g_prof_sync_ns{0}, g_prof_scenes{0}, g_prof_sec[8];
-const char* const kProfSec[8] = {"setup+launch0", "regroup", "label tables", "descriptors", "layer launches", "final clustering", "export+eval", "other"};
+const char* const kProfSec[8] = {"setup+launch0", "grouping", "label tables", "descriptors", "layer launches", "final clustering", "export+eval", "other"};
 const bool g_host_profile = getenv("SG_HOST_PROFILE") != nullptr;
 
 }  // namespace
@@ -189,9 +190,7 @@ static hipError_t timed_event_sync(hipEvent_t ev) {
     return e;
 }
 
-#define PL_CHECK(call) do { int rc__ = (call); if (rc__ < 0) { sg_partition_destroy(part); return rc__; } } while (0)
-#define PL_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { sg_partition_destroy(part); \
-    return sg::fail(SG_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); } } while (0)
+#define PL_CHECK(call) do { int rc__ = (call); if (rc__ < 0) return rc__; } while (0)
 
 // Small transfers between the pipeline's pinned arena and the device go through a KERNEL on the scene's stream (sg::copy_by_kernel; pinned
 // memory is mapped into the device's address space): on the copy engines each of them cost a queue round trip of its own, and behind bulk
@@ -200,7 +199,7 @@ static hipError_t timed_event_sync(hipEvent_t ev) {
 static bool pl_sdma() { static const bool v = getenv("SG_ENGINE_COPY") && std::string(getenv("SG_ENGINE_COPY")) == "sdma"; return v; }
 #define PL_COPY(dst, src, bytes, kind, stream_)                                                                              \
     do {                                                                                                                     \
-        if (pl_sdma()) { PL_HIP(hipMemcpyAsync((dst), (src), (bytes), (kind), (stream_))); }                                 \
+        if (pl_sdma()) { SG_HIP(hipMemcpyAsync((dst), (src), (bytes), (kind), (stream_))); }                                 \
         else { PL_CHECK(sg::copy_by_kernel((void*)(dst), (const void*)(src), (size_t)(bytes), (stream_))); }                 \
     } while (0)
 
@@ -223,8 +222,6 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
         }
     } prof_scope;
     auto prof_last = std::chrono::steady_clock::now();
-    long long prof_sync_seen = g_host_profile ? 0 : 0;
-    (void)prof_sync_seen;
     auto lap = [&](int sec) {                                // host-profile: time since the previous lap goes to section `sec` (< 0: dropped)
         if (!g_host_profile) return;
         const auto now = std::chrono::steady_clock::now();
@@ -238,18 +235,14 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
     SG_REQUIRE(!tape || mode == SG_MODE_INS_INFER, "the training tape needs the full (ins_infer) forward");
     const float* W = pl->w.p;
     pl->n_ev = 0;
-    out->stalled = 0; out->used_fallback = 0;
-    for (int i = 0; i < 5; ++i) out->trace[i] = 0;
 
     // (the partition itself -- S member lists -- is built further down, behind the first launches: the GPU is idle until those are queued,
     // and one scene alone pays for every microsecond the host spends in front of them)
-    sg_partition* part = nullptr;
-    int max_ins = 1;
-    for (int s = 0; s < S; ++s) max_ins = std::max(max_ins, sc->h_seg_ins[s] + 2);
-    if (sg_eval_ws_bytes(max_ins) > pl->ws_eval.n)
-        return sg::fail(SG_EUNSUP, "weak instance ids up to %d exceed the pipeline's metric workspace (max_segments + 2)", max_ins - 2);
+    SceneGrouping g;
+    g.begin(sc, mode, pl->h_tables.p, out, dbg);
+    if (sg_eval_ws_bytes(g.max_ins) > pl->ws_eval.n)
+        return sg::fail(SG_EUNSUP, "weak instance ids up to %d exceed the pipeline's metric workspace (max_segments + 2)", g.max_ins - 2);
 
-    int32_t* tab = pl->h_tables.p;                       // [14,S]
     // The label vectors of a layer leave as soon as its tables exist: table rows H2D, k_export for those rows, vectors D2H -- all on the
     // pipeline's second stream, beside the next layer's kernels (one scene alone used to wait for 8.4 MB / 28 MB of labels to cross PCIe
     // behind its last kernel: 0.17 / 0.55 ms at 150k / 500k points).  The rows of h_tables / tables / labels of different layers are disjoint.
@@ -260,17 +253,11 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
     } side_guard{side};
     SG_HIP(hipEventRecord(pl->ev_side, st));               // the scene's arrays are ready for `st`: so they are for `side`
     SG_HIP(hipStreamWaitEvent(side, pl->ev_side, 0));
-    // tables_for() only fills the host rows (the partition changes with the next grouping pass); the second stream's calls -- ~20 API calls per
-    // scene -- are issued by flush_exports() right in front of the NEXT stream sync, i.e. while the layer just launched runs (issued where the
-    // tables are made they cost a scene 0.24 ms of host time with the GPU idle)
+    // a grouping step only fills the host rows (the partition changes with the next grouping pass); pend() queues the rows it wrote, and the
+    // second stream's calls -- ~20 API calls per scene -- are issued by flush_exports() right in front of the NEXT stream sync, i.e. while the
+    // layer just launched runs (issued where the tables are made they cost a scene 0.24 ms of host time with the GPU idle)
     int pend_row[5], pend_rows[5], npend = 0;
-    auto tables_for = [&](int first_row, bool with_seg) -> int {
-        int32_t* a = tab + (size_t)first_row * S;
-        const int rc = sg_partition_export_tables(part, with_seg ? a : nullptr, with_seg ? a + S : a, with_seg ? a + 2 * (size_t)S : a + S);
-        if (rc < 0) return rc;
-        pend_row[npend] = first_row; pend_rows[npend] = with_seg ? 3 : 2; ++npend;
-        return SG_OK;
-    };
+    auto pend = [&] { pend_row[npend] = g.wrote.first; pend_rows[npend] = g.wrote.count; ++npend; };
     auto flush_exports = [&](bool last) -> int {
         for (int i = 0; i + 1 < npend;) {                   // consecutive row ranges leave as one (layer_4.* + final.* at the end: five rows, three calls)
             if (pend_row[i] + pend_rows[i] == pend_row[i + 1]) {
@@ -282,7 +269,7 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
         for (int i = 0; i < npend; ++i) {
             const int rows = pend_rows[i];
             const size_t t0 = (size_t)pend_row[i] * S, l0 = (size_t)pend_row[i] * V;
-            if (hipMemcpyAsync(pl->tables.p + t0, tab + t0, (size_t)rows * S * 4, hipMemcpyHostToDevice, side) != hipSuccess)
+            if (hipMemcpyAsync(pl->tables.p + t0, g.tab + t0, (size_t)rows * S * 4, hipMemcpyHostToDevice, side) != hipSuccess)
                 return sg::fail(SG_EHIP, "label tables: H2D failed");
             const int rc2 = sg_export_labels(sc->d_unmap, V, sc->d_seg_of_point, N, pl->tables.p + t0, rows, S, pl->labels.p + l0, (void*)side);
             if (rc2 < 0) return rc2;
@@ -301,12 +288,10 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
     PL_CHECK(sg_contract_point_edges(sc->d_adj, E0, sc->d_seg_of_point, N, S, pl->adj1.p, cap1, pl->count.p, pl->ws_contract.p,
                                      pl->ws_contract.n, stv));
     PL_COPY(pl->h_count.p, pl->count.p, 4, hipMemcpyDeviceToHost, st);
-    PL_HIP(hipEventRecord(pl->ev_count, st));
+    SG_HIP(hipEventRecord(pl->ev_count, st));
     pl->mark(0);
-    int max_seg = 0;
-    for (int s = 0; s < S; ++s) max_seg = std::max(max_seg, sc->h_seg_size[s]);
     PL_CHECK(sg::fps_sample_hint(sc->d_data, N, 6, sc->d_seg_points, sc->d_seg_off, S, 64, 6, 1, pl->samples.p, nullptr, pl->ws_fps.p,
-                                 pl->ws_fps.n, stv, max_seg));
+                                 pl->ws_fps.n, stv, g.max_seg));
     if (mode == SG_MODE_INS_INFER) {
         // once per scene: segment boxes, Morton order inside every over-segment + boxes of its 32-point chunks (kNN
         // pruning) -- one launch unless a segment exceeds a block's LDS
@@ -314,7 +299,7 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
         co[0] = 0;
         for (int s = 0; s < S; ++s) co[s + 1] = co[s] + (sc->h_seg_size[s] + 31) / 32;
         PL_COPY(pl->seg_chunk_off.p, co, (size_t)(S + 1) * 4, hipMemcpyHostToDevice, st);
-        PL_CHECK(sg_segment_sort_boxes(sc->d_data, N, sc->d_seg_points, sc->d_seg_off, sc->d_seg_of_point, S, pl->seg_chunk_off.p, max_seg,
+        PL_CHECK(sg_segment_sort_boxes(sc->d_data, N, sc->d_seg_points, sc->d_seg_off, sc->d_seg_of_point, S, pl->seg_chunk_off.p, g.max_seg,
                                        pl->segbox.p, pl->sperm.p, pl->chunk_box.p, pl->seg_sums.p, pl->ws_sort.p, pl->ws_sort.n, stv));
         PL_COPY(pl->h_seg_sums.p, pl->seg_sums.p, (size_t)S * 3 * 8, hipMemcpyDeviceToHost, st);     // ready at the sync below
     }
@@ -322,71 +307,35 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
     PL_CHECK(sg_mlp1_forward(pl->samples.p, S, W + pl->o_m1w, W + pl->o_m1g, W + pl->o_m1b, pl->feat1.p, 128, pl->ws_mlp1.p,
                              pl->ws_mlp1.n, stv));
     pl->mark(2);
-    part = sg_partition_create(S, sc->h_seg_first, sc->h_seg_size, sc->h_seg_ins, sc->h_seg_sem);
-    if (!part) return SG_EINVAL;
+    PL_CHECK(g.create_partition());
     lap(0);
     // only the edge count is needed here, and it has been on the host since the first kernel finished: the sampling / sorting / MLP1 launches
     // above keep the GPU busy while the distance launch and its copies are queued behind them (one full stream sync less per scene)
-    PL_HIP(timed_event_sync(pl->ev_count));
+    SG_HIP(timed_event_sync(pl->ev_count));
     lap(-1);
     int E1 = pl->h_count.p[0];
-    if (E1 > cap1) { sg_partition_destroy(part); return sg::fail(SG_ENOMEM, "adjacency capacity exceeded (%d > %d)", E1, cap1); }
+    if (E1 > cap1) return sg::fail(SG_ENOMEM, "adjacency capacity exceeded (%d > %d)", E1, cap1);
     PL_CHECK(sg_edge_distance(pl->feat1.p, 128, 128, pl->adj1.p, E1, pl->dist.p, stv));
     PL_COPY(pl->h_adj.p, pl->adj1.p, (size_t)E1 * 8, hipMemcpyDeviceToHost, st);
     PL_COPY(pl->h_dist.p, pl->dist.p, (size_t)E1 * 4, hipMemcpyDeviceToHost, st);
     if (dbg) {
-        if (dbg->d_samples1) PL_HIP(hipMemcpyAsync(dbg->d_samples1, pl->samples.p, (size_t)S * 64 * 6 * 4, hipMemcpyDeviceToDevice, st));
-        if (dbg->d_feat1) PL_HIP(hipMemcpyAsync(dbg->d_feat1, pl->feat1.p, (size_t)S * 128 * 4, hipMemcpyDeviceToDevice, st));
+        if (dbg->d_samples1) SG_HIP(hipMemcpyAsync(dbg->d_samples1, pl->samples.p, (size_t)S * 64 * 6 * 4, hipMemcpyDeviceToDevice, st));
+        if (dbg->d_feat1) SG_HIP(hipMemcpyAsync(dbg->d_feat1, pl->feat1.p, (size_t)S * 128 * 4, hipMemcpyDeviceToDevice, st));
     }
     pl->mark(3);
 
-    LayerDesc Lcur, Lnew;
-    freeze_layer(part, S, Lcur);                          // layer 1: every segment its own cluster
-    out->trace[0] = Lcur.C;
-    PL_CHECK(tables_for(0, true));                        // layer_1.{seg,ins,sem}
+    PL_CHECK(g.layer1());                                 // (no device result needed: its rows leave in front of the sync)
+    pend();
     PL_CHECK(flush_exports(false));
     lap(2);
-    PL_HIP(timed_sync(st));
+    SG_HIP(timed_sync(st));
     lap(-1);
-
-    std::vector<int32_t> adj(pl->h_adj.p, pl->h_adj.p + 2 * (size_t)E1), adj_next;
-    std::vector<uint8_t> connected, keep;
-    int E = E1;
-    auto tap_adj = [&](int i, const std::vector<int32_t>& a, int rows) {
-        if (dbg && dbg->h_adj[i]) std::copy(a.begin(), a.begin() + 2 * (size_t)rows, dbg->h_adj[i]);
-        if (dbg) dbg->n_adj[i] = rows;
-    };
-    auto tap_dist = [&](int i, int rows) { if (dbg && dbg->h_dist[i]) std::copy(pl->h_dist.p, pl->h_dist.p + rows, dbg->h_dist[i]); };
-    tap_adj(0, adj, E);
-    tap_dist(0, E);
-
-    // group + re-index + contract; returns the new layer in Lnew and the contracted adjacency in adj
-    auto regroup = [&](float th) -> int {
-        connected.assign(std::max(E, 1), 0);
-        int rc = sg_partition_group_nearby(part, Lcur.root.data(), Lcur.C, pl->h_dist.p, adj.data(), E, th, connected.data());
-        if (rc == SG_ESTALL) { out->stalled = 1; rc = SG_OK; sg::err_buf()[0] = 0; }   // downgraded: no stale message stays behind
-        if (rc < 0) return rc;
-        keep.resize(connected.size());
-        for (size_t i = 0; i < connected.size(); ++i) keep[i] = !connected[i];
-        adj_next.resize(2 * (size_t)std::max(E, 1));
-        const int En = sg_partition_contract(part, Lcur.root.data(), adj.data(), E, keep.data(), adj_next.data());
-        if (En < 0) return En;
-        freeze_layer(part, S, Lnew);
-        adj.assign(adj_next.begin(), adj_next.begin() + 2 * (size_t)En);
-        E = En;
-        return SG_OK;
-    };
-
-    PL_CHECK(regroup(mode == SG_MODE_SEM_INFER ? 3.0f : 6.0f));
+    PL_CHECK(g.structural(pl->h_adj.p, pl->h_dist.p, E1));
+    pend();
     lap(1);
-    out->trace[1] = Lnew.C;
-    PL_CHECK(tables_for(3, true));                        // layer_2.*
-    lap(2);
-    tap_adj(1, adj, E);
 
-    int n_tables = 6;
-    int ins_row = 4, sem_row = 5;
-
+    const LayerDesc& Lcur = g.Lcur;
+    const LayerDesc& Lnew = g.Lnew;
     if (mode == SG_MODE_INS_INFER) {
         // ---------------- semantic grouping layers (model.py:786-865) ----------------------------------
         const float* feat_prev = pl->feat1.p;             // features of the PREVIOUS numbering (rows = Lcur clusters)
@@ -395,7 +344,7 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
         float* gcn_out = pl->featB.p;
         bool have_seed = false;
         for (int layer = 0; layer < 2; ++layer) {
-            const int C = Lnew.C, Dcat = feat_prev_dim + 64;
+            const int C = Lnew.C, E = g.E, Dcat = feat_prev_dim + 64;
             const int sb = 4 + 6 * layer;                 // stage index base
             pl->mark(-1);
             // ---- descriptor block ----
@@ -415,11 +364,6 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
             const bool seeded = knn_variant == 8 && layer == 1 && have_seed;
             const int waves_per_tile = pl->knn_variant == 1 || pl->knn_variant == 2 || pl->knn_variant == 4 ? pl->knn_variant : 0;
             if (knn_variant == 8) knn_variant = 1;
-            std::vector<int32_t> seg_prevcl(seeded ? S : 0);
-            for (int sg = 0; seeded && sg < S; ++sg) {
-                const int pc = Lcur.cl_of_seg[sg];
-                seg_prevcl[sg] = Lcur.cl_pt_off[pc + 1] - Lcur.cl_pt_off[pc] > 20 ? pc : -1;
-            }
             std::vector<int32_t> slot_chunk0(S + 1, 0), cl_chunk_off(C + 1, 0), tile_chunk0(T, 0);
             if (knn_variant == 0) {
                 for (int i = 0; i < S; ++i) slot_chunk0[i + 1] = slot_chunk0[i] + (sc->h_seg_size[Lnew.order[i]] + 31) / 32;
@@ -433,58 +377,30 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
                     }
                 }
             }
-            // parents: old clusters (Lcur numbering) absorbed by each new cluster, in old order (model.py:766-768)
-            std::vector<int32_t> goff(C + 1, 0), gidx(Lcur.C), cl_of_order(S);
-            for (int j = 0; j < Lcur.C; ++j) ++goff[Lnew.cl_of_seg[Lcur.root[j]] + 1];
-            for (int c = 0; c < C; ++c) goff[c + 1] += goff[c];
-            {
-                std::vector<int32_t> fill(goff.begin(), goff.end() - 1);
-                for (int j = 0; j < Lcur.C; ++j) gidx[fill[Lnew.cl_of_seg[Lcur.root[j]]]++] = j;
-            }
-            for (int i = 0; i < S; ++i) cl_of_order[i] = Lnew.cl_of_seg[Lnew.order[i]];
-            // cluster centroids (combine_centralized_pointcloud, model.py:429-436) from the per-segment coordinate sums:
-            // the sum is carried in double, so its grouping does not show in the fp32 result
-            std::vector<int32_t> cl_mean_bits(3 * (size_t)C);
-            for (int c = 0; c < C; ++c) {
-                double sx = 0.0, sy = 0.0, sz = 0.0;
-                for (int i = Lnew.cl_seg_off[c]; i < Lnew.cl_seg_off[c + 1]; ++i) {
-                    const double* q = pl->h_seg_sums.p + 3 * (size_t)Lnew.order[i];
-                    sx += q[0]; sy += q[1]; sz += q[2];
-                }
-                const double cnt = (double)(Lnew.cl_pt_off[c + 1] - Lnew.cl_pt_off[c]);
-                const float m[3] = {(float)(sx / cnt), (float)(sy / cnt), (float)(sz / cnt)};
-                std::memcpy(&cl_mean_bits[3 * (size_t)c], m, 12);
-            }
-            // symmetric CSR of the cluster graph
-            std::vector<int32_t> rowptr(C + 1, 0), col(2 * (size_t)E), eid(2 * (size_t)E);
-            for (int e = 0; e < E; ++e) { ++rowptr[adj[2 * e] + 1]; ++rowptr[adj[2 * e + 1] + 1]; }
-            for (int c = 0; c < C; ++c) rowptr[c + 1] += rowptr[c];
-            {
-                std::vector<int32_t> fill(rowptr.begin(), rowptr.end() - 1);
-                for (int e = 0; e < E; ++e) {
-                    const int a = adj[2 * e], b = adj[2 * e + 1];
-                    col[fill[a]] = b; eid[fill[a]++] = e;
-                    col[fill[b]] = a; eid[fill[b]++] = e;
-                }
-            }
+            // the layer's arrays at their DescOffsets in the pinned block
             DescOffsets o;
             size_t cur = 0;
-            auto put = [&](const std::vector<int32_t>& v, size_t count) {
-                const size_t at = cur;
-                std::copy(v.begin(), v.begin() + count, pl->h_desc.p + at);
-                cur += (count + 3) / 4 * 4;
-                return at;
-            };
-            o.order = put(Lnew.order, S); o.dst = put(Lnew.dst, S); o.cl = put(cl_of_order, S); o.cl_pt_off = put(Lnew.cl_pt_off, C + 1);
-            o.cl_seg_off = put(Lnew.cl_seg_off, C + 1);
-            o.tile_cl = put(tile_cl, T); o.tile_lo = put(tile_lo, T); o.tile_hi = put(tile_hi, T);
-            o.seg_prevcl = put(seg_prevcl, seg_prevcl.size());
-            o.cl_mean = put(cl_mean_bits, cl_mean_bits.size());
-            o.slot_chunk0 = put(slot_chunk0, S + 1); o.cl_chunk_off = put(cl_chunk_off, C + 1); o.tile_chunk0 = put(tile_chunk0, T);
-            o.goff = put(goff, C + 1); o.gidx = put(gidx, Lcur.C); o.adj = put(adj, 2 * (size_t)E);
-            o.rowptr = put(rowptr, C + 1); o.col = put(col, 2 * (size_t)E); o.eid = put(eid, 2 * (size_t)E);
+            auto carve = [&](size_t count) { const size_t at = cur; cur += (count + 3) / 4 * 4; return at; };
+            o.order = carve(S); o.dst = carve(S); o.cl = carve(S); o.cl_pt_off = carve(C + 1); o.cl_seg_off = carve(C + 1);
+            o.tile_cl = carve(T); o.tile_lo = carve(T); o.tile_hi = carve(T);
+            o.seg_prevcl = carve(seeded ? S : 0);
+            o.cl_mean = carve(3 * (size_t)C);
+            o.slot_chunk0 = carve(S + 1); o.cl_chunk_off = carve(C + 1); o.tile_chunk0 = carve(T);
+            o.goff = carve(C + 1); o.gidx = carve(Lcur.C); o.adj = carve(2 * (size_t)E);
+            o.rowptr = carve(C + 1); o.col = carve(2 * (size_t)E); o.eid = carve(2 * (size_t)E);
             o.total = cur;
-            if (o.total > pl->desc.n) { sg_partition_destroy(part); return sg::fail(SG_ENOMEM, "descriptor buffer too small"); }
+            if (o.total > pl->desc.n) return sg::fail(SG_ENOMEM, "descriptor buffer too small");
+            int32_t* h = pl->h_desc.p;
+            auto put = [&](size_t at, const std::vector<int32_t>& v, size_t count) { std::copy_n(v.data(), count, h + at); };
+            put(o.order, Lnew.order, S); put(o.dst, Lnew.dst, S); fill_cl_of_order(Lnew, h + o.cl);
+            put(o.cl_pt_off, Lnew.cl_pt_off, C + 1); put(o.cl_seg_off, Lnew.cl_seg_off, C + 1);
+            put(o.tile_cl, tile_cl, T); put(o.tile_lo, tile_lo, T); put(o.tile_hi, tile_hi, T);
+            if (seeded) fill_seg_prevcl(Lcur, h + o.seg_prevcl);
+            fill_cl_mean(Lnew, pl->h_seg_sums.p, reinterpret_cast<float*>(h + o.cl_mean));
+            put(o.slot_chunk0, slot_chunk0, S + 1); put(o.cl_chunk_off, cl_chunk_off, C + 1); put(o.tile_chunk0, tile_chunk0, T);
+            fill_parents(Lcur, Lnew, h + o.goff, h + o.gidx);
+            put(o.adj, g.adj, 2 * (size_t)E);
+            fill_csr(g.adj.data(), E, C, h + o.rowptr, h + o.col, h + o.eid);
             lap(3);
             PL_COPY(pl->desc.p, pl->h_desc.p, o.total * 4, hipMemcpyHostToDevice, st);
             const int32_t* dd = pl->desc.p;
@@ -497,9 +413,7 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
             PL_CHECK(sg::group_max_rows_fill(feat_prev, feat_prev_stride, feat_prev_dim, dd + o.goff, dd + o.gidx, C, cat, Dcat, 64, stv));
             pl->mark(sb + 0);
             pl->mark(sb + 1);                              // (centring is part of the layout kernel now)
-            // point 0 is the first member of segment 0; its member-order position is that segment's dst
-            int pos0 = 0;
-            for (int i = 0; i < S; ++i) if (Lnew.order[i] == 0) { pos0 = Lnew.dst[i]; break; }
+            const int pos0 = pos_of_point0(Lnew);
             pl->mark_kernel_start();
             if (knn_variant == 0) {
                 PL_CHECK(sg_knn_chunk_table(dd + o.order, dd + o.dst, sc->d_seg_off, pl->seg_chunk_off.p, pl->chunk_box.p, S,
@@ -544,109 +458,67 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
                 PL_COPY(pl->h_feat.p, gcn_out, (size_t)C * Dcat * 4, hipMemcpyDeviceToHost, st);
             if (dbg) {
                 if (dbg->d_pointfeat[layer]) PL_CHECK(sg::edgeconv_apply(pl->pf.p, N, affine[0], affine[1], dbg->d_pointfeat[layer], stv));
-                if (dbg->d_knn[layer]) PL_HIP(hipMemcpyAsync(dbg->d_knn[layer], pl->knn.p, (size_t)N * 20 * 4, hipMemcpyDeviceToDevice, st));
-                if (dbg->d_members[layer]) PL_HIP(hipMemcpyAsync(dbg->d_members[layer], pl->members.p, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-                if (dbg->d_cat[layer]) PL_HIP(hipMemcpyAsync(dbg->d_cat[layer], cat, (size_t)C * Dcat * 4, hipMemcpyDeviceToDevice, st));
+                if (dbg->d_knn[layer]) SG_HIP(hipMemcpyAsync(dbg->d_knn[layer], pl->knn.p, (size_t)N * 20 * 4, hipMemcpyDeviceToDevice, st));
+                if (dbg->d_members[layer]) SG_HIP(hipMemcpyAsync(dbg->d_members[layer], pl->members.p, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+                if (dbg->d_cat[layer]) SG_HIP(hipMemcpyAsync(dbg->d_cat[layer], cat, (size_t)C * Dcat * 4, hipMemcpyDeviceToDevice, st));
             }
             if (tape) {
                 sg_tape::Layer& TL = tape->layer[layer];
                 TL.o = o; TL.C = C; TL.Cprev = Lcur.C; TL.Dcat = Dcat; TL.Dprev = feat_prev_dim; TL.E = E;
                 if ((size_t)N * 12 > TL.x9m.n || (size_t)N * 20 > TL.knn.n || (size_t)N * 64 > TL.pf.n || o.total > TL.desc.n || (size_t)C * Dcat > TL.cat.n ||
-                    (size_t)C * Dcat > TL.gcn.n) {
-                    sg_partition_destroy(part);
+                    (size_t)C * Dcat > TL.gcn.n)
                     return sg::fail(SG_ENOMEM, "training tape smaller than the scene");
-                }
-                PL_HIP(hipMemcpyAsync(TL.x9m.p, pl->x9m.p, (size_t)N * 12 * 4, hipMemcpyDeviceToDevice, st));
-                PL_HIP(hipMemcpyAsync(TL.knn.p, pl->knn.p, (size_t)N * 20 * 4, hipMemcpyDeviceToDevice, st));
-                PL_HIP(hipMemcpyAsync(TL.pf.p, pl->pf.p, (size_t)N * 64 * 4, hipMemcpyDeviceToDevice, st));
-                PL_HIP(hipMemcpyAsync(TL.desc.p, pl->desc.p, o.total * 4, hipMemcpyDeviceToDevice, st));
-                PL_HIP(hipMemcpyAsync(TL.cat.p, cat, (size_t)C * Dcat * 4, hipMemcpyDeviceToDevice, st));
-                PL_HIP(hipMemcpyAsync(TL.gcn.p, gcn_out, (size_t)C * Dcat * 4, hipMemcpyDeviceToDevice, st));
-                PL_HIP(hipMemcpyAsync(TL.bn_last.p, affine[2], 128 * 4, hipMemcpyDeviceToDevice, st));
+                SG_HIP(hipMemcpyAsync(TL.x9m.p, pl->x9m.p, (size_t)N * 12 * 4, hipMemcpyDeviceToDevice, st));
+                SG_HIP(hipMemcpyAsync(TL.knn.p, pl->knn.p, (size_t)N * 20 * 4, hipMemcpyDeviceToDevice, st));
+                SG_HIP(hipMemcpyAsync(TL.pf.p, pl->pf.p, (size_t)N * 64 * 4, hipMemcpyDeviceToDevice, st));
+                SG_HIP(hipMemcpyAsync(TL.desc.p, pl->desc.p, o.total * 4, hipMemcpyDeviceToDevice, st));
+                SG_HIP(hipMemcpyAsync(TL.cat.p, cat, (size_t)C * Dcat * 4, hipMemcpyDeviceToDevice, st));
+                SG_HIP(hipMemcpyAsync(TL.gcn.p, gcn_out, (size_t)C * Dcat * 4, hipMemcpyDeviceToDevice, st));
+                SG_HIP(hipMemcpyAsync(TL.bn_last.p, affine[2], 128 * 4, hipMemcpyDeviceToDevice, st));
             }
             pl->mark(sb + 5);
             PL_CHECK(flush_exports(false));                  // the finished layers' label rows, beside this layer's kernels
             lap(4);
-            PL_HIP(timed_sync(st));
+            SG_HIP(timed_sync(st));
             lap(-1);
             if (dbg && dbg->h_gcn[layer]) std::copy(pl->h_feat.p, pl->h_feat.p + (size_t)C * Dcat, dbg->h_gcn[layer]);
-            tap_dist(1 + layer, E);
-
-            // ---- grouping on the GCN features (model.py:802-815 / 843-856) ----
-            Lcur = Lnew;
-            PL_CHECK(regroup(2.0f));
+            PL_CHECK(g.semantic(layer, pl->h_dist.p));
+            pend();
             lap(1);
-            out->trace[2 + layer] = Lnew.C;
-            PL_CHECK(tables_for(6 + 3 * layer, true));    // layer_3.* / layer_4.*
-            lap(2);
-            tap_adj(2 + layer, adj, E);
             // next layer: previous features = this GCN output (featB); its concat goes to featA again and its
             // GCN output back into featB -- safe, the stream runs group_max_rows(featB -> featA) before gcn writes featB
             feat_prev = gcn_out; feat_prev_stride = Dcat; feat_prev_dim = Dcat;
         }
 
         // ---------------- final clustering (model.py:868-888) ------------------------------------------
-        // Feat_4 = max over absorbed rows of the gcn_3 output (host copy), adj_4 = current adj
-        const int D4 = 256;
-        std::vector<float> feat4((size_t)Lnew.C * D4, -INFINITY);
-        for (int j = 0; j < Lcur.C; ++j) {
-            float* dstp = &feat4[(size_t)Lnew.cl_of_seg[Lcur.root[j]] * D4];
-            const float* src = pl->h_feat.p + (size_t)j * D4;
-            for (int k = 0; k < D4; ++k) dstp[k] = std::max(dstp[k], src[k]);
-        }
-        std::vector<int32_t> root5(Lnew.root.begin(), Lnew.root.begin() + Lnew.C);
-        root5.resize(S);
-        int C5 = Lnew.C, E5 = E;
-        adj.resize(2 * (size_t)std::max(E, 1));
-        const int need_fallback = sg_partition_group_unlabeled(part, root5.data(), &C5, feat4.data(), D4, adj.data(), &E5);
-        if (need_fallback < 0) { sg_partition_destroy(part); return need_fallback; }
-        if (need_fallback) {
-            // FPS-1024 over the current clusters (model.py:479), XYZ only, no transform
-            LayerDesc L5;
-            freeze_layer(part, S, L5);
-            std::vector<int32_t> cl_of_order(S);
-            for (int i = 0; i < S; ++i) cl_of_order[i] = L5.cl_of_seg[L5.order[i]];
-            size_t cur = 0;
-            auto put = [&](const std::vector<int32_t>& v, size_t count) {
-                const size_t at = cur;
-                std::copy(v.begin(), v.begin() + count, pl->h_desc.p + at);
-                cur += (count + 3) / 4 * 4;
-                return at;
-            };
-            const size_t o_order = put(L5.order, S), o_dst = put(L5.dst, S), o_cl = put(cl_of_order, S), o_off = put(L5.cl_pt_off, L5.C + 1);
+        int rc = g.final_clustering(pl->h_feat.p);
+        if (rc == 1) {                                     // the FPS-1024 fallback
             pl->mark(-1);
-            PL_COPY(pl->desc.p, pl->h_desc.p, cur * 4, hipMemcpyHostToDevice, st);
-            const int32_t* dd = pl->desc.p;
-            PL_CHECK(sg_gather_members(sc->d_seg_points, sc->d_seg_off, S, dd + o_order, dd + o_dst, dd + o_cl, pl->members.p, nullptr, nullptr, nullptr, stv));
-            int max_cl = 0;
-            for (int c = 0; c < L5.C; ++c) max_cl = std::max(max_cl, L5.cl_pt_off[c + 1] - L5.cl_pt_off[c]);
-            PL_CHECK(pl->need_fallback_buffers());
-            PL_CHECK(sg::fps_sample_hint(sc->d_data, N, 6, pl->members.p, dd + o_off, L5.C, 1024, 3, 0, pl->samples_big.p, nullptr,
-                                         pl->ws_fps.p, pl->ws_fps.n, stv, max_cl));
-            PL_HIP(hipMemcpyAsync(pl->h_samples.p, pl->samples_big.p, (size_t)L5.C * 1024 * 3 * 4, hipMemcpyDeviceToHost, st));
+            PL_CHECK(fallback_fps1024(pl, sc, g.L5, st));
             pl->mark(16);
             lap(5);
-            PL_HIP(timed_sync(st));
+            SG_HIP(timed_sync(st));
             lap(-1);
-            PL_CHECK(sg_partition_unlabeled_fallback(part, L5.root.data(), L5.C, pl->h_samples.p, 1024));
-            out->used_fallback = 1;
+            rc = g.final_fallback(pl->h_samples.p);
         }
-        out->trace[4] = sg_partition_num_clusters(part);
+        PL_CHECK(rc);
+        pend();                                            // final.{ins,sem}
         if (tape || (dbg && dbg->h_feat5 && dbg->h_ins5 && dbg->h_sem5)) {
             // Feat_5 + the weak labels of the final clusters: what the train-mode tail consumes (model.py:900-914).  After the
             // FPS-1024 fallback the reference max-aggregates once more into the final numbering (model.py:495-507).
+            const int D4 = 256;
             LayerDesc L6;
-            const int C6 = freeze_layer(part, S, L6);
+            const int C6 = freeze_layer(g.partition(), S, L6);
             std::vector<float> f6((size_t)C6 * D4, -INFINITY);
-            for (int j = 0; j < C5; ++j) {
-                float* dstp = &f6[(size_t)L6.cl_of_seg[root5[j]] * D4];
-                const float* src = &feat4[(size_t)j * D4];
+            for (int j = 0; j < g.C5; ++j) {
+                float* dstp = &f6[(size_t)L6.cl_of_seg[g.root5[j]] * D4];
+                const float* src = &g.feat4[(size_t)j * D4];
                 for (int k = 0; k < D4; ++k) dstp[k] = std::max(dstp[k], src[k]);
             }
             std::vector<int32_t> ins6(C6), sem6(C6);
             for (int c = 0; c < C6; ++c) {
                 double np_ = 0.0;
-                PL_CHECK(sg_partition_label(part, L6.root[c], &ins6[c], &sem6[c], &np_));
+                PL_CHECK(sg_partition_label(g.partition(), L6.root[c], &ins6[c], &sem6[c], &np_));
             }
             if (dbg->h_feat5 && dbg->h_ins5 && dbg->h_sem5) {
                 std::copy(f6.begin(), f6.end(), dbg->h_feat5);
@@ -657,36 +529,29 @@ int sg_pipeline_forward(sg_pipeline* pl, const sg_scene* sc, int mode, sg_result
             if (tape) {
                 // rows of the last GCN output (Lcur numbering) -> final cluster: the composition of the max-aggregations above
                 tape->C6 = C6; tape->N = N; tape->S = S;
-                tape->fin_goff.assign(C6 + 1, 0);
+                tape->fin_goff.resize(C6 + 1);
                 tape->fin_gidx.resize(Lcur.C);
-                for (int j = 0; j < Lcur.C; ++j) ++tape->fin_goff[L6.cl_of_seg[Lcur.root[j]] + 1];
-                for (int c = 0; c < C6; ++c) tape->fin_goff[c + 1] += tape->fin_goff[c];
-                std::vector<int32_t> fill(tape->fin_goff.begin(), tape->fin_goff.end() - 1);
-                for (int j = 0; j < Lcur.C; ++j) tape->fin_gidx[fill[L6.cl_of_seg[Lcur.root[j]]]++] = j;
+                fill_parents(Lcur, L6, tape->fin_goff.data(), tape->fin_gidx.data());
                 tape->feat5.swap(f6);
                 tape->ins5.swap(ins6); tape->sem5.swap(sem6);
                 tape->filled = true;
             }
         }
-        PL_CHECK(tables_for(12, false));                  // final.{ins,sem}
-        n_tables = 14; ins_row = 12; sem_row = 13;
     }
 
     // ---------------- export + evaluate (model.py:525-655) -------------------------------------------
     pl->mark(-1);
-    if (out->h_tables) std::memcpy(out->h_tables, tab, (size_t)n_tables * S * 4);     // optional: the tables the vectors are looked up in (.sgl)
+    if (out->h_tables) std::memcpy(out->h_tables, g.tab, (size_t)g.n_tables() * S * 4);     // optional: the tables the vectors are looked up in (.sgl)
     PL_CHECK(flush_exports(true));                         // whatever is left (at least the final rows)
-    PL_HIP(hipStreamWaitEvent(st, pl->ev_side, 0));        // the metric kernels read the LAST exported rows on the device
+    SG_HIP(hipStreamWaitEvent(st, pl->ev_side, 0));        // the metric kernels read the LAST exported rows on the device
     pl->mark(17);
-    PL_CHECK(sg::evaluate_landing(sc->d_gt, pl->labels.p + (size_t)sem_row * V, pl->labels.p + (size_t)ins_row * V, V, max_ins, out->iou_sem,
-                                  out->iou_ins, out->acc, pl->ws_eval.p, pl->ws_eval.n, stv, reinterpret_cast<uint32_t*>(pl->h_eval.p)));
+    PL_CHECK(sg::evaluate_landing(sc->d_gt, pl->labels.p + (size_t)g.sem_row() * V, pl->labels.p + (size_t)g.ins_row() * V, V, g.max_ins,
+                                  out->iou_sem, out->iou_ins, out->acc, pl->ws_eval.p, pl->ws_eval.n, stv, reinterpret_cast<uint32_t*>(pl->h_eval.p)));
     pl->mark(18);
     lap(6);
-    PL_HIP(timed_sync(st));
-    PL_HIP(timed_sync(side));                             // the last rows' D2H
+    SG_HIP(timed_sync(st));
+    SG_HIP(timed_sync(side));                             // the last rows' D2H
     lap(-1);
-    sg_partition_destroy(part);
-    part = nullptr;
 
     for (float& m : pl->stage_ms) m = 0.f;
     for (int i = 1; i < pl->n_ev; ++i) {

@@ -1,5 +1,5 @@
 // Private layout of sg_pipeline (shared by pipeline.cpp, the single-scene path, and engine.cpp, which drives several
-// pipelines' buffers with batched launches).  Not part of the C ABI.
+// pipelines' buffers with batched launches; the host grouping both run between launches is scene_host.h).  Not part of the C ABI.
 #pragma once
 #include "sg_common.h"
 
@@ -120,17 +120,6 @@ struct sg_pipeline {
 };
 
 namespace sgp {
-
-struct LayerDesc {               // host view of one frozen numbering + what the device needs for it
-    int C = 0, T = 0;
-    std::vector<int32_t> root, cl_of_seg, order, cl_seg_off, cl_pt_off, dst;
-};
-
-inline int freeze_layer(const sg_partition* part, int S, LayerDesc& L) {
-    L.root.resize(S); L.cl_of_seg.resize(S); L.order.resize(S); L.cl_seg_off.resize(S + 1); L.cl_pt_off.resize(S + 1); L.dst.resize(S);
-    L.C = sg_partition_layer(part, L.root.data(), L.cl_of_seg.data(), L.order.data(), L.cl_seg_off.data(), L.cl_pt_off.data(), L.dst.data());
-    return L.C;
-}
 
 // Device descriptor block of one layer, carved from ONE pinned buffer and shipped in ONE H2D copy.
 struct DescOffsets {
