@@ -584,6 +584,12 @@ int  sg_expand_labels(const int32_t* h_tables, int nvec, int S, const int32_t* h
  * seg_of_vertex are copied (tag and flush semantics as sg_writer_submit_scene_tables). */
 int  sg_writer_submit_scene_sgl(sg_writer* w, const char* out_dir, const int32_t* h_tables, int S, const int32_t* h_seg_of_vertex, int V,
                                 int nvec, long long tag);
+/* One coloured mesh (label visualisation, below): <path> = head | vertex block | tail, the three pieces BY REFERENCE with the tag / flush
+ * semantics of sg_writer_submit_scene (untouched until sg_writer_wait_tag(w, tag) for a tag >= 0, or sg_writer_flush, returned).  The
+ * file is written under a temporary name in the same directory and renamed; its directory (the reference's visualize/) is created if
+ * it is missing. */
+int  sg_writer_submit_ply(sg_writer* w, const char* path, const void* h_head, long long head_bytes, const void* h_vertices,
+                          long long vertex_bytes, const void* h_tail, long long tail_bytes, long long tag);
 int  sg_writer_wait_tag(sg_writer* w, long long tag);
 int  sg_writer_flush(sg_writer* w);
 void sg_writer_destroy(sg_writer* w);
@@ -627,6 +633,69 @@ size_t sg_eval_tables_ws_bytes(int B, int nlayers, const long long* h_desc);
 int sg_eval_tables(int B, const long long* h_desc, const int32_t* d_tables, int nvec, const void* d_seg_of_vertex, int sov_width,
                    const int32_t* d_gt, int nlayers, const int* h_layer_rows, float* h_iou_sem, float* h_iou_ins, float* h_acc,
                    void* d_ws, size_t ws_bytes, void* stream);
+
+/* =============================================================================================
+ * Label visualisation (reference seggroup/dataset/scannet/util.py:431-527: visualize_labels, visualize_grouping_process; csrc/
+ * kernels_visualize.hip, csrc/visualize.cpp).  A vertex takes one of 41 palette colours (index 0 white, 1..40 ScanNet's class colours)
+ * chosen by its label; the coloured mesh is the source PLY with the red / green / blue byte of every vertex record replaced.  Colours travel
+ * as one-byte palette INDICES until the record kernel writes them.
+ *   semantic  -1, 0 -> white; l -> colour l (1..40; anything else is SG_EINVAL, the reference raises IndexError)
+ *   instance  -1, 0 -> white; white where the semantic label is 1 or 2 (if one is given); l -> colour (l - 1) mod 40 + 1
+ *   segment   -1 -> white; l -> colour rank mod 40 + 1, rank = position of l among the ascending distinct values that OCCUR among the
+ *             vertices (an occurring -1 counts as rank 0); with shuffled positions h_perm: colour h_perm[rank] mod 40 + 1
+ *   grouping  (vector form only; second = the segment labels) ins != -1 -> colour (rank - 1) mod 40 + 1, otherwise (seg * mult) mod 40 + 1
+ * Two calls per form: *_unique sorts the occurring values (radix sort + adjacent-unique, integer work only), keeps them in the workspace
+ * and returns their number, the length over which the caller draws the reference's shuffle; *_apply forms the colours.  Both SYNCHRONISE
+ * the stream; the workspace must stay untouched between them.
+ * ============================================================================================= */
+#define SG_NUM_COLOURS 40
+#define SG_COLOUR_MAX_ROWS 16   /* rows of one table-form call / of one record launch */
+#define SG_COLOUR_SEMANTIC 0
+#define SG_COLOUR_INSTANCE 1
+#define SG_COLOUR_SEGMENT 2
+#define SG_COLOUR_GROUPING 3
+
+/* Table form: d_tables [nvec,S] + d_seg_of_vertex [V] (sov_width 2: uint16 with 0xFFFF = -1, or 4: int32), h_types [nvec] = SG_COLOUR_*.
+ * _unique: h_counts [nvec] = distinct occurring values of every segment row (0 for the others).  _apply: d_cidx [nvec, S+1] palette
+ * indices, slot S = a vertex without a segment; h_sem_rows [nvec] (may be NULL) = per instance row the semantic row that whitens it, or -1;
+ * h_perm / h_perm_off [nvec] (may be NULL): row r's shuffled positions start at h_perm[h_perm_off[r]] (h_counts[r] of them), -1 = none. */
+size_t sg_colour_tables_ws_bytes(int S);
+int sg_colour_tables_unique(const int32_t* d_tables, int nvec, int S, const void* d_seg_of_vertex, int sov_width, int V, const int* h_types,
+                            int* h_counts, void* d_ws, size_t ws_bytes, void* stream);
+int sg_colour_tables_apply(const int32_t* d_tables, int nvec, int S, const int* h_types, const int* h_sem_rows, const int* h_counts,
+                           const int32_t* h_perm, const long long* h_perm_off, uint8_t* d_cidx, void* d_ws, size_t ws_bytes, void* stream);
+
+/* Vector form: d_labels [V] int32 of one type.  d_second [V] (instance: the semantic labels, may be NULL; grouping: the segment labels). */
+size_t sg_colour_vector_ws_bytes(int V);
+int sg_colour_vector_unique(const int32_t* d_labels, int V, int type, int* h_count, void* d_ws, size_t ws_bytes, void* stream);
+int sg_colour_vector_apply(const int32_t* d_labels, int V, int type, const int32_t* d_second, int count, const int32_t* h_perm, int mult,
+                           uint8_t* d_cidx, void* d_ws, size_t ws_bytes, void* stream);
+
+/* The per-vertex hot path: for every requested row r a complete vertex block d_out[r] = [V, stride] bytes, equal to d_src with the bytes at
+ * off_r / off_g / off_b of every record replaced by the row's colour of that vertex -- ONE launch for all rows (the source record and
+ * seg_of_vertex[v] are read once).  Table form: d_cidx [*, ld] with ld >= S + 1, vertex v reads d_cidx[h_rows[r] * ld + slot(v)].  Vector
+ * form (d_seg_of_vertex NULL): ld >= V, vertex v reads d_cidx[h_rows[r] * ld + v].  A 16-byte record with the colour in its last word
+ * (ScanNet's float x, y, z; uchar r, g, b, a) takes a path of 16-byte loads and stores when d_src / d_out are 16-byte aligned.
+ * _batch: B scenes in one launch (scene = grid.y); d_desc DEVICE [B,7] int64 = {source offset (bytes), V, seg_of_vertex offset (entries), S,
+ * d_cidx offset (bytes), ld, output offset (bytes)}; scene b's row r starts at d_out + out_off + r * V * stride.  For the 16-byte path the
+ * source and output offsets must be multiples of 16.  No synchronisation. */
+int sg_ply_vertex_records_device(const void* d_src, int V, int stride, int off_r, int off_g, int off_b, const void* d_seg_of_vertex, int sov_width,
+                                 int S, const uint8_t* d_cidx, long long ld, int nrows, const int* h_rows, void* d_out, void* stream);
+int sg_ply_vertex_records_device_batch(int B, const long long* d_desc, int max_V, int max_S, const void* d_src, int stride, int off_r, int off_g,
+                                       int off_b, const void* d_seg_of_vertex, int sov_width, const uint8_t* d_cidx, int nrows, const int* h_rows,
+                                       void* d_out, void* stream);
+
+/* Plan of a binary_little_endian PLY file (untrusted: every size in 64-bit arithmetic against the file's length).  h_plan [SG_PLY_PLAN_WORDS]
+ * = {offset of the vertex block, V, bytes per vertex, offset of red, green, blue inside a vertex, offset of what follows the vertex block,
+ * its length, the file's length, length of the header text}.  SG_EINVAL for ASCII / big-endian files, a truncated header, a vertex
+ * element with a list property, missing or non-uchar colour properties, more than SG_MAX_POINTS vertices, a vertex block beyond the file. */
+#define SG_PLY_PLAN_WORDS 10
+int sg_ply_plan(const char* path, long long* h_plan);
+
+/* visualize_labels' adj_path step (util.py:445-454) over a CSR of the symmetric adjacency: every vertex that carries a label (!= -1) when
+ * the call starts hands, in ascending vertex order, the value it holds at its turn to all of its neighbours -- order-dependent, exactly
+ * the reference's result, in O(V + E) instead of a dense [V,V] matrix.  In place. */
+int sg_dilate_labels(int32_t* h_labels, int V, const long long* h_indptr, const int32_t* h_indices);
 
 /* =============================================================================================
  * Raw scan -> hot-path inputs (reference seggroup/dataset/scannet/util.py).  The compute parts

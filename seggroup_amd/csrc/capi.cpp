@@ -1,11 +1,13 @@
 // Error plumbing, version / device probe, and the label-file writers (a16 file side,
 // reference seggroup/model.py:536-547) of libseggroup_hip.so.
+#include <atomic>
 #include <cerrno>
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
 #include <map>
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <sys/uio.h>
 #include <unistd.h>
 #include <condition_variable>
@@ -267,11 +269,44 @@ int write_vector_files(int dfd, const char* name, const int32_t* vec, int V, int
 }
 }  // namespace
 
+namespace {
+std::atomic<unsigned long long> g_ply_tmp_counter{0};
+
+// one coloured mesh: <path> = head | vertex block | tail, written under a temporary name in the same directory and renamed (a crashed run
+// never leaves a truncated .ply under the final name); the file's directory is created if it is missing (the reference's visualize/)
+int write_ply_file(const std::string& path, const void* const seg[3], const size_t len[3]) {
+    const size_t slash = path.rfind('/');
+    if (slash != std::string::npos && slash > 0) {
+        const std::string dir = path.substr(0, slash);
+        if (mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) return sg::fail(SG_EINVAL, "ply writer: cannot create %s: %s", dir.c_str(), strerror(errno));
+    }
+    const std::string tmp = path + ".tmp." + std::to_string((long long)getpid()) + "." + std::to_string(g_ply_tmp_counter++);
+    const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_EXCL | O_CLOEXEC, 0666);
+    if (fd < 0) return sg::fail(SG_EINVAL, "ply writer: cannot create %s: %s", tmp.c_str(), strerror(errno));
+    struct iovec iov[3];
+    int cnt = 0;
+    for (int i = 0; i < 3; ++i)
+        if (len[i]) { iov[cnt].iov_base = const_cast<void*>(seg[i]); iov[cnt].iov_len = len[i]; ++cnt; }
+    const int rc = cnt ? write_all(fd, iov, cnt) : 0;
+    if (close(fd) != 0 || rc != 0) {
+        unlink(tmp.c_str());
+        return sg::fail(SG_EINVAL, "ply writer: short write to %s", tmp.c_str());
+    }
+    if (rename(tmp.c_str(), path.c_str()) != 0) {
+        const int e = errno;
+        unlink(tmp.c_str());
+        return sg::fail(SG_EINVAL, "ply writer: cannot rename to %s: %s", path.c_str(), strerror(e));
+    }
+    return SG_OK;
+}
+}  // namespace
+
 struct sg_writer {
     // a scene (dir + nvec vectors of V values at `base`, stride V; not owned) or one owned vector (`own`, full path without extension in dir)
     // ... or a scene as tables: `own` = [nvec * S] tables followed by [V] seg_of_vertex, S > 0
     // ... or the same written as <dir>/pseudo_labels.sgl (sgl)
-    struct Job { std::string dir; const int32_t* base = nullptr; int V = 0, nvec = 0, formats = 0, S = 0; long long tag = 0; std::vector<int32_t> own; bool sgl = false; };
+    struct Job { std::string dir; const int32_t* base = nullptr; int V = 0, nvec = 0, formats = 0, S = 0; long long tag = 0; std::vector<int32_t> own; bool sgl = false;
+                 bool ply = false; const void* seg[3] = {nullptr, nullptr, nullptr}; size_t len[3] = {0, 0, 0}; };   // ... or one .ply file (dir = its path), three pieces by reference
     std::mutex mu;
     std::condition_variable cv_job, cv_idle;
     std::deque<Job> q;
@@ -298,7 +333,9 @@ struct sg_writer {
             }
             cv_idle.notify_all();
             int rc = 0;
-            if (j.sgl) {
+            if (j.ply) {
+                rc = write_ply_file(j.dir, j.seg, j.len);
+            } else if (j.sgl) {
                 const int32_t* tab = j.own.data();
                 rc = sg_write_sgl((j.dir + "/pseudo_labels.sgl").c_str(), tab, j.nvec, j.S, tab + (size_t)j.nvec * j.S, j.V);
             } else if (j.S > 0) {
@@ -394,6 +431,18 @@ int sg_writer_submit_scene_sgl(sg_writer* w, const char* out_dir, const int32_t*
     j.own.resize((size_t)nvec * S + (size_t)V);
     std::memcpy(j.own.data(), h_tables, (size_t)nvec * S * 4);
     if (V > 0) std::memcpy(j.own.data() + (size_t)nvec * S, h_seg_of_vertex, (size_t)V * 4);
+    return w->push(std::move(j));
+}
+
+int sg_writer_submit_ply(sg_writer* w, const char* path, const void* h_head, long long head_bytes, const void* h_vertices, long long vertex_bytes,
+                         const void* h_tail, long long tail_bytes, long long tag) {
+    if (!w || !path || !*path || head_bytes < 0 || vertex_bytes < 0 || tail_bytes < 0 || (head_bytes > 0 && !h_head) || (vertex_bytes > 0 && !h_vertices) ||
+        (tail_bytes > 0 && !h_tail))
+        return sg::fail(SG_EINVAL, "sg_writer_submit_ply: bad arguments");
+    sg_writer::Job j;
+    j.dir = path; j.ply = true; j.tag = tag;
+    j.seg[0] = h_head; j.seg[1] = h_vertices; j.seg[2] = h_tail;
+    j.len[0] = (size_t)head_bytes; j.len[1] = (size_t)vertex_bytes; j.len[2] = (size_t)tail_bytes;
     return w->push(std::move(j));
 }
 

@@ -168,6 +168,9 @@ __global__ __launch_bounds__(kThreads) void k_head_flags(const K* __restrict__ k
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i < n) flag[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1 : 0;
 }
+// (templates although nothing varies: the header is included by more than one kernel file, and a plain __global__ function would be
+// defined once per file)
+template <int kUnused = 0>
 __global__ __launch_bounds__(kThreads) void k_scan_tiles(int* __restrict__ a, int n, int* __restrict__ tile_sum) {
     __shared__ int part[kThreads];
     const size_t base = (size_t)blockIdx.x * kTile + (size_t)threadIdx.x * kItems;
@@ -187,6 +190,7 @@ __global__ __launch_bounds__(kThreads) void k_scan_tiles(int* __restrict__ a, in
     for (int i = 0; i < kItems; ++i) { if (base + i < (size_t)n) a[base + i] = run; run += v[i]; }
     if (threadIdx.x == kThreads - 1) tile_sum[blockIdx.x] = part[threadIdx.x];
 }
+template <int kUnused = 0>
 __global__ __launch_bounds__(1024) void k_scan_tile_sums(int* __restrict__ tile_sum, int ntiles, int* __restrict__ total) {
     // one slot past the tiles receives the grand total
     block_scan_inplace(tile_sum, ntiles + 1);
@@ -245,8 +249,8 @@ inline void unique_sorted(const K* keys, int n, K* out, int* head_index, int* d_
     int* flag = scratch;
     int* tsum = scratch + n;
     k_head_flags<K><<<(n + kThreads - 1) / kThreads, kThreads, 0, st>>>(keys, n, flag);
-    k_scan_tiles<<<nt, kThreads, 0, st>>>(flag, n, tsum);
-    k_scan_tile_sums<<<1, 1024, 0, st>>>(tsum, nt, d_count);
+    k_scan_tiles<><<<nt, kThreads, 0, st>>>(flag, n, tsum);
+    k_scan_tile_sums<><<<1, 1024, 0, st>>>(tsum, nt, d_count);
     k_compact_heads<K><<<(n + kThreads - 1) / kThreads, kThreads, 0, st>>>(keys, flag, tsum, n, out, head_index);
 }
 

@@ -19,6 +19,7 @@ HOST_LIB_OVERRIDE = os.environ.get("SEGGROUP_HIP_HOST_LIB")
 
 SG_OK, SG_EINVAL, SG_EHIP, SG_ENOMEM, SG_ESTALL, SG_EUNSUP = 0, -1, -2, -3, -4, -5
 MODE_INS_INFER, MODE_SEM_INFER = 0, 1
+COLOUR_SEMANTIC, COLOUR_INSTANCE, COLOUR_SEGMENT, COLOUR_GROUPING = 0, 1, 2, 3
 NUM_LABEL_VECTORS = 14
 LABEL_NAMES = [f"layer_{l}.{k}" for l in (1, 2, 3, 4) for k in ("seg", "ins", "sem")] + ["final.ins", "final.sem"]
 
@@ -203,6 +204,17 @@ SIGNATURES = {
     "sg_eval_tables": (_I, [_I, vp, vp, _I, vp, _I, vp, _I, vp, vp, vp, vp, vp, _Z, vp]),
     "sg_pack_build": (_I, [vp, C.c_char_p, C.c_char_p]),
     "sg_pack_build_many": (_I, [vp, vp, vp, _I, _I, vp]),
+    "sg_writer_submit_ply": (_I, [vp, C.c_char_p, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, C.c_longlong]),
+    "sg_colour_tables_ws_bytes": (_Z, [_I]),
+    "sg_colour_tables_unique": (_I, [vp, _I, _I, vp, _I, _I, vp, vp, vp, _Z, vp]),
+    "sg_colour_tables_apply": (_I, [vp, _I, _I, vp, vp, vp, vp, vp, vp, vp, _Z, vp]),
+    "sg_colour_vector_ws_bytes": (_Z, [_I]),
+    "sg_colour_vector_unique": (_I, [vp, _I, _I, C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_colour_vector_apply": (_I, [vp, _I, _I, vp, _I, vp, _I, vp, vp, _Z, vp]),
+    "sg_ply_vertex_records_device": (_I, [vp, _I, _I, _I, _I, _I, vp, _I, _I, vp, C.c_longlong, _I, vp, vp, vp]),
+    "sg_ply_vertex_records_device_batch": (_I, [_I, vp, _I, _I, vp, _I, _I, _I, _I, vp, _I, vp, _I, vp, vp, vp]),
+    "sg_ply_plan": (_I, [C.c_char_p, vp]),
+    "sg_dilate_labels": (_I, [vp, _I, vp, vp]),
     "sg_writer_wait_tag": (_I, [vp, C.c_longlong]),
     "sg_writer_flush": (_I, [vp]),
     "sg_writer_destroy": (None, [vp]),

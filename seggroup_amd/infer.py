@@ -2,7 +2,8 @@
 """Inference driver: the drop-in for the reference's `seggroup/infer.py` (pseudo-label generation).
 
 Same command line (infer.py:195-212): `-n/--exp_name`, `--label_style`, `--sem_infer | --ins_infer`,
-`-j/--workers`, `--no_cuda` (rejected: there is no CPU path), `--seed`, `-v/--visualize` (ignored);
+`-j/--workers`, `--no_cuda` (rejected: there is no CPU path), `--seed`, `-v/--visualize` (coloured meshes under
+`results/<exp>/<scene>/<mode>/visualize/`, seggroup_amd/visualize.py; the scans' meshes come from `--mesh_root`);
 same checkpoint (`checkpoints/<exp>/models/last.t7`, keys with or without `module.`), same
 CWD-relative dataset tree, same `results/<exp>/<scene>/<mode>/*.txt` outputs (+ `.npy` twins), same
 log lines in `checkpoints/<exp>/run_infer.log`.
@@ -46,9 +47,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('-j', '--workers', default=8, type=int, metavar='N', help='Number of data loading workers (default: 8).')
     p.add_argument('--no_cuda', action='store_true', help="Don't use CUDA (rejected: the hot path is GPU only).")
     p.add_argument('--seed', type=int, default=1, metavar='S', help='Random seed (default: 1)')
-    p.add_argument('-v', '--visualize', action='store_true', help='Visualize results (ignored).')
+    p.add_argument('-v', '--visualize', action='store_true', help='Visualize results.')
     # additions of this build
     p.add_argument('--root', type=str, default='.', help='directory holding dataset/, checkpoints/, results/ (default: CWD)')
+    p.add_argument('--mesh_root', type=str, default='/data1/antao/Documents/Datasets/ScanNet_raw',
+                   help='raw ScanNet directory: -v reads <mesh_root>/scans/<scene>/<scene>_vh_clean_2.ply (default: the reference\'s literal path)')
     p.add_argument('--sampler', choices=['shard', 'reference'], default='shard',
                    help="scene->rank assignment: 'shard' = i mod W (no padding); 'reference' = DistributedSampler order")
     p.add_argument('--out-format', type=str, default='txt,npy',
@@ -241,8 +244,9 @@ def run_worker(rank: int, world: int, args, forward_fn: Optional[Callable] = Non
     if forward_fn is None:
         from .data import ScanNet
         from .model import SegModel
-        model = SegModel(exp_name=args.exp_name, cuda=True, visualize=False, sem_infer=args.sem_infer, ins_infer=args.ins_infer,
-                         data_root=args.root, out_formats=tuple(args.out_format.split(',')), label_style=args.label_style).to(dev)
+        model = SegModel(exp_name=args.exp_name, cuda=True, visualize=bool(getattr(args, 'visualize', False)), sem_infer=args.sem_infer,
+                         ins_infer=args.ins_infer, data_root=args.root, out_formats=tuple(args.out_format.split(',')), label_style=args.label_style,
+                         **({'mesh_root': args.mesh_root} if getattr(args, 'mesh_root', None) else {})).to(dev)
         if rank == 0:
             io.cprint('Network parameters: {}'.format(sum(x.nelement() for x in model.parameters())))
         ckpt_path = os.path.join(args.root, 'checkpoints', args.exp_name, 'models', 'last.t7')
@@ -318,6 +322,20 @@ def _run_packed(rank, world, args, model, scene_list, mine, acc, io, dev):
 
     names = [scene_list[i][:-1] for i in mine]
     formats = tuple(args.out_format.split(','))
+    # -v: the coloured meshes are made BEHIND the engine, from the tables and seg_of_vertex a finished scene's result holds, on a stream of
+    # their own and through the writer pool below.  Every mesh must exist before anything is started.
+    vis = None
+    if getattr(args, 'visualize', False):
+        import torch
+        from . import visualize as vis
+        if args.label_transfer != 'tables' and 'sgl' not in formats:
+            print("-v colours the meshes from the label tables: use --label-transfer tables (the default) or add sgl to --out-format")
+            raise SystemExit(1)
+        for n in dict.fromkeys(names):
+            if not os.path.isfile(vis.scene_mesh_path(args.mesh_root, n)):
+                raise FileNotFoundError(vis.scene_mesh_path(args.mesh_root, n))
+        vis_stream = torch.cuda.Stream(device=dev)
+        vis_keep = []                                       # (ticket id, mesh pieces, pinned vertex blocks): alive until their files are written
     mode = hip.MODE_SEM_INFER if args.sem_infer else hip.MODE_INS_INFER
     workers = max(1, int(args.workers))
 
@@ -398,6 +416,11 @@ def _run_packed(rank, world, args, model, scene_list, mine, acc, io, dev):
         if prof is not None:
             prof["engine_wait"] += time.time() - t_a
             t_a = time.time()
+        if vis is not None:
+            # the vertex blocks of the ticket before this one are on disk before this one's are made: one batch of them is alive at a time
+            hip.check(hip.lib().sg_writer_wait_tag(writer.handle, int(t.id) - 1))
+            vis_keep[:] = [k for k in vis_keep if k[0] >= int(t.id)]
+            mesh_of = {s_.name: vis.read_source(vis.scene_mesh_path(args.mesh_root, s_.name)) for s_ in t.scenes}
         for s_, r in zip(t.scenes, results):
             acc.add(r.iou_sem, r.iou_ins, r.acc)
             done += 1
@@ -408,6 +431,14 @@ def _run_packed(rank, world, args, model, scene_list, mine, acc, io, dev):
                 print('[rank %d] %s: a <5-point cluster could not be merged (reference would not terminate); sweep cut short' % (rank, s_.name), flush=True)
             if rank == 0:
                 io.cprint(progress_line(min(done * world, len(scene_list)), len(scene_list), acc.summary()))
+            if vis is not None:
+                # the permutations of the shuffled layers come from generators seeded by (--seed, scene, layer): a scene's files do not
+                # depend on the engine's shape, the batch order or the number of ranks
+                tab, sov = r.compact()
+                with torch.cuda.stream(vis_stream):
+                    _, host = vis.visualize_scene(mesh_of[s_.name], tab, sov, model.output_root(s_.name), rngs=vis.scene_generators(args.seed, s_.name),
+                                                  device=dev, writer=writer.handle, tag=int(t.id), flush=False)
+                vis_keep.append((int(t.id), mesh_of.pop(s_.name), host))
             if hasattr(s_, "release"):
                 s_.release()                                # the loader's slot is free for the batch after next
         if prof is not None:
@@ -443,6 +474,8 @@ def _run_packed(rank, world, args, model, scene_list, mine, acc, io, dev):
         consume(tickets.pop(0))
     t_a = time.time()
     writer.flush()
+    if vis is not None:
+        vis_keep.clear()
     if prof is not None:
         prof["final_flush"] = time.time() - t_a
         print("[driver profile] %s engine created in %.3f s, start-up %.3f s, total %.3f s" % ({k: round(v, 3) for k, v in prof.items()}, t_engine, startup or 0.0,

@@ -583,11 +583,15 @@ class SegModel(nn.Module):
     """
 
     def __init__(self, exp_name='exp', cuda=True, visualize=False, sem_infer=False, ins_infer=False,
-                 data_root: Optional[str] = None, out_formats=("txt", "npy"), label_style: str = "manual"):
+                 data_root: Optional[str] = None, out_formats=("txt", "npy"), label_style: str = "manual",
+                 mesh_root: str = '/data1/antao/Documents/Datasets/ScanNet_raw'):
         super().__init__()
         self.exp_name = exp_name
         self.cuda_flag = cuda
         self.visualize = visualize
+        # visualize=True: every exported vector also as a coloured mesh under <output_root>/visualize/ (seggroup_amd/visualize.py); the
+        # scan's mesh is <mesh_root>/scans/<scene>/<scene>_vh_clean_2.ply -- the default is the reference's literal directory (model.py:700)
+        self.mesh_root = mesh_root
         self.sem_infer = sem_infer
         self.ins_infer = ins_infer
         self.out_formats = tuple(out_formats)
@@ -653,9 +657,15 @@ class SegModel(nn.Module):
     # -- forward ------------------------------------------------------------------------------------
     def forward_scene(self, sc: DeviceScene, write: bool = True) -> SceneResult:
         """Hot path on a staged scene.  Returns the SceneResult; writes the label files if `write`."""
+        mesh = None
+        if self.visualize and write:                         # a missing mesh is an error before any GPU work
+            from . import visualize as _vis
+            mesh = _vis.read_source(_vis.scene_mesh_path(self.mesh_root, sc.name))
+            if mesh.V != sc.V:
+                raise ValueError('Loaded labels = ' + str(sc.V) + 'vs mesh vertices = ' + str(mesh.V))
         with self._lock:
             if self.sem_infer or self.ins_infer:
-                res = self.pipeline_for(sc).forward(sc, self.mode(), want_tables=write and "sgl" in self.out_formats)
+                res = self.pipeline_for(sc).forward(sc, self.mode(), want_tables=write and ("sgl" in self.out_formats or mesh is not None))
             else:                                            # train mode: the same forward, recorded for the backward (csrc/trainer.cpp)
                 res = self.trainer_for(sc).forward(sc)
             if write:
@@ -665,6 +675,10 @@ class SegModel(nn.Module):
                     self._writer.submit(self.output_root(sc.name), res, self.out_formats)
                 else:
                     write_label_files(self.output_root(sc.name), res, self.out_formats)
+                if mesh is not None:
+                    # the reference's calls in its order (model.py:739-891): layers 2, 3, 4 draw one global random.shuffle each
+                    tab, sov = res.compact()
+                    _vis.visualize_scene(mesh, tab, sov, self.output_root(sc.name), device=sc.device)
             self.last_result = res
         return res
 

@@ -3,7 +3,7 @@
 
 Same command line (train.py:225-247): `-n/--exp_name`, `-r/--resume`, `--epochs` (6), `--label_style`, `--use_sgd` (True: SGD with
 lr * 100, else Adam), `-j/--workers`, `--lr` (0.001), `--momentum` (0.9), `--no_cuda` (rejected: there is no CPU path), `--seed`,
-`-v/--visualize` (ignored); same dataset tree, same pseudo-label files under `results/<exp>/<scene>/epoch_<n>/` (`epoch_last` for
+`-v/--visualize` (every epoch's pseudo labels also as coloured meshes under `epoch_<n>/visualize/`, meshes from `--mesh_root`); same dataset tree, same pseudo-label files under `results/<exp>/<scene>/epoch_<n>/` (`epoch_last` for
 the final epoch, model.py:688-691), same log lines in `checkpoints/<exp>/run.log`, same checkpoints
 `checkpoints/<exp>/models/{epoch_<n>,last}.t7` = {'epoch', 'state_dict' (DDP's 'module.' keys), 'optimizer' (torch.optim layout)}, so
 the reference's infer.py / --resume read what this writes and vice versa.
@@ -40,9 +40,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--momentum', type=float, default=0.9, metavar='M', help='SGD momentum (default: 0.9)')
     p.add_argument('--no_cuda', action='store_true', help="Don't use CUDA (rejected: the hot path is GPU only).")
     p.add_argument('--seed', type=int, default=1, metavar='S', help='Random seed (default: 1)')
-    p.add_argument('-v', '--visualize', action='store_true', help='Visualize results (ignored).')
+    p.add_argument('-v', '--visualize', action='store_true', help='Visualize results.')
     # additions of this build
     p.add_argument('--root', type=str, default='.', help='directory holding dataset/, checkpoints/, results/ (default: CWD)')
+    p.add_argument('--mesh_root', type=str, default='/data1/antao/Documents/Datasets/ScanNet_raw',
+                   help='raw ScanNet directory: -v reads <mesh_root>/scans/<scene>/<scene>_vh_clean_2.ply (default: the reference\'s literal path)')
     p.add_argument('--out-format', type=str, default='txt,npy', help='comma list of txt,npy,sgl; empty = no pseudo-label files while training')
     p.add_argument('--world-size', type=int, default=0, help='processes to spawn (default: one per visible GPU)')
     p.add_argument('--backend', type=str, default='nccl', help='torch.distributed backend (nccl = RCCL on ROCm)')
@@ -233,6 +235,18 @@ def run_worker(rank: int, world: int, args, make_trainer: Optional[Callable] = N
     from concurrent.futures import ThreadPoolExecutor
     pool = ThreadPoolExecutor(max_workers=2)
     result = None
+
+    # -v: the exported vectors of every scene also as coloured meshes (seggroup_amd/visualize.py), from the result's label tables; the shuffled
+    # layers' permutations are seeded by (--seed, scene, layer), so the files do not depend on the number of ranks
+    def visualize(res, name, out_root):
+        tab, sov = res.compact()
+        vis.visualize_scene(vis.read_source(vis.scene_mesh_path(args.mesh_root, name)), tab, sov, out_root, rngs=vis.scene_generators(args.seed, name), device=dev)
+    vis = None
+    if getattr(args, 'visualize', False) and dev is not None:
+        from . import visualize as vis
+        for n in names:
+            if not os.path.isfile(vis.scene_mesh_path(args.mesh_root, n)):
+                raise FileNotFoundError(vis.scene_mesh_path(args.mesh_root, n))
     for epoch in range(start_epoch, args.epochs):
         tag = 'last' if epoch == args.epochs - 1 else str(epoch + 1)              # train.py:135-138
         mine = epoch_indices(len(names), rank, world, epoch)
@@ -266,6 +280,9 @@ def run_worker(rank: int, world: int, args, make_trainer: Optional[Callable] = N
                 if writer is not None:
                     for si, res in zip(grp, ress):
                         writer.submit(os.path.join(args.root, 'results', args.exp_name, names[si], 'epoch_' + tag), res, formats)
+                if vis is not None:
+                    for si, res in zip(grp, ress):
+                        visualize(res, names[si], os.path.join(args.root, 'results', args.exp_name, names[si], 'epoch_' + tag))
                 seen += len(grp)
                 if rank == 0:
                     log.add(summed)
@@ -293,6 +310,8 @@ def run_worker(rank: int, world: int, args, make_trainer: Optional[Callable] = N
             if writer is not None:
                 out_root = os.path.join(args.root, 'results', args.exp_name, names[si], 'epoch_' + tag)
                 writer.submit(out_root, res, formats)
+            if vis is not None:
+                visualize(res, names[si], os.path.join(args.root, 'results', args.exp_name, names[si], 'epoch_' + tag))
             if rank == 0:
                 log.add(summed)
                 io.cprint(log.line('Epoch[%d/%d](%04d/%04d)' % (epoch + 1, args.epochs, (i + 1) * world, len(names))))
