@@ -635,6 +635,45 @@ int sg_eval_tables(int B, const long long* h_desc, const int32_t* d_tables, int 
                    void* d_ws, size_t ws_bytes, void* stream);
 
 /* =============================================================================================
+ * ScanNet instance AP / AP50 / AP25 of pseudo labels (csrc/kernels_ap.hip, csrc/ap.cpp).  Ground-truth id of a vertex:
+ * gt_id = sem*1000 + ins where ins > 0, else 0; sem outside 0..40 or ins >= 1000 is SG_EINVAL.  ALL vertices count.
+ *
+ * sg_ap_contingency: B scenes, h_desc HOST [B,6] int64 as sg_eval_tables' ({-, S, seg_of_vertex offset, V, gt offset, -}; entries 0 and 5
+ * are not read).  Per scene: the sorted ground-truth list, G entries (id, count), entry 0 = id 0 (count may be 0); first_vertex [S+1]
+ * (lowest vertex of every slot, -1 for none; slot = the vertex's segment, S for a vertex without one); the non-zero cells of the
+ * [S+1, G] contingency as (slot, g, count) int32 triples in (slot, g) order.  Outputs are concatenated in scene order:
+ * h_counts [B,2] int64 = {G, triples}, h_gt [sum G, 2], h_first_vertex [sum (S+1)], h_triples [sum triples, 3] (at most V per scene;
+ * triples_cap in triples).  gt_cap bounds G and sizes the workspace ((S+1) * gt_cap cells per scene): a scene with more ids is
+ * SG_ENOMEM with h_counts[.,0] filled, so the caller can size a second call.  flags bit 0: plain per-vertex atomics (no in-wave merge of
+ * equal keys; same results, for measurement).  Integer atomics only: the same bytes on every run.  SYNCHRONISES the stream.
+ * _vectors: one scene from an instance vector, slot(v) = d_ins[v] (values <= 0 -> slot 0), S = the largest value (a larger one is
+ * SG_EINVAL); its workspace is sg_ap_contingency_ws_bytes(1, {0, S, 0, V, 0, 0}, gt_cap).
+ *
+ * sg_ap_fold (host): one layer's match record from a scene's triples and that layer's table rows h_ins_row / h_sem_row [n_row]
+ * (n_slots = n_row + 1: the last slot has no label; n_slots = n_row: the vector form, ins_row[slot] = slot, sem_row[slot] = the sem
+ * value at first_vertex[slot]).  Predicted instances = distinct ins values > 0 in ascending order (mask order); label = sem at the lowest
+ * vertex; kept when the label is one of the 18 benchmark classes and the instance has >= 100 vertices.
+ *   h_pred  [P,6] = {mask index, ins value, label id, vertex count, void intersection, matches}      h_n[3] = {P, M, Gv}
+ *   h_match [M,2] = {ground-truth record, intersection}, per prediction in ascending ground-truth id, same class only
+ *   h_gtrec [Gv,3] = {gt_id, class id, vertex count} of the ground-truth instances of the 18 classes, ascending gt_id
+ * sg_ap_match (host): greedy matching of a record (ScanNet's evaluate_semantic_instance) at n_overlaps thresholds; h_conf [P] or NULL
+ * (1.0).  Pairs of (class c, overlap o) are h_y_true / h_y_score [h_y_off[c*n+o], h_y_off[c*n+o+1]); h_info [18*n, 3] = {hard false
+ * negatives, has_gt, has_pred}.  y_cap >= n_overlaps * (Gv + M + P) always suffices.
+ * ============================================================================================= */
+size_t sg_ap_contingency_ws_bytes(int B, const long long* h_desc, int gt_cap);
+int sg_ap_contingency(int B, const long long* h_desc, const void* d_seg_of_vertex, int sov_width, const int32_t* d_gt, int gt_cap, int flags,
+                      long long* h_counts, int32_t* h_gt, int32_t* h_first_vertex, int32_t* h_triples, long long triples_cap, void* d_ws,
+                      size_t ws_bytes, void* stream);
+int sg_ap_contingency_vectors(const int32_t* d_ins, int V, int S, const int32_t* d_gt, int gt_cap, int flags, long long* h_counts, int32_t* h_gt,
+                              int32_t* h_first_vertex, int32_t* h_triples, long long triples_cap, void* d_ws, size_t ws_bytes, void* stream);
+int sg_ap_fold(const int32_t* h_triples, long long T, const int32_t* h_first_vertex, int n_slots, const int32_t* h_gt, int G,
+               const int32_t* h_ins_row, const int32_t* h_sem_row, int n_row, int32_t* h_pred, long long pred_cap, int32_t* h_match,
+               long long match_cap, int32_t* h_gtrec, long long gtrec_cap, long long* h_n);
+int sg_ap_match(const int32_t* h_pred, long long P, const int32_t* h_match, long long M, const int32_t* h_gtrec, long long Gv,
+                const double* h_conf, const double* h_overlaps, int n_overlaps, double* h_y_score, uint8_t* h_y_true, long long y_cap,
+                long long* h_y_off, int32_t* h_info);
+
+/* =============================================================================================
  * Label visualisation (reference seggroup/dataset/scannet/util.py:431-527: visualize_labels, visualize_grouping_process; csrc/
  * kernels_visualize.hip, csrc/visualize.cpp).  A vertex takes one of 41 palette colours (index 0 white, 1..40 ScanNet's class colours)
  * chosen by its label; the coloured mesh is the source PLY with the red / green / blue byte of every vertex record replaced.  Colours travel

@@ -2,7 +2,7 @@
 """Re-score saved pseudo labels of any layer and any stage: the working counterpart of the reference's `seggroup/evaluate.py`.
 
     python -m seggroup_amd.evaluate -n EXP [--layer 1|2|3|4|final|all] [--stage epoch_last] [--root .] [--scenes LIST]
-                                    [--format auto|sgl|npy|txt] [--json PATH]
+                                    [--format auto|sgl|npy|txt] [--json PATH] [--ap]
 
 Reads `results/<exp>/<scene>/<stage>/` of every scene in the list: `pseudo_labels.sgl` (seggroup_amd/pseudo_labels.py), or the per-vector
 `layer_<k>.{ins,sem}` / `final.{ins,sem}` files as `.npy` or `.txt`; `--format auto` takes the first of those three a scene has.  Ground
@@ -19,6 +19,10 @@ Deviations from the reference script, on purpose:
   * `--layer all` (every layer the files hold in one pass) and `--format` / `--json` are additions.
 `.sgl` inputs are evaluated from their tables on the GPU (`sg_eval_tables`: every layer in one pass over a scene's vertices);
 `.npy` / `.txt` vectors through `sg_evaluate` per scene and layer.  All three give identical accumulators.
+`--ap` adds the ScanNet instance benchmark's AP / AP_50% / AP_25% over the 18 instance classes under each layer's report (seggroup_amd/ap.py,
+DESIGN.md 9d: all vertices count, confidence 1.0 for every instance): one `sg_ap_contingency` pass per `.sgl` scene serves every layer, the
+vector formats take one `sg_ap_contingency_vectors` pass per layer.  sem_infer directories hold no instance grouping beyond layer 2, so AP
+is defined there for layers 1 and 2 only.
 """
 from __future__ import annotations
 
@@ -58,6 +62,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--label_style", type=str, default="manual", help="label style of the scene packs the ground truth is read from")
     p.add_argument("--batch", type=int, default=64, help="scenes per GPU launch")
     p.add_argument("-j", "--workers", type=int, default=8, help="threads reading label and ground-truth files")
+    p.add_argument("--ap", action="store_true", help="also print ScanNet instance AP / AP_50%% / AP_25%% per layer (and an \"ap\" object in --json)")
     return p
 
 
@@ -81,7 +86,7 @@ def find_format(d: str, fmt: str = "auto") -> Optional[Tuple[str, str]]:
     return None
 
 
-def discover(root: str, exp: str, stage: str, names: Sequence[str], fmt: str, layer: str):
+def discover(root: str, exp: str, stage: str, names: Sequence[str], fmt: str, layer: str, ap: bool = False):
     """-> ([(scene, directory, format, mode)], layers to evaluate).  Raises SystemExit naming every scene without labels, and when the
     requested layer does not exist in a scene's mode (sem_infer files stop at layer 2)."""
     found, missing = [], []
@@ -105,7 +110,8 @@ def discover(root: str, exp: str, stage: str, names: Sequence[str], fmt: str, la
     else:
         if layer not in LAYERS_OF_MODE[mode]:
             raise SystemExit("--layer %s: the labels under results/%s/*/%s are sem_infer labels (layers 1 and 2 only; that forward returns "
-                             "after layer 2, model.py:781-783)" % (layer, exp, stage))
+                             "after layer 2, model.py:781-783)%s" % (layer, exp, stage, "; they hold no instance grouping beyond layer 2, so "
+                                                                    "--ap is defined for --layer 1, 2 or all there" if ap else ""))
         layers = [layer]
     return found, layers
 
@@ -195,6 +201,43 @@ def eval_vectors(gt: np.ndarray, lab, layers: Sequence[str], device) -> np.ndarr
     return out
 
 
+def ap_tables_batch(items, gts: Sequence[np.ndarray], layers: Sequence[str], device) -> list:
+    """sg_ap_contingency over B scenes, then every layer's fold and matching on the host: -> [B][L] ap.Matches."""
+    from . import ap
+    conts = ap.contingency_batch(items, gts, device)
+    return [[ap.layer_matches(c, p.tables[LAYER_ROWS[l][0]], p.tables[LAYER_ROWS[l][1]]) for l in layers] for c, p in zip(conts, items)]
+
+
+def ap_vectors(gt: np.ndarray, lab, layers: Sequence[str], device) -> list:
+    """sg_ap_contingency_vectors per layer on uploaded vectors: -> [L] ap.Matches."""
+    import torch
+    from . import ap
+    g = np.ascontiguousarray(gt, dtype=np.int32).reshape(-1, 2)
+    g_gt = torch.from_numpy(g if g.size else np.zeros((1, 2), np.int32)).to(device)
+    out = []
+    for l in layers:
+        ins, sem = lab[l]
+        cont = ap.contingency_vector(ins, gt, device, g_gt=g_gt)
+        out.append(ap.layer_matches(cont, *ap.vector_rows(cont, sem)))
+    return out
+
+
+def report_ap(accs: Dict[str, Accumulator], ap_accs, exp: str, stage: str, sem_mode: bool) -> dict:
+    """Each layer's report followed by its AP table; -> {layer: the "ap" object of --json}."""
+    from . import ap
+    out = {}
+    for l in accs:
+        report({l: accs[l]}, exp, stage)
+        avgs = ap.compute_averages(ap_accs[l].ap())
+        print("Instance AP, layer %s  (%d scenes, 18 classes, AP = mean over IoU 0.50:0.05:0.90, every instance with confidence 1)" % (l, ap_accs[l].scenes))
+        for ln in ap.report_lines(avgs):
+            print(ln)
+        out[l] = ap.to_json(avgs)
+    if sem_mode:
+        print("note: sem_infer labels hold no instance grouping beyond layer 2: AP is defined for layers 1 and 2 only")
+    return out
+
+
 def accumulate(per_scene: Sequence[np.ndarray], layers: Sequence[str]) -> Dict[str, Accumulator]:
     """per_scene[i] = float32 [L, 164] of scene i (scene-list order) -> one Accumulator per layer (the float64 sums infer.py forms)."""
     accs = {l: Accumulator() for l in layers}
@@ -225,7 +268,8 @@ def to_json(accs: Dict[str, Accumulator], exp: str, stage: str, formats: Dict[st
 def run(args) -> Dict[str, Accumulator]:
     import torch
     names = scene_names(args.root, args.scenes)
-    found, layers = discover(args.root, args.exp_name, args.stage, names, args.format, args.layer)
+    want_ap = bool(getattr(args, "ap", False))
+    found, layers = discover(args.root, args.exp_name, args.stage, names, args.format, args.layer, want_ap)
     if not torch.cuda.is_available():
         raise SystemExit("seggroup_amd.evaluate runs its counting on the GPU (no CPU fallback)")
     hip.require_device()
@@ -234,6 +278,7 @@ def run(args) -> Dict[str, Accumulator]:
     jobs = [((f, layers, args.root, args.label_style)) for f in found]
     batches = [jobs[k:k + max(1, args.batch)] for k in range(0, len(jobs), max(1, args.batch))]
     per_scene: List[np.ndarray] = []
+    ap_scene: list = []
     fmt_count: Dict[str, int] = {}
     with ThreadPoolExecutor(max_workers=max(1, args.workers)) as pool:
         nxt = pool.map(load_scene, batches[0]) if batches else None
@@ -252,13 +297,33 @@ def run(args) -> Dict[str, Accumulator]:
                 if res[i] is None:
                     res[i] = eval_vectors(x[1], x[3], layers, dev)
             per_scene.extend(res)
+            if want_ap:
+                apm: list = [None] * len(loaded)
+                if sgl:
+                    for (i, _), m in zip(sgl, ap_tables_batch([x[3] for _, x in sgl], [x[1] for _, x in sgl], layers, dev)):
+                        apm[i] = m
+                ap_scene.extend(m if m is not None else ap_vectors(x[1], x[3], layers, dev) for m, x in zip(apm, loaded))
     accs = accumulate(per_scene, layers)
+    ap_json = None
+    if want_ap:
+        from . import ap
+        ap_accs = {l: ap.APAccumulator() for l in layers}
+        for m in ap_scene:
+            for k, l in enumerate(layers):
+                ap_accs[l].add(m[k])
     elapsed = time.time() - t0
-    report(accs, args.exp_name, args.stage)
+    if want_ap:
+        ap_json = report_ap(accs, ap_accs, args.exp_name, args.stage, bool(found) and found[0][3] == "sem")
+    else:
+        report(accs, args.exp_name, args.stage)
     print("evaluated %d scenes x %d layer(s) in %.3f s (%s)" % (len(found), len(layers), elapsed, ", ".join("%s %d" % kv for kv in sorted(fmt_count.items()))))
     if args.json:
         with open(args.json, "w") as f:
-            json.dump(to_json(accs, args.exp_name, args.stage, fmt_count, elapsed), f)
+            js = to_json(accs, args.exp_name, args.stage, fmt_count, elapsed)
+            if ap_json is not None:
+                for l, a in ap_json.items():
+                    js["layers"][l]["ap"] = a
+            json.dump(js, f)
     return accs
 
 

@@ -202,6 +202,11 @@ SIGNATURES = {
     "sg_expand_labels_device_batch": (_I, [_I, vp, _I, _I, vp, _I, vp, _I, vp, _I, vp]),
     "sg_eval_tables_ws_bytes": (_Z, [_I, _I, vp]),
     "sg_eval_tables": (_I, [_I, vp, vp, _I, vp, _I, vp, _I, vp, vp, vp, vp, vp, _Z, vp]),
+    "sg_ap_contingency_ws_bytes": (_Z, [_I, vp, _I]),
+    "sg_ap_contingency": (_I, [_I, vp, vp, _I, vp, _I, _I, vp, vp, vp, vp, C.c_longlong, vp, _Z, vp]),
+    "sg_ap_contingency_vectors": (_I, [vp, _I, _I, vp, _I, _I, vp, vp, vp, vp, C.c_longlong, vp, _Z, vp]),
+    "sg_ap_fold": (_I, [vp, C.c_longlong, vp, _I, vp, _I, vp, vp, _I, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp]),
+    "sg_ap_match": (_I, [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, vp, _I, vp, vp, C.c_longlong, vp, vp]),
     "sg_pack_build": (_I, [vp, C.c_char_p, C.c_char_p]),
     "sg_pack_build_many": (_I, [vp, vp, vp, _I, _I, vp]),
     "sg_writer_submit_ply": (_I, [vp, C.c_char_p, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, C.c_longlong]),
