@@ -787,6 +787,33 @@ int sg_segment_lists(const int32_t* d_seg_indices, int V, const int64_t* d_mappe
  * the index of its smallest member, [] elsewhere.  Host arrays of sg_segment_lists (any group order). */
 int sg_write_seg_json(const char* path, const int32_t* h_seg_points, const int32_t* h_seg_off, int G, int Np);
 
+/* Mesh over-segmentation: the `segs.json` that every producer above starts from, made from the mesh itself -- a
+ * graph-based segmenter in the style of ScanNet's Segmentator (Felzenszwalb-Huttenlocher merging over the mesh edges, weighted by
+ * the difference of the vertex normals, with kThresh and segMinVerts).  The contract is the specification in DESIGN.md 8d, NOT byte
+ * equality with the files ScanNet ships (that tool leaves the order of equal weights open).
+ *
+ * sg_overseg_edges (device): d_xyz [V,3] f32 finite and d_faces [F,3] in 0..V-1, both checked on the device (SG_EINVAL) ->
+ *   d_face_normals [F,3] (may be NULL), d_normals [V,3] (sum of the face normals in ascending face index, normalised; zeros where the
+ *   sum has no length), and the unique undirected edges a < b (sg_mesh_adjacency's raw list, with its limits and its errors) in
+ *   ascending (w, a, b): d_edges [*h_E,2] int32 and d_w [*h_E]; both need room for 3F rows.  Synchronises the stream.
+ * sg_overseg_merge (host, no GPU needed): the two ordered passes over those edges and the ids -- h_seg_indices[v] = the lowest vertex
+ *   of v's component.  The arrays are untrusted: a vertex outside 0..V-1, a >= b, or weights that do not ascend are SG_EINVAL.
+ * sg_overseg_scan: both for one scan, ids on the host.
+ * sg_write_segs_json: {"params": {"kThresh": "%f", "segMinVerts": "%d"}, "sceneId": ..., "segIndices": [...]} as json.dump lays
+ *   it out, under a temporary name and renamed. */
+size_t sg_overseg_ws_bytes(int V, int F);
+int sg_overseg_edges(const float* d_xyz, int V, const int32_t* d_faces, int F, float* d_face_normals, float* d_normals, int32_t* d_edges,
+                     float* d_w, int* h_E, void* d_ws, size_t ws_bytes, void* stream);
+int sg_overseg_merge(const int32_t* h_edges, const float* h_w, int E, int V, float k_thresh, int seg_min_verts, int32_t* h_seg_indices);
+int sg_overseg_scan(const float* d_xyz, int V, const int32_t* d_faces, int F, float k_thresh, int seg_min_verts, int32_t* h_seg_indices,
+                    void* d_ws, size_t ws_bytes, void* stream);
+/* Stage times of sg_overseg_edges by events (tools/time_overseg.py): after sg_overseg_set_timing(1) the calling thread's calls record
+ * them; sg_overseg_stage_times copies the last call's microseconds (room for 8 floats) and returns the number of stages. */
+int sg_overseg_set_timing(int on);
+int sg_overseg_stage_times(float* h_us, int cap);
+const char* sg_overseg_stage_name(int i);
+int sg_write_segs_json(const char* path, const char* scene_id, const int32_t* h_seg_indices, int V, float k_thresh, int seg_min_verts);
+
 /* =============================================================================================
  * Training step, operator level: the train-mode tail of SegModel.forward + its backward, and the backward
  * of every operator in front of it (group max, point->cluster max, GCN, EdgeConv MLP2 / MLP3, MLP1); further down the whole step

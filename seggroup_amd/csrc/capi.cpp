@@ -124,6 +124,7 @@ struct TlBuf {
     }
 };
 int write_vector_files(int dfd, const char* name, const int32_t* vec, int V, int formats, TlBuf& tl);      // below, with the writer pool
+int write_all(int fd, const struct iovec* iov, int cnt);
 }  // namespace
 
 int sg_write_label_txt(const char* path, const int32_t* h_vec, int V) {
@@ -179,6 +180,51 @@ int sg_write_seg_json(const char* path, const int32_t* h_seg_points, const int32
     if (!f) return sg::fail(SG_EINVAL, "sg_write_seg_json: cannot open %s: %s", path, strerror(errno));
     const size_t w = fwrite(buf.data(), 1, buf.size(), f);
     if (fclose(f) != 0 || w != buf.size()) return sg::fail(SG_EINVAL, "sg_write_seg_json: short write to %s", path);
+    return SG_OK;
+}
+
+// `<scene>_vh_clean_2.<kThresh>.segs.json` of the mesh over-segmenter (overseg.cpp), in the layout json.dump gives the dictionary
+// {"params": {"kThresh": "%f", "segMinVerts": "%d"}, "sceneId": ..., "segIndices": [...]} -- the parameters as strings, like the files
+// ScanNet ships.  Written under a temporary name in the same directory and renamed: a reader never sees half a file.
+int sg_write_segs_json(const char* path, const char* scene_id, const int32_t* h_seg_indices, int V, float k_thresh, int seg_min_verts) {
+    if (!path || !scene_id || V < 0 || (V > 0 && !h_seg_indices)) return sg::fail(SG_EINVAL, "sg_write_segs_json: bad arguments");
+    for (const char* c = scene_id; *c; ++c)
+        if ((unsigned char)*c < 0x20 || *c == '"' || *c == '\\' || (unsigned char)*c >= 0x7f)
+            return sg::fail(SG_EINVAL, "sg_write_segs_json: the scene id needs escaping, which is not supported");
+    for (int v = 0; v < V; ++v)
+        if (h_seg_indices[v] < 0) return sg::fail(SG_EINVAL, "sg_write_segs_json: segment id %d of vertex %d is negative", h_seg_indices[v], v);
+    char head[256];
+    const int hl = snprintf(head, sizeof head, "{\"params\": {\"kThresh\": \"%f\", \"segMinVerts\": \"%d\"}, \"sceneId\": \"", (double)k_thresh, seg_min_verts);
+    if (hl <= 0 || hl >= (int)sizeof head) return sg::fail(SG_EINVAL, "sg_write_segs_json: k_thresh = %g cannot be recorded", (double)k_thresh);
+    static thread_local TlBuf tl;
+    const size_t id_len = strlen(scene_id);
+    char* const buf = tl.need((size_t)hl + id_len + (size_t)V * 12 + 64);
+    if (!buf) return sg::fail(SG_ENOMEM, "sg_write_segs_json: out of memory");
+    char* o = buf;
+    memcpy(o, head, (size_t)hl); o += hl;
+    memcpy(o, scene_id, id_len); o += id_len;
+    static const char mid[] = "\", \"segIndices\": [";
+    memcpy(o, mid, sizeof mid - 1); o += sizeof mid - 1;
+    for (int v = 0; v < V; ++v) {
+        if (v) { *o++ = ','; *o++ = ' '; }
+        o = put_u32(o, (uint32_t)h_seg_indices[v]);
+    }
+    *o++ = ']'; *o++ = '}';
+    static std::atomic<unsigned long long> counter{0};
+    const std::string tmp = std::string(path) + ".tmp." + std::to_string((long long)getpid()) + "." + std::to_string(counter++);
+    const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_EXCL | O_CLOEXEC, 0666);
+    if (fd < 0) return sg::fail(SG_EINVAL, "sg_write_segs_json: cannot create %s: %s", tmp.c_str(), strerror(errno));
+    const struct iovec iov[1] = {{buf, (size_t)(o - buf)}};
+    const int rc = write_all(fd, iov, 1);
+    if (close(fd) != 0 || rc != 0) {
+        unlink(tmp.c_str());
+        return sg::fail(SG_EINVAL, "sg_write_segs_json: short write to %s", tmp.c_str());
+    }
+    if (rename(tmp.c_str(), path) != 0) {
+        const int e = errno;
+        unlink(tmp.c_str());
+        return sg::fail(SG_EINVAL, "sg_write_segs_json: cannot rename to %s: %s", path, strerror(e));
+    }
     return SG_OK;
 }
 

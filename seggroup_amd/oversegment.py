@@ -1,0 +1,192 @@
+"""Mesh over-segmentation: a scan's `_vh_clean_2.ply` -> `<scene>_vh_clean_2.<kThresh>.segs.json`.
+
+The over-segmentation is the one input of `prepare.py` / `labels.py` that used to come from outside (ScanNet ships it, made by its
+Segmentator tool).  This is a graph-based segmenter of the same family -- Felzenszwalb-Huttenlocher merging over the mesh edges,
+weighted by the difference of the vertex normals, with `kThresh` and `segMinVerts` -- so a mesh that is not a ScanNet download can go
+through the whole project.  The contract is the specification in DESIGN.md 8d (the tie order is defined, the result is deterministic);
+it is NOT byte equality with the files ScanNet ships.
+
+Normals, edges, weights and the sort run on the GPU (`sg_overseg_edges`), the order-dependent merge chain on the host
+(`sg_overseg_merge`, usable without a GPU); there is no other path.
+
+    python -m seggroup_amd.oversegment --scans DIR [--scenes LIST] [--k-thresh 0.01] [--seg-min-verts 20] [--force] [--workers 4]
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import os
+import sys
+from typing import Optional
+
+import numpy as np
+
+from . import hip
+
+MAX_WORKERS = 16
+
+
+def segs_json_name(scene_name: str, k_thresh: float = 0.01) -> str:
+    return "%s_vh_clean_2.%f.segs.json" % (scene_name, float(np.float32(k_thresh)))
+
+
+def _stream_ptr(stream):
+    return None if stream is None else stream.cuda_stream
+
+
+def _on(stream):
+    """The caller's stream as torch's current one (uploads, allocations and the library's launches share it), behind whatever the
+    current stream has queued."""
+    import torch
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())
+    return torch.cuda.stream(stream)
+
+
+def _mesh_tensors(xyz, faces, dev):
+    import torch
+    from .prepare import _t
+    d_xyz, d_f = _t(xyz, torch.float32, dev), _t(faces, torch.int32, dev)
+    if d_xyz.dim() != 2 or d_xyz.shape[1] != 3 or d_f.dim() != 2 or d_f.shape[1] != 3:
+        raise ValueError("oversegment: xyz must be [V,3] and faces [F,3]")
+    if d_xyz.shape[0] < 1:
+        raise ValueError("oversegment: a mesh needs at least one vertex")
+    return d_xyz, d_f, int(d_xyz.shape[0]), int(d_f.shape[0])
+
+
+def device_edges(xyz, faces, device=None, stream=None, want_face_normals: bool = False):
+    """The device stages of one mesh -> dict(face_normals [F,3] | None, normals [V,3], edges [E,2] i32, w [E]) of device tensors:
+    the unique undirected edges in ascending (w, a, b)."""
+    import torch
+    from .prepare import _dev, _ws
+    dev = _dev(device)
+    lib = hip.lib()
+    with torch.cuda.device(dev), _on(stream):
+        d_xyz, d_f, v, f = _mesh_tensors(xyz, faces, dev)
+        fn = torch.empty((f, 3), dtype=torch.float32, device=dev) if want_face_normals else None
+        nrm = torch.empty((v, 3), dtype=torch.float32, device=dev)
+        edges = torch.empty((max(3 * f, 1), 2), dtype=torch.int32, device=dev)
+        w = torch.empty(max(3 * f, 1), dtype=torch.float32, device=dev)
+        ws = _ws(lib.sg_overseg_ws_bytes(v, f), dev)
+        n_e = C.c_int(0)
+        hip.check(lib.sg_overseg_edges(d_xyz.data_ptr(), v, d_f.data_ptr() if f else None, f, fn.data_ptr() if fn is not None and f else None,
+                                       nrm.data_ptr(), edges.data_ptr(), w.data_ptr(), C.byref(n_e), ws.data_ptr(), ws.numel(),
+                                       _stream_ptr(stream)))
+        (stream.synchronize() if stream is not None else torch.cuda.synchronize())
+    return dict(face_normals=fn, normals=nrm, edges=edges[:n_e.value], w=w[:n_e.value])
+
+
+def vertex_normals(xyz, faces, device=None):
+    """-> [V,3] f32 device tensor: the face normals summed per vertex in ascending face index, normalised."""
+    return device_edges(xyz, faces, device=device)["normals"]
+
+
+def edge_weights(xyz, faces, device=None):
+    """-> (edges [E,2] i32, w [E] f32) device tensors in ascending (w, a, b)."""
+    r = device_edges(xyz, faces, device=device)
+    return r["edges"], r["w"]
+
+
+def merge_edges(edges, w, num_vertices: int, k_thresh: float = 0.01, seg_min_verts: int = 20) -> np.ndarray:
+    """The host chain over edges sorted by ascending (w, a, b) -> int32 [V].  Needs no GPU."""
+    e = np.ascontiguousarray(np.asarray(edges), dtype=np.int32).reshape(-1, 2)
+    ww = np.ascontiguousarray(np.asarray(w), dtype=np.float32).reshape(-1)
+    if ww.shape[0] != e.shape[0]:
+        raise ValueError("merge_edges: one weight per edge")
+    out = np.empty(max(int(num_vertices), 0), dtype=np.int32)
+    hip.check(hip.lib().sg_overseg_merge(e.ctypes.data if e.size else None, ww.ctypes.data if ww.size else None, e.shape[0], int(num_vertices),
+                                         float(k_thresh), int(seg_min_verts), out.ctypes.data if out.size else None))
+    return out
+
+
+def segment_mesh(xyz, faces, k_thresh: float = 0.01, seg_min_verts: int = 20, device=None, stream=None) -> np.ndarray:
+    """-> int32 [V]: seg_indices[v] = the lowest vertex index of v's segment (non-contiguous ids, like ScanNet's)."""
+    import torch
+    from .prepare import _dev, _ws
+    dev = _dev(device)
+    lib = hip.lib()
+    with torch.cuda.device(dev), _on(stream):
+        d_xyz, d_f, v, f = _mesh_tensors(xyz, faces, dev)
+        out = np.empty(v, dtype=np.int32)
+        ws = _ws(lib.sg_overseg_ws_bytes(v, f), dev)
+        hip.check(lib.sg_overseg_scan(d_xyz.data_ptr(), v, d_f.data_ptr() if f else None, f, float(k_thresh), int(seg_min_verts),
+                                      out.ctypes.data if v else None, ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+    return out
+
+
+def write_segs_json(path: str, seg_indices, scene_id: str, k_thresh: float = 0.01, seg_min_verts: int = 20) -> None:
+    seg = np.ascontiguousarray(np.asarray(seg_indices), dtype=np.int32).reshape(-1)
+    hip.check(hip.lib().sg_write_segs_json(os.fspath(path).encode(), scene_id.encode(), seg.ctypes.data if seg.size else None, seg.shape[0],
+                                           float(k_thresh), int(seg_min_verts)))
+
+
+def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int = 20, force: bool = False, device=None, stream=None,
+                     plydata=None) -> Optional[str]:
+    """Writes the scan's segs.json next to its mesh; -> the path, or None when the file was there already (never overwritten without
+    `force`)."""
+    from .prepare import _scene_name, mesh_arrays, read_ply
+    name = _scene_name(scene_path)
+    out = os.path.join(scene_path, segs_json_name(name, k_thresh))
+    if os.path.exists(out) and not force:
+        return None
+    if plydata is None:
+        plydata = read_ply(os.path.join(scene_path, name + "_vh_clean_2.ply"))
+    xyz, _, faces = mesh_arrays(plydata)
+    seg = segment_mesh(xyz, faces, k_thresh, seg_min_verts, device=device, stream=stream)
+    write_segs_json(out, seg, name, k_thresh, seg_min_verts)
+    return out
+
+
+def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_min_verts: int = 20, force: bool = False, workers: int = 4,
+                      device=None):
+    """Every scan directory under `scans_dir` (or the named ones) -> (written paths, skipped scene names).  Workers are threads, each
+    with its own stream and workspace: the host chain of one scan overlaps the device work of the next."""
+    import concurrent.futures
+    import threading
+
+    import torch
+    from .prepare import _dev
+    dev = _dev(device)
+    if scenes is None:
+        scenes = sorted(d for d in os.listdir(scans_dir) if os.path.exists(os.path.join(scans_dir, d, d + "_vh_clean_2.ply")))
+    workers = max(1, min(int(workers), MAX_WORKERS, max(len(scenes), 1)))
+    local = threading.local()
+
+    def one(scene):
+        if not hasattr(local, "stream"):
+            with torch.cuda.device(dev):
+                local.stream = torch.cuda.Stream(device=dev)
+        return scene, oversegment_scan(os.path.join(scans_dir, scene), k_thresh, seg_min_verts, force, device=dev, stream=local.stream)
+
+    written, skipped = [], []
+    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
+        for scene, path in pool.map(one, scenes):
+            (written.append(path) if path is not None else skipped.append(scene))
+    return written, skipped
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m seggroup_amd.oversegment", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--scans", required=True, help="directory of scan directories (<scene>/<scene>_vh_clean_2.ply)")
+    ap.add_argument("--scenes", default=None, help="text file with one scene name per line (default: every scan with a mesh)")
+    ap.add_argument("--k-thresh", type=float, default=0.01)
+    ap.add_argument("--seg-min-verts", type=int, default=20)
+    ap.add_argument("--force", action="store_true", help="overwrite existing segs.json files")
+    ap.add_argument("--workers", type=int, default=4, help=f"threads, each with its own stream (at most {MAX_WORKERS})")
+    ap.add_argument("--device", default=None)
+    a = ap.parse_args(argv)
+    scenes = None
+    if a.scenes:
+        with open(a.scenes) as f:
+            scenes = [ln.strip() for ln in f if ln.strip()]
+    written, skipped = oversegment_scans(a.scans, scenes, a.k_thresh, a.seg_min_verts, a.force, a.workers, a.device)
+    for p in written:
+        print("wrote", p)
+    for s in skipped:
+        print("skipped", s, "(segs.json exists; --force overwrites)")
+    print(f"{len(written)} written, {len(skipped)} skipped")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

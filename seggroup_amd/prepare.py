@@ -12,8 +12,10 @@ names, same files, same bytes -- the compute runs on the GPU through the C ABI (
 
 Paths are relative to `root` (the reference uses the working directory).  `plydata` may be a `plyfile.PlyData`
 (not installed here) or the `PlyMesh` of `read_ply` below: only `['vertex'][name]`, `['face']['vertex_indices']`
-and `.count` are used.  Ground-truth / weak-label generation (util.py:129-170, 268-427, 697-768) needs ScanNet's
-annotation files and stays out of scope.
+and `.count` are used.  Ground-truth / weak-label generation (util.py:129-170, 268-427, 697-768) lives in labels.py and
+needs ScanNet's annotation files.  The over-segmentation (`<scene>_vh_clean_2.0.010000.segs.json`) that these producers
+start from is read from the scan directory; `prepare_scene(..., oversegment=True)` makes a missing one from the mesh
+first (oversegment.py).  Only annotating a scan -- the aggregation and click files -- stays out of scope.
 """
 from __future__ import annotations
 
@@ -322,12 +324,16 @@ from .labels import (generate_real_label_pth, generate_real_labels, generate_seg
 
 
 def prepare_scene(scene_path, item, num_points: int = 150000, root: str = ".", perm=None, device=None, label_style: Optional[str] = None,
-                  manual_label_path: Optional[str] = None):
+                  manual_label_path: Optional[str] = None, oversegment: bool = False):
     """What prepare_data.py:36-71 + prepare_weak_label.py:60-90 do for one scan: point cloud, mapper / unmapper, segment lists,
     mesh adjacency and -- with `label_style` and ScanNet's annotation files next to the mesh -- the ground-truth and weak-label
-    files, i.e. every input of SegModel.forward."""
+    files, i.e. every input of SegModel.forward.  `oversegment=True`: a scan without a segs.json gets one from its mesh first
+    (oversegment.py, default parameters); an existing file is never overwritten."""
     scene_name = _scene_name(scene_path)
     ply = read_ply(os.path.join(scene_path, scene_name + "_vh_clean_2.ply"))
+    if oversegment:
+        from .oversegment import oversegment_scan
+        oversegment_scan(scene_path, device=device, plydata=ply)
     generate_pointcloud_pth(scene_path, item, num_points, ply, root=root, perm=perm, device=device)
     generate_seg_labels_and_ds_set(scene_path, root=root, device=device)
     generate_mesh_adjcency_pth(scene_name, ply, root=root, device=device)

@@ -443,6 +443,40 @@ def make_raw_scan(grid_w: int, grid_h: int, seed: int, *, name: Optional[str] = 
     return RawScan(name or f"scan{seed:04d}_00", xyz, rgb, faces[forder].astype(np.int32), seg.astype(np.int32), perm)
 
 
+
+def make_room_scan(grid_w: int, grid_h: int, seed: int = 0, *, jitter: float = 0.0, name: Optional[str] = None, cell: float = 0.04,
+                   box_height: float = 0.3) -> RawScan:
+    """A W x H vertex lattice (two faces per cell, no duplicates) folded at a right angle into a floor (z = 0) and a wall, with a box
+    raised out of the floor: the lattice rows below the fold lie in the floor, the rest climb the wall; a rectangle of floor vertices is
+    lifted by `box_height`, which stretches the cells around it into the box's steep rims.  Without jitter the floor, the wall and the box
+    top are exactly flat -- nearly every edge weight of the mesh over-segmenter (oversegment.py) is then an exact tie; `jitter` moves
+    every coordinate by up to +-jitter.  seg_indices names the part a vertex was built as (floor, wall, box: ids 7 * part + 3)."""
+    w, h = int(grid_w), int(grid_h)
+    if w < 8 or h < 8:
+        raise ValueError("make_room_scan: the lattice needs at least 8 x 8 vertices")
+    v0 = w * h
+    col, row = np.meshgrid(np.arange(w, dtype=np.int64), np.arange(h, dtype=np.int64))
+    col, row = col.reshape(-1), row.reshape(-1)
+    fold = (3 * h) // 5                                        # rows below it are floor
+    on_wall = row >= fold
+    x = col.astype(np.float64) * cell
+    y = np.where(on_wall, (fold - 1) * cell, row * cell)
+    z = np.where(on_wall, (row - (fold - 1)) * cell, 0.0)
+    c0, c1, r0, r1 = w // 4, w // 2, fold // 4, fold // 2
+    in_box = (col >= c0) & (col <= c1) & (row >= r0) & (row <= r1)
+    z = np.where(in_box, box_height, z)
+    xyz = np.stack([x, y, z], 1)
+    if jitter:
+        xyz = xyz + (uniform01(seed, 50, 3 * v0).reshape(v0, 3).astype(np.float64) - 0.5) * (2.0 * float(jitter))
+    rgb = (uniform01(seed, 51, 3 * v0) * 256).astype(np.int64).clip(0, 255).astype(np.uint8).reshape(v0, 3)
+    vid = np.arange(v0, dtype=np.int64).reshape(h, w)
+    a, b, c, d = vid[:-1, :-1].reshape(-1), vid[:-1, 1:].reshape(-1), vid[1:, :-1].reshape(-1), vid[1:, 1:].reshape(-1)
+    faces = np.concatenate([np.stack([a, b, c], 1), np.stack([b, d, c], 1)], 0)
+    part = np.where(in_box, 2, np.where(on_wall, 1, 0))
+    perm = np.argsort(splitmix64(seed, 52, v0), kind="stable").astype(np.int64)
+    return RawScan(name or f"room{seed:04d}_00", xyz.astype(np.float32), rgb, faces.astype(np.int32), (part * 7 + 3).astype(np.int32), perm)
+
+
 # ------------------------------------------------------------------------------------------------
 # synthetic ANNOTATIONS of a raw scan (what ScanNet ships next to the mesh), for the label producers of seggroup_amd/labels.py
 # ------------------------------------------------------------------------------------------------
