@@ -814,6 +814,34 @@ int sg_overseg_stage_times(float* h_us, int cap);
 const char* sg_overseg_stage_name(int i);
 int sg_write_segs_json(const char* path, const char* scene_id, const int32_t* h_seg_indices, int V, float k_thresh, int seg_min_verts);
 
+/* Segment vote: what re-keying a scan's annotations onto another over-segmentation needs on the device.  Every vertex has a
+ * row id d_ids[v] (any non-negative int32: not contiguous, may exceed V) and a column d_cols[v] in 0..n_cols-1; both are checked on the
+ * device (SG_EINVAL).  Rows come out in ascending id order, *h_R of them; every output needs room for V entries.
+ *   per vertex  d_rank = the position of its id among the sorted distinct ids, d_vertex_winner = the winner of its row
+ *   per row     d_row_ids, d_row_count = its vertices, d_winner = the column most of its vertices hold (ties: the lowest column),
+ *               d_winner_count, d_distinct = how many columns it holds, d_tied = 1 when another column is as frequent as the winner,
+ *               d_first_vertex = the lowest vertex of the row that holds the winner
+ * Integers only, the same bytes on every run, O(V) memory (no rows x columns table).  Synchronises the stream twice (check, row count); the
+ * outputs are ordered on the stream.  sg_segment_rank is the first half alone: ranks, ids and counts.
+ * sg_rekey_clicks (host, no GPU needed): click i was made on source segment h_click_seg[i] at raw vertex h_click_point[i].  A point
+ *   inside 0..V-1 whose source segment is that one keeps the point and lands on h_new_seg[point] (how = 0); otherwise the click lands on
+ *   the new segment that holds most of the source segment -- row tables of the vote with rows = source segments, columns = ranks of the new
+ *   ones: h_row_ids ascending, h_row_winner in 0..S-1 indexing h_new_ids, h_row_first -- at that intersection's lowest vertex (how = 1); a
+ *   source segment without a row is dropped (how = 2, outputs -1).  The arrays are untrusted (SG_EINVAL). */
+size_t sg_segment_vote_ws_bytes(int V);
+int sg_segment_rank(const int32_t* d_ids, int V, int32_t* d_rank, int32_t* d_row_ids, int32_t* d_row_count, int* h_R, void* d_ws,
+                    size_t ws_bytes, void* stream);
+int sg_segment_vote(const int32_t* d_ids, const int32_t* d_cols, int V, int n_cols, int32_t* d_rank, int32_t* d_vertex_winner,
+                    int32_t* d_row_ids, int32_t* d_row_count, int32_t* d_winner, int32_t* d_winner_count, int32_t* d_distinct, int32_t* d_tied,
+                    int32_t* d_first_vertex, int* h_R, void* d_ws, size_t ws_bytes, void* stream);
+/* Stage times of sg_segment_vote by events (tools/time_rekey.py), as sg_overseg_set_timing: room for 7 floats. */
+int sg_segment_vote_set_timing(int on);
+int sg_segment_vote_stage_times(float* h_us, int cap);
+const char* sg_segment_vote_stage_name(int i);
+int sg_rekey_clicks(const int32_t* h_src_seg, const int32_t* h_new_seg, int V, const int32_t* h_row_ids, const int32_t* h_row_winner,
+                    const int32_t* h_row_first, int R, const int32_t* h_new_ids, int S, const int64_t* h_click_seg,
+                    const int64_t* h_click_point, int n, int32_t* h_out_seg, int32_t* h_out_point, int32_t* h_out_how);
+
 /* =============================================================================================
  * Training step, operator level: the train-mode tail of SegModel.forward + its backward, and the backward
  * of every operator in front of it (group max, point->cluster max, GCN, EdgeConv MLP2 / MLP3, MLP1); further down the whole step

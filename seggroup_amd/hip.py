@@ -115,6 +115,13 @@ SIGNATURES = {
     "sg_overseg_stage_times": (_I, [vp, _I]),
     "sg_overseg_stage_name": (C.c_char_p, [_I]),
     "sg_write_segs_json": (_I, [C.c_char_p, C.c_char_p, vp, _I, C.c_float, _I]),
+    "sg_segment_vote_ws_bytes": (_Z, [_I]),
+    "sg_segment_rank": (_I, [vp, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_segment_vote": (_I, [vp, vp, _I, _I] + [vp] * 9 + [C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_segment_vote_set_timing": (_I, [_I]),
+    "sg_segment_vote_stage_times": (_I, [vp, _I]),
+    "sg_segment_vote_stage_name": (C.c_char_p, [_I]),
+    "sg_rekey_clicks": (_I, [vp, vp, _I, vp, vp, vp, _I, vp, _I, vp, vp, _I, vp, vp, vp]),
     "sg_train_tail_ws_bytes": (_Z, [_I, _I]),
     "sg_train_tail_forward": (_I, [vp, _I, vp, _I, vp, vp, vp, vp, vp, vp, _Z, vp]),
     "sg_train_tail_backward": (_I, [_I, _I, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, _Z, vp]),

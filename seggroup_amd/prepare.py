@@ -15,7 +15,8 @@ Paths are relative to `root` (the reference uses the working directory).  `plyda
 and `.count` are used.  Ground-truth / weak-label generation (util.py:129-170, 268-427, 697-768) lives in labels.py and
 needs ScanNet's annotation files.  The over-segmentation (`<scene>_vh_clean_2.0.010000.segs.json`) that these producers
 start from is read from the scan directory; `prepare_scene(..., oversegment=True)` makes a missing one from the mesh
-first (oversegment.py).  Only annotating a scan -- the aggregation and click files -- stays out of scope.
+first (oversegment.py), and rekey.py carries a scan's annotation files over to such a segmentation.  Only annotating a scan -- making
+the aggregation and click files in the first place -- stays out of scope.
 """
 from __future__ import annotations
 
