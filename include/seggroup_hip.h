@@ -814,6 +814,34 @@ int sg_overseg_stage_times(float* h_us, int cap);
 const char* sg_overseg_stage_name(int i);
 int sg_write_segs_json(const char* path, const char* scene_id, const int32_t* h_seg_indices, int V, float k_thresh, int seg_min_verts);
 
+/* Point-cloud over-segmentation: the same segs.json for a scan that has no faces.  The graph is the kNN graph of the
+ * cloud, the normals come from the covariance of every point's neighbourhood, the edge order and the host chain are 8d's.
+ *
+ * sg_pointcloud_knn: d_knn [N,k+1] int32 = the complete top-(k+1) list of every point against the whole cloud, in the scores and the tie
+ *   rule of sg_pointcloud_adjacency (descending score, the lower index first among equals); entry 0, normally the point itself, is kept.
+ *   d_points rows of `stride` floats, xyz first; k in {5, 10, 20}; N <= k is SG_EINVAL, N > SG_MAX_POINTS is SG_EUNSUP.
+ * sg_pointcloud_normals: d_normals [N,3] from d_xyz [N,3] and such a table (entries are checked on the device): the eigenvector of the
+ *   smallest eigenvalue of the list points' covariance by a cyclic Jacobi iteration with a fixed number of sweeps, not re-normalised,
+ *   turned towards h_viewpoint (3 floats on the host; NULL: the centre of the cloud's bounding box).  Its workspace is
+ *   sg_pointcloud_knn_ws_bytes(N).
+ * sg_pcseg_edges: d_xyz [N,3] finite (checked on the device, SG_EINVAL) -> d_knn [N,k+1] (may be NULL), d_normals [N,3] and the unique
+ *   undirected pairs a < b over (i, list[i][t]), t = 1..k, in ascending (w, a, b): d_edges [*h_E,2] int32 and d_w [*h_E]; both need room
+ *   for N*k rows.  Synchronises the stream.
+ * sg_pcseg_scan: those stages and sg_overseg_merge for one cloud, ids on the host.
+ * Stage times of sg_pcseg_edges by events, as sg_overseg_set_timing: room for 7 floats (tools/time_pcseg.py). */
+size_t sg_pointcloud_knn_ws_bytes(int N);
+int sg_pointcloud_knn(const float* d_points, int stride, int N, int k, int32_t* d_knn, void* d_ws, size_t ws_bytes, void* stream);
+int sg_pointcloud_normals(const float* d_xyz, int N, const int32_t* d_knn, int k, const float* h_viewpoint, float* d_normals, void* d_ws,
+                          size_t ws_bytes, void* stream);
+size_t sg_pcseg_ws_bytes(int N, int k);
+int sg_pcseg_edges(const float* d_xyz, int N, int k, const float* h_viewpoint, int32_t* d_knn, float* d_normals, int32_t* d_edges, float* d_w,
+                   int* h_E, void* d_ws, size_t ws_bytes, void* stream);
+int sg_pcseg_scan(const float* d_xyz, int N, int k, const float* h_viewpoint, float k_thresh, int seg_min_verts, int32_t* h_seg_indices,
+                  void* d_ws, size_t ws_bytes, void* stream);
+int sg_pcseg_set_timing(int on);
+int sg_pcseg_stage_times(float* h_us, int cap);
+const char* sg_pcseg_stage_name(int i);
+
 /* Segment vote: what re-keying a scan's annotations onto another over-segmentation needs on the device.  Every vertex has a
  * row id d_ids[v] (any non-negative int32: not contiguous, may exceed V) and a column d_cols[v] in 0..n_cols-1; both are checked on the
  * device (SG_EINVAL).  Rows come out in ascending id order, *h_R of them; every output needs room for V entries.

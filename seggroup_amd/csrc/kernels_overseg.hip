@@ -17,6 +17,7 @@
 // sorted edges runs on the host (overseg.cpp).
 #include "sg_common.h"
 #include "sort_device.h"
+#include "overseg_device.h"
 
 namespace {
 
@@ -31,7 +32,7 @@ __device__ __forceinline__ F3 normalised(float x, float y, float z) {
     return F3{0.0f, 0.0f, 0.0f};
 }
 
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+using sgos::finite_f32;
 
 // flag |= 1: a coordinate is not finite; flag |= 2: a face id is outside 0..V-1
 __global__ __launch_bounds__(kBlock) void k_os_check(const float* __restrict__ xyz, int V, const int32_t* __restrict__ faces, int F,
@@ -101,8 +102,7 @@ __global__ __launch_bounds__(kBlock) void k_os_weights(const int64_t* __restrict
     const float c = (nbx * dx + nby * dy) + nbz * dz;
     if (c > 0.0f) w = w * w;
     w_out[e] = w;
-    const unsigned bits = __float_as_uint(w);
-    key[e] = bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);           // ascending as unsigned <=> ascending as fp32, negatives included
+    key[e] = sgos::weight_key(w);
     idx[e] = e;
 }
 
@@ -168,32 +168,21 @@ const char* const kStageNames[kStages] = {"check", "face_normals", "incidence_so
 thread_local bool t_timing = false;
 thread_local float t_stage_us[kStages];
 
-struct StageClock {
-    hipEvent_t ev[kStages + 1];
-    int made = 0, next = 0;
-    hipStream_t st;
-    explicit StageClock(hipStream_t s) : st(s) {
-        if (!t_timing) return;
-        for (int i = 0; i < kStages; ++i) t_stage_us[i] = 0.0f;
-        for (; made <= kStages; ++made)
-            if (hipEventCreate(&ev[made]) != hipSuccess) break;
-        if (made <= kStages) { drop(); return; }
-        tick();
-    }
-    void tick() { if (made && next <= kStages) (void)hipEventRecord(ev[next++], st); }     // the end of stage next - 1
-    void drop() { for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]); made = 0; }
-    ~StageClock() {
-        if (!made) return;
-        if (next > 1 && hipEventSynchronize(ev[next - 1]) == hipSuccess)
-            for (int i = 1; i < next; ++i) {
-                float ms = 0.0f;
-                if (hipEventElapsedTime(&ms, ev[i - 1], ev[i]) == hipSuccess) t_stage_us[i - 1] = ms * 1000.0f;
-            }
-        drop();
-    }
-};
+using StageClock = sgos::StageClock<kStages>;
 
 }  // namespace
+
+// the stages both segmenters share (overseg_device.h)
+const int* sgos::sort_by_weight(unsigned int* k0, unsigned int* k1, int* v0, int* v1, int* hist, int E, hipStream_t st) {
+    sgsort::Lists<unsigned int, int> W{};
+    W.kin[0] = k0; W.kout[0] = k1; W.vin[0] = v0; W.vout[0] = v1; W.hist[0] = hist; W.n[0] = E;
+    sgsort::radix_sort<unsigned int, int, true>(W, 1, 0, 32, st);
+    return W.vin[0];
+}
+
+void sgos::gather_edges(const int* idx, int E, const int64_t* adj, const float* w, int32_t* edges, float* w_sorted, hipStream_t st) {
+    k_os_gather<<<sg::cdiv(E, kBlock), kBlock, 0, st>>>(idx, E, adj, w, edges, w_sorted);
+}
 
 extern "C" {
 
@@ -224,7 +213,7 @@ int sg_overseg_edges(const float* d_xyz, int V, const int32_t* d_faces, int F, f
     if (!p.ok) return sg::fail(SG_ENOMEM, "sg_overseg_edges: workspace too small (%zu < %zu)", ws_bytes, sg_overseg_ws_bytes(V, F));
     hipStream_t st = sg::as_stream(stream);
     const int n = 3 * F;
-    StageClock clock(st);
+    StageClock clock(st, t_timing, t_stage_us);
     // 0. the inputs are the caller's: nothing reads through a face id before this check has passed
     SG_HIP(hipMemsetAsync(p.flag, 0, 4, st));
     k_os_check<<<sg::cdiv(3ll * std::max(V, F), kBlock), kBlock, 0, st>>>(d_xyz, V, d_faces, F, p.flag);
@@ -262,11 +251,9 @@ int sg_overseg_edges(const float* d_xyz, int V, const int32_t* d_faces, int F, f
     // 4. weights and keys, 5. ascending (w, a, b): a stable sort of the lexicographic list by the key (the incidence buffers are free again)
     k_os_weights<<<sg::cdiv(E, kBlock), kBlock, 0, st>>>(p.adj, E, d_xyz, d_normals, p.w, p.k0, p.v0);
     clock.tick();
-    sgsort::Lists<unsigned int, int> W{};
-    W.kin[0] = p.k0; W.kout[0] = p.k1; W.vin[0] = p.v0; W.vout[0] = p.v1; W.hist[0] = p.hist; W.n[0] = E;
-    sgsort::radix_sort<unsigned int, int, true>(W, 1, 0, 32, st);
+    const int* order = sgos::sort_by_weight(p.k0, p.k1, p.v0, p.v1, p.hist, E, st);
     clock.tick();
-    k_os_gather<<<sg::cdiv(E, kBlock), kBlock, 0, st>>>(W.vin[0], E, p.adj, p.w, d_edges, d_w);
+    sgos::gather_edges(order, E, p.adj, p.w, d_edges, d_w, st);
     clock.tick();
     SG_LAUNCH_CHECK();
     *h_E = E;

@@ -1,0 +1,446 @@
+// Point-cloud over-segmentation, device side: the twin of kernels_overseg.hip for a scan that has no faces.  The graph is
+// the kNN graph of the cloud, the normals come from the neighbourhoods' covariance; the edge order and the host chain are 8d's.
+//
+//   k_pc_pack           coordinates finite (one flag word), (x, y, z, |p|^2) per point, the cloud's bounding box (order-free min / max)
+//   k_pc_knn            the complete top-(k+1) list of every point against the whole cloud: cloud_knn_device.h, the score and the tie
+//                       rule of sg_pointcloud_adjacency's k_nearest_k
+//   k_pc_normals        one thread per point: mean and the six covariance sums over its list in list order, a cyclic Jacobi iteration
+//                       with the rotations written out for the pairs (0,1), (0,2), (1,2) on scalars (nothing is indexed at run time),
+//                       the eigenvector of the smallest eigenvalue, turned towards the viewpoint
+//   edges               (i, L[i][t]), t = 1..k, without the self pairs, as sorted unique pair keys: a < b in lexicographic order
+//   k_pc_weights        8d's weight after the two normals have been aligned (the viewpoint test may have fallen either way)
+//   sort + gather       8d's, the same code (overseg_device.h)
+//
+// Every fp32 operation is written op by op and rounded once (-ffp-contract=off; only + - * / sqrt and comparisons, the explicit FMAs of
+// pair_score aside), which tests/test_gpu_pcseg.py holds to the NumPy statement of the specification (tests/pcseg_ref.py) bit for bit.
+#include <cmath>
+
+#include "sg_common.h"
+#include "sort_device.h"
+#include "cloud_knn_device.h"
+#include "overseg_device.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kSweeps = 5;          // after five sweeps every off-diagonal is exactly 0 on the measured clouds
+using sgcloud::kTile;
+
+struct Misc {
+    int flag;                       // |= 1: a coordinate is not finite; |= 2: a list has an unfilled entry (scores not finite); |= 4: a
+                                    // caller's list names a point outside 0..N-1
+    int count;                      // unique pair keys
+    unsigned int lo[3], hi[3];      // the bounding box as sgos::weight_key words
+    float view[3];
+};
+
+__device__ __forceinline__ float unkey(unsigned int k) { return __uint_as_float(k & 0x80000000u ? k ^ 0x80000000u : ~k); }
+
+__global__ void k_pc_init(Misc* __restrict__ m, int has_view, float vx, float vy, float vz) {
+    m->flag = 0;
+    m->count = 0;
+    for (int a = 0; a < 3; ++a) { m->lo[a] = 0xffffffffu; m->hi[a] = 0u; }
+    m->view[0] = has_view ? vx : 0.0f; m->view[1] = has_view ? vy : 0.0f; m->view[2] = has_view ? vz : 0.0f;
+}
+
+__global__ __launch_bounds__(kBlock) void k_pc_pack(const float* __restrict__ p, int stride, int N, float4* __restrict__ cand,
+                                                    Misc* __restrict__ m) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = i < N;
+    float c[3] = {0.0f, 0.0f, 0.0f};
+    if (live) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) c[a] = p[(size_t)i * stride + a];
+        cand[i] = sgcloud::with_norm(c[0], c[1], c[2]);
+        if (!(sgos::finite_f32(c[0]) && sgos::finite_f32(c[1]) && sgos::finite_f32(c[2]))) atomicOr(&m->flag, 1);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        unsigned int lo = live ? sgos::weight_key(c[a]) : 0xffffffffu, hi = live ? lo : 0u;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            lo = min(lo, (unsigned int)__shfl_xor((int)lo, off));
+            hi = max(hi, (unsigned int)__shfl_xor((int)hi, off));
+        }
+        if ((threadIdx.x & 63) == 0) { atomicMin(&m->lo[a], lo); atomicMax(&m->hi[a], hi); }
+    }
+}
+
+// the default viewpoint: the centre of the bounding box, (min + max) * 0.5 per axis
+__global__ void k_pc_view(Misc* __restrict__ m) {
+    for (int a = 0; a < 3; ++a) m->view[a] = (unkey(m->lo[a]) + unkey(m->hi[a])) * 0.5f;
+}
+
+template <int KK>
+__global__ __launch_bounds__(kTile) void k_pc_knn(const float4* __restrict__ cand, int N, int32_t* __restrict__ table, Misc* __restrict__ m) {
+    __shared__ float4 tile[kTile];
+    const int u = blockIdx.x * kTile + threadIdx.x;
+    const bool live = u < N;
+    const float4 me = cand[live ? u : 0];
+    float bs[KK];
+    int bi[KK];
+    sgcloud::top_scores<KK>(cand, N, me, tile, bs, bi);
+    if (!live) return;
+    bool unfilled = false;
+#pragma unroll
+    for (int t = 0; t < KK; ++t) {
+        unfilled |= bi[t] >= N;                                // fewer than KK finite scores: the coordinates overflow the score
+        table[(size_t)u * KK + t] = bi[t] < N ? bi[t] : u;     // nothing downstream reads through an index that is not a point
+    }
+    if (unfilled) atomicOr(&m->flag, 2);
+}
+
+// one Jacobi rotation of the pair (p, q); r is the third index.  a_rp, a_rq: the two off-diagonals that share r; v_ip, v_iq: the columns
+// p and q of the accumulated rotation.  A pair whose off-diagonal is exactly 0 is skipped.
+__device__ __forceinline__ void rotate(float& app, float& aqq, float& apq, float& arp, float& arq, float& v0p, float& v0q, float& v1p,
+                                       float& v1q, float& v2p, float& v2q) {
+    if (apq == 0.0f) return;
+    const float theta = (aqq - app) / (2.0f * apq);
+    const float sgn = theta >= 0.0f ? 1.0f : -1.0f;
+    const float t = sgn / (__builtin_fabsf(theta) + __builtin_sqrtf(theta * theta + 1.0f));      // theta * theta = +inf gives t = 0
+    const float c = 1.0f / __builtin_sqrtf(t * t + 1.0f);
+    const float s = t * c;
+    const float h = t * apq;
+    app = app - h;
+    aqq = aqq + h;
+    apq = 0.0f;
+    const float rp = arp, rq = arq;
+    arp = c * rp - s * rq;
+    arq = s * rp + c * rq;
+    const float x0 = v0p, y0 = v0q, x1 = v1p, y1 = v1q, x2 = v2p, y2 = v2q;
+    v0p = c * x0 - s * y0; v0q = s * x0 + c * y0;
+    v1p = c * x1 - s * y1; v1q = s * x1 + c * y1;
+    v2p = c * x2 - s * y2; v2q = s * x2 + c * y2;
+}
+
+// c2 if b2, else c1 if b1, else c0
+__device__ __forceinline__ float pick(float c0, float c1, float c2, bool b1, bool b2) {
+    const unsigned int m1 = b1 ? ~0u : 0u, m2 = b2 ? ~0u : 0u;
+    const unsigned int lo = (__float_as_uint(c1) & m1) | (__float_as_uint(c0) & ~m1);
+    return __uint_as_float((__float_as_uint(c2) & m2) | (lo & ~m2));
+}
+
+// p: rows of `stride` floats, xyz first.  table [N,KK]: every point's list; an entry outside 0..N-1 (a caller's table) raises flag 4 and
+// counts as the point itself.
+template <int KK>
+__global__ __launch_bounds__(kBlock) void k_pc_normals(const float* __restrict__ p, int stride, int N, const int32_t* __restrict__ table,
+                                                       Misc* __restrict__ m, float* __restrict__ nrm) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    const int32_t* L = table + (size_t)i * KK;
+    // 2. the mean: the sum in list order from +0, divided by (float)(k + 1)
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    bool bad = false;
+#pragma unroll
+    for (int t = 0; t < KK; ++t) {
+        int j = L[t];
+        if ((unsigned)j >= (unsigned)N) { bad = true; j = i; }
+        sx = sx + p[(size_t)j * stride]; sy = sy + p[(size_t)j * stride + 1]; sz = sz + p[(size_t)j * stride + 2];
+    }
+    if (bad) atomicOr(&m->flag, 4);
+    const float kk = (float)KK;
+    const float mx = sx / kk, my = sy / kk, mz = sz / kk;
+    // 3. the six covariance sums in list order from +0, not normalised
+    float a00 = 0.0f, a01 = 0.0f, a02 = 0.0f, a11 = 0.0f, a12 = 0.0f, a22 = 0.0f;
+#pragma unroll
+    for (int t = 0; t < KK; ++t) {
+        int j = L[t];
+        if ((unsigned)j >= (unsigned)N) j = i;
+        const float qx = p[(size_t)j * stride] - mx, qy = p[(size_t)j * stride + 1] - my, qz = p[(size_t)j * stride + 2] - mz;
+        a00 = a00 + qx * qx; a01 = a01 + qx * qy; a02 = a02 + qx * qz;
+        a11 = a11 + qy * qy; a12 = a12 + qy * qz; a22 = a22 + qz * qz;
+    }
+    // 4. cyclic Jacobi, pairs (0,1), (0,2), (1,2); v_rc = row r, column c of the accumulated rotation
+    float v00 = 1.0f, v01 = 0.0f, v02 = 0.0f, v10 = 0.0f, v11 = 1.0f, v12 = 0.0f, v20 = 0.0f, v21 = 0.0f, v22 = 1.0f;
+#pragma unroll 1
+    for (int sweep = 0; sweep < kSweeps; ++sweep) {
+        rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+        rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+        rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+    }
+    // the column whose diagonal entry is smallest, the lowest index among equal entries
+    // (selected by masks: written as branches, the compiler turns the three candidates into a table in scratch)
+    const bool b1 = a11 < a00;
+    const float dm = b1 ? a11 : a00;
+    const bool b2 = a22 < dm;
+    float nx = pick(v00, v01, v02, b1, b2), ny = pick(v10, v11, v12, b1, b2), nz = pick(v20, v21, v22, b1, b2);
+    // 5. towards the viewpoint
+    const float dx = m->view[0] - p[(size_t)i * stride], dy = m->view[1] - p[(size_t)i * stride + 1], dz = m->view[2] - p[(size_t)i * stride + 2];
+    const float s = (nx * dx + ny * dy) + nz * dz;
+    if (s < 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+    nrm[(size_t)i * 3] = nx; nrm[(size_t)i * 3 + 1] = ny; nrm[(size_t)i * 3 + 2] = nz;
+}
+
+// 6. pair key of (i, L[i][t]), t = 1..k, at i * k + t - 1: lo << 32 | hi; a self pair (coincident points) becomes ~0 and sorts to the end
+__global__ __launch_bounds__(kBlock) void k_pc_edge_keys(const int32_t* __restrict__ table, int N, int k, unsigned long long* __restrict__ keys) {
+    const size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= (size_t)N * k) return;
+    const int i = (int)(e / (unsigned)k), t = (int)(e % (unsigned)k) + 1;
+    const int j = table[(size_t)i * (k + 1) + t];
+    keys[e] = j == i ? ~0ull : ((unsigned long long)(unsigned)min(i, j) << 32) | (unsigned)max(i, j);
+}
+
+__global__ __launch_bounds__(kBlock) void k_pc_unpack(const unsigned long long* __restrict__ keys, int n, int64_t* __restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    out[(size_t)i * 2] = (int64_t)(keys[i] >> 32);
+    out[(size_t)i * 2 + 1] = (int64_t)(keys[i] & 0xffffffffull);
+}
+
+// 7. weight and sort key of edge e = (a, b) of the lexicographic list; idx[e] = e
+__global__ __launch_bounds__(kBlock) void k_pc_weights(const int64_t* __restrict__ adj, int E, const float4* __restrict__ cand,
+                                                       const float* __restrict__ vn, float* __restrict__ w_out,
+                                                       unsigned int* __restrict__ key, int* __restrict__ idx) {
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= E) return;
+    const size_t a = (size_t)adj[(size_t)e * 2], b = (size_t)adj[(size_t)e * 2 + 1];
+    const float nax = vn[a * 3], nay = vn[a * 3 + 1], naz = vn[a * 3 + 2];
+    const float nbx = vn[b * 3], nby = vn[b * 3 + 1], nbz = vn[b * 3 + 2];
+    float d = (nax * nbx + nay * nby) + naz * nbz;
+    const float4 pa = cand[a], pb = cand[b];
+    const float dx = pb.x - pa.x, dy = pb.y - pa.y, dz = pb.z - pa.z;
+    float c = (nbx * dx + nby * dy) + nbz * dz;
+    if (d < 0.0f) { d = -d; c = -c; }                                     // the same surface seen from the other side
+    float w = 1.0f - d;
+    if (c > 0.0f) w = w * w;
+    w_out[e] = w;
+    key[e] = sgos::weight_key(w);
+    idx[e] = e;
+}
+
+int bits_for(long long n) {
+    int b = 1;
+    while ((1ll << b) < n) ++b;
+    return b;
+}
+
+struct Plan {                       // the workspace of one cloud; n = N * k
+    size_t n;
+    float4* cand;                   // [N]
+    Misc* misc;
+    int32_t* knn;                   // [N, k+1]
+    unsigned long long *p0, *p1, *p2;       // pair keys
+    int* hist;
+    int* scratch;
+    int64_t* adj;                   // [n,2] the lexicographic list
+    float* w;                       // [E] weights in that order
+    unsigned int *k0, *k1;          // weight keys
+    int *v0, *v1;                   // edge indices
+    // outputs of sg_pcseg_scan, which has no caller's buffers for them
+    float* vn;
+    int32_t* edges;
+    float* w_sorted;
+    bool ok;
+};
+
+Plan carve(void* d_ws, size_t ws_bytes, int N, int k) {
+    Plan p{};
+    p.n = (size_t)std::max(N, 1) * std::max(k, 1);
+    const size_t np = (size_t)std::max(N, 1);
+    sg::Carver cv(d_ws, ws_bytes);
+    p.cand = cv.take<float4>(np);
+    p.misc = cv.take<Misc>(1);
+    p.knn = cv.take<int32_t>(np * (std::max(k, 1) + 1));
+    p.p0 = cv.take<unsigned long long>(p.n);
+    p.p1 = cv.take<unsigned long long>(p.n);
+    p.p2 = cv.take<unsigned long long>(p.n);
+    p.hist = cv.take<int>(sgsort::hist_ints((long long)p.n));
+    p.scratch = cv.take<int>(sgsort::unique_ints((long long)p.n));
+    p.adj = cv.take<int64_t>(p.n * 2);
+    p.w = cv.take<float>(p.n);
+    p.k0 = cv.take<unsigned int>(p.n);
+    p.k1 = cv.take<unsigned int>(p.n);
+    p.v0 = cv.take<int>(p.n);
+    p.v1 = cv.take<int>(p.n);
+    p.vn = cv.take<float>(np * 3);
+    p.edges = cv.take<int32_t>(p.n * 2);
+    p.w_sorted = cv.take<float>(p.n);
+    p.ok = cv.ok;
+    return p;
+}
+
+int check_k(const char* who, int N, int k) {
+    if (k != 5 && k != 10 && k != 20) return sg::fail(SG_EUNSUP, "%s: k = %d is not built (5, 10 = the reference's default, 20)", who, k);
+    if (N <= k) return sg::fail(SG_EINVAL, "%s: %d points for k = %d (topk(k + 1) raises in the reference)", who, N, k);
+    if (N > SG_MAX_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; a cloud holds at most %d", who, N, SG_MAX_POINTS);
+    return SG_OK;
+}
+
+void launch_knn(const float4* cand, int N, int k, int32_t* table, Misc* m, hipStream_t st) {
+    if (k == 5) k_pc_knn<6><<<sg::cdiv(N, kTile), kTile, 0, st>>>(cand, N, table, m);
+    else if (k == 10) k_pc_knn<11><<<sg::cdiv(N, kTile), kTile, 0, st>>>(cand, N, table, m);
+    else k_pc_knn<21><<<sg::cdiv(N, kTile), kTile, 0, st>>>(cand, N, table, m);
+}
+
+void launch_normals(const float* p, int stride, int N, int k, const int32_t* table, Misc* m, float* nrm, hipStream_t st) {
+    if (k == 5) k_pc_normals<6><<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(p, stride, N, table, m, nrm);
+    else if (k == 10) k_pc_normals<11><<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(p, stride, N, table, m, nrm);
+    else k_pc_normals<21><<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(p, stride, N, table, m, nrm);
+}
+
+int viewpoint_ok(const char* who, const float* v) {
+    if (v && !(std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]))) return sg::fail(SG_EINVAL, "%s: the viewpoint is not finite", who);
+    return SG_OK;
+}
+
+// sg_pcseg_set_timing(1): the calling thread's next sg_pcseg_edges calls bracket their stages with events (tools/time_pcseg.py)
+constexpr int kStages = 7;
+const char* const kStageNames[kStages] = {"check", "knn", "normals", "edges", "weights", "weight_sort", "gather"};
+thread_local bool t_timing = false;
+thread_local float t_stage_us[kStages];
+
+}  // namespace
+
+extern "C" {
+
+int sg_pcseg_set_timing(int on) { t_timing = on != 0; return SG_OK; }
+
+int sg_pcseg_stage_times(float* h_us, int cap) {
+    SG_REQUIRE(h_us && cap >= kStages, "sg_pcseg_stage_times: room for %d floats is needed", kStages);
+    for (int i = 0; i < kStages; ++i) h_us[i] = t_stage_us[i];
+    return kStages;
+}
+
+const char* sg_pcseg_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+
+size_t sg_pointcloud_knn_ws_bytes(int N) { return sg::align_up((size_t)std::max(N, 1) * 16) + sg::align_up(sizeof(Misc)); }
+
+int sg_pointcloud_knn(const float* d_points, int stride, int N, int k, int32_t* d_knn, void* d_ws, size_t ws_bytes, void* stream) {
+    SG_REQUIRE(d_points && stride >= 3 && N > 0 && d_knn && d_ws, "sg_pointcloud_knn: bad arguments");
+    const int rc = check_k("sg_pointcloud_knn", N, k);
+    if (rc < 0) return rc;
+    sg::Carver cv(d_ws, ws_bytes);
+    float4* cand = cv.take<float4>(N);
+    Misc* misc = cv.take<Misc>(1);
+    if (!cv.ok) return sg::fail(SG_ENOMEM, "sg_pointcloud_knn: workspace too small (%zu < %zu)", ws_bytes, sg_pointcloud_knn_ws_bytes(N));
+    hipStream_t st = sg::as_stream(stream);
+    k_pc_init<<<1, 1, 0, st>>>(misc, 1, 0.0f, 0.0f, 0.0f);
+    k_pc_pack<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(d_points, stride, N, cand, misc);
+    launch_knn(cand, N, k, d_knn, misc, st);
+    int flag = 0;
+    SG_HIP(hipMemcpyAsync(&flag, &misc->flag, 4, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (flag & 1) return sg::fail(SG_EINVAL, "sg_pointcloud_knn: a coordinate is not finite");
+    if (flag & 2) return sg::fail(SG_EINVAL, "sg_pointcloud_knn: the coordinates are too large for the fp32 pair score");
+    return SG_OK;
+}
+
+int sg_pointcloud_normals(const float* d_xyz, int N, const int32_t* d_knn, int k, const float* h_viewpoint, float* d_normals, void* d_ws,
+                          size_t ws_bytes, void* stream) {
+    SG_REQUIRE(d_xyz && N > 0 && d_knn && d_normals && d_ws, "sg_pointcloud_normals: bad arguments");
+    int rc = check_k("sg_pointcloud_normals", N, k);
+    if (rc < 0) return rc;
+    if ((rc = viewpoint_ok("sg_pointcloud_normals", h_viewpoint)) < 0) return rc;
+    sg::Carver cv(d_ws, ws_bytes);
+    float4* cand = cv.take<float4>(N);
+    Misc* misc = cv.take<Misc>(1);
+    if (!cv.ok) return sg::fail(SG_ENOMEM, "sg_pointcloud_normals: workspace too small (%zu < %zu)", ws_bytes, sg_pointcloud_knn_ws_bytes(N));
+    hipStream_t st = sg::as_stream(stream);
+    k_pc_init<<<1, 1, 0, st>>>(misc, h_viewpoint != nullptr, h_viewpoint ? h_viewpoint[0] : 0.0f, h_viewpoint ? h_viewpoint[1] : 0.0f,
+                               h_viewpoint ? h_viewpoint[2] : 0.0f);
+    k_pc_pack<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(d_xyz, 3, N, cand, misc);
+    if (!h_viewpoint) k_pc_view<<<1, 1, 0, st>>>(misc);
+    launch_normals(d_xyz, 3, N, k, d_knn, misc, d_normals, st);
+    int flag = 0;
+    SG_HIP(hipMemcpyAsync(&flag, &misc->flag, 4, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (flag & 1) return sg::fail(SG_EINVAL, "sg_pointcloud_normals: a coordinate is not finite");
+    if (flag & 4) return sg::fail(SG_EINVAL, "sg_pointcloud_normals: a list names a point outside 0..%d", N - 1);
+    return SG_OK;
+}
+
+size_t sg_pcseg_ws_bytes(int N, int k) {
+    const size_t np = (size_t)std::max(N, 1), kk = (size_t)std::max(k, 1), n = np * kk;
+    return sg::align_up(np * 16) + sg::align_up(sizeof(Misc)) + sg::align_up(np * (kk + 1) * 4) + 3 * sg::align_up(n * 8) +
+           sg::align_up(sgsort::hist_ints((long long)n) * 4) + sg::align_up(sgsort::unique_ints((long long)n) * 4) + sg::align_up(n * 16) +
+           5 * sg::align_up(n * 4) + sg::align_up(np * 12) + sg::align_up(n * 8) + sg::align_up(n * 4);
+}
+
+int sg_pcseg_edges(const float* d_xyz, int N, int k, const float* h_viewpoint, int32_t* d_knn, float* d_normals, int32_t* d_edges, float* d_w,
+                   int* h_E, void* d_ws, size_t ws_bytes, void* stream) {
+    SG_REQUIRE(N > 0 && d_xyz && d_normals && d_edges && d_w && h_E && d_ws, "sg_pcseg_edges: bad arguments");
+    *h_E = 0;
+    int rc = check_k("sg_pcseg_edges", N, k);
+    if (rc < 0) return rc;
+    if ((rc = viewpoint_ok("sg_pcseg_edges", h_viewpoint)) < 0) return rc;
+    const Plan p = carve(d_ws, ws_bytes, N, k);
+    if (!p.ok) return sg::fail(SG_ENOMEM, "sg_pcseg_edges: workspace too small (%zu < %zu)", ws_bytes, sg_pcseg_ws_bytes(N, k));
+    hipStream_t st = sg::as_stream(stream);
+    const int n = N * k;
+    sgos::StageClock<kStages> clock(st, t_timing, t_stage_us);
+    // 0. the coordinates are the caller's
+    k_pc_init<<<1, 1, 0, st>>>(p.misc, h_viewpoint != nullptr, h_viewpoint ? h_viewpoint[0] : 0.0f, h_viewpoint ? h_viewpoint[1] : 0.0f,
+                               h_viewpoint ? h_viewpoint[2] : 0.0f);
+    k_pc_pack<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(d_xyz, 3, N, p.cand, p.misc);
+    int flag = 0;
+    SG_HIP(hipMemcpyAsync(&flag, &p.misc->flag, 4, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    if (flag & 1) return sg::fail(SG_EINVAL, "sg_pcseg_edges: a coordinate is not finite");
+    clock.tick();
+    // 1. the lists
+    int32_t* table = d_knn ? d_knn : p.knn;
+    launch_knn(p.cand, N, k, table, p.misc, st);
+    clock.tick();
+    // 2-5. normals
+    if (!h_viewpoint) k_pc_view<<<1, 1, 0, st>>>(p.misc);
+    launch_normals(reinterpret_cast<const float*>(p.cand), 4, N, k, table, p.misc, d_normals, st);
+    clock.tick();
+    // 6. the unique undirected pairs a < b in lexicographic order
+    k_pc_edge_keys<<<sg::cdiv(n, kBlock), kBlock, 0, st>>>(table, N, k, p.p0);
+    sgsort::Lists<unsigned long long, int> L{};
+    L.kin[0] = p.p0; L.kout[0] = p.p1; L.hist[0] = p.hist; L.n[0] = n;
+    const int field = std::min(32, bits_for((long long)N + 1) + 1);           // one bit more than an id carries: ~0 must come out last
+    sgsort::radix_sort<unsigned long long, int, false>(L, 1, 0, field, st);
+    sgsort::radix_sort<unsigned long long, int, false>(L, 1, 32, field, st);
+    unsigned long long* uniq = p.p2;
+    sgsort::unique_sorted<unsigned long long>(L.kin[0], n, uniq, nullptr, &p.misc->count, p.scratch, st);
+    int fc[2] = {0, 0};
+    SG_HIP(hipMemcpyAsync(fc, p.misc, 8, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (fc[0] & 2) return sg::fail(SG_EINVAL, "sg_pcseg_edges: the coordinates are too large for the fp32 pair score");
+    int E = fc[1];
+    if (E < 1 || E > n) return sg::fail(SG_EHIP, "sg_pcseg_edges: %d pair keys from %d points", E, N);
+    unsigned long long tail = 0;
+    SG_HIP(hipMemcpyAsync(&tail, uniq + E - 1, 8, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    if (tail == ~0ull) --E;                                                    // the self pairs, if any, collapsed into one trailing key
+    if (E > 0) k_pc_unpack<<<sg::cdiv(E, kBlock), kBlock, 0, st>>>(uniq, E, p.adj);
+    clock.tick();
+    if (E == 0) { SG_LAUNCH_CHECK(); return SG_OK; }
+    // 7. weights and keys, 8. ascending (w, a, b) and the gather: 8d's stages
+    k_pc_weights<<<sg::cdiv(E, kBlock), kBlock, 0, st>>>(p.adj, E, p.cand, d_normals, p.w, p.k0, p.v0);
+    clock.tick();
+    const int* order = sgos::sort_by_weight(p.k0, p.k1, p.v0, p.v1, p.hist, E, st);
+    clock.tick();
+    sgos::gather_edges(order, E, p.adj, p.w, d_edges, d_w, st);
+    clock.tick();
+    SG_LAUNCH_CHECK();
+    *h_E = E;
+    return SG_OK;
+}
+
+int sg_pcseg_scan(const float* d_xyz, int N, int k, const float* h_viewpoint, float k_thresh, int seg_min_verts, int32_t* h_seg_indices,
+                  void* d_ws, size_t ws_bytes, void* stream) {
+    SG_REQUIRE(N > 0 && d_xyz && h_seg_indices && d_ws, "sg_pcseg_scan: bad arguments");
+    const int rc0 = check_k("sg_pcseg_scan", N, k);
+    if (rc0 < 0) return rc0;
+    const Plan p = carve(d_ws, ws_bytes, N, k);
+    if (!p.ok) return sg::fail(SG_ENOMEM, "sg_pcseg_scan: workspace too small (%zu < %zu)", ws_bytes, sg_pcseg_ws_bytes(N, k));
+    int E = 0;
+    const int rc = sg_pcseg_edges(d_xyz, N, k, h_viewpoint, nullptr, p.vn, p.edges, p.w_sorted, &E, d_ws, ws_bytes, stream);
+    if (rc < 0) return rc;
+    std::vector<int32_t> h_edges((size_t)E * 2);
+    std::vector<float> h_w((size_t)E);
+    if (E > 0) {
+        hipStream_t st = sg::as_stream(stream);
+        SG_HIP(hipMemcpyAsync(h_edges.data(), p.edges, (size_t)E * 8, hipMemcpyDeviceToHost, st));
+        SG_HIP(hipMemcpyAsync(h_w.data(), p.w_sorted, (size_t)E * 4, hipMemcpyDeviceToHost, st));
+        SG_HIP(hipStreamSynchronize(st));
+    }
+    return sg_overseg_merge(h_edges.data(), h_w.data(), E, N, k_thresh, seg_min_verts, h_seg_indices);
+}
+
+}  // extern "C"

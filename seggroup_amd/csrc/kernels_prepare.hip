@@ -17,17 +17,12 @@
 // spatial index is not worth its exactness proof.
 #include "sg_common.h"
 #include "sort_device.h"
+#include "cloud_knn_device.h"
 
 namespace {
 
-constexpr int kTile = 256;      // candidates staged per LDS tile = queries per block
-
-// score of candidate c = (x, y, z, yy) for the query (qx, qy, qz) with squared norm qq, in the reference's order
-__device__ inline float pair_score(float qx, float qy, float qz, float qq, const float4& c) {
-    const float tt = __builtin_fmaf(qz, c.z, __builtin_fmaf(qy, c.y, qx * c.x));      // MKL's K=3 dot product
-    const float inner = -2.0f * tt;
-    return ((-qq) - inner) - c.w;
-}
+using sgcloud::kTile;          // candidates staged per LDS tile = queries per block
+using sgcloud::pair_score;     // cloud_knn_device.h: the score and the top-KK selection, shared with sg_pointcloud_knn (kernels_pcseg.hip)
 
 // [n,3] (row stride `stride` floats) -> float4 (x, y, z, (x*x + y*y) + z*z): torch.sum(y**2, dim=1)
 __global__ void k_pack_xyzw(const float* __restrict__ p, int stride, int n, float4* __restrict__ out) {
@@ -82,30 +77,7 @@ __global__ __launch_bounds__(kTile) void k_nearest_k(const float4* __restrict__ 
     const float4 me = cand[live ? u : 0];
     float bs[KK];
     int bi[KK];
-#pragma unroll
-    for (int t = 0; t < KK; ++t) { bs[t] = -INFINITY; bi[t] = 0x7fffffff; }
-    for (int c0 = 0; c0 < N; c0 += kTile) {
-        __syncthreads();
-        tile[threadIdx.x] = c0 + threadIdx.x < N ? cand[c0 + threadIdx.x] : make_float4(0.f, 0.f, 0.f, INFINITY);
-        __syncthreads();
-        const int m = min(kTile, N - c0);
-        for (int j = 0; j < m; ++j) {
-            const float sc = pair_score(me.x, me.y, me.z, me.w, tile[j]);
-            if (sc > bs[KK - 1]) {                             // candidates arrive in ascending index: `>` keeps the earlier one of a tie
-                float v = sc;
-                int id = c0 + j;
-                bool placed = false;
-#pragma unroll
-                for (int t = 0; t < KK; ++t) {
-                    if (placed || v > bs[t]) {
-                        placed = true;
-                        const float tv = bs[t]; const int ti = bi[t];
-                        bs[t] = v; bi[t] = id; v = tv; id = ti;
-                    }
-                }
-            }
-        }
-    }
+    sgcloud::top_scores<KK>(cand, N, me, tile, bs, bi);
     if (live) {
 #pragma unroll
         for (int t = 1; t < KK; ++t) {

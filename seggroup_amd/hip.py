@@ -115,6 +115,15 @@ SIGNATURES = {
     "sg_overseg_stage_times": (_I, [vp, _I]),
     "sg_overseg_stage_name": (C.c_char_p, [_I]),
     "sg_write_segs_json": (_I, [C.c_char_p, C.c_char_p, vp, _I, C.c_float, _I]),
+    "sg_pointcloud_knn_ws_bytes": (_Z, [_I]),
+    "sg_pointcloud_knn": (_I, [vp, _I, _I, _I, vp, vp, _Z, vp]),
+    "sg_pointcloud_normals": (_I, [vp, _I, vp, _I, vp, vp, vp, _Z, vp]),
+    "sg_pcseg_ws_bytes": (_Z, [_I, _I]),
+    "sg_pcseg_edges": (_I, [vp, _I, _I, vp, vp, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_pcseg_scan": (_I, [vp, _I, _I, vp, C.c_float, _I, vp, vp, _Z, vp]),
+    "sg_pcseg_set_timing": (_I, [_I]),
+    "sg_pcseg_stage_times": (_I, [vp, _I]),
+    "sg_pcseg_stage_name": (C.c_char_p, [_I]),
     "sg_segment_vote_ws_bytes": (_Z, [_I]),
     "sg_segment_rank": (_I, [vp, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_segment_vote": (_I, [vp, vp, _I, _I] + [vp] * 9 + [C.POINTER(C.c_int), vp, _Z, vp]),

@@ -1,4 +1,4 @@
-"""Mesh over-segmentation: a scan's `_vh_clean_2.ply` -> `<scene>_vh_clean_2.<kThresh>.segs.json`.
+"""Over-segmentation: a scan's `_vh_clean_2.ply` -> `<scene>_vh_clean_2.<kThresh>.segs.json` (DESIGN.md 8d for a mesh, 8f for a cloud).
 
 The over-segmentation is the one input of `prepare.py` / `labels.py` that used to come from outside (ScanNet ships it, made by its
 Segmentator tool).  This is a graph-based segmenter of the same family -- Felzenszwalb-Huttenlocher merging over the mesh edges,
@@ -9,7 +9,12 @@ it is NOT byte equality with the files ScanNet ships.
 Normals, edges, weights and the sort run on the GPU (`sg_overseg_edges`), the order-dependent merge chain on the host
 (`sg_overseg_merge`, usable without a GPU); there is no other path.
 
+A PLY without faces (a laser scan, a fused depth cloud) takes the point-cloud path on its own: the graph is the kNN graph of the cloud,
+the normals come from the covariance of every point's k + 1 nearest points (`sg_pcseg_edges`), the order of the edges and the chain are
+the mesh path's.  `--pointcloud` sends a mesh down that path too; its faces are ignored.
+
     python -m seggroup_amd.oversegment --scans DIR [--scenes LIST] [--k-thresh 0.01] [--seg-min-verts 20] [--force] [--workers 4]
+                                       [--pointcloud] [--knn {5,10,20}] [--viewpoint X Y Z]
 """
 from __future__ import annotations
 
@@ -114,6 +119,88 @@ def segment_mesh(xyz, faces, k_thresh: float = 0.01, seg_min_verts: int = 20, de
     return out
 
 
+def _cloud_tensor(xyz, dev):
+    import torch
+    from .prepare import _t
+    d_xyz = _t(xyz, torch.float32, dev)
+    if d_xyz.dim() != 2 or d_xyz.shape[1] != 3:
+        raise ValueError("oversegment: xyz must be [N,3]")
+    if d_xyz.shape[0] < 1:
+        raise ValueError("oversegment: a cloud needs at least one point")
+    return d_xyz, int(d_xyz.shape[0])
+
+
+def _viewpoint(viewpoint):
+    """-> (ctypes float[3] or None); the host array the library reads"""
+    if viewpoint is None:
+        return None
+    v = np.asarray(viewpoint, dtype=np.float32).reshape(-1)
+    if v.shape[0] != 3:
+        raise ValueError("oversegment: the viewpoint is three coordinates")
+    return (C.c_float * 3)(*v.tolist())
+
+
+def pointcloud_edges(xyz, k: int = 10, viewpoint=None, device=None, stream=None):
+    """The device stages of one cloud -> dict(knn [N,k+1] i32, normals [N,3], edges [E,2] i32, w [E]) of device tensors:
+    every point's k + 1 best-scoring points, the covariance normals turned towards the viewpoint (default: the centre of the bounding
+    box), and the unique undirected kNN pairs a < b in ascending (w, a, b)."""
+    import torch
+    from .prepare import _dev, _ws
+    dev = _dev(device)
+    lib = hip.lib()
+    k = int(k)
+    with torch.cuda.device(dev), _on(stream):
+        d_xyz, n = _cloud_tensor(xyz, dev)
+        knn = torch.empty((n, k + 1), dtype=torch.int32, device=dev)
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        edges = torch.empty((max(n * k, 1), 2), dtype=torch.int32, device=dev)
+        w = torch.empty(max(n * k, 1), dtype=torch.float32, device=dev)
+        ws = _ws(lib.sg_pcseg_ws_bytes(n, k), dev)
+        n_e = C.c_int(0)
+        hip.check(lib.sg_pcseg_edges(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), knn.data_ptr(), nrm.data_ptr(), edges.data_ptr(),
+                                     w.data_ptr(), C.byref(n_e), ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+        (stream.synchronize() if stream is not None else torch.cuda.synchronize())
+    return dict(knn=knn, normals=nrm, edges=edges[:n_e.value], w=w[:n_e.value])
+
+
+def pointcloud_normals(xyz, k: int = 10, viewpoint=None, knn=None, device=None):
+    """-> [N,3] f32 device tensor: per point the eigenvector of the smallest eigenvalue of its k + 1 nearest points' covariance, not
+    re-normalised, turned towards the viewpoint.  `knn`: a table of `prepare.pointcloud_knn` (made when not given)."""
+    import torch
+    from .prepare import _dev, _t, _ws, pointcloud_knn
+    dev = _dev(device)
+    lib = hip.lib()
+    k = int(k)
+    with torch.cuda.device(dev):
+        d_xyz, n = _cloud_tensor(xyz, dev)
+        table = pointcloud_knn(d_xyz, k, device=dev) if knn is None else _t(knn, torch.int32, dev)
+        if table.dim() != 2 or tuple(table.shape) != (n, k + 1):
+            raise ValueError("pointcloud_normals: knn must be [N, k+1]")
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        ws = _ws(lib.sg_pointcloud_knn_ws_bytes(n), dev)
+        hip.check(lib.sg_pointcloud_normals(d_xyz.data_ptr(), n, table.data_ptr(), k, _viewpoint(viewpoint), nrm.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), None))
+        torch.cuda.synchronize()
+    return nrm
+
+
+def segment_pointcloud(xyz, k: int = 10, k_thresh: float = 0.01, seg_min_verts: int = 20, viewpoint=None, device=None,
+                       stream=None) -> np.ndarray:
+    """-> int32 [N]: seg_indices[i] = the lowest point index of i's segment, for a cloud without faces."""
+    import torch
+    from .prepare import _dev, _ws
+    dev = _dev(device)
+    lib = hip.lib()
+    k = int(k)
+    with torch.cuda.device(dev), _on(stream):
+        d_xyz, n = _cloud_tensor(xyz, dev)
+        out = np.empty(n, dtype=np.int32)
+        ws = _ws(lib.sg_pcseg_ws_bytes(n, k), dev)
+        hip.check(lib.sg_pcseg_scan(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), float(k_thresh), int(seg_min_verts), out.ctypes.data,
+                                    ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+    return out
+
+
 def write_segs_json(path: str, seg_indices, scene_id: str, k_thresh: float = 0.01, seg_min_verts: int = 20) -> None:
     seg = np.ascontiguousarray(np.asarray(seg_indices), dtype=np.int32).reshape(-1)
     hip.check(hip.lib().sg_write_segs_json(os.fspath(path).encode(), scene_id.encode(), seg.ctypes.data if seg.size else None, seg.shape[0],
@@ -121,9 +208,10 @@ def write_segs_json(path: str, seg_indices, scene_id: str, k_thresh: float = 0.0
 
 
 def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int = 20, force: bool = False, device=None, stream=None,
-                     plydata=None) -> Optional[str]:
+                     plydata=None, pointcloud: bool = False, knn: int = 10, viewpoint=None) -> Optional[str]:
     """Writes the scan's segs.json next to its mesh; -> the path, or None when the file was there already (never overwritten without
-    `force`)."""
+    `force`).  A scan without faces is segmented as a point cloud (`knn` neighbours, normals towards `viewpoint`); `pointcloud=True`
+    does the same to a mesh, ignoring its faces."""
     from .prepare import _scene_name, mesh_arrays, read_ply
     name = _scene_name(scene_path)
     out = os.path.join(scene_path, segs_json_name(name, k_thresh))
@@ -132,13 +220,16 @@ def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int
     if plydata is None:
         plydata = read_ply(os.path.join(scene_path, name + "_vh_clean_2.ply"))
     xyz, _, faces = mesh_arrays(plydata)
-    seg = segment_mesh(xyz, faces, k_thresh, seg_min_verts, device=device, stream=stream)
+    if pointcloud or faces.shape[0] == 0:
+        seg = segment_pointcloud(xyz, knn, k_thresh, seg_min_verts, viewpoint=viewpoint, device=device, stream=stream)
+    else:
+        seg = segment_mesh(xyz, faces, k_thresh, seg_min_verts, device=device, stream=stream)
     write_segs_json(out, seg, name, k_thresh, seg_min_verts)
     return out
 
 
 def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_min_verts: int = 20, force: bool = False, workers: int = 4,
-                      device=None):
+                      device=None, pointcloud: bool = False, knn: int = 10, viewpoint=None):
     """Every scan directory under `scans_dir` (or the named ones) -> (written paths, skipped scene names).  Workers are threads, each
     with its own stream and workspace: the host chain of one scan overlaps the device work of the next."""
     import concurrent.futures
@@ -156,7 +247,8 @@ def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_m
         if not hasattr(local, "stream"):
             with torch.cuda.device(dev):
                 local.stream = torch.cuda.Stream(device=dev)
-        return scene, oversegment_scan(os.path.join(scans_dir, scene), k_thresh, seg_min_verts, force, device=dev, stream=local.stream)
+        return scene, oversegment_scan(os.path.join(scans_dir, scene), k_thresh, seg_min_verts, force, device=dev, stream=local.stream,
+                                       pointcloud=pointcloud, knn=knn, viewpoint=viewpoint)
 
     written, skipped = [], []
     with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
@@ -174,12 +266,17 @@ def main(argv=None) -> int:
     ap.add_argument("--force", action="store_true", help="overwrite existing segs.json files")
     ap.add_argument("--workers", type=int, default=4, help=f"threads, each with its own stream (at most {MAX_WORKERS})")
     ap.add_argument("--device", default=None)
+    ap.add_argument("--pointcloud", action="store_true", help="segment every scan as a point cloud (a scan without faces always is); faces are ignored")
+    ap.add_argument("--knn", type=int, default=10, choices=(5, 10, 20), help="neighbours per point of the point-cloud path")
+    ap.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
+                    help="the point-cloud path turns its normals towards this point (default: the centre of the bounding box)")
     a = ap.parse_args(argv)
     scenes = None
     if a.scenes:
         with open(a.scenes) as f:
             scenes = [ln.strip() for ln in f if ln.strip()]
-    written, skipped = oversegment_scans(a.scans, scenes, a.k_thresh, a.seg_min_verts, a.force, a.workers, a.device)
+    written, skipped = oversegment_scans(a.scans, scenes, a.k_thresh, a.seg_min_verts, a.force, a.workers, a.device, pointcloud=a.pointcloud,
+                                         knn=a.knn, viewpoint=a.viewpoint)
     for p in written:
         print("wrote", p)
     for s in skipped:

@@ -109,12 +109,23 @@ def write_ply(path: str, xyz, rgb, faces) -> None:
         f.write(fc.tobytes())
 
 
+def has_faces(plydata) -> bool:
+    """False for a point cloud: a PLY without a face element, or with an empty one."""
+    try:
+        return plydata["face"].count > 0
+    except KeyError:
+        return False
+
+
 def mesh_arrays(plydata):
-    """-> xyz f32 [V,3], rgb u8 [V,3], faces i32 [F,3] from a PlyMesh / plyfile.PlyData."""
-    vtx, face = plydata["vertex"], plydata["face"]
+    """-> xyz f32 [V,3], rgb u8 [V,3], faces i32 [F,3] from a PlyMesh / plyfile.PlyData.  A PLY without a face element, or with an
+    empty one (a point cloud), gives faces of shape [0,3]."""
+    vtx = plydata["vertex"]
     xyz = np.stack([np.asarray(vtx[k], dtype=np.float32) for k in ("x", "y", "z")], 1)
     rgb = np.stack([np.asarray(vtx[k], dtype=np.uint8) for k in ("red", "green", "blue")], 1)
-    vi = face["vertex_indices"]
+    if not has_faces(plydata):
+        return np.ascontiguousarray(xyz), np.ascontiguousarray(rgb), np.zeros((0, 3), np.int32)
+    vi = plydata["face"]["vertex_indices"]
     faces = np.asarray(vi, dtype=np.int32) if isinstance(vi, np.ndarray) and vi.ndim == 2 else \
         np.stack([np.asarray(x, dtype=np.int32) for x in vi]) if len(vi) else np.zeros((0, 3), np.int32)
     if faces.ndim != 2 or faces.shape[1] != 3:
@@ -244,6 +255,38 @@ def get_adj_from_pointcloud(pointcloud, k=10, device=None):
     return out[:cnt.value].cpu()
 
 
+def pointcloud_knn(pointcloud, k=10, device=None):
+    """-> int32 [N, k+1] device tensor: the complete top-(k + 1) list of every point against the whole cloud, in the scores and the tie
+    rule of get_adj_from_pointcloud (descending score, the lower index first); entry 0, normally the point itself, is kept."""
+    import torch
+    dev = _dev(device)
+    lib = hip.lib()
+    pts = _t(pointcloud, torch.float32, dev)
+    if pts.dim() != 2 or pts.shape[1] < 3:
+        raise ValueError("pointcloud_knn: the cloud must be [N, >= 3]")
+    n, stride = int(pts.shape[0]), int(pts.shape[1])
+    out = torch.empty((n, int(k) + 1), dtype=torch.int32, device=dev)
+    ws = _ws(lib.sg_pointcloud_knn_ws_bytes(n), dev)
+    with torch.cuda.device(dev):
+        hip.check(lib.sg_pointcloud_knn(pts.data_ptr(), stride, n, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), None))
+        torch.cuda.synchronize()
+    return out
+
+
+def get_adj_from_cloud_scan(xyz, unmapper=None, k=10, device=None):
+    """A scan without faces: the point graph stands in for the mesh edges.  -> (adj, adj_resampled): get_adj_from_pointcloud(xyz, k), and
+    those rows mapped through the unmapper, per-row sorted and unique, rows with i == j dropped like get_adj_from_mesh drops them."""
+    import torch
+    raw = get_adj_from_pointcloud(xyz, k, device=device)
+    if unmapper is None:
+        return raw, None
+    un = torch.as_tensor(unmapper, dtype=torch.long).cpu()
+    raw_ne = raw[raw[:, 0] != raw[:, 1]]
+    res = torch.sort(un[raw_ne], dim=1)[0]
+    res = torch.unique(res, dim=0) if res.shape[0] else res.reshape(0, 2)
+    return raw, res
+
+
 # ---- the reference's file-producing functions -------------------------------------------------------------------------
 def _scene_name(scene_path: str) -> str:
     return os.path.split(scene_path[:-1] if scene_path.endswith("/") else scene_path)[-1]
@@ -301,8 +344,9 @@ def generate_seg_labels_and_ds_set(scene_path, root: str = ".", device=None):
                                     h_off.shape[0] - 1, h_pts.shape[0]))
 
 
-def generate_mesh_adjcency_pth(scene_name, plydata=None, root: str = ".", scene_path: Optional[str] = None, device=None):
-    """util.py:795-811: adj/mesh/raw/<s>/<s>.adj.pth and adj/mesh/resampled/<s>/<s>.adj.pth (skipped when both exist)."""
+def generate_mesh_adjcency_pth(scene_name, plydata=None, root: str = ".", scene_path: Optional[str] = None, device=None, knn: int = 10):
+    """util.py:795-811: adj/mesh/raw/<s>/<s>.adj.pth and adj/mesh/resampled/<s>/<s>.adj.pth (skipped when both exist).  A scan without
+    faces gets the kNN graph of its points (`knn` neighbours) under the same names."""
     import torch
     p1 = os.path.join(root, "adj", "mesh", "raw", scene_name, scene_name + ".adj.pth")
     p2 = os.path.join(root, "adj", "mesh", "resampled", scene_name, scene_name + ".adj.pth")
@@ -313,7 +357,10 @@ def generate_mesh_adjcency_pth(scene_name, plydata=None, root: str = ".", scene_
             raise ValueError("generate_mesh_adjcency_pth: pass plydata or scene_path")
         plydata = read_ply(os.path.join(scene_path, scene_name + "_vh_clean_2.ply"))
     unmapper = torch.load(os.path.join(root, "data", "resampled", scene_name, scene_name + ".unmap.pth"))
-    adj, adj_resampled = get_adj_from_mesh(plydata, unmapper, device=device)
+    if not has_faces(plydata):
+        adj, adj_resampled = get_adj_from_cloud_scan(mesh_arrays(plydata)[0], unmapper, knn, device=device)
+    else:
+        adj, adj_resampled = get_adj_from_mesh(plydata, unmapper, device=device)
     for p, t in ((p1, adj), (p2, adj_resampled)):
         os.makedirs(os.path.dirname(p), exist_ok=True)
         torch.save(t, p)
@@ -325,19 +372,22 @@ from .labels import (generate_real_label_pth, generate_real_labels, generate_seg
 
 
 def prepare_scene(scene_path, item, num_points: int = 150000, root: str = ".", perm=None, device=None, label_style: Optional[str] = None,
-                  manual_label_path: Optional[str] = None, oversegment: bool = False):
+                  manual_label_path: Optional[str] = None, oversegment: bool = False, knn: int = 10):
     """What prepare_data.py:36-71 + prepare_weak_label.py:60-90 do for one scan: point cloud, mapper / unmapper, segment lists,
     mesh adjacency and -- with `label_style` and ScanNet's annotation files next to the mesh -- the ground-truth and weak-label
     files, i.e. every input of SegModel.forward.  `oversegment=True`: a scan without a segs.json gets one from its mesh first
-    (oversegment.py, default parameters); an existing file is never overwritten."""
+    (oversegment.py, default parameters); an existing file is never overwritten.  A scan without faces (a point cloud) is segmented
+    over the kNN graph of its points (`knn` neighbours), and that graph stands in for the mesh adjacency."""
     scene_name = _scene_name(scene_path)
     ply = read_ply(os.path.join(scene_path, scene_name + "_vh_clean_2.ply"))
     if oversegment:
         from .oversegment import oversegment_scan
-        oversegment_scan(scene_path, device=device, plydata=ply)
+        oversegment_scan(scene_path, device=device, plydata=ply, knn=knn)
+    elif not has_faces(ply) and not os.path.exists(os.path.join(scene_path, scene_name + "_vh_clean_2.0.010000.segs.json")):
+        raise ValueError(f"{scene_name}: a scan without faces and without a segs.json: pass oversegment=True to make one from the points")
     generate_pointcloud_pth(scene_path, item, num_points, ply, root=root, perm=perm, device=device)
     generate_seg_labels_and_ds_set(scene_path, root=root, device=device)
-    generate_mesh_adjcency_pth(scene_name, ply, root=root, device=device)
+    generate_mesh_adjcency_pth(scene_name, ply, root=root, device=device, knn=knn)
     if label_style is not None:
         generate_real_labels(scene_path, root=root)
         generate_real_label_pth(scene_path, root=root)
