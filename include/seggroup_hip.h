@@ -842,6 +842,25 @@ int sg_pcseg_set_timing(int on);
 int sg_pcseg_stage_times(float* h_us, int cap);
 const char* sg_pcseg_stage_name(int i);
 
+/* Voxel thinning of a large cloud: one input point per occupied voxel of edge `voxel`, and every point's thinned point.
+ * The cell of a point is floor((p - lo) / voxel) per axis, lo = the cloud's minimum; a voxel's representative is its point nearest the
+ * cell centre (fp32, op by op as 8g writes it), the lowest index among equals.  d_points rows of `stride` floats, xyz first.
+ *   *h_M = occupied voxels; d_rep[0..M) = the representatives' indices, ASCENDING (not in voxel order); d_thin_of_point[i] = j where
+ *   d_rep[j] stands for i's voxel.  Both need room for N entries.  h_lo3 (may be NULL) receives lo.  Integers only: the same bytes on
+ *   every run.  1 <= N <= SG_MAX_CLOUD_POINTS (above: SG_EUNSUP; the kNN's SG_MAX_POINTS does not apply here).
+ * SG_EINVAL: a null pointer, stride < 3, N < 1, voxel not finite or <= 0, a workspace below sg_cloud_thin_ws_bytes(N) (all before the
+ *   first HIP call), a coordinate that is not finite (checked on the device before anything else).  SG_EUNSUP: an axis with 2^21 cells
+ *   or more ("voxel too small for the cloud's extent").
+ * Synchronises the stream twice (check and box, voxel count); the outputs are ordered on the stream.
+ * Stage times by events, as sg_overseg_set_timing: room for 6 floats (tools/time_thin.py). */
+#define SG_MAX_CLOUD_POINTS (1 << 27)
+size_t sg_cloud_thin_ws_bytes(int N);          /* 0 when N < 1 or N > SG_MAX_CLOUD_POINTS */
+int sg_cloud_thin(const float* d_points, int stride, int N, float voxel, int32_t* d_rep, int32_t* d_thin_of_point, int* h_M,
+                  float* h_lo3, void* d_ws, size_t ws_bytes, void* stream);
+int sg_cloud_thin_set_timing(int on);
+int sg_cloud_thin_stage_times(float* h_us, int cap);
+const char* sg_cloud_thin_stage_name(int i);
+
 /* Segment vote: what re-keying a scan's annotations onto another over-segmentation needs on the device.  Every vertex has a
  * row id d_ids[v] (any non-negative int32: not contiguous, may exceed V) and a column d_cols[v] in 0..n_cols-1; both are checked on the
  * device (SG_EINVAL).  Rows come out in ascending id order, *h_R of them; every output needs room for V entries.

@@ -124,6 +124,11 @@ SIGNATURES = {
     "sg_pcseg_set_timing": (_I, [_I]),
     "sg_pcseg_stage_times": (_I, [vp, _I]),
     "sg_pcseg_stage_name": (C.c_char_p, [_I]),
+    "sg_cloud_thin_ws_bytes": (_Z, [_I]),
+    "sg_cloud_thin": (_I, [vp, _I, _I, C.c_float, vp, vp, C.POINTER(C.c_int), vp, vp, _Z, vp]),
+    "sg_cloud_thin_set_timing": (_I, [_I]),
+    "sg_cloud_thin_stage_times": (_I, [vp, _I]),
+    "sg_cloud_thin_stage_name": (C.c_char_p, [_I]),
     "sg_segment_vote_ws_bytes": (_Z, [_I]),
     "sg_segment_rank": (_I, [vp, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_segment_vote": (_I, [vp, vp, _I, _I] + [vp] * 9 + [C.POINTER(C.c_int), vp, _Z, vp]),

@@ -13,8 +13,11 @@ A PLY without faces (a laser scan, a fused depth cloud) takes the point-cloud pa
 the normals come from the covariance of every point's k + 1 nearest points (`sg_pcseg_edges`), the order of the edges and the chain are
 the mesh path's.  `--pointcloud` sends a mesh down that path too; its faces are ignored.
 
+A cloud above 2^20 points is thinned on a voxel grid first (`voxel=H` / `--voxel H`): the segmenter sees one point per
+occupied voxel, and every point takes the id of its voxel's representative.
+
     python -m seggroup_amd.oversegment --scans DIR [--scenes LIST] [--k-thresh 0.01] [--seg-min-verts 20] [--force] [--workers 4]
-                                       [--pointcloud] [--knn {5,10,20}] [--viewpoint X Y Z]
+                                       [--pointcloud] [--knn {5,10,20}] [--viewpoint X Y Z] [--voxel H]
 """
 from __future__ import annotations
 
@@ -185,13 +188,28 @@ def pointcloud_normals(xyz, k: int = 10, viewpoint=None, knn=None, device=None):
 
 
 def segment_pointcloud(xyz, k: int = 10, k_thresh: float = 0.01, seg_min_verts: int = 20, viewpoint=None, device=None,
-                       stream=None) -> np.ndarray:
-    """-> int32 [N]: seg_indices[i] = the lowest point index of i's segment, for a cloud without faces."""
+                       stream=None, voxel: Optional[float] = None) -> np.ndarray:
+    """-> int32 [N]: seg_indices[i] = the lowest point index of i's segment, for a cloud without faces.
+
+    `voxel`: thin the cloud on a grid of that edge first and segment the representatives with the same parameters -- the
+    segmenter sees only the thinned cloud (its default viewpoint is that cloud's box centre, `seg_min_verts` counts thinned points) --;
+    every point then takes its representative's id, as a raw index: rep[seg_thin[thin_of_point]], the segment's lowest representative.
+    That is how a cloud above 2^20 points is segmented; a grid that leaves every point alone gives the un-thinned ids."""
     import torch
     from .prepare import _dev, _ws
     dev = _dev(device)
     lib = hip.lib()
     k = int(k)
+    if voxel is not None:
+        from .thin import thin_cloud
+        with torch.cuda.device(dev), _on(stream):
+            d_all = _cloud_tensor(xyz, dev)[0]
+        rep, top, _ = thin_cloud(d_all, voxel, device=dev, stream=stream)
+        with torch.cuda.device(dev), _on(stream):
+            d_thin = d_all.index_select(0, rep.long())
+        seg_thin = segment_pointcloud(d_thin, k, k_thresh, seg_min_verts, viewpoint=viewpoint, device=dev, stream=stream)
+        rep_h = rep.cpu().numpy()
+        return np.ascontiguousarray(rep_h[seg_thin[top.cpu().numpy()]], dtype=np.int32)
     with torch.cuda.device(dev), _on(stream):
         d_xyz, n = _cloud_tensor(xyz, dev)
         out = np.empty(n, dtype=np.int32)
@@ -208,10 +226,11 @@ def write_segs_json(path: str, seg_indices, scene_id: str, k_thresh: float = 0.0
 
 
 def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int = 20, force: bool = False, device=None, stream=None,
-                     plydata=None, pointcloud: bool = False, knn: int = 10, viewpoint=None) -> Optional[str]:
+                     plydata=None, pointcloud: bool = False, knn: int = 10, viewpoint=None, voxel: Optional[float] = None) -> Optional[str]:
     """Writes the scan's segs.json next to its mesh; -> the path, or None when the file was there already (never overwritten without
     `force`).  A scan without faces is segmented as a point cloud (`knn` neighbours, normals towards `viewpoint`); `pointcloud=True`
-    does the same to a mesh, ignoring its faces."""
+    does the same to a mesh, ignoring its faces.  `voxel`: the point-cloud path thins on that grid first (`segment_pointcloud`); on the
+    mesh path it is an error, not ignored."""
     from .prepare import _scene_name, mesh_arrays, read_ply
     name = _scene_name(scene_path)
     out = os.path.join(scene_path, segs_json_name(name, k_thresh))
@@ -221,7 +240,9 @@ def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int
         plydata = read_ply(os.path.join(scene_path, name + "_vh_clean_2.ply"))
     xyz, _, faces = mesh_arrays(plydata)
     if pointcloud or faces.shape[0] == 0:
-        seg = segment_pointcloud(xyz, knn, k_thresh, seg_min_verts, viewpoint=viewpoint, device=device, stream=stream)
+        seg = segment_pointcloud(xyz, knn, k_thresh, seg_min_verts, viewpoint=viewpoint, device=device, stream=stream, voxel=voxel)
+    elif voxel is not None:
+        raise ValueError(f"{name}: voxel thinning belongs to the point-cloud path; this scan is a mesh (pass pointcloud=True to ignore its faces)")
     else:
         seg = segment_mesh(xyz, faces, k_thresh, seg_min_verts, device=device, stream=stream)
     write_segs_json(out, seg, name, k_thresh, seg_min_verts)
@@ -229,7 +250,7 @@ def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int
 
 
 def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_min_verts: int = 20, force: bool = False, workers: int = 4,
-                      device=None, pointcloud: bool = False, knn: int = 10, viewpoint=None):
+                      device=None, pointcloud: bool = False, knn: int = 10, viewpoint=None, voxel: Optional[float] = None):
     """Every scan directory under `scans_dir` (or the named ones) -> (written paths, skipped scene names).  Workers are threads, each
     with its own stream and workspace: the host chain of one scan overlaps the device work of the next."""
     import concurrent.futures
@@ -248,13 +269,25 @@ def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_m
             with torch.cuda.device(dev):
                 local.stream = torch.cuda.Stream(device=dev)
         return scene, oversegment_scan(os.path.join(scans_dir, scene), k_thresh, seg_min_verts, force, device=dev, stream=local.stream,
-                                       pointcloud=pointcloud, knn=knn, viewpoint=viewpoint)
+                                       pointcloud=pointcloud, knn=knn, viewpoint=viewpoint, voxel=voxel)
 
     written, skipped = [], []
     with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
         for scene, path in pool.map(one, scenes):
             (written.append(path) if path is not None else skipped.append(scene))
     return written, skipped
+
+
+def _declared_faces(ply_path: str) -> int:
+    """the face count a PLY's header declares (0 without a face element); the body is not read"""
+    with open(ply_path, "rb") as f:
+        for _ in range(256):
+            tok = f.readline().split()
+            if not tok or tok[0] == b"end_header":
+                break
+            if len(tok) == 3 and tok[0] == b"element" and tok[1] == b"face":
+                return int(tok[2])
+    return 0
 
 
 def main(argv=None) -> int:
@@ -270,13 +303,21 @@ def main(argv=None) -> int:
     ap.add_argument("--knn", type=int, default=10, choices=(5, 10, 20), help="neighbours per point of the point-cloud path")
     ap.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                     help="the point-cloud path turns its normals towards this point (default: the centre of the bounding box)")
+    ap.add_argument("--voxel", type=float, default=None, metavar="H",
+                    help="the point-cloud path thins the cloud on a voxel grid of this edge first (needed above 2^20 points)")
     a = ap.parse_args(argv)
     scenes = None
     if a.scenes:
         with open(a.scenes) as f:
             scenes = [ln.strip() for ln in f if ln.strip()]
+    if a.voxel is not None and not a.pointcloud:
+        names = scenes if scenes is not None else sorted(d for d in os.listdir(a.scans) if os.path.exists(os.path.join(a.scans, d, d + "_vh_clean_2.ply")))
+        meshes = [s for s in names if _declared_faces(os.path.join(a.scans, s, s + "_vh_clean_2.ply")) > 0]
+        if meshes:
+            ap.error("--voxel thins point clouds, and %s %s faces: add --pointcloud to ignore them" % (", ".join(meshes[:5]),
+                                                                                                       "has" if len(meshes) == 1 else "have"))
     written, skipped = oversegment_scans(a.scans, scenes, a.k_thresh, a.seg_min_verts, a.force, a.workers, a.device, pointcloud=a.pointcloud,
-                                         knn=a.knn, viewpoint=a.viewpoint)
+                                         knn=a.knn, viewpoint=a.viewpoint, voxel=a.voxel)
     for p in written:
         print("wrote", p)
     for s in skipped:
