@@ -861,6 +861,41 @@ int sg_cloud_thin_set_timing(int on);
 int sg_cloud_thin_stage_times(float* h_us, int cap);
 const char* sg_cloud_thin_stage_name(int i);
 
+/* Exact grid-indexed kNN: sg_pointcloud_knn's table, bit for bit, from a uniform grid over the bounding box.  A query walks
+ * the cells round its own in rings and stops once  Lb > delta - s_kth : Lb a true lower bound of the squared distance to every point it
+ * has not seen, delta = 2^-19 * max|p|^2 a bound of the pair score's distance from -d^2.  Queries that are not settled within the ring
+ * limit are finished against the whole cloud, so neither the cell edge nor the ring limit can change a result; both only cost time.
+ *   cell = 0: the library picks the edge from the data (a first guess, the occupied cells counted, one correction); cell > 0 forces it.
+ *   k in {5, 10, 20} (else SG_EUNSUP); N <= k is SG_EINVAL; N > SG_MAX_GRID_POINTS is SG_EUNSUP (checked before anything is touched).
+ *   SG_EINVAL: a coordinate that is not finite.  SG_EUNSUP: 4 * max|p|^2 or delta not finite (the message names sg_pointcloud_knn, which
+ *   decides such a cloud); a forced cell that gives an axis 2^21 cells or more, or more cells than the dense table's max(2^22, 4 N).
+ *   SG_ENOMEM: a workspace below sg_pointcloud_knn_grid_ws_bytes(N, k) (0 when N or k is outside the envelope).
+ * A cloud whose points crowd into one cell (a million coincident points) stays exact and costs what brute force costs.
+ * Synchronises the stream (box; the occupied cells when the library picks the edge; the queue's length).
+ * Stage times by events, as sg_overseg_set_timing: room for 7 floats.  sg_pointcloud_knn_grid_stats: the calling thread's last call ->
+ *   h[0..2] cells per axis, h[3] occupied cells, h[4] the largest cell, h[5] the bits of the fp32 cell edge, h[6] the largest ring count of
+ *   a query the rings settled, h[7] queries finished against the whole cloud, h[8] pair scores evaluated (counted in timed calls only).
+ * sg_pointcloud_knn_grid_set_tuning: the calling thread's target occupancy (points per occupied cell) and ring limit; 0 = the default
+ *   (tools/time_knn_grid.py sweeps them).
+ * The indexed twins of the point-cloud segmenter take index = SG_KNN_BRUTE (exactly the functions above, SG_MAX_POINTS included) or
+ *   SG_KNN_GRID (lists from sg_pointcloud_knn_grid with `cell`, up to SG_MAX_GRID_POINTS); every later stage is the same code. */
+#define SG_MAX_GRID_POINTS (1 << 24)
+#define SG_KNN_BRUTE 0
+#define SG_KNN_GRID 1
+size_t sg_pointcloud_knn_grid_ws_bytes(int N, int k);
+int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, float cell, int32_t* d_knn, void* d_ws, size_t ws_bytes,
+                           void* stream);
+int sg_pointcloud_knn_grid_set_timing(int on);
+int sg_pointcloud_knn_grid_stage_times(float* h_us, int cap);
+const char* sg_pointcloud_knn_grid_stage_name(int i);
+int sg_pointcloud_knn_grid_stats(int64_t* h, int cap);
+int sg_pointcloud_knn_grid_set_tuning(int target_occupancy, int ring_limit);
+size_t sg_pcseg_ws_bytes_indexed(int N, int k, int index);
+int sg_pcseg_edges_indexed(const float* d_xyz, int N, int k, const float* h_viewpoint, int index, float cell, int32_t* d_knn, float* d_normals,
+                           int32_t* d_edges, float* d_w, int* h_E, void* d_ws, size_t ws_bytes, void* stream);
+int sg_pcseg_scan_indexed(const float* d_xyz, int N, int k, const float* h_viewpoint, int index, float cell, float k_thresh, int seg_min_verts,
+                          int32_t* h_seg_indices, void* d_ws, size_t ws_bytes, void* stream);
+
 /* Segment vote: what re-keying a scan's annotations onto another over-segmentation needs on the device.  Every vertex has a
  * row id d_ids[v] (any non-negative int32: not contiguous, may exceed V) and a column d_cols[v] in 0..n_cols-1; both are checked on the
  * device (SG_EINVAL).  Rows come out in ascending id order, *h_R of them; every output needs room for V entries.

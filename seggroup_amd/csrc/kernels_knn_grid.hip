@@ -1,0 +1,564 @@
+// Exact grid-indexed kNN of a point cloud: the table of sg_pointcloud_knn -- every point's k + 1 best-scoring points of the
+// WHOLE cloud in sgcloud::pair_score, descending score, the lower original index first among equal scores -- bit for bit, without scoring
+// every pair.  A uniform grid over the bounding box; a query walks the cells round its own in rings and stops once no point outside the
+// block it has seen can reach its list: the rule is  Lb > delta - s_kth  with Lb a true lower bound of the squared distance to any unseen
+// point and delta = 2^-19 * max|p|^2 a bound of |score + d^2| (the score is not the distance: its rounding error grows with |p|^2).
+// Queries the rings do not settle are queued and finished by sgcloud::top_scores over the whole cloud, so the ring limit is a
+// performance knob only, as is the cell edge.
+//
+//   k_grid_box          coordinates finite (one flag word), (x, y, z, |p|^2) per point, the bounding box, M2 = max |p|^2
+//   k_grid_cells        per point its cell on 8g's formula floor((p - lo) / h) and the key (cz * ny + cy) * nx + cx: x runs fastest, so
+//                       the cells (cx - r .. cx + r, y, z) of one row are ONE contiguous range of the sorted points
+//   sort                stable radix sort of (key, index) over the key's bits in use (sort_device.h); k_grid_gather: the points in sorted order
+//   k_grid_table        dense: start[c] = the first sorted point whose key is >= c, c = 0 .. cells; k_grid_cellstats: occupied, the largest
+//   k_grid_search       one wave per 64 sorted points.  The lanes of one cell form a group and share their candidates: the rows of the
+//                       block are staged through LDS in tiles of 256 (float4 + original index), every lane of the group scores its own
+//                       query and inserts by (score, original index) into a register list.  Ring 1 is the 3 x 3 x 3 block, ring r adds
+//                       the shell at Chebyshev distance r; a group stops when all its lanes are settled or its block covers the grid.
+//   k_grid_fallback     the queued queries against the whole cloud in original order (cloud_knn_device.h)
+//
+// The lists are written at the ORIGINAL row with ORIGINAL indices.  Plain launches, vector stores.
+#include <cmath>
+#include <cstring>
+
+#include "sg_common.h"
+#include "sort_device.h"
+#include "cloud_knn_device.h"
+#include "overseg_device.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWave = 64;                       // queries per block of the search: one wave
+constexpr int kGTile = 256;                     // candidates staged per LDS tile of the search
+constexpr int kBoxBlocks = 1024;
+constexpr float kCellLimit = 2097152.0f;        // 2^21 cells per axis, as in 8g
+constexpr int kMinCells = 1 << 22;              // the dense table holds max(2^22, 4 N) cells
+constexpr int kTargetOccupancy = 48;            // points per occupied cell the library aims at
+constexpr int kRingLimit = 8;
+constexpr int kMaxRingLimit = 64;
+constexpr float kShrink = 0.998046875f;         // 1 - 2^-9: swallows every rounding of the settled test
+constexpr int kNumStats = 9;
+using sgcloud::kTile;
+
+struct Misc {
+    unsigned long long evals;       // pair scores evaluated (timed calls only)
+    int flag;                       // |= 1: a coordinate is not finite
+    int nq;                         // queued queries
+    int maxring;                    // the largest ring count of a settled query
+    int heads;                      // occupied cells of the probe
+    int occupied, maxcell;          // of the grid in use
+    unsigned int m2;                // bits of max |p|^2 (non-negative: ascending as unsigned)
+    unsigned int lo[3], hi[3];      // the bounding box as sgos::weight_key words
+};
+
+struct Grid {
+    float lo[3];
+    float h;
+    int nc[3];
+    int ncells;
+    float delta, slack;
+    int rmax;
+};
+
+inline float unkey_host(unsigned int k) {
+    const unsigned int b = k & 0x80000000u ? k ^ 0x80000000u : ~k;
+    float f;
+    std::memcpy(&f, &b, 4);
+    return f;
+}
+
+__global__ void k_grid_init(Misc* __restrict__ m) {
+    m->evals = 0ull;
+    m->flag = 0; m->nq = 0; m->maxring = 0; m->heads = 0; m->occupied = 0; m->maxcell = 0; m->m2 = 0u;
+    for (int a = 0; a < 3; ++a) { m->lo[a] = 0xffffffffu; m->hi[a] = 0u; }
+}
+
+// k_thin_box's shape (a fixed number of blocks, 7 atomics per block) with k_pc_pack's output
+__global__ __launch_bounds__(kBlock) void k_grid_box(const float* __restrict__ p, int stride, int N, float4* __restrict__ cand,
+                                                     Misc* __restrict__ m) {
+    __shared__ unsigned int s_lo[3][kBlock / 64], s_hi[3][kBlock / 64], s_m2[kBlock / 64];
+    unsigned int lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u}, m2 = 0u;
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)N; i += (size_t)gridDim.x * kBlock) {
+        float c[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            c[a] = p[i * stride + a];
+            bad |= !sgos::finite_f32(c[a]);
+            const unsigned int key = sgos::weight_key(c[a]);
+            lo[a] = min(lo[a], key);
+            hi[a] = max(hi[a], key);
+        }
+        const float4 v = sgcloud::with_norm(c[0], c[1], c[2]);
+        cand[i] = v;
+        m2 = max(m2, __float_as_uint(v.w));
+    }
+    if (bad) atomicOr(&m->flag, 1);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = min(lo[a], (unsigned int)__shfl_xor((int)lo[a], off));
+            hi[a] = max(hi[a], (unsigned int)__shfl_xor((int)hi[a], off));
+        }
+        m2 = max(m2, (unsigned int)__shfl_xor((int)m2, off));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { s_lo[a][wave] = lo[a]; s_hi[a][wave] = hi[a]; }
+        s_m2[wave] = m2;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        unsigned int l = s_lo[a][0], h = s_hi[a][0];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) { l = min(l, s_lo[a][w]); h = max(h, s_hi[a][w]); }
+        atomicMin(&m->lo[a], l);
+        atomicMax(&m->hi[a], h);
+    } else if (threadIdx.x == 3) {
+        unsigned int v = s_m2[0];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) v = max(v, s_m2[w]);
+        atomicMax(&m->m2, v);
+    }
+}
+
+// the cell of point i on 8g's formula; the host derived nc[] with the same operations from the box's maximum and the cell is monotone in
+// the coordinate, so 0 <= f < nc -- the clamp never acts, it only keeps a table index in range whatever happens
+__global__ __launch_bounds__(kBlock) void k_grid_cells(const float4* __restrict__ cand, int N, Grid g, unsigned long long* __restrict__ key,
+                                                       int* __restrict__ idx) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    const float4 p = cand[i];
+    const float q0 = (p.x - g.lo[0]) / g.h, q1 = (p.y - g.lo[1]) / g.h, q2 = (p.z - g.lo[2]) / g.h;
+    const int c0 = min(max((int)__builtin_floorf(q0), 0), g.nc[0] - 1);
+    const int c1 = min(max((int)__builtin_floorf(q1), 0), g.nc[1] - 1);
+    const int c2 = min(max((int)__builtin_floorf(q2), 0), g.nc[2] - 1);
+    key[i] = (unsigned long long)((c2 * g.nc[1] + c1) * g.nc[0] + c0);
+    idx[i] = i;
+}
+
+// occupied cells = run heads of the sorted keys: one atomic per block
+__global__ __launch_bounds__(kBlock) void k_grid_heads(const unsigned long long* __restrict__ skey, int N, int* __restrict__ heads) {
+    __shared__ int part[kBlock / 64];
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    const bool head = s < N && (s == 0 || skey[s] != skey[s - 1]);
+    const int n = __builtin_popcountll(__builtin_amdgcn_ballot_w64(head));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) t += part[w];
+        if (t) atomicAdd(heads, t);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_grid_gather(const float4* __restrict__ cand, const int* __restrict__ sidx, int N,
+                                                        float4* __restrict__ spts) {
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s < N) spts[s] = cand[sidx[s]];
+}
+
+// start[c] = the number of sorted keys below c, c = 0 .. ncells (start[ncells] = N)
+__global__ __launch_bounds__(kBlock) void k_grid_table(const unsigned long long* __restrict__ skey, int N, int ncells, int* __restrict__ start) {
+    const int c = blockIdx.x * kBlock + threadIdx.x;
+    if (c > ncells) return;
+    int lo = 0, hi = N;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (skey[mid] < (unsigned long long)c) lo = mid + 1; else hi = mid;
+    }
+    start[c] = lo;
+}
+
+__global__ __launch_bounds__(kBlock) void k_grid_cellstats(const int* __restrict__ start, int ncells, Misc* __restrict__ m) {
+    __shared__ int s_occ[kBlock / 64], s_max[kBlock / 64];
+    const int c = blockIdx.x * kBlock + threadIdx.x;
+    int n = c < ncells ? start[c + 1] - start[c] : 0;
+    const int occ = __builtin_popcountll(__builtin_amdgcn_ballot_w64(n > 0));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) n = max(n, __shfl_xor(n, off));
+    if ((threadIdx.x & 63) == 0) { s_occ[threadIdx.x >> 6] = occ; s_max[threadIdx.x >> 6] = n; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0, mx = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) { t += s_occ[w]; mx = max(mx, s_max[w]); }
+        if (t) { atomicAdd(&m->occupied, t); atomicMax(&m->maxcell, mx); }
+    }
+}
+
+// (score, original index): the higher score first, the lower index first among equal scores -- whatever order the candidates arrive in
+template <int KK>
+__device__ __forceinline__ void insert(float sc, int id, float (&bs)[KK], int (&bi)[KK]) {
+    if (sc > bs[KK - 1] || (sc == bs[KK - 1] && id < bi[KK - 1])) {
+        float v = sc;
+        int w = id;
+        bool placed = false;
+#pragma unroll
+        for (int t = 0; t < KK; ++t) {
+            if (placed || v > bs[t] || (v == bs[t] && w < bi[t])) {
+                placed = true;
+                const float tv = bs[t]; const int ti = bi[t];
+                bs[t] = v; bi[t] = w; v = tv; w = ti;
+            }
+        }
+    }
+}
+
+// the sorted points [a, b) (wave-uniform) through LDS in tiles; the lanes with `active` score them
+template <int KK>
+__device__ __forceinline__ void scan_range(int a, int b, bool active, const float4& me, const float4* __restrict__ spts,
+                                           const int* __restrict__ sidx, float4* tile, int* tidx, float (&bs)[KK], int (&bi)[KK],
+                                           unsigned int& evals) {
+    const int lane = threadIdx.x;
+    for (int c0 = a; c0 < b; c0 += kGTile) {
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kGTile / kWave; ++u) {
+            const int e = c0 + u * kWave + lane;
+            if (e < b) { tile[u * kWave + lane] = spts[e]; tidx[u * kWave + lane] = sidx[e]; }
+        }
+        __syncthreads();
+        const int n = min(kGTile, b - c0);
+        if (active) {
+            for (int j = 0; j < n; ++j) insert<KK>(sgcloud::pair_score(me.x, me.y, me.z, me.w, tile[j]), tidx[j], bs, bi);
+            evals += (unsigned int)n;
+        }
+    }
+}
+
+template <int KK>
+__global__ __launch_bounds__(kWave) void k_grid_search(const float4* __restrict__ spts, const int* __restrict__ sidx,
+                                                       const unsigned long long* __restrict__ skey, const int* __restrict__ start, Grid g, int N,
+                                                       int32_t* __restrict__ table, int* __restrict__ queue, Misc* __restrict__ m, int counting) {
+    __shared__ float4 tile[kGTile];
+    __shared__ int tidx[kGTile];
+    const int s = blockIdx.x * kWave + threadIdx.x;
+    const bool live = s < N;
+    const int sl = live ? s : N - 1;
+    const float4 me = spts[sl];
+    const int mycell = (int)skey[sl];
+    const int orig = sidx[sl];
+    float bs[KK];
+    int bi[KK];
+#pragma unroll
+    for (int t = 0; t < KK; ++t) { bs[t] = -INFINITY; bi[t] = 0x7fffffff; }
+    const int nx = g.nc[0], ny = g.nc[1], nz = g.nc[2];
+    bool done = !live, queued = false;
+    int myr = 0;
+    unsigned int evals = 0u;
+    for (;;) {
+        const unsigned long long pending = __builtin_amdgcn_ballot_w64(!done);
+        if (pending == 0ull) break;
+        const int leader = __builtin_ctzll(pending);
+        const int gcell = __builtin_amdgcn_readfirstlane(__shfl(mycell, leader));
+        const bool ingroup = !done && mycell == gcell;
+        const int gx = gcell % nx, gy = (gcell / nx) % ny, gz = gcell / (nx * ny);
+        for (int r = 1; r <= g.rmax; ++r) {
+            const bool act = ingroup && !done;
+            for (int dz = -r; dz <= r; ++dz) {
+                const int z = gz + dz;
+                if (z < 0 || z >= nz) continue;
+                for (int dy = -r; dy <= r; ++dy) {
+                    const int y = gy + dy;
+                    if (y < 0 || y >= ny) continue;
+                    const int row = (z * ny + y) * nx;
+                    const bool inner = r > 1 && max(abs(dy), abs(dz)) < r;
+                    if (!inner) {                                   // the whole row piece of the block
+                        const int x0 = max(gx - r, 0), x1 = min(gx + r, nx - 1);
+                        scan_range<KK>(start[row + x0], start[row + x1 + 1], act, me, spts, sidx, tile, tidx, bs, bi, evals);
+                    } else {                                        // the block of ring r - 1 holds the middle: the two end cells
+                        if (gx - r >= 0) scan_range<KK>(start[row + gx - r], start[row + gx - r + 1], act, me, spts, sidx, tile, tidx, bs, bi, evals);
+                        if (gx + r < nx) scan_range<KK>(start[row + gx + r], start[row + gx + r + 1], act, me, spts, sidx, tile, tidx, bs, bi, evals);
+                    }
+                }
+            }
+            // every point outside the block is at least gap away along one axis; the whole grid seen settles everybody
+            const bool all = gx - r <= 0 && gx + r >= nx - 1 && gy - r <= 0 && gy + r >= ny - 1 && gz - r <= 0 && gz + r >= nz - 1;
+            const float gap = (float)r * g.h - g.slack;
+            const float lhs = (gap * gap) * kShrink;
+            const float rhs = g.delta - bs[KK - 1];
+            const bool full = bi[KK - 1] != 0x7fffffff;
+            if (act && (all || (full && gap > 0.0f && lhs > rhs))) { done = true; myr = r; }
+            if (__builtin_amdgcn_ballot_w64(ingroup && !done) == 0ull) break;
+        }
+        if (ingroup && !done) { done = true; queued = true; }
+    }
+    if (live) {
+        if (queued) {
+            queue[atomicAdd(&m->nq, 1)] = orig;
+        } else {
+#pragma unroll
+            for (int t = 0; t < KK; ++t) table[(size_t)orig * KK + t] = bi[t];
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) myr = max(myr, __shfl_xor(myr, off));
+    if (threadIdx.x == 0 && myr > 0) atomicMax(&m->maxring, myr);
+    if (counting) {
+        unsigned long long e = evals;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) e += __shfl_xor(e, off);
+        if (threadIdx.x == 0) atomicAdd(&m->evals, e);
+    }
+}
+
+// the queued queries (original indices) against the whole cloud in original order: k_pc_knn for a compacted list
+template <int KK>
+__global__ __launch_bounds__(kTile) void k_grid_fallback(const float4* __restrict__ cand, int N, const int* __restrict__ queue, int nq,
+                                                         int32_t* __restrict__ table, Misc* __restrict__ m, int counting) {
+    __shared__ float4 tile[kTile];
+    const int u = blockIdx.x * kTile + threadIdx.x;
+    const bool live = u < nq;
+    const int q = live ? queue[u] : 0;
+    const bool sane = (unsigned)q < (unsigned)N;
+    const float4 me = cand[sane ? q : 0];
+    float bs[KK];
+    int bi[KK];
+    sgcloud::top_scores<KK>(cand, N, me, tile, bs, bi);
+    if (live && sane) {
+#pragma unroll
+        for (int t = 0; t < KK; ++t) table[(size_t)q * KK + t] = bi[t] < N ? bi[t] : q;
+    }
+    if (counting && threadIdx.x == 0) atomicAdd(&m->evals, (unsigned long long)min(kTile, nq - blockIdx.x * kTile) * (unsigned long long)N);
+}
+
+int bits_for_cells(long long cells) {           // bits that hold 0..cells-1; none for one cell
+    int b = 0;
+    while (b < 62 && (1ll << b) < cells) ++b;
+    return b;
+}
+
+long long cell_cap(int N) { return std::max<long long>(kMinCells, 4ll * N); }
+
+struct Plan {
+    Misc* misc;
+    float4 *cand, *spts;            // [N] original order, sorted order
+    unsigned long long *k0, *k1;
+    int *v0, *v1;
+    int* hist;
+    int* start;                     // [cell_cap + 1]
+    int* queue;                     // [N]
+    bool ok;
+};
+
+Plan carve(void* d_ws, size_t ws_bytes, int N) {
+    Plan p{};
+    const size_t n = (size_t)std::max(N, 1);
+    sg::Carver cv(d_ws, ws_bytes);
+    p.misc = cv.take<Misc>(1);
+    p.cand = cv.take<float4>(n);
+    p.spts = cv.take<float4>(n);
+    p.k0 = cv.take<unsigned long long>(n);
+    p.k1 = cv.take<unsigned long long>(n);
+    p.v0 = cv.take<int>(n);
+    p.v1 = cv.take<int>(n);
+    p.hist = cv.take<int>(sgsort::hist_ints((long long)n));
+    p.start = cv.take<int>((size_t)cell_cap(N) + 1);
+    p.queue = cv.take<int>(n);
+    p.ok = cv.ok;
+    return p;
+}
+
+// the cells per axis of edge h, in the device's arithmetic (the cell of the box's maximum + 1); false: an axis reaches 2^21 cells
+bool cells_of(const float ext[3], float h, int nc[3], long long* total) {
+    *total = 1;
+    for (int a = 0; a < 3; ++a) {
+        const float q = ext[a] / h;
+        if (!(q < kCellLimit)) return false;
+        nc[a] = (int)std::floor(q) + 1;
+        *total *= nc[a];
+    }
+    return true;
+}
+
+constexpr int kStages = 7;
+const char* const kStageNames[kStages] = {"box", "probe", "cells", "sort", "table", "search", "fallback"};
+thread_local bool t_timing = false;
+thread_local float t_stage_us[kStages];
+thread_local int64_t t_stats[kNumStats];
+thread_local int t_target = 0, t_ring_limit = 0;        // 0: the defaults
+
+template <int KK>
+void launch_search(const Plan& p, const unsigned long long* skey, const int* sidx, const Grid& g, int N, int32_t* table, int counting,
+                   hipStream_t st) {
+    k_grid_search<KK><<<sg::cdiv(N, kWave), kWave, 0, st>>>(p.spts, sidx, skey, p.start, g, N, table, p.queue, p.misc, counting);
+}
+
+template <int KK>
+void launch_fallback(const Plan& p, int N, int nq, int32_t* table, int counting, hipStream_t st) {
+    k_grid_fallback<KK><<<sg::cdiv(nq, kTile), kTile, 0, st>>>(p.cand, N, p.queue, nq, table, p.misc, counting);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sg_pointcloud_knn_grid_set_timing(int on) { t_timing = on != 0; return SG_OK; }
+
+int sg_pointcloud_knn_grid_stage_times(float* h_us, int cap) {
+    SG_REQUIRE(h_us && cap >= kStages, "sg_pointcloud_knn_grid_stage_times: room for %d floats is needed", kStages);
+    for (int i = 0; i < kStages; ++i) h_us[i] = t_stage_us[i];
+    return kStages;
+}
+
+const char* sg_pointcloud_knn_grid_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+
+int sg_pointcloud_knn_grid_stats(int64_t* h, int cap) {
+    SG_REQUIRE(h && cap >= kNumStats, "sg_pointcloud_knn_grid_stats: room for %d words is needed", kNumStats);
+    for (int i = 0; i < kNumStats; ++i) h[i] = t_stats[i];
+    return kNumStats;
+}
+
+int sg_pointcloud_knn_grid_set_tuning(int target_occupancy, int ring_limit) {
+    SG_REQUIRE(target_occupancy >= 0 && target_occupancy <= 4096 && ring_limit >= 0 && ring_limit <= kMaxRingLimit,
+               "sg_pointcloud_knn_grid_set_tuning: target occupancy 0..4096 and ring limit 0..%d (0: the default)", kMaxRingLimit);
+    t_target = target_occupancy;
+    t_ring_limit = ring_limit;
+    return SG_OK;
+}
+
+size_t sg_pointcloud_knn_grid_ws_bytes(int N, int k) {
+    if (N < 1 || N > SG_MAX_GRID_POINTS || (k != 5 && k != 10 && k != 20)) return 0;
+    const size_t n = (size_t)N;
+    return sg::align_up(sizeof(Misc)) + 2 * sg::align_up(n * 16) + 2 * sg::align_up(n * 8) + 3 * sg::align_up(n * 4) +
+           sg::align_up(sgsort::hist_ints((long long)n) * 4) + sg::align_up(((size_t)cell_cap(N) + 1) * 4);
+}
+
+int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, float cell, int32_t* d_knn, void* d_ws, size_t ws_bytes,
+                           void* stream) {
+    const char* who = "sg_pointcloud_knn_grid";
+    for (int i = 0; i < kNumStats; ++i) t_stats[i] = 0;
+    if (k != 5 && k != 10 && k != 20) return sg::fail(SG_EUNSUP, "%s: k = %d is not built (5, 10 = the reference's default, 20)", who, k);
+    SG_REQUIRE(N > 0, "%s: bad arguments", who);
+    if (N <= k) return sg::fail(SG_EINVAL, "%s: %d points for k = %d (topk(k + 1) raises in the reference)", who, N, k);
+    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
+    SG_REQUIRE(d_points && stride >= 3 && d_knn && d_ws, "%s: bad arguments", who);
+    SG_REQUIRE(std::isfinite(cell) && cell >= 0.0f, "%s: the cell edge must be finite and positive, or 0 for the library's choice (%g)", who, (double)cell);
+    const Plan p = carve(d_ws, ws_bytes, N);
+    if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_pointcloud_knn_grid_ws_bytes(N, k));
+    hipStream_t st = sg::as_stream(stream);
+    const int nb = sg::cdiv(N, kBlock);
+    const int counting = t_timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, t_timing, t_stage_us);
+    // box
+    k_grid_init<<<1, 1, 0, st>>>(p.misc);
+    k_grid_box<<<std::min(nb, kBoxBlocks), kBlock, 0, st>>>(d_points, stride, N, p.cand, p.misc);
+    Misc hm{};
+    SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (hm.flag & 1) return sg::fail(SG_EINVAL, "%s: a coordinate is not finite", who);
+    float m2;
+    std::memcpy(&m2, &hm.m2, 4);
+    const float delta = std::max(std::ldexp(m2, -19), std::ldexp(1.0f, -100));
+    if (!std::isfinite(4.0f * m2) || !std::isfinite(delta))
+        return sg::fail(SG_EUNSUP, "%s: the coordinates are too large for the grid's score margin (max |p|^2 = %g); the brute-force path "
+                                   "(sg_pointcloud_knn) decides such a cloud", who, (double)m2);
+    clock.tick();
+    Grid g{};
+    float ext[3], emax = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        g.lo[a] = unkey_host(hm.lo[a]);
+        ext[a] = unkey_host(hm.hi[a]) - g.lo[a];
+        emax = std::max(emax, ext[a]);
+    }
+    g.delta = delta;
+    g.slack = std::ldexp(emax, -21);                    // 8 u E, u = 2^-24
+    g.rmax = t_ring_limit > 0 ? t_ring_limit : kRingLimit;
+    const long long cap = cell_cap(N);
+    long long total = 0;
+    // h, enlarged until no axis reaches 2^21 cells and the grid fits the table
+    auto fit = [&](float h) {
+        if (!(h > 0.0f) || !std::isfinite(h)) h = 1.0f;
+        for (int tries = 0; tries < 400; ++tries) {
+            if (cells_of(ext, h, g.nc, &total) && total <= cap) return h;
+            h *= 1.25f;
+        }
+        return emax > 0.0f ? emax * 2.0f : 1.0f;        // one cell per axis
+    };
+    sgsort::Lists<unsigned long long, int> L{};
+    auto bin = [&](float h) {                           // cells and sort at edge h
+        g.h = h;
+        cells_of(ext, h, g.nc, &total);
+        g.ncells = (int)total;
+        k_grid_cells<<<nb, kBlock, 0, st>>>(p.cand, N, g, p.k0, p.v0);
+    };
+    auto sort = [&]() {
+        L = sgsort::Lists<unsigned long long, int>{};
+        L.kin[0] = p.k0; L.kout[0] = p.k1; L.vin[0] = p.v0; L.vout[0] = p.v1; L.hist[0] = p.hist; L.n[0] = N;
+        sgsort::radix_sort<unsigned long long, int, true>(L, 1, 0, bits_for_cells(g.ncells), st);
+    };
+    bool binned = false;
+    if (cell > 0.0f) {
+        if (!cells_of(ext, cell, g.nc, &total))
+            return sg::fail(SG_EUNSUP, "%s: cell too small for the cloud's extent (%g / %g is not below %g cells on an axis)", who, (double)emax,
+                            (double)cell, (double)kCellLimit);
+        if (total > cap)
+            return sg::fail(SG_EUNSUP, "%s: a cell of %g gives %lld cells; the table of %d points holds %lld", who, (double)cell, total, N, cap);
+        clock.tick();
+    } else {
+        // first guess: the cloud as a surface of the box's half area (a line: its length), `target` points per cell
+        const float target = (float)(t_target > 0 ? t_target : kTargetOccupancy);
+        const float area = ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2];
+        const float h0 = fit(std::max(std::sqrt(target * area / (float)N), target * emax / (float)N));
+        bin(h0);
+        sort();
+        k_grid_heads<<<nb, kBlock, 0, st>>>(L.kin[0], N, &p.misc->heads);
+        int heads = 0;
+        SG_HIP(hipMemcpyAsync(&heads, &p.misc->heads, 4, hipMemcpyDeviceToHost, st));
+        SG_HIP(hipStreamSynchronize(st));
+        SG_LAUNCH_CHECK();
+        if (heads < 1 || heads > N) return sg::fail(SG_EHIP, "%s: %d occupied cells from %d points", who, heads, N);
+        // one correction towards the target: on a surface the occupancy grows with h^2
+        const float occ = (float)N / (float)heads;
+        cell = h0;
+        binned = true;
+        if (occ < 0.75f * target || occ > 1.5f * target) {
+            const float h1 = fit(h0 * std::sqrt(target / occ));
+            if (h1 != h0) { cell = h1; binned = false; }
+        }
+        clock.tick();
+    }
+    if (!binned) bin(cell);
+    clock.tick();
+    if (!binned) sort();
+    const unsigned long long* skey = L.kin[0] ? L.kin[0] : p.k0;
+    const int* sidx = L.vin[0] ? L.vin[0] : p.v0;
+    k_grid_gather<<<nb, kBlock, 0, st>>>(p.cand, sidx, N, p.spts);
+    clock.tick();
+    k_grid_table<<<sg::cdiv((long long)g.ncells + 1, kBlock), kBlock, 0, st>>>(skey, N, g.ncells, p.start);
+    k_grid_cellstats<<<sg::cdiv(g.ncells, kBlock), kBlock, 0, st>>>(p.start, g.ncells, p.misc);
+    clock.tick();
+    if (k == 5) launch_search<6>(p, skey, sidx, g, N, d_knn, counting, st);
+    else if (k == 10) launch_search<11>(p, skey, sidx, g, N, d_knn, counting, st);
+    else launch_search<21>(p, skey, sidx, g, N, d_knn, counting, st);
+    clock.tick();
+    SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    const int nq = hm.nq;
+    if (nq < 0 || nq > N) return sg::fail(SG_EHIP, "%s: %d queued queries from %d points", who, nq, N);
+    if (nq > 0) {
+        if (k == 5) launch_fallback<6>(p, N, nq, d_knn, counting, st);
+        else if (k == 10) launch_fallback<11>(p, N, nq, d_knn, counting, st);
+        else launch_fallback<21>(p, N, nq, d_knn, counting, st);
+        if (counting) SG_HIP(hipMemcpyAsync(&hm.evals, &p.misc->evals, 8, hipMemcpyDeviceToHost, st));
+        SG_HIP(hipStreamSynchronize(st));
+    }
+    clock.tick();
+    SG_LAUNCH_CHECK();
+    unsigned int hbits;
+    std::memcpy(&hbits, &g.h, 4);
+    t_stats[0] = g.nc[0]; t_stats[1] = g.nc[1]; t_stats[2] = g.nc[2];
+    t_stats[3] = hm.occupied; t_stats[4] = hm.maxcell; t_stats[5] = (int64_t)hbits;
+    t_stats[6] = hm.maxring; t_stats[7] = nq; t_stats[8] = (int64_t)hm.evals;
+    return SG_OK;
+}
+
+}  // extern "C"

@@ -3,7 +3,8 @@
 //
 //   k_pc_pack           coordinates finite (one flag word), (x, y, z, |p|^2) per point, the cloud's bounding box (order-free min / max)
 //   k_pc_knn            the complete top-(k+1) list of every point against the whole cloud: cloud_knn_device.h, the score and the tie
-//                       rule of sg_pointcloud_adjacency's k_nearest_k
+//                       rule of sg_pointcloud_adjacency's k_nearest_k; with index = SG_KNN_GRID the same table comes from the exact grid
+//                       index instead (kernels_knn_grid.hip) and every later stage is unchanged
 //   k_pc_normals        one thread per point: mean and the six covariance sums over its list in list order, a cyclic Jacobi iteration
 //                       with the rotations written out for the pairs (0,1), (0,2), (1,2) on scalars (nothing is indexed at run time),
 //                       the eigenvector of the smallest eigenvalue, turned towards the viewpoint
@@ -230,10 +231,12 @@ struct Plan {                       // the workspace of one cloud; n = N * k
     float* vn;
     int32_t* edges;
     float* w_sorted;
+    char* grid;                     // sg_pointcloud_knn_grid's workspace (index = SG_KNN_GRID only)
+    size_t grid_bytes;
     bool ok;
 };
 
-Plan carve(void* d_ws, size_t ws_bytes, int N, int k) {
+Plan carve(void* d_ws, size_t ws_bytes, int N, int k, int index) {
     Plan p{};
     p.n = (size_t)std::max(N, 1) * std::max(k, 1);
     const size_t np = (size_t)std::max(N, 1);
@@ -255,14 +258,21 @@ Plan carve(void* d_ws, size_t ws_bytes, int N, int k) {
     p.vn = cv.take<float>(np * 3);
     p.edges = cv.take<int32_t>(p.n * 2);
     p.w_sorted = cv.take<float>(p.n);
+    if (index == SG_KNN_GRID) {
+        p.grid_bytes = sg_pointcloud_knn_grid_ws_bytes(N, k);
+        p.grid = cv.take<char>(p.grid_bytes);
+    }
     p.ok = cv.ok;
     return p;
 }
 
-int check_k(const char* who, int N, int k) {
+// index: SG_KNN_BRUTE scores every pair (k_pc_knn), SG_KNN_GRID takes the lists from the grid (kernels_knn_grid.hip)
+int check_k(const char* who, int N, int k, int index = SG_KNN_BRUTE) {
+    if (index != SG_KNN_BRUTE && index != SG_KNN_GRID) return sg::fail(SG_EINVAL, "%s: index = %d (SG_KNN_BRUTE or SG_KNN_GRID)", who, index);
+    const int cap = index == SG_KNN_GRID ? SG_MAX_GRID_POINTS : SG_MAX_POINTS;
     if (k != 5 && k != 10 && k != 20) return sg::fail(SG_EUNSUP, "%s: k = %d is not built (5, 10 = the reference's default, 20)", who, k);
     if (N <= k) return sg::fail(SG_EINVAL, "%s: %d points for k = %d (topk(k + 1) raises in the reference)", who, N, k);
-    if (N > SG_MAX_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; a cloud holds at most %d", who, N, SG_MAX_POINTS);
+    if (N > cap) return sg::fail(SG_EUNSUP, "%s: %d points; a cloud holds at most %d", who, N, cap);
     return SG_OK;
 }
 
@@ -288,6 +298,106 @@ constexpr int kStages = 7;
 const char* const kStageNames[kStages] = {"check", "knn", "normals", "edges", "weights", "weight_sort", "gather"};
 thread_local bool t_timing = false;
 thread_local float t_stage_us[kStages];
+
+
+size_t pcseg_ws_bytes(int N, int k, int index) {
+    const size_t np = (size_t)std::max(N, 1), kk = (size_t)std::max(k, 1), n = np * kk;
+    return sg::align_up(np * 16) + sg::align_up(sizeof(Misc)) + sg::align_up(np * (kk + 1) * 4) + 3 * sg::align_up(n * 8) +
+           sg::align_up(sgsort::hist_ints((long long)n) * 4) + sg::align_up(sgsort::unique_ints((long long)n) * 4) + sg::align_up(n * 16) +
+           5 * sg::align_up(n * 4) + sg::align_up(np * 12) + sg::align_up(n * 8) + sg::align_up(n * 4) +
+           (index == SG_KNN_GRID ? sg::align_up(sg_pointcloud_knn_grid_ws_bytes(N, k)) : 0);
+}
+
+// sg_pcseg_edges and its indexed twin: only stage 1, the lists, knows the index
+int pcseg_edges(const char* who, const float* d_xyz, int N, int k, const float* h_viewpoint, int index, float cell, int32_t* d_knn,
+                float* d_normals, int32_t* d_edges, float* d_w, int* h_E, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!(N > 0 && d_xyz && d_normals && d_edges && d_w && h_E && d_ws)) return sg::fail(SG_EINVAL, "%s: bad arguments", who);
+    *h_E = 0;
+    int rc = check_k(who, N, k, index);
+    if (rc < 0) return rc;
+    if ((rc = viewpoint_ok(who, h_viewpoint)) < 0) return rc;
+    const Plan p = carve(d_ws, ws_bytes, N, k, index);
+    if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, pcseg_ws_bytes(N, k, index));
+    hipStream_t st = sg::as_stream(stream);
+    const int n = N * k;                                                       // N <= 2^24, k <= 20: below 2^31
+    sgos::StageClock<kStages> clock(st, t_timing, t_stage_us);
+    // 0. the coordinates are the caller's
+    k_pc_init<<<1, 1, 0, st>>>(p.misc, h_viewpoint != nullptr, h_viewpoint ? h_viewpoint[0] : 0.0f, h_viewpoint ? h_viewpoint[1] : 0.0f,
+                               h_viewpoint ? h_viewpoint[2] : 0.0f);
+    k_pc_pack<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(d_xyz, 3, N, p.cand, p.misc);
+    int flag = 0;
+    SG_HIP(hipMemcpyAsync(&flag, &p.misc->flag, 4, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    if (flag & 1) return sg::fail(SG_EINVAL, "%s: a coordinate is not finite", who);
+    clock.tick();
+    // 1. the lists
+    int32_t* table = d_knn ? d_knn : p.knn;
+    if (index == SG_KNN_GRID) {
+        if ((rc = sg_pointcloud_knn_grid(d_xyz, 3, N, k, cell, table, p.grid, p.grid_bytes, stream)) < 0) return rc;
+    } else {
+        launch_knn(p.cand, N, k, table, p.misc, st);
+    }
+    clock.tick();
+    // 2-5. normals
+    if (!h_viewpoint) k_pc_view<<<1, 1, 0, st>>>(p.misc);
+    launch_normals(reinterpret_cast<const float*>(p.cand), 4, N, k, table, p.misc, d_normals, st);
+    clock.tick();
+    // 6. the unique undirected pairs a < b in lexicographic order
+    k_pc_edge_keys<<<sg::cdiv(n, kBlock), kBlock, 0, st>>>(table, N, k, p.p0);
+    sgsort::Lists<unsigned long long, int> L{};
+    L.kin[0] = p.p0; L.kout[0] = p.p1; L.hist[0] = p.hist; L.n[0] = n;
+    const int field = std::min(32, bits_for((long long)N + 1) + 1);           // one bit more than an id carries: ~0 must come out last
+    sgsort::radix_sort<unsigned long long, int, false>(L, 1, 0, field, st);
+    sgsort::radix_sort<unsigned long long, int, false>(L, 1, 32, field, st);
+    unsigned long long* uniq = p.p2;
+    sgsort::unique_sorted<unsigned long long>(L.kin[0], n, uniq, nullptr, &p.misc->count, p.scratch, st);
+    int fc[2] = {0, 0};
+    SG_HIP(hipMemcpyAsync(fc, p.misc, 8, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (fc[0] & 2) return sg::fail(SG_EINVAL, "%s: the coordinates are too large for the fp32 pair score", who);
+    int E = fc[1];
+    if (E < 1 || E > n) return sg::fail(SG_EHIP, "%s: %d pair keys from %d points", who, E, N);
+    unsigned long long tail = 0;
+    SG_HIP(hipMemcpyAsync(&tail, uniq + E - 1, 8, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    if (tail == ~0ull) --E;                                                    // the self pairs, if any, collapsed into one trailing key
+    if (E > 0) k_pc_unpack<<<sg::cdiv(E, kBlock), kBlock, 0, st>>>(uniq, E, p.adj);
+    clock.tick();
+    if (E == 0) { SG_LAUNCH_CHECK(); return SG_OK; }
+    // 7. weights and keys, 8. ascending (w, a, b) and the gather: 8d's stages
+    k_pc_weights<<<sg::cdiv(E, kBlock), kBlock, 0, st>>>(p.adj, E, p.cand, d_normals, p.w, p.k0, p.v0);
+    clock.tick();
+    const int* order = sgos::sort_by_weight(p.k0, p.k1, p.v0, p.v1, p.hist, E, st);
+    clock.tick();
+    sgos::gather_edges(order, E, p.adj, p.w, d_edges, d_w, st);
+    clock.tick();
+    SG_LAUNCH_CHECK();
+    *h_E = E;
+    return SG_OK;
+}
+
+int pcseg_scan(const char* who, const float* d_xyz, int N, int k, const float* h_viewpoint, int index, float cell, float k_thresh,
+               int seg_min_verts, int32_t* h_seg_indices, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!(N > 0 && d_xyz && h_seg_indices && d_ws)) return sg::fail(SG_EINVAL, "%s: bad arguments", who);
+    const int rc0 = check_k(who, N, k, index);
+    if (rc0 < 0) return rc0;
+    const Plan p = carve(d_ws, ws_bytes, N, k, index);
+    if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, pcseg_ws_bytes(N, k, index));
+    int E = 0;
+    const int rc = pcseg_edges(index == SG_KNN_GRID ? "sg_pcseg_edges_indexed" : "sg_pcseg_edges", d_xyz, N, k, h_viewpoint, index, cell, nullptr,
+                               p.vn, p.edges, p.w_sorted, &E, d_ws, ws_bytes, stream);
+    if (rc < 0) return rc;
+    std::vector<int32_t> h_edges((size_t)E * 2);
+    std::vector<float> h_w((size_t)E);
+    if (E > 0) {
+        hipStream_t st = sg::as_stream(stream);
+        SG_HIP(hipMemcpyAsync(h_edges.data(), p.edges, (size_t)E * 8, hipMemcpyDeviceToHost, st));
+        SG_HIP(hipMemcpyAsync(h_w.data(), p.w_sorted, (size_t)E * 4, hipMemcpyDeviceToHost, st));
+        SG_HIP(hipStreamSynchronize(st));
+    }
+    return sg_overseg_merge(h_edges.data(), h_w.data(), E, N, k_thresh, seg_min_verts, h_seg_indices);
+}
 
 }  // namespace
 
@@ -351,96 +461,33 @@ int sg_pointcloud_normals(const float* d_xyz, int N, const int32_t* d_knn, int k
     return SG_OK;
 }
 
-size_t sg_pcseg_ws_bytes(int N, int k) {
-    const size_t np = (size_t)std::max(N, 1), kk = (size_t)std::max(k, 1), n = np * kk;
-    return sg::align_up(np * 16) + sg::align_up(sizeof(Misc)) + sg::align_up(np * (kk + 1) * 4) + 3 * sg::align_up(n * 8) +
-           sg::align_up(sgsort::hist_ints((long long)n) * 4) + sg::align_up(sgsort::unique_ints((long long)n) * 4) + sg::align_up(n * 16) +
-           5 * sg::align_up(n * 4) + sg::align_up(np * 12) + sg::align_up(n * 8) + sg::align_up(n * 4);
+size_t sg_pcseg_ws_bytes(int N, int k) { return pcseg_ws_bytes(N, k, SG_KNN_BRUTE); }
+
+size_t sg_pcseg_ws_bytes_indexed(int N, int k, int index) {
+    if (index == SG_KNN_GRID) return sg_pointcloud_knn_grid_ws_bytes(N, k) ? pcseg_ws_bytes(N, k, index) : 0;
+    return index == SG_KNN_BRUTE ? pcseg_ws_bytes(N, k, index) : 0;
 }
 
 int sg_pcseg_edges(const float* d_xyz, int N, int k, const float* h_viewpoint, int32_t* d_knn, float* d_normals, int32_t* d_edges, float* d_w,
                    int* h_E, void* d_ws, size_t ws_bytes, void* stream) {
-    SG_REQUIRE(N > 0 && d_xyz && d_normals && d_edges && d_w && h_E && d_ws, "sg_pcseg_edges: bad arguments");
-    *h_E = 0;
-    int rc = check_k("sg_pcseg_edges", N, k);
-    if (rc < 0) return rc;
-    if ((rc = viewpoint_ok("sg_pcseg_edges", h_viewpoint)) < 0) return rc;
-    const Plan p = carve(d_ws, ws_bytes, N, k);
-    if (!p.ok) return sg::fail(SG_ENOMEM, "sg_pcseg_edges: workspace too small (%zu < %zu)", ws_bytes, sg_pcseg_ws_bytes(N, k));
-    hipStream_t st = sg::as_stream(stream);
-    const int n = N * k;
-    sgos::StageClock<kStages> clock(st, t_timing, t_stage_us);
-    // 0. the coordinates are the caller's
-    k_pc_init<<<1, 1, 0, st>>>(p.misc, h_viewpoint != nullptr, h_viewpoint ? h_viewpoint[0] : 0.0f, h_viewpoint ? h_viewpoint[1] : 0.0f,
-                               h_viewpoint ? h_viewpoint[2] : 0.0f);
-    k_pc_pack<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(d_xyz, 3, N, p.cand, p.misc);
-    int flag = 0;
-    SG_HIP(hipMemcpyAsync(&flag, &p.misc->flag, 4, hipMemcpyDeviceToHost, st));
-    SG_HIP(hipStreamSynchronize(st));
-    if (flag & 1) return sg::fail(SG_EINVAL, "sg_pcseg_edges: a coordinate is not finite");
-    clock.tick();
-    // 1. the lists
-    int32_t* table = d_knn ? d_knn : p.knn;
-    launch_knn(p.cand, N, k, table, p.misc, st);
-    clock.tick();
-    // 2-5. normals
-    if (!h_viewpoint) k_pc_view<<<1, 1, 0, st>>>(p.misc);
-    launch_normals(reinterpret_cast<const float*>(p.cand), 4, N, k, table, p.misc, d_normals, st);
-    clock.tick();
-    // 6. the unique undirected pairs a < b in lexicographic order
-    k_pc_edge_keys<<<sg::cdiv(n, kBlock), kBlock, 0, st>>>(table, N, k, p.p0);
-    sgsort::Lists<unsigned long long, int> L{};
-    L.kin[0] = p.p0; L.kout[0] = p.p1; L.hist[0] = p.hist; L.n[0] = n;
-    const int field = std::min(32, bits_for((long long)N + 1) + 1);           // one bit more than an id carries: ~0 must come out last
-    sgsort::radix_sort<unsigned long long, int, false>(L, 1, 0, field, st);
-    sgsort::radix_sort<unsigned long long, int, false>(L, 1, 32, field, st);
-    unsigned long long* uniq = p.p2;
-    sgsort::unique_sorted<unsigned long long>(L.kin[0], n, uniq, nullptr, &p.misc->count, p.scratch, st);
-    int fc[2] = {0, 0};
-    SG_HIP(hipMemcpyAsync(fc, p.misc, 8, hipMemcpyDeviceToHost, st));
-    SG_HIP(hipStreamSynchronize(st));
-    SG_LAUNCH_CHECK();
-    if (fc[0] & 2) return sg::fail(SG_EINVAL, "sg_pcseg_edges: the coordinates are too large for the fp32 pair score");
-    int E = fc[1];
-    if (E < 1 || E > n) return sg::fail(SG_EHIP, "sg_pcseg_edges: %d pair keys from %d points", E, N);
-    unsigned long long tail = 0;
-    SG_HIP(hipMemcpyAsync(&tail, uniq + E - 1, 8, hipMemcpyDeviceToHost, st));
-    SG_HIP(hipStreamSynchronize(st));
-    if (tail == ~0ull) --E;                                                    // the self pairs, if any, collapsed into one trailing key
-    if (E > 0) k_pc_unpack<<<sg::cdiv(E, kBlock), kBlock, 0, st>>>(uniq, E, p.adj);
-    clock.tick();
-    if (E == 0) { SG_LAUNCH_CHECK(); return SG_OK; }
-    // 7. weights and keys, 8. ascending (w, a, b) and the gather: 8d's stages
-    k_pc_weights<<<sg::cdiv(E, kBlock), kBlock, 0, st>>>(p.adj, E, p.cand, d_normals, p.w, p.k0, p.v0);
-    clock.tick();
-    const int* order = sgos::sort_by_weight(p.k0, p.k1, p.v0, p.v1, p.hist, E, st);
-    clock.tick();
-    sgos::gather_edges(order, E, p.adj, p.w, d_edges, d_w, st);
-    clock.tick();
-    SG_LAUNCH_CHECK();
-    *h_E = E;
-    return SG_OK;
+    return pcseg_edges("sg_pcseg_edges", d_xyz, N, k, h_viewpoint, SG_KNN_BRUTE, 0.0f, d_knn, d_normals, d_edges, d_w, h_E, d_ws, ws_bytes, stream);
+}
+
+int sg_pcseg_edges_indexed(const float* d_xyz, int N, int k, const float* h_viewpoint, int index, float cell, int32_t* d_knn, float* d_normals,
+                           int32_t* d_edges, float* d_w, int* h_E, void* d_ws, size_t ws_bytes, void* stream) {
+    return pcseg_edges("sg_pcseg_edges_indexed", d_xyz, N, k, h_viewpoint, index, cell, d_knn, d_normals, d_edges, d_w, h_E, d_ws, ws_bytes,
+                       stream);
 }
 
 int sg_pcseg_scan(const float* d_xyz, int N, int k, const float* h_viewpoint, float k_thresh, int seg_min_verts, int32_t* h_seg_indices,
                   void* d_ws, size_t ws_bytes, void* stream) {
-    SG_REQUIRE(N > 0 && d_xyz && h_seg_indices && d_ws, "sg_pcseg_scan: bad arguments");
-    const int rc0 = check_k("sg_pcseg_scan", N, k);
-    if (rc0 < 0) return rc0;
-    const Plan p = carve(d_ws, ws_bytes, N, k);
-    if (!p.ok) return sg::fail(SG_ENOMEM, "sg_pcseg_scan: workspace too small (%zu < %zu)", ws_bytes, sg_pcseg_ws_bytes(N, k));
-    int E = 0;
-    const int rc = sg_pcseg_edges(d_xyz, N, k, h_viewpoint, nullptr, p.vn, p.edges, p.w_sorted, &E, d_ws, ws_bytes, stream);
-    if (rc < 0) return rc;
-    std::vector<int32_t> h_edges((size_t)E * 2);
-    std::vector<float> h_w((size_t)E);
-    if (E > 0) {
-        hipStream_t st = sg::as_stream(stream);
-        SG_HIP(hipMemcpyAsync(h_edges.data(), p.edges, (size_t)E * 8, hipMemcpyDeviceToHost, st));
-        SG_HIP(hipMemcpyAsync(h_w.data(), p.w_sorted, (size_t)E * 4, hipMemcpyDeviceToHost, st));
-        SG_HIP(hipStreamSynchronize(st));
-    }
-    return sg_overseg_merge(h_edges.data(), h_w.data(), E, N, k_thresh, seg_min_verts, h_seg_indices);
+    return pcseg_scan("sg_pcseg_scan", d_xyz, N, k, h_viewpoint, SG_KNN_BRUTE, 0.0f, k_thresh, seg_min_verts, h_seg_indices, d_ws, ws_bytes, stream);
+}
+
+int sg_pcseg_scan_indexed(const float* d_xyz, int N, int k, const float* h_viewpoint, int index, float cell, float k_thresh, int seg_min_verts,
+                          int32_t* h_seg_indices, void* d_ws, size_t ws_bytes, void* stream) {
+    return pcseg_scan("sg_pcseg_scan_indexed", d_xyz, N, k, h_viewpoint, index, cell, k_thresh, seg_min_verts, h_seg_indices, d_ws, ws_bytes,
+                      stream);
 }
 
 }  // extern "C"

@@ -21,6 +21,24 @@ SG_OK, SG_EINVAL, SG_EHIP, SG_ENOMEM, SG_ESTALL, SG_EUNSUP = 0, -1, -2, -3, -4, 
 MODE_INS_INFER, MODE_SEM_INFER = 0, 1
 COLOUR_SEMANTIC, COLOUR_INSTANCE, COLOUR_SEGMENT, COLOUR_GROUPING = 0, 1, 2, 3
 NUM_LABEL_VECTORS = 14
+KNN_BRUTE, KNN_GRID = 0, 1
+KNN_INDEX = {"brute": KNN_BRUTE, "grid": KNN_GRID}
+MAX_GRID_POINTS = 1 << 24
+
+
+def knn_index(index) -> int:
+    """'brute' | 'grid' -> SG_KNN_BRUTE | SG_KNN_GRID; anything else is a ValueError"""
+    if not isinstance(index, str) or index not in KNN_INDEX:
+        raise ValueError("index must be 'brute' or 'grid', not %r" % (index,))
+    return KNN_INDEX[index]
+
+
+def knn_cell(cell) -> float:
+    """the grid's forced cell edge; None or 0: the library picks it"""
+    c = 0.0 if cell is None else float(cell)
+    if not (c >= 0.0) or c == float("inf"):
+        raise ValueError("cell must be a finite edge > 0, or None for the library's choice")
+    return c
 LABEL_NAMES = [f"layer_{l}.{k}" for l in (1, 2, 3, 4) for k in ("seg", "ins", "sem")] + ["final.ins", "final.sem"]
 
 c_f32p = C.POINTER(C.c_float)
@@ -129,6 +147,16 @@ SIGNATURES = {
     "sg_cloud_thin_set_timing": (_I, [_I]),
     "sg_cloud_thin_stage_times": (_I, [vp, _I]),
     "sg_cloud_thin_stage_name": (C.c_char_p, [_I]),
+    "sg_pointcloud_knn_grid_ws_bytes": (_Z, [_I, _I]),
+    "sg_pointcloud_knn_grid": (_I, [vp, _I, _I, _I, C.c_float, vp, vp, _Z, vp]),
+    "sg_pointcloud_knn_grid_set_timing": (_I, [_I]),
+    "sg_pointcloud_knn_grid_stage_times": (_I, [vp, _I]),
+    "sg_pointcloud_knn_grid_stage_name": (C.c_char_p, [_I]),
+    "sg_pointcloud_knn_grid_stats": (_I, [vp, _I]),
+    "sg_pointcloud_knn_grid_set_tuning": (_I, [_I, _I]),
+    "sg_pcseg_ws_bytes_indexed": (_Z, [_I, _I, _I]),
+    "sg_pcseg_edges_indexed": (_I, [vp, _I, _I, vp, _I, C.c_float, vp, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_pcseg_scan_indexed": (_I, [vp, _I, _I, vp, _I, C.c_float, C.c_float, _I, vp, vp, _Z, vp]),
     "sg_segment_vote_ws_bytes": (_Z, [_I]),
     "sg_segment_rank": (_I, [vp, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_segment_vote": (_I, [vp, vp, _I, _I] + [vp] * 9 + [C.POINTER(C.c_int), vp, _Z, vp]),

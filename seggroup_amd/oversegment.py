@@ -16,8 +16,12 @@ the mesh path's.  `--pointcloud` sends a mesh down that path too; its faces are 
 A cloud above 2^20 points is thinned on a voxel grid first (`voxel=H` / `--voxel H`): the segmenter sees one point per
 occupied voxel, and every point takes the id of its voxel's representative.
 
+`index="grid"` / `--index grid` takes the point-cloud path's neighbour lists from the exact grid index instead of scoring
+every pair: the same lists bit for bit, hence the same segs.json, in a fraction of the time and up to 2^24 points.  With `--voxel` the
+cloud is thinned first and the grid works on the representatives.
+
     python -m seggroup_amd.oversegment --scans DIR [--scenes LIST] [--k-thresh 0.01] [--seg-min-verts 20] [--force] [--workers 4]
-                                       [--pointcloud] [--knn {5,10,20}] [--viewpoint X Y Z] [--voxel H]
+                                       [--pointcloud] [--knn {5,10,20}] [--viewpoint X Y Z] [--voxel H] [--index {brute,grid}]
 """
 from __future__ import annotations
 
@@ -143,25 +147,45 @@ def _viewpoint(viewpoint):
     return (C.c_float * 3)(*v.tolist())
 
 
-def pointcloud_edges(xyz, k: int = 10, viewpoint=None, device=None, stream=None):
+def knn_grid_stats() -> dict:
+    """What the calling thread's last grid-indexed kNN did: cells per axis, occupied cells, the largest cell, the cell edge
+    used, the largest ring count of a query the rings settled, the queries finished against the whole cloud, and the pair scores
+    evaluated (counted in timed calls only)."""
+    h = (C.c_int64 * 16)()
+    hip.check(hip.lib().sg_pointcloud_knn_grid_stats(h, 16))
+    return dict(cells=(int(h[0]), int(h[1]), int(h[2])), occupied=int(h[3]), largest_cell=int(h[4]),
+                cell=float(np.array([h[5]], dtype=np.uint32).view(np.float32)[0]), max_ring=int(h[6]), fallback=int(h[7]), scores=int(h[8]))
+
+
+def pointcloud_edges(xyz, k: int = 10, viewpoint=None, device=None, stream=None, index: str = "brute", cell=None):
     """The device stages of one cloud -> dict(knn [N,k+1] i32, normals [N,3], edges [E,2] i32, w [E]) of device tensors:
     every point's k + 1 best-scoring points, the covariance normals turned towards the viewpoint (default: the centre of the bounding
-    box), and the unique undirected kNN pairs a < b in ascending (w, a, b)."""
+    box), and the unique undirected kNN pairs a < b in ascending (w, a, b).  `index="grid"`: the lists come from the exact grid index
+    (`cell` forces its cell edge) -- the same bytes, up to 2^24 points."""
     import torch
     from .prepare import _dev, _ws
+    which, edge = hip.knn_index(index), hip.knn_cell(cell)
     dev = _dev(device)
     lib = hip.lib()
     k = int(k)
     with torch.cuda.device(dev), _on(stream):
         d_xyz, n = _cloud_tensor(xyz, dev)
+        if which == hip.KNN_GRID:
+            if n > hip.MAX_GRID_POINTS or lib.sg_pcseg_ws_bytes_indexed(n, k, which) == 0:      # refused before anything is allocated
+                hip.check(lib.sg_pointcloud_knn_grid(None, 3, n, k, edge, None, None, 0, None))
         knn = torch.empty((n, k + 1), dtype=torch.int32, device=dev)
         nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
         edges = torch.empty((max(n * k, 1), 2), dtype=torch.int32, device=dev)
         w = torch.empty(max(n * k, 1), dtype=torch.float32, device=dev)
-        ws = _ws(lib.sg_pcseg_ws_bytes(n, k), dev)
         n_e = C.c_int(0)
-        hip.check(lib.sg_pcseg_edges(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), knn.data_ptr(), nrm.data_ptr(), edges.data_ptr(),
-                                     w.data_ptr(), C.byref(n_e), ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+        if which == hip.KNN_GRID:
+            ws = _ws(lib.sg_pcseg_ws_bytes_indexed(n, k, which), dev)
+            hip.check(lib.sg_pcseg_edges_indexed(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), which, edge, knn.data_ptr(), nrm.data_ptr(),
+                                                 edges.data_ptr(), w.data_ptr(), C.byref(n_e), ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+        else:
+            ws = _ws(lib.sg_pcseg_ws_bytes(n, k), dev)
+            hip.check(lib.sg_pcseg_edges(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), knn.data_ptr(), nrm.data_ptr(), edges.data_ptr(),
+                                         w.data_ptr(), C.byref(n_e), ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
         (stream.synchronize() if stream is not None else torch.cuda.synchronize())
     return dict(knn=knn, normals=nrm, edges=edges[:n_e.value], w=w[:n_e.value])
 
@@ -188,15 +212,19 @@ def pointcloud_normals(xyz, k: int = 10, viewpoint=None, knn=None, device=None):
 
 
 def segment_pointcloud(xyz, k: int = 10, k_thresh: float = 0.01, seg_min_verts: int = 20, viewpoint=None, device=None,
-                       stream=None, voxel: Optional[float] = None) -> np.ndarray:
+                       stream=None, voxel: Optional[float] = None, index: str = "brute", cell=None) -> np.ndarray:
     """-> int32 [N]: seg_indices[i] = the lowest point index of i's segment, for a cloud without faces.
 
     `voxel`: thin the cloud on a grid of that edge first and segment the representatives with the same parameters -- the
     segmenter sees only the thinned cloud (its default viewpoint is that cloud's box centre, `seg_min_verts` counts thinned points) --;
     every point then takes its representative's id, as a raw index: rep[seg_thin[thin_of_point]], the segment's lowest representative.
-    That is how a cloud above 2^20 points is segmented; a grid that leaves every point alone gives the un-thinned ids."""
+    That is how a cloud above 2^20 points is segmented; a grid that leaves every point alone gives the un-thinned ids.
+
+    `index="grid"`: the neighbour lists come from the exact grid index (`cell` forces its cell edge): the same ids, and a
+    cloud of up to 2^24 points is segmented at full resolution.  With `voxel` the grid works on the representatives."""
     import torch
     from .prepare import _dev, _ws
+    which, edge = hip.knn_index(index), hip.knn_cell(cell)
     dev = _dev(device)
     lib = hip.lib()
     k = int(k)
@@ -207,15 +235,22 @@ def segment_pointcloud(xyz, k: int = 10, k_thresh: float = 0.01, seg_min_verts: 
         rep, top, _ = thin_cloud(d_all, voxel, device=dev, stream=stream)
         with torch.cuda.device(dev), _on(stream):
             d_thin = d_all.index_select(0, rep.long())
-        seg_thin = segment_pointcloud(d_thin, k, k_thresh, seg_min_verts, viewpoint=viewpoint, device=dev, stream=stream)
+        seg_thin = segment_pointcloud(d_thin, k, k_thresh, seg_min_verts, viewpoint=viewpoint, device=dev, stream=stream, index=index, cell=cell)
         rep_h = rep.cpu().numpy()
         return np.ascontiguousarray(rep_h[seg_thin[top.cpu().numpy()]], dtype=np.int32)
     with torch.cuda.device(dev), _on(stream):
         d_xyz, n = _cloud_tensor(xyz, dev)
         out = np.empty(n, dtype=np.int32)
-        ws = _ws(lib.sg_pcseg_ws_bytes(n, k), dev)
-        hip.check(lib.sg_pcseg_scan(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), float(k_thresh), int(seg_min_verts), out.ctypes.data,
-                                    ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+        if which == hip.KNN_GRID:
+            if n > hip.MAX_GRID_POINTS or lib.sg_pcseg_ws_bytes_indexed(n, k, which) == 0:      # refused before anything is allocated
+                hip.check(lib.sg_pointcloud_knn_grid(None, 3, n, k, edge, None, None, 0, None))
+            ws = _ws(lib.sg_pcseg_ws_bytes_indexed(n, k, which), dev)
+            hip.check(lib.sg_pcseg_scan_indexed(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), which, edge, float(k_thresh), int(seg_min_verts),
+                                                out.ctypes.data, ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+        else:
+            ws = _ws(lib.sg_pcseg_ws_bytes(n, k), dev)
+            hip.check(lib.sg_pcseg_scan(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), float(k_thresh), int(seg_min_verts), out.ctypes.data,
+                                        ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
     return out
 
 
@@ -226,12 +261,15 @@ def write_segs_json(path: str, seg_indices, scene_id: str, k_thresh: float = 0.0
 
 
 def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int = 20, force: bool = False, device=None, stream=None,
-                     plydata=None, pointcloud: bool = False, knn: int = 10, viewpoint=None, voxel: Optional[float] = None) -> Optional[str]:
+                     plydata=None, pointcloud: bool = False, knn: int = 10, viewpoint=None, voxel: Optional[float] = None,
+                     index: str = "brute") -> Optional[str]:
     """Writes the scan's segs.json next to its mesh; -> the path, or None when the file was there already (never overwritten without
     `force`).  A scan without faces is segmented as a point cloud (`knn` neighbours, normals towards `viewpoint`); `pointcloud=True`
     does the same to a mesh, ignoring its faces.  `voxel`: the point-cloud path thins on that grid first (`segment_pointcloud`); on the
-    mesh path it is an error, not ignored."""
+    mesh path it is an error, not ignored.  `index`: "brute" or "grid", the point-cloud path's neighbour search; on
+    the mesh path "grid" is an error as well."""
     from .prepare import _scene_name, mesh_arrays, read_ply
+    hip.knn_index(index)
     name = _scene_name(scene_path)
     out = os.path.join(scene_path, segs_json_name(name, k_thresh))
     if os.path.exists(out) and not force:
@@ -240,9 +278,11 @@ def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int
         plydata = read_ply(os.path.join(scene_path, name + "_vh_clean_2.ply"))
     xyz, _, faces = mesh_arrays(plydata)
     if pointcloud or faces.shape[0] == 0:
-        seg = segment_pointcloud(xyz, knn, k_thresh, seg_min_verts, viewpoint=viewpoint, device=device, stream=stream, voxel=voxel)
+        seg = segment_pointcloud(xyz, knn, k_thresh, seg_min_verts, viewpoint=viewpoint, device=device, stream=stream, voxel=voxel, index=index)
     elif voxel is not None:
         raise ValueError(f"{name}: voxel thinning belongs to the point-cloud path; this scan is a mesh (pass pointcloud=True to ignore its faces)")
+    elif index != "brute":
+        raise ValueError(f"{name}: the grid index belongs to the point-cloud path; this scan is a mesh (pass pointcloud=True to ignore its faces)")
     else:
         seg = segment_mesh(xyz, faces, k_thresh, seg_min_verts, device=device, stream=stream)
     write_segs_json(out, seg, name, k_thresh, seg_min_verts)
@@ -250,7 +290,7 @@ def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int
 
 
 def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_min_verts: int = 20, force: bool = False, workers: int = 4,
-                      device=None, pointcloud: bool = False, knn: int = 10, viewpoint=None, voxel: Optional[float] = None):
+                      device=None, pointcloud: bool = False, knn: int = 10, viewpoint=None, voxel: Optional[float] = None, index: str = "brute"):
     """Every scan directory under `scans_dir` (or the named ones) -> (written paths, skipped scene names).  Workers are threads, each
     with its own stream and workspace: the host chain of one scan overlaps the device work of the next."""
     import concurrent.futures
@@ -258,6 +298,7 @@ def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_m
 
     import torch
     from .prepare import _dev
+    hip.knn_index(index)
     dev = _dev(device)
     if scenes is None:
         scenes = sorted(d for d in os.listdir(scans_dir) if os.path.exists(os.path.join(scans_dir, d, d + "_vh_clean_2.ply")))
@@ -269,7 +310,7 @@ def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_m
             with torch.cuda.device(dev):
                 local.stream = torch.cuda.Stream(device=dev)
         return scene, oversegment_scan(os.path.join(scans_dir, scene), k_thresh, seg_min_verts, force, device=dev, stream=local.stream,
-                                       pointcloud=pointcloud, knn=knn, viewpoint=viewpoint, voxel=voxel)
+                                       pointcloud=pointcloud, knn=knn, viewpoint=viewpoint, voxel=voxel, index=index)
 
     written, skipped = [], []
     with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
@@ -305,19 +346,24 @@ def main(argv=None) -> int:
                     help="the point-cloud path turns its normals towards this point (default: the centre of the bounding box)")
     ap.add_argument("--voxel", type=float, default=None, metavar="H",
                     help="the point-cloud path thins the cloud on a voxel grid of this edge first (needed above 2^20 points)")
+    ap.add_argument("--index", default="brute", choices=("brute", "grid"),
+                    help="neighbour search of the point-cloud path: every pair, or the exact grid index (the same lists; up to 2^24 points)")
     a = ap.parse_args(argv)
     scenes = None
     if a.scenes:
         with open(a.scenes) as f:
             scenes = [ln.strip() for ln in f if ln.strip()]
-    if a.voxel is not None and not a.pointcloud:
+    if (a.voxel is not None or a.index != "brute") and not a.pointcloud:
         names = scenes if scenes is not None else sorted(d for d in os.listdir(a.scans) if os.path.exists(os.path.join(a.scans, d, d + "_vh_clean_2.ply")))
         meshes = [s for s in names if _declared_faces(os.path.join(a.scans, s, s + "_vh_clean_2.ply")) > 0]
-        if meshes:
+        if meshes and a.voxel is not None:
             ap.error("--voxel thins point clouds, and %s %s faces: add --pointcloud to ignore them" % (", ".join(meshes[:5]),
                                                                                                        "has" if len(meshes) == 1 else "have"))
+        if meshes:
+            ap.error("--index grid indexes point clouds, and %s %s faces: add --pointcloud to ignore them" % (", ".join(meshes[:5]),
+                                                                                                              "has" if len(meshes) == 1 else "have"))
     written, skipped = oversegment_scans(a.scans, scenes, a.k_thresh, a.seg_min_verts, a.force, a.workers, a.device, pointcloud=a.pointcloud,
-                                         knn=a.knn, viewpoint=a.viewpoint, voxel=a.voxel)
+                                         knn=a.knn, viewpoint=a.viewpoint, voxel=a.voxel, index=a.index)
     for p in written:
         print("wrote", p)
     for s in skipped:

@@ -255,16 +255,28 @@ def get_adj_from_pointcloud(pointcloud, k=10, device=None):
     return out[:cnt.value].cpu()
 
 
-def pointcloud_knn(pointcloud, k=10, device=None):
+def pointcloud_knn(pointcloud, k=10, device=None, index="brute", cell=None):
     """-> int32 [N, k+1] device tensor: the complete top-(k + 1) list of every point against the whole cloud, in the scores and the tie
-    rule of get_adj_from_pointcloud (descending score, the lower index first); entry 0, normally the point itself, is kept."""
+    rule of get_adj_from_pointcloud (descending score, the lower index first); entry 0, normally the point itself, is kept.
+    `index="grid"`: the same table from the exact grid index, up to 2^24 points; `cell` forces its cell edge (a
+    performance knob: the table does not depend on it)."""
     import torch
+    which, edge = hip.knn_index(index), hip.knn_cell(cell)
     dev = _dev(device)
     lib = hip.lib()
     pts = _t(pointcloud, torch.float32, dev)
     if pts.dim() != 2 or pts.shape[1] < 3:
         raise ValueError("pointcloud_knn: the cloud must be [N, >= 3]")
     n, stride = int(pts.shape[0]), int(pts.shape[1])
+    if which == hip.KNN_GRID:
+        if n > hip.MAX_GRID_POINTS:                                 # refused before anything is allocated
+            hip.check(lib.sg_pointcloud_knn_grid(None, stride, n, int(k), edge, None, None, 0, None))
+        out = torch.empty((n, int(k) + 1), dtype=torch.int32, device=dev)
+        ws = _ws(lib.sg_pointcloud_knn_grid_ws_bytes(n, int(k)), dev)
+        with torch.cuda.device(dev):
+            hip.check(lib.sg_pointcloud_knn_grid(pts.data_ptr(), stride, n, int(k), edge, out.data_ptr(), ws.data_ptr(), ws.numel(), None))
+            torch.cuda.synchronize()
+        return out
     out = torch.empty((n, int(k) + 1), dtype=torch.int32, device=dev)
     ws = _ws(lib.sg_pointcloud_knn_ws_bytes(n), dev)
     with torch.cuda.device(dev):
