@@ -896,6 +896,30 @@ int sg_pcseg_edges_indexed(const float* d_xyz, int N, int k, const float* h_view
 int sg_pcseg_scan_indexed(const float* d_xyz, int N, int k, const float* h_viewpoint, int index, float cell, float k_thresh, int seg_min_verts,
                           int32_t* h_seg_indices, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Exact grid-indexed nearest point between two clouds: sg_nearest_point's d_idx, bit for bit, without scoring every pair.
+ * For every query row u of d_x [U, x_stride >= 3] the candidate row of d_y [N, y_stride >= 3] with the largest pair score (|q|^2 formed as
+ * (x*x + y*y) + z*z), the lowest candidate index among equal scores, int64.  d_d2 (may be NULL) receives (dx*dx + dy*dy) + dz*dz of
+ * d = x[u] - y[idx[u]], each operation rounded once.  The search is sg_pointcloud_knn_grid's with a list of one entry: the index holds the
+ * candidates, the box, the largest extent and max|p|^2 are taken over the union of both clouds, the queries are binned by the same cell
+ * formula and sorted by cell, and a query is settled when  Lb > delta - s_best .  Queries unsettled at the ring limit (a query far from
+ * every candidate, a block without candidates) are finished by sg_nearest_point's kernel, so neither the cell edge nor the ring limit nor
+ * the stream can change a result.
+ *   0 <= U <= SG_MAX_CLOUD_POINTS, 1 <= N <= SG_MAX_GRID_POINTS (above: SG_EUNSUP, checked before anything is touched); U = 0 is SG_OK
+ *   and touches nothing.  SG_EINVAL: null pointers, a stride below 3, N < 1, U < 0, a cell edge that is negative or not finite, a workspace
+ *   below sg_nearest_point_grid_ws_bytes(U, N) (0 outside the envelope) -- all before the first device call --, a coordinate of either
+ *   cloud that is not finite (checked on the device before anything reads through it).  SG_EUNSUP: 4 * max|p|^2 or delta not finite (the
+ *   message names sg_nearest_point), a forced cell that gives an axis 2^21 cells or more or more cells than max(2^22, 4 N).
+ * Synchronises the stream like sg_pointcloud_knn_grid.  Stage times, statistics (the same nine words; the `search` stage holds the
+ * queries' binning and sort, the `fallback` stage the queue and d2) and tuning per calling thread, as above. */
+size_t sg_nearest_point_grid_ws_bytes(int U, int N);
+int sg_nearest_point_grid(const float* d_x, int x_stride, int U, const float* d_y, int y_stride, int N, float cell, int64_t* d_idx, float* d_d2,
+                          void* d_ws, size_t ws_bytes, void* stream);
+int sg_nearest_point_grid_set_timing(int on);
+int sg_nearest_point_grid_stage_times(float* h_us, int cap);
+const char* sg_nearest_point_grid_stage_name(int i);
+int sg_nearest_point_grid_stats(int64_t* h, int cap);
+int sg_nearest_point_grid_set_tuning(int target_occupancy, int ring_limit);
+
 /* Segment vote: what re-keying a scan's annotations onto another over-segmentation needs on the device.  Every vertex has a
  * row id d_ids[v] (any non-negative int32: not contiguous, may exceed V) and a column d_cols[v] in 0..n_cols-1; both are checked on the
  * device (SG_EINVAL).  Rows come out in ascending id order, *h_R of them; every output needs room for V entries.

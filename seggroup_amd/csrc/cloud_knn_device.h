@@ -50,4 +50,9 @@ __device__ __forceinline__ void top_scores(const float4* __restrict__ cand, int 
     }
 }
 
+// kernels_prepare.hip: sg_nearest_point's kernel for the queries qid[0..U) (rows of qxyz; the identity when qid is null) against
+// cand[0..N) = with_norm(y); out[scatter ? row : u] = the best-scoring candidate, the lowest index among equal scores
+void launch_nearest(const float* qxyz, int qstride, const int32_t* qid, int U, const float4* cand, int N, int64_t* out, int scatter,
+                    hipStream_t st);
+
 }  // namespace sgcloud

@@ -18,6 +18,10 @@
 //   k_grid_fallback     the queued queries against the whole cloud in original order (cloud_knn_device.h)
 //
 // The lists are written at the ORIGINAL row with ORIGINAL indices.  Plain launches, vector stores.
+//
+// sg_nearest_point_grid is the two-cloud, one-entry form: the same stages index the candidates y (box, E and M2 over the union
+// of both clouds), the queries x are binned by the same formula and sorted by cell key, k_nearest_search walks the rings, and the queue is
+// finished by sg_nearest_point's own kernel.  Both entry points build their index through build_index.
 #include <cmath>
 #include <cstring>
 
@@ -232,6 +236,42 @@ __device__ __forceinline__ void scan_range(int a, int b, bool active, const floa
     }
 }
 
+// ring r round the cell (gx, gy, gz): ring 1 is the 3 x 3 x 3 block, ring r > 1 the shell at Chebyshev distance r (whole row pieces where
+// |dy| or |dz| is r, the two end cells elsewhere).  Wave-uniform; the lanes with `act` score what is staged.
+template <int KK>
+__device__ __forceinline__ void scan_ring(const Grid& g, int gx, int gy, int gz, int r, const int* __restrict__ start, bool act, const float4& me,
+                                          const float4* __restrict__ spts, const int* __restrict__ sidx, float4* tile, int* tidx, float (&bs)[KK],
+                                          int (&bi)[KK], unsigned int& evals) {
+    const int nx = g.nc[0], ny = g.nc[1], nz = g.nc[2];
+    for (int dz = -r; dz <= r; ++dz) {
+        const int z = gz + dz;
+        if (z < 0 || z >= nz) continue;
+        for (int dy = -r; dy <= r; ++dy) {
+            const int y = gy + dy;
+            if (y < 0 || y >= ny) continue;
+            const int row = (z * ny + y) * nx;
+            const bool inner = r > 1 && max(abs(dy), abs(dz)) < r;
+            if (!inner) {                                   // the whole row piece of the block
+                const int x0 = max(gx - r, 0), x1 = min(gx + r, nx - 1);
+                scan_range<KK>(start[row + x0], start[row + x1 + 1], act, me, spts, sidx, tile, tidx, bs, bi, evals);
+            } else {                                        // the block of ring r - 1 holds the middle: the two end cells
+                if (gx - r >= 0) scan_range<KK>(start[row + gx - r], start[row + gx - r + 1], act, me, spts, sidx, tile, tidx, bs, bi, evals);
+                if (gx + r < nx) scan_range<KK>(start[row + gx + r], start[row + gx + r + 1], act, me, spts, sidx, tile, tidx, bs, bi, evals);
+            }
+        }
+    }
+}
+
+// after ring r: every point outside the block is at least gap away along one axis; the whole grid seen settles everybody.
+// s_last: the last score of the list, full: the list holds that many candidates
+__device__ __forceinline__ bool ring_settles(const Grid& g, int gx, int gy, int gz, int r, float s_last, bool full) {
+    const bool all = gx - r <= 0 && gx + r >= g.nc[0] - 1 && gy - r <= 0 && gy + r >= g.nc[1] - 1 && gz - r <= 0 && gz + r >= g.nc[2] - 1;
+    const float gap = (float)r * g.h - g.slack;
+    const float lhs = (gap * gap) * kShrink;
+    const float rhs = g.delta - s_last;
+    return all || (full && gap > 0.0f && lhs > rhs);
+}
+
 template <int KK>
 __global__ __launch_bounds__(kWave) void k_grid_search(const float4* __restrict__ spts, const int* __restrict__ sidx,
                                                        const unsigned long long* __restrict__ skey, const int* __restrict__ start, Grid g, int N,
@@ -248,7 +288,7 @@ __global__ __launch_bounds__(kWave) void k_grid_search(const float4* __restrict_
     int bi[KK];
 #pragma unroll
     for (int t = 0; t < KK; ++t) { bs[t] = -INFINITY; bi[t] = 0x7fffffff; }
-    const int nx = g.nc[0], ny = g.nc[1], nz = g.nc[2];
+    const int nx = g.nc[0], ny = g.nc[1];
     bool done = !live, queued = false;
     int myr = 0;
     unsigned int evals = 0u;
@@ -261,30 +301,8 @@ __global__ __launch_bounds__(kWave) void k_grid_search(const float4* __restrict_
         const int gx = gcell % nx, gy = (gcell / nx) % ny, gz = gcell / (nx * ny);
         for (int r = 1; r <= g.rmax; ++r) {
             const bool act = ingroup && !done;
-            for (int dz = -r; dz <= r; ++dz) {
-                const int z = gz + dz;
-                if (z < 0 || z >= nz) continue;
-                for (int dy = -r; dy <= r; ++dy) {
-                    const int y = gy + dy;
-                    if (y < 0 || y >= ny) continue;
-                    const int row = (z * ny + y) * nx;
-                    const bool inner = r > 1 && max(abs(dy), abs(dz)) < r;
-                    if (!inner) {                                   // the whole row piece of the block
-                        const int x0 = max(gx - r, 0), x1 = min(gx + r, nx - 1);
-                        scan_range<KK>(start[row + x0], start[row + x1 + 1], act, me, spts, sidx, tile, tidx, bs, bi, evals);
-                    } else {                                        // the block of ring r - 1 holds the middle: the two end cells
-                        if (gx - r >= 0) scan_range<KK>(start[row + gx - r], start[row + gx - r + 1], act, me, spts, sidx, tile, tidx, bs, bi, evals);
-                        if (gx + r < nx) scan_range<KK>(start[row + gx + r], start[row + gx + r + 1], act, me, spts, sidx, tile, tidx, bs, bi, evals);
-                    }
-                }
-            }
-            // every point outside the block is at least gap away along one axis; the whole grid seen settles everybody
-            const bool all = gx - r <= 0 && gx + r >= nx - 1 && gy - r <= 0 && gy + r >= ny - 1 && gz - r <= 0 && gz + r >= nz - 1;
-            const float gap = (float)r * g.h - g.slack;
-            const float lhs = (gap * gap) * kShrink;
-            const float rhs = g.delta - bs[KK - 1];
-            const bool full = bi[KK - 1] != 0x7fffffff;
-            if (act && (all || (full && gap > 0.0f && lhs > rhs))) { done = true; myr = r; }
+            scan_ring<KK>(g, gx, gy, gz, r, start, act, me, spts, sidx, tile, tidx, bs, bi, evals);
+            if (act && ring_settles(g, gx, gy, gz, r, bs[KK - 1], bi[KK - 1] != 0x7fffffff)) { done = true; myr = r; }
             if (__builtin_amdgcn_ballot_w64(ingroup && !done) == 0ull) break;
         }
         if (ingroup && !done) { done = true; queued = true; }
@@ -328,6 +346,70 @@ __global__ __launch_bounds__(kTile) void k_grid_fallback(const float4* __restric
     if (counting && threadIdx.x == 0) atomicAdd(&m->evals, (unsigned long long)min(kTile, nq - blockIdx.x * kTile) * (unsigned long long)N);
 }
 
+// The two-cloud, one-entry form: one wave per 64 queries in the order of their cell keys; the lanes of one cell form a group
+// and share the staged candidate tiles exactly as in k_grid_search, the list is (best score, its original index).  A query whose block
+// holds no candidate keeps -inf and is unsettled by construction.  The result goes to the query's ORIGINAL row; queries unsettled at the
+// ring limit are queued with their original index for k_nearest (kernels_prepare.hip).
+__global__ __launch_bounds__(kWave) void k_nearest_search(const float4* __restrict__ spts, const int* __restrict__ sidx, const int* __restrict__ start,
+                                                          Grid g, const float4* __restrict__ qpts, const unsigned long long* __restrict__ qskey,
+                                                          const int* __restrict__ qsidx, int U, int64_t* __restrict__ out, int* __restrict__ queue,
+                                                          Misc* __restrict__ m, int counting) {
+    __shared__ float4 tile[kGTile];
+    __shared__ int tidx[kGTile];
+    const int s = blockIdx.x * kWave + threadIdx.x;
+    const bool live = s < U;
+    const int sl = live ? s : U - 1;
+    const int orig = qsidx[sl];
+    const float4 me = qpts[orig];
+    const int mycell = (int)qskey[sl];
+    float bs[1] = {-INFINITY};
+    int bi[1] = {0x7fffffff};
+    const int nx = g.nc[0], ny = g.nc[1];
+    bool done = !live, queued = false;
+    int myr = 0;
+    unsigned int evals = 0u;
+    for (;;) {
+        const unsigned long long pending = __builtin_amdgcn_ballot_w64(!done);
+        if (pending == 0ull) break;
+        const int leader = __builtin_ctzll(pending);
+        const int gcell = __builtin_amdgcn_readfirstlane(__shfl(mycell, leader));
+        const bool ingroup = !done && mycell == gcell;
+        const int gx = gcell % nx, gy = (gcell / nx) % ny, gz = gcell / (nx * ny);
+        for (int r = 1; r <= g.rmax; ++r) {
+            const bool act = ingroup && !done;
+            scan_ring<1>(g, gx, gy, gz, r, start, act, me, spts, sidx, tile, tidx, bs, bi, evals);
+            if (act && ring_settles(g, gx, gy, gz, r, bs[0], bi[0] != 0x7fffffff)) { done = true; myr = r; }
+            if (__builtin_amdgcn_ballot_w64(ingroup && !done) == 0ull) break;
+        }
+        if (ingroup && !done) { done = true; queued = true; }
+    }
+    if (live) {
+        if (queued) queue[atomicAdd(&m->nq, 1)] = orig;
+        else out[orig] = (int64_t)bi[0];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) myr = max(myr, __shfl_xor(myr, off));
+    if (threadIdx.x == 0 && myr > 0) atomicMax(&m->maxring, myr);
+    if (counting) {
+        unsigned long long e = evals;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) e += __shfl_xor(e, off);
+        if (threadIdx.x == 0) atomicAdd(&m->evals, e);
+    }
+}
+
+// d2[u] = (dx*dx + dy*dy) + dz*dz with d = x[u] - y[idx[u]], every operation rounded once (the file is built without contraction)
+__global__ __launch_bounds__(kBlock) void k_nearest_d2(const float* __restrict__ x, int xs, int U, const float* __restrict__ y, int ys, int N,
+                                                       const int64_t* __restrict__ idx, float* __restrict__ d2) {
+    const int u = blockIdx.x * kBlock + threadIdx.x;
+    if (u >= U) return;
+    const int64_t j = idx[u];
+    if (j < 0 || j >= (int64_t)N) { d2[u] = INFINITY; return; }
+    const float dx = x[(size_t)u * xs] - y[(size_t)j * ys], dy = x[(size_t)u * xs + 1] - y[(size_t)j * ys + 1];
+    const float dz = x[(size_t)u * xs + 2] - y[(size_t)j * ys + 2];
+    d2[u] = (dx * dx + dy * dy) + dz * dz;
+}
+
 int bits_for_cells(long long cells) {           // bits that hold 0..cells-1; none for one cell
     int b = 0;
     while (b < 62 && (1ll << b) < cells) ++b;
@@ -347,10 +429,8 @@ struct Plan {
     bool ok;
 };
 
-Plan carve(void* d_ws, size_t ws_bytes, int N) {
-    Plan p{};
+void carve(sg::Carver& cv, Plan& p, int N) {
     const size_t n = (size_t)std::max(N, 1);
-    sg::Carver cv(d_ws, ws_bytes);
     p.misc = cv.take<Misc>(1);
     p.cand = cv.take<float4>(n);
     p.spts = cv.take<float4>(n);
@@ -362,7 +442,44 @@ Plan carve(void* d_ws, size_t ws_bytes, int N) {
     p.start = cv.take<int>((size_t)cell_cap(N) + 1);
     p.queue = cv.take<int>(n);
     p.ok = cv.ok;
+}
+
+Plan carve(void* d_ws, size_t ws_bytes, int N) {
+    Plan p{};
+    sg::Carver cv(d_ws, ws_bytes);
+    carve(cv, p, N);
     return p;
+}
+
+size_t plan_bytes(int N) {
+    const size_t n = (size_t)N;
+    return sg::align_up(sizeof(Misc)) + 2 * sg::align_up(n * 16) + 2 * sg::align_up(n * 8) + 3 * sg::align_up(n * 4) +
+           sg::align_up(sgsort::hist_ints((long long)n) * 4) + sg::align_up(((size_t)cell_cap(N) + 1) * 4);
+}
+
+// the queries of the two-cloud search: (x, y, z, |q|^2) in original order, their cell keys and the sort's buffers, the queue
+struct QueryPlan {
+    float4* pts;
+    unsigned long long *k0, *k1;
+    int *v0, *v1;
+    int* hist;
+    int* queue;
+};
+
+void carve(sg::Carver& cv, QueryPlan& q, int U) {
+    const size_t n = (size_t)std::max(U, 1);
+    q.pts = cv.take<float4>(n);
+    q.k0 = cv.take<unsigned long long>(n);
+    q.k1 = cv.take<unsigned long long>(n);
+    q.v0 = cv.take<int>(n);
+    q.v1 = cv.take<int>(n);
+    q.hist = cv.take<int>(sgsort::hist_ints((long long)n));
+    q.queue = cv.take<int>(n);
+}
+
+size_t query_plan_bytes(int U) {
+    const size_t n = (size_t)std::max(U, 1);
+    return sg::align_up(n * 16) + 2 * sg::align_up(n * 8) + 3 * sg::align_up(n * 4) + sg::align_up(sgsort::hist_ints((long long)n) * 4);
 }
 
 // the cells per axis of edge h, in the device's arithmetic (the cell of the box's maximum + 1); false: an axis reaches 2^21 cells
@@ -379,76 +496,61 @@ bool cells_of(const float ext[3], float h, int nc[3], long long* total) {
 
 constexpr int kStages = 7;
 const char* const kStageNames[kStages] = {"box", "probe", "cells", "sort", "table", "search", "fallback"};
-thread_local bool t_timing = false;
-thread_local float t_stage_us[kStages];
-thread_local int64_t t_stats[kNumStats];
-thread_local int t_target = 0, t_ring_limit = 0;        // 0: the defaults
 
-template <int KK>
-void launch_search(const Plan& p, const unsigned long long* skey, const int* sidx, const Grid& g, int N, int32_t* table, int counting,
-                   hipStream_t st) {
-    k_grid_search<KK><<<sg::cdiv(N, kWave), kWave, 0, st>>>(p.spts, sidx, skey, p.start, g, N, table, p.queue, p.misc, counting);
-}
+// what a thread asked for and what its last call left: one set per entry point (the kNN, the nearest point)
+struct Session {
+    bool timing = false;
+    float stage_us[kStages];
+    int64_t stats[kNumStats];
+    int target = 0, ring_limit = 0;         // 0: the defaults
+};
+thread_local Session t_knn, t_nearest;
 
-template <int KK>
-void launch_fallback(const Plan& p, int N, int nq, int32_t* table, int counting, hipStream_t st) {
-    k_grid_fallback<KK><<<sg::cdiv(nq, kTile), kTile, 0, st>>>(p.cand, N, p.queue, nq, table, p.misc, counting);
-}
-
-}  // namespace
-
-extern "C" {
-
-int sg_pointcloud_knn_grid_set_timing(int on) { t_timing = on != 0; return SG_OK; }
-
-int sg_pointcloud_knn_grid_stage_times(float* h_us, int cap) {
-    SG_REQUIRE(h_us && cap >= kStages, "sg_pointcloud_knn_grid_stage_times: room for %d floats is needed", kStages);
-    for (int i = 0; i < kStages; ++i) h_us[i] = t_stage_us[i];
+int stage_times(const Session& s, const char* who, float* h_us, int cap) {
+    SG_REQUIRE(h_us && cap >= kStages, "%s: room for %d floats is needed", who, kStages);
+    for (int i = 0; i < kStages; ++i) h_us[i] = s.stage_us[i];
     return kStages;
 }
 
-const char* sg_pointcloud_knn_grid_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
-
-int sg_pointcloud_knn_grid_stats(int64_t* h, int cap) {
-    SG_REQUIRE(h && cap >= kNumStats, "sg_pointcloud_knn_grid_stats: room for %d words is needed", kNumStats);
-    for (int i = 0; i < kNumStats; ++i) h[i] = t_stats[i];
+int stats_of(const Session& s, const char* who, int64_t* h, int cap) {
+    SG_REQUIRE(h && cap >= kNumStats, "%s: room for %d words is needed", who, kNumStats);
+    for (int i = 0; i < kNumStats; ++i) h[i] = s.stats[i];
     return kNumStats;
 }
 
-int sg_pointcloud_knn_grid_set_tuning(int target_occupancy, int ring_limit) {
+int set_tuning(Session& s, const char* who, int target_occupancy, int ring_limit) {
     SG_REQUIRE(target_occupancy >= 0 && target_occupancy <= 4096 && ring_limit >= 0 && ring_limit <= kMaxRingLimit,
-               "sg_pointcloud_knn_grid_set_tuning: target occupancy 0..4096 and ring limit 0..%d (0: the default)", kMaxRingLimit);
-    t_target = target_occupancy;
-    t_ring_limit = ring_limit;
+               "%s: target occupancy 0..4096 and ring limit 0..%d (0: the default)", who, kMaxRingLimit);
+    s.target = target_occupancy;
+    s.ring_limit = ring_limit;
     return SG_OK;
 }
 
-size_t sg_pointcloud_knn_grid_ws_bytes(int N, int k) {
-    if (N < 1 || N > SG_MAX_GRID_POINTS || (k != 5 && k != 10 && k != 20)) return 0;
-    const size_t n = (size_t)N;
-    return sg::align_up(sizeof(Misc)) + 2 * sg::align_up(n * 16) + 2 * sg::align_up(n * 8) + 3 * sg::align_up(n * 4) +
-           sg::align_up(sgsort::hist_ints((long long)n) * 4) + sg::align_up(((size_t)cell_cap(N) + 1) * 4);
+void leave_stats(Session& s, const Grid& g, const Misc& hm, int nq, unsigned long long evals) {
+    unsigned int hbits;
+    std::memcpy(&hbits, &g.h, 4);
+    s.stats[0] = g.nc[0]; s.stats[1] = g.nc[1]; s.stats[2] = g.nc[2];
+    s.stats[3] = hm.occupied; s.stats[4] = hm.maxcell; s.stats[5] = (int64_t)hbits;
+    s.stats[6] = hm.maxring; s.stats[7] = nq; s.stats[8] = (int64_t)evals;
 }
 
-int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, float cell, int32_t* d_knn, void* d_ws, size_t ws_bytes,
-                           void* stream) {
-    const char* who = "sg_pointcloud_knn_grid";
-    for (int i = 0; i < kNumStats; ++i) t_stats[i] = 0;
-    if (k != 5 && k != 10 && k != 20) return sg::fail(SG_EUNSUP, "%s: k = %d is not built (5, 10 = the reference's default, 20)", who, k);
-    SG_REQUIRE(N > 0, "%s: bad arguments", who);
-    if (N <= k) return sg::fail(SG_EINVAL, "%s: %d points for k = %d (topk(k + 1) raises in the reference)", who, N, k);
-    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
-    SG_REQUIRE(d_points && stride >= 3 && d_knn && d_ws, "%s: bad arguments", who);
-    SG_REQUIRE(std::isfinite(cell) && cell >= 0.0f, "%s: the cell edge must be finite and positive, or 0 for the library's choice (%g)", who, (double)cell);
-    const Plan p = carve(d_ws, ws_bytes, N);
-    if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_pointcloud_knn_grid_ws_bytes(N, k));
-    hipStream_t st = sg::as_stream(stream);
+struct Index {
+    Grid g;
+    const unsigned long long* skey;     // the candidates' sorted keys
+    const int* sidx;                    // and their original indices
+};
+
+// The stages box, probe, cells, sort and table over the N candidates of `d_points`: p.cand, p.spts, p.start and
+// the sorted keys / indices.  With queries (d_q, U > 0) the finite check, the box, E and M2 run over the UNION of the two clouds and
+// q_pts receives the queries' (x, y, z, |q|^2); the index itself holds the candidates only.  `brute`: the entry point that decides a cloud
+// whose score margin is not finite.
+int build_index(const char* who, const char* brute, const Session& ses, const float* d_points, int stride, int N, const float* d_q, int qstride,
+                int U, float4* q_pts, float cell, const Plan& p, sgos::StageClock<kStages>& clock, hipStream_t st, Index* out) {
     const int nb = sg::cdiv(N, kBlock);
-    const int counting = t_timing ? 1 : 0;
-    sgos::StageClock<kStages> clock(st, t_timing, t_stage_us);
     // box
     k_grid_init<<<1, 1, 0, st>>>(p.misc);
     k_grid_box<<<std::min(nb, kBoxBlocks), kBlock, 0, st>>>(d_points, stride, N, p.cand, p.misc);
+    if (U > 0) k_grid_box<<<std::min(sg::cdiv(U, kBlock), kBoxBlocks), kBlock, 0, st>>>(d_q, qstride, U, q_pts, p.misc);
     Misc hm{};
     SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
     SG_HIP(hipStreamSynchronize(st));
@@ -459,9 +561,10 @@ int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, floa
     const float delta = std::max(std::ldexp(m2, -19), std::ldexp(1.0f, -100));
     if (!std::isfinite(4.0f * m2) || !std::isfinite(delta))
         return sg::fail(SG_EUNSUP, "%s: the coordinates are too large for the grid's score margin (max |p|^2 = %g); the brute-force path "
-                                   "(sg_pointcloud_knn) decides such a cloud", who, (double)m2);
+                                   "(%s) decides such a cloud", who, (double)m2, brute);
     clock.tick();
-    Grid g{};
+    Grid& g = out->g;
+    g = Grid{};
     float ext[3], emax = 0.0f;
     for (int a = 0; a < 3; ++a) {
         g.lo[a] = unkey_host(hm.lo[a]);
@@ -470,7 +573,7 @@ int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, floa
     }
     g.delta = delta;
     g.slack = std::ldexp(emax, -21);                    // 8 u E, u = 2^-24
-    g.rmax = t_ring_limit > 0 ? t_ring_limit : kRingLimit;
+    g.rmax = ses.ring_limit > 0 ? ses.ring_limit : kRingLimit;
     const long long cap = cell_cap(N);
     long long total = 0;
     // h, enlarged until no axis reaches 2^21 cells and the grid fits the table
@@ -504,7 +607,7 @@ int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, floa
         clock.tick();
     } else {
         // first guess: the cloud as a surface of the box's half area (a line: its length), `target` points per cell
-        const float target = (float)(t_target > 0 ? t_target : kTargetOccupancy);
+        const float target = (float)(ses.target > 0 ? ses.target : kTargetOccupancy);
         const float area = ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2];
         const float h0 = fit(std::max(std::sqrt(target * area / (float)N), target * emax / (float)N));
         bin(h0);
@@ -528,17 +631,68 @@ int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, floa
     if (!binned) bin(cell);
     clock.tick();
     if (!binned) sort();
-    const unsigned long long* skey = L.kin[0] ? L.kin[0] : p.k0;
-    const int* sidx = L.vin[0] ? L.vin[0] : p.v0;
-    k_grid_gather<<<nb, kBlock, 0, st>>>(p.cand, sidx, N, p.spts);
+    out->skey = L.kin[0] ? L.kin[0] : p.k0;
+    out->sidx = L.vin[0] ? L.vin[0] : p.v0;
+    k_grid_gather<<<nb, kBlock, 0, st>>>(p.cand, out->sidx, N, p.spts);
     clock.tick();
-    k_grid_table<<<sg::cdiv((long long)g.ncells + 1, kBlock), kBlock, 0, st>>>(skey, N, g.ncells, p.start);
+    k_grid_table<<<sg::cdiv((long long)g.ncells + 1, kBlock), kBlock, 0, st>>>(out->skey, N, g.ncells, p.start);
     k_grid_cellstats<<<sg::cdiv(g.ncells, kBlock), kBlock, 0, st>>>(p.start, g.ncells, p.misc);
     clock.tick();
-    if (k == 5) launch_search<6>(p, skey, sidx, g, N, d_knn, counting, st);
-    else if (k == 10) launch_search<11>(p, skey, sidx, g, N, d_knn, counting, st);
-    else launch_search<21>(p, skey, sidx, g, N, d_knn, counting, st);
+    return SG_OK;
+}
+
+template <int KK>
+void launch_search(const Plan& p, const unsigned long long* skey, const int* sidx, const Grid& g, int N, int32_t* table, int counting,
+                   hipStream_t st) {
+    k_grid_search<KK><<<sg::cdiv(N, kWave), kWave, 0, st>>>(p.spts, sidx, skey, p.start, g, N, table, p.queue, p.misc, counting);
+}
+
+template <int KK>
+void launch_fallback(const Plan& p, int N, int nq, int32_t* table, int counting, hipStream_t st) {
+    k_grid_fallback<KK><<<sg::cdiv(nq, kTile), kTile, 0, st>>>(p.cand, N, p.queue, nq, table, p.misc, counting);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sg_pointcloud_knn_grid_set_timing(int on) { t_knn.timing = on != 0; return SG_OK; }
+int sg_pointcloud_knn_grid_stage_times(float* h_us, int cap) { return stage_times(t_knn, "sg_pointcloud_knn_grid_stage_times", h_us, cap); }
+const char* sg_pointcloud_knn_grid_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+int sg_pointcloud_knn_grid_stats(int64_t* h, int cap) { return stats_of(t_knn, "sg_pointcloud_knn_grid_stats", h, cap); }
+int sg_pointcloud_knn_grid_set_tuning(int target_occupancy, int ring_limit) {
+    return set_tuning(t_knn, "sg_pointcloud_knn_grid_set_tuning", target_occupancy, ring_limit);
+}
+
+size_t sg_pointcloud_knn_grid_ws_bytes(int N, int k) {
+    if (N < 1 || N > SG_MAX_GRID_POINTS || (k != 5 && k != 10 && k != 20)) return 0;
+    return plan_bytes(N);
+}
+
+int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, float cell, int32_t* d_knn, void* d_ws, size_t ws_bytes,
+                           void* stream) {
+    const char* who = "sg_pointcloud_knn_grid";
+    for (int i = 0; i < kNumStats; ++i) t_knn.stats[i] = 0;
+    if (k != 5 && k != 10 && k != 20) return sg::fail(SG_EUNSUP, "%s: k = %d is not built (5, 10 = the reference's default, 20)", who, k);
+    SG_REQUIRE(N > 0, "%s: bad arguments", who);
+    if (N <= k) return sg::fail(SG_EINVAL, "%s: %d points for k = %d (topk(k + 1) raises in the reference)", who, N, k);
+    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
+    SG_REQUIRE(d_points && stride >= 3 && d_knn && d_ws, "%s: bad arguments", who);
+    SG_REQUIRE(std::isfinite(cell) && cell >= 0.0f, "%s: the cell edge must be finite and positive, or 0 for the library's choice (%g)", who, (double)cell);
+    const Plan p = carve(d_ws, ws_bytes, N);
+    if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_pointcloud_knn_grid_ws_bytes(N, k));
+    hipStream_t st = sg::as_stream(stream);
+    const int counting = t_knn.timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, t_knn.timing, t_knn.stage_us);
+    Index ix{};
+    const int rc = build_index(who, "sg_pointcloud_knn", t_knn, d_points, stride, N, nullptr, 0, 0, nullptr, cell, p, clock, st, &ix);
+    if (rc != SG_OK) return rc;
+    const Grid& g = ix.g;
+    if (k == 5) launch_search<6>(p, ix.skey, ix.sidx, g, N, d_knn, counting, st);
+    else if (k == 10) launch_search<11>(p, ix.skey, ix.sidx, g, N, d_knn, counting, st);
+    else launch_search<21>(p, ix.skey, ix.sidx, g, N, d_knn, counting, st);
     clock.tick();
+    Misc hm{};
     SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
     SG_HIP(hipStreamSynchronize(st));
     SG_LAUNCH_CHECK();
@@ -553,11 +707,69 @@ int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, floa
     }
     clock.tick();
     SG_LAUNCH_CHECK();
-    unsigned int hbits;
-    std::memcpy(&hbits, &g.h, 4);
-    t_stats[0] = g.nc[0]; t_stats[1] = g.nc[1]; t_stats[2] = g.nc[2];
-    t_stats[3] = hm.occupied; t_stats[4] = hm.maxcell; t_stats[5] = (int64_t)hbits;
-    t_stats[6] = hm.maxring; t_stats[7] = nq; t_stats[8] = (int64_t)hm.evals;
+    leave_stats(t_knn, g, hm, nq, hm.evals);
+    return SG_OK;
+}
+
+int sg_nearest_point_grid_set_timing(int on) { t_nearest.timing = on != 0; return SG_OK; }
+int sg_nearest_point_grid_stage_times(float* h_us, int cap) { return stage_times(t_nearest, "sg_nearest_point_grid_stage_times", h_us, cap); }
+const char* sg_nearest_point_grid_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+int sg_nearest_point_grid_stats(int64_t* h, int cap) { return stats_of(t_nearest, "sg_nearest_point_grid_stats", h, cap); }
+int sg_nearest_point_grid_set_tuning(int target_occupancy, int ring_limit) {
+    return set_tuning(t_nearest, "sg_nearest_point_grid_set_tuning", target_occupancy, ring_limit);
+}
+
+size_t sg_nearest_point_grid_ws_bytes(int U, int N) {
+    if (U < 0 || U > SG_MAX_CLOUD_POINTS || N < 1 || N > SG_MAX_GRID_POINTS) return 0;
+    return plan_bytes(N) + query_plan_bytes(U);
+}
+
+int sg_nearest_point_grid(const float* d_x, int x_stride, int U, const float* d_y, int y_stride, int N, float cell, int64_t* d_idx, float* d_d2,
+                          void* d_ws, size_t ws_bytes, void* stream) {
+    const char* who = "sg_nearest_point_grid";
+    for (int i = 0; i < kNumStats; ++i) t_nearest.stats[i] = 0;
+    SG_REQUIRE(N >= 1 && U >= 0, "%s: bad arguments (%d queries, %d candidates)", who, U, N);
+    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d candidates; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
+    if (U > SG_MAX_CLOUD_POINTS) return sg::fail(SG_EUNSUP, "%s: %d queries; a call takes at most %d", who, U, SG_MAX_CLOUD_POINTS);
+    SG_REQUIRE(y_stride >= 3 && x_stride >= 3, "%s: rows of at least 3 floats (x: %d, y: %d)", who, x_stride, y_stride);
+    SG_REQUIRE(std::isfinite(cell) && cell >= 0.0f, "%s: the cell edge must be finite and positive, or 0 for the library's choice (%g)", who, (double)cell);
+    if (U == 0) return SG_OK;
+    SG_REQUIRE(d_x && d_y && d_idx && d_ws, "%s: bad arguments", who);
+    SG_REQUIRE(ws_bytes >= sg_nearest_point_grid_ws_bytes(U, N), "%s: workspace too small (%zu < %zu)", who, ws_bytes,
+               sg_nearest_point_grid_ws_bytes(U, N));
+    Plan p{};
+    QueryPlan q{};
+    sg::Carver cv(d_ws, ws_bytes);
+    carve(cv, p, N);
+    carve(cv, q, U);
+    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_nearest_point_grid_ws_bytes(U, N));
+    hipStream_t st = sg::as_stream(stream);
+    const int counting = t_nearest.timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, t_nearest.timing, t_nearest.stage_us);
+    Index ix{};
+    const int rc = build_index(who, "sg_nearest_point", t_nearest, d_y, y_stride, N, d_x, x_stride, U, q.pts, cell, p, clock, st, &ix);
+    if (rc != SG_OK) return rc;
+    const Grid& g = ix.g;
+    // the queries in the order of their cell keys: 64 consecutive ones are a wave's groups
+    const int ub = sg::cdiv(U, kBlock);
+    k_grid_cells<<<ub, kBlock, 0, st>>>(q.pts, U, g, q.k0, q.v0);
+    sgsort::Lists<unsigned long long, int> L{};
+    L.kin[0] = q.k0; L.kout[0] = q.k1; L.vin[0] = q.v0; L.vout[0] = q.v1; L.hist[0] = q.hist; L.n[0] = U;
+    sgsort::radix_sort<unsigned long long, int, true>(L, 1, 0, bits_for_cells(g.ncells), st);
+    k_nearest_search<<<sg::cdiv(U, kWave), kWave, 0, st>>>(p.spts, ix.sidx, p.start, g, q.pts, L.kin[0], L.vin[0], U, d_idx, q.queue, p.misc, counting);
+    clock.tick();
+    Misc hm{};
+    SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    const int nq = hm.nq;
+    if (nq < 0 || nq > U) return sg::fail(SG_EHIP, "%s: %d queued queries from %d", who, nq, U);
+    // the queue against every candidate in original order: sg_nearest_point's kernel, scattered to the queries' rows
+    if (nq > 0) sgcloud::launch_nearest(d_x, x_stride, q.queue, nq, p.cand, N, d_idx, 1, st);
+    if (d_d2) k_nearest_d2<<<ub, kBlock, 0, st>>>(d_x, x_stride, U, d_y, y_stride, N, d_idx, d_d2);
+    clock.tick();
+    SG_LAUNCH_CHECK();
+    leave_stats(t_nearest, g, hm, nq, counting ? hm.evals + (unsigned long long)nq * (unsigned long long)N : 0ull);
     return SG_OK;
 }
 

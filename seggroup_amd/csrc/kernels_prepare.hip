@@ -13,8 +13,8 @@
 // eight over all 64 bits), exclusive scans and an adjacent-unique compaction.
 // All of it is index / byte work (HBM- and sort-bound) except the nearest-point search, a brute-force scan in the
 // reference's exact fp32 formula  s_ij = ((-xx_i) - (-2 x_i.y_j)) - yy_j  (argmax, lowest j on ties): at ScanNet's worst
-// case (380k unsampled vertices x 150k samples = 5.7e10 pairs) that is ~4.6e11 VALU lane-ops, ~15 ms on MI355X, so a
-// spatial index is not worth its exactness proof.
+// case (380k unsampled vertices x 150k samples = 5.7e10 pairs) that is ~4.6e11 VALU lane-ops, ~15 ms on MI355X.  Beyond that shape the
+// exact grid index of kernels_knn_grid.hip (sg_nearest_point_grid) gives the same indices; its queue ends in k_nearest.
 #include "sg_common.h"
 #include "sort_device.h"
 #include "cloud_knn_device.h"
@@ -192,6 +192,11 @@ int sort_unique_edges(unsigned long long* const* a, unsigned long long* const* b
 }
 
 }  // namespace
+
+void sgcloud::launch_nearest(const float* qxyz, int qstride, const int32_t* qid, int U, const float4* cand, int N, int64_t* out, int scatter,
+                             hipStream_t st) {
+    k_nearest<<<sg::cdiv(U, kTile), kTile, 0, st>>>(qxyz, qstride, qid, U, cand, N, out, scatter);
+}
 
 extern "C" {
 

@@ -24,6 +24,8 @@ NUM_LABEL_VECTORS = 14
 KNN_BRUTE, KNN_GRID = 0, 1
 KNN_INDEX = {"brute": KNN_BRUTE, "grid": KNN_GRID}
 MAX_GRID_POINTS = 1 << 24
+MAX_POINTS = 1 << 20
+MAX_CLOUD_POINTS = 1 << 27
 
 
 def knn_index(index) -> int:
@@ -157,6 +159,13 @@ SIGNATURES = {
     "sg_pcseg_ws_bytes_indexed": (_Z, [_I, _I, _I]),
     "sg_pcseg_edges_indexed": (_I, [vp, _I, _I, vp, _I, C.c_float, vp, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_pcseg_scan_indexed": (_I, [vp, _I, _I, vp, _I, C.c_float, C.c_float, _I, vp, vp, _Z, vp]),
+    "sg_nearest_point_grid_ws_bytes": (_Z, [_I, _I]),
+    "sg_nearest_point_grid": (_I, [vp, _I, _I, vp, _I, _I, C.c_float, vp, vp, vp, _Z, vp]),
+    "sg_nearest_point_grid_set_timing": (_I, [_I]),
+    "sg_nearest_point_grid_stage_times": (_I, [vp, _I]),
+    "sg_nearest_point_grid_stage_name": (C.c_char_p, [_I]),
+    "sg_nearest_point_grid_stats": (_I, [vp, _I]),
+    "sg_nearest_point_grid_set_tuning": (_I, [_I, _I]),
     "sg_segment_vote_ws_bytes": (_Z, [_I]),
     "sg_segment_rank": (_I, [vp, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_segment_vote": (_I, [vp, vp, _I, _I] + [vp] * 9 + [C.POINTER(C.c_int), vp, _Z, vp]),

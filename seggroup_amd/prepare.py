@@ -20,6 +20,7 @@ the aggregation and click files in the first place -- stays out of scope.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import json
 import os
@@ -157,9 +158,49 @@ def _t(a, dtype, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype)
 
 
-def get_unmapper(x, y, device=None):
-    """util.py:538-550: for every row of x [U,3] the index of its nearest row of y [N,3] (LongTensor on the device)."""
+def nearest_grid_stats() -> dict:
+    """What the calling thread's last grid-indexed nearest-point search did: cells per axis, occupied cells and the largest
+    cell of the candidates' index, the cell edge used, the largest ring count of a query the rings settled, the queries finished against
+    every candidate, and the pair scores evaluated (counted in timed calls only)."""
+    h = (C.c_int64 * 16)()
+    hip.check(hip.lib().sg_nearest_point_grid_stats(h, 16))
+    return dict(cells=(int(h[0]), int(h[1]), int(h[2])), occupied=int(h[3]), largest_cell=int(h[4]),
+                cell=float(np.array([h[5]], dtype=np.uint32).view(np.float32)[0]), max_ring=int(h[6]), fallback=int(h[7]), scores=int(h[8]))
+
+
+def nearest_point_grid(x, y, cell=None, device=None, stream=None, want_d2=True):
+    """sg_nearest_point_grid: for every row of x [U, >= 3] the index of its best-scoring row of y [N, >= 3], exactly
+    get_unmapper's, from the exact grid index -> (idx int64 [U], d2 float32 [U] or None), device tensors.  `cell` forces the cell edge
+    (a performance knob: the result does not depend on it)."""
     import torch
+    edge = hip.knn_cell(cell)
+    dev = _dev(device)
+    lib = hip.lib()
+    with torch.cuda.device(dev), (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+        dx, dy = _t(x, torch.float32, dev), _t(y, torch.float32, dev)
+        if dx.dim() != 2 or dy.dim() != 2 or dx.shape[1] < 3 or dy.shape[1] < 3:
+            raise ValueError("nearest_point_grid: x and y must be [*, >= 3]")
+        u, n = int(dx.shape[0]), int(dy.shape[0])
+        sp = stream.cuda_stream if stream is not None else None
+        need = lib.sg_nearest_point_grid_ws_bytes(u, n)
+        if need == 0:                                               # outside the envelope: the library says why, nothing is allocated
+            hip.check(lib.sg_nearest_point_grid(None, int(dx.shape[1]), u, None, int(dy.shape[1]), n, edge, None, None, None, 0, sp))
+        idx = torch.empty(u, dtype=torch.int64, device=dev)
+        d2 = torch.empty(u, dtype=torch.float32, device=dev) if want_d2 else None
+        ws = _ws(need, dev)
+        hip.check(lib.sg_nearest_point_grid(dx.data_ptr(), int(dx.shape[1]), u, dy.data_ptr(), int(dy.shape[1]), n, edge, idx.data_ptr(),
+                                            d2.data_ptr() if want_d2 else None, ws.data_ptr(), ws.numel(), sp))
+        (stream.synchronize() if stream is not None else torch.cuda.current_stream(dev).synchronize())
+    return idx, d2
+
+
+def get_unmapper(x, y, device=None, index="brute", cell=None):
+    """util.py:538-550: for every row of x [U,3] the index of its nearest row of y [N,3] (LongTensor on the device).
+    `index="grid"`: the same indices from the exact grid index (`cell` forces its cell edge)."""
+    import torch
+    which, edge = hip.knn_index(index), hip.knn_cell(cell)
+    if which == hip.KNN_GRID:
+        return nearest_point_grid(x, y, cell=edge, device=device, want_d2=False)[0]
     dev = _dev(device)
     lib = hip.lib()
     dx, dy = _t(x, torch.float32, dev), _t(y, torch.float32, dev)
@@ -172,13 +213,26 @@ def get_unmapper(x, y, device=None):
     return out
 
 
-def sample_points(xyz, rgb, mapper, device=None):
-    """The compute of generate_pointcloud_pth: -> (pointcloud_sampled [Np,6] f32, unmapper [V] i64, #unsampled vertices)."""
+def sample_points(xyz, rgb, mapper, device=None, index="brute"):
+    """The compute of generate_pointcloud_pth: -> (pointcloud_sampled [Np,6] f32, unmapper [V] i64, #unsampled vertices).
+    `index="grid"`: the unsampled vertices find their nearest sampled point through the exact grid index -- the same
+    unmapper."""
     import torch
+    which = hip.knn_index(index)
     dev = _dev(device)
     lib = hip.lib()
     d_xyz, d_rgb, d_map = _t(xyz, torch.float32, dev), _t(rgb, torch.uint8, dev), _t(mapper, torch.int64, dev)
     v, n = d_xyz.shape[0], d_map.shape[0]
+    if which == hip.KNN_GRID:
+        # the gather and the unmapper of the sampled vertices are index work (the last occurrence of a vertex in the mapper wins);
+        # the search of the compacted `missing` list is the library's
+        pcl = torch.cat([d_xyz[d_map], (d_rgb[d_map].to(torch.float64) / 127.5 - 1.0).to(torch.float32)], 1).contiguous()
+        unmap = torch.full((v,), -1, dtype=torch.int64, device=dev)
+        unmap.scatter_reduce_(0, d_map, torch.arange(n, dtype=torch.int64, device=dev), "amax", include_self=True)
+        missing = torch.nonzero(unmap < 0).reshape(-1)
+        if missing.numel():
+            unmap[missing] = nearest_point_grid(d_xyz[missing].contiguous(), pcl, device=dev, want_d2=False)[0]
+        return pcl, unmap, int(missing.numel())
     pcl = torch.empty((n, 6), dtype=torch.float32, device=dev)
     unmap = torch.empty(v, dtype=torch.int64, device=dev)
     ws = _ws(lib.sg_prep_sample_ws_bytes(v, n), dev)
@@ -318,7 +372,7 @@ def make_mapper(num_vertices: int, num_points: int, perm=None):
     return index_remainder
 
 
-def generate_pointcloud_pth(scene_path, item, num_points, plydata=None, root: str = ".", perm=None, device=None):
+def generate_pointcloud_pth(scene_path, item, num_points, plydata=None, root: str = ".", perm=None, device=None, index: str = "brute"):
     """util.py:633-693: `.pcl.pth` f32 [num_points,6], `.info.pth`, `.map.pth`, `.unmap.pth` under data/resampled/<scene>/."""
     import torch
     scene_name = _scene_name(scene_path)
@@ -326,7 +380,7 @@ def generate_pointcloud_pth(scene_path, item, num_points, plydata=None, root: st
         plydata = read_ply(os.path.join(scene_path, scene_name + "_vh_clean_2.ply"))
     xyz, rgb, _ = mesh_arrays(plydata)
     mapper = make_mapper(xyz.shape[0], num_points, perm)
-    pcl, unmap, _ = sample_points(xyz, rgb, mapper, device=device)
+    pcl, unmap, _ = sample_points(xyz, rgb, mapper, device=device, index=index)
     out = os.path.join(root, "data", "resampled", scene_name)
     os.makedirs(out, exist_ok=True)
     torch.save(pcl.cpu(), os.path.join(out, scene_name + ".pcl.pth"))
@@ -384,12 +438,14 @@ from .labels import (generate_real_label_pth, generate_real_labels, generate_seg
 
 
 def prepare_scene(scene_path, item, num_points: int = 150000, root: str = ".", perm=None, device=None, label_style: Optional[str] = None,
-                  manual_label_path: Optional[str] = None, oversegment: bool = False, knn: int = 10):
+                  manual_label_path: Optional[str] = None, oversegment: bool = False, knn: int = 10, index: str = "brute"):
     """What prepare_data.py:36-71 + prepare_weak_label.py:60-90 do for one scan: point cloud, mapper / unmapper, segment lists,
     mesh adjacency and -- with `label_style` and ScanNet's annotation files next to the mesh -- the ground-truth and weak-label
     files, i.e. every input of SegModel.forward.  `oversegment=True`: a scan without a segs.json gets one from its mesh first
     (oversegment.py, default parameters); an existing file is never overwritten.  A scan without faces (a point cloud) is segmented
-    over the kNN graph of its points (`knn` neighbours), and that graph stands in for the mesh adjacency."""
+    over the kNN graph of its points (`knn` neighbours), and that graph stands in for the mesh adjacency.  `index="grid"`: the
+    unsampled vertices' nearest sampled point comes from the exact grid index; the files are the same."""
+    hip.knn_index(index)
     scene_name = _scene_name(scene_path)
     ply = read_ply(os.path.join(scene_path, scene_name + "_vh_clean_2.ply"))
     if oversegment:
@@ -397,7 +453,7 @@ def prepare_scene(scene_path, item, num_points: int = 150000, root: str = ".", p
         oversegment_scan(scene_path, device=device, plydata=ply, knn=knn)
     elif not has_faces(ply) and not os.path.exists(os.path.join(scene_path, scene_name + "_vh_clean_2.0.010000.segs.json")):
         raise ValueError(f"{scene_name}: a scan without faces and without a segs.json: pass oversegment=True to make one from the points")
-    generate_pointcloud_pth(scene_path, item, num_points, ply, root=root, perm=perm, device=device)
+    generate_pointcloud_pth(scene_path, item, num_points, ply, root=root, perm=perm, device=device, index=index)
     generate_seg_labels_and_ds_set(scene_path, root=root, device=device)
     generate_mesh_adjcency_pth(scene_name, ply, root=root, device=device, knn=knn)
     if label_style is not None:
