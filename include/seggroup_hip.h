@@ -35,6 +35,7 @@ extern "C" {
 #define SG_ENOMEM     -3   /* workspace too small / allocation failed                              */
 #define SG_ESTALL     -4   /* reference would loop forever (model.py:228-239)       */
 #define SG_EUNSUP     -5   /* size outside the supported envelope (documented per function)        */
+#define SG_EINTERNAL  -6   /* a bounded device loop ran out of its budget: a defect, never the input */
 
 #define SG_MODE_INS_INFER 0   /* infer.py --ins_infer : all five layers (model.py:684-897)         */
 #define SG_MODE_SEM_INFER 1   /* infer.py --sem_infer : returns after layer 2 (model.py:781-783)   */
@@ -919,6 +920,36 @@ int sg_nearest_point_grid_stage_times(float* h_us, int cap);
 const char* sg_nearest_point_grid_stage_name(int i);
 int sg_nearest_point_grid_stats(int64_t* h, int cap);
 int sg_nearest_point_grid_set_tuning(int target_occupancy, int ring_limit);
+
+/* Connected components of a scan's graph.  Vertices 0..V-1, 1 <= V <= SG_MAX_CLOUD_POINTS; the undirected graph comes from
+ * one of three sources:
+ *   sg_components_edges  d_edges int32 [E,2], 0 <= E < 2^30: a row (a, a) is a no-op, duplicates and both orientations are allowed, no order
+ *                        is assumed (the ascending-weight lists of sg_overseg_edges / sg_pcseg_edges and lexicographic ones alike).
+ *   sg_components_faces  d_faces int32 [F,3]: the three sides of every face; a degenerate face contributes what is left of it.
+ *   sg_components_knn    d_knn int32 [N,row] as sg_pointcloud_knn / sg_pointcloud_knn_grid write it (row = k + 1 >= 2), V = N: the pairs
+ *                        (i, L[i][t]), t = 1..row-1 (entry 0 is skipped whatever it holds), that have j != i and d2 <= r2, where
+ *                        d = p_j - p_i, d2 = (d0*d0 + d1*d1) + d2*d2 and r2 = max_edge * max_edge, fp32, each operation rounded once.
+ *                        max_edge = +inf admits every pair.  Points are rows of `stride` >= 3 floats.  This is the kNN graph cut at a
+ *                        length, not a radius graph.
+ * d_label (may be NULL) int32 [V]: a pair counts only when both ends hold the same value (any value).
+ *   d_comp [V] = the lowest vertex index of the vertex's component; d_size [V] (may be NULL) = the component's vertex count, at every
+ *   vertex; *h_C = the number of components = #{v : d_comp[v] == v}.  Integers only: the same bytes on every run.  E = 0 and F = 0 are
+ *   valid: every vertex is its own component.
+ * SG_EINVAL: a null pointer, V < 1, E or F < 0, stride < 3, row < 2, max_edge that is 0, negative or NaN, a workspace below
+ *   sg_components_ws_bytes(V) (all before the first HIP call); a vertex index outside 0..V-1, in the kNN form a coordinate that is not
+ *   finite (one flag word on the device, read with the call's single synchronisation; the outputs are then undefined).  SG_EUNSUP: V above
+ *   SG_MAX_CLOUD_POINTS, E >= 2^30.  SG_EINTERNAL: a chase ran out of its 2 V + 4 steps, which no input can cause.
+ * Synchronises the stream once.  Stage times by events, as sg_overseg_set_timing: room for 4 floats (tools/time_components.py). */
+size_t sg_components_ws_bytes(int V);          /* 0 when V < 1 or V > SG_MAX_CLOUD_POINTS */
+int sg_components_edges(const int32_t* d_edges, long long E, int V, const int32_t* d_label, int32_t* d_comp, int32_t* d_size, int* h_C,
+                        void* d_ws, size_t ws_bytes, void* stream);
+int sg_components_faces(const int32_t* d_faces, int F, int V, const int32_t* d_label, int32_t* d_comp, int32_t* d_size, int* h_C,
+                        void* d_ws, size_t ws_bytes, void* stream);
+int sg_components_knn(const float* d_points, int stride, const int32_t* d_knn, int N, int row, float max_edge, const int32_t* d_label,
+                      int32_t* d_comp, int32_t* d_size, int* h_C, void* d_ws, size_t ws_bytes, void* stream);
+int sg_components_set_timing(int on);
+int sg_components_stage_times(float* h_us, int cap);
+const char* sg_components_stage_name(int i);
 
 /* Segment vote: what re-keying a scan's annotations onto another over-segmentation needs on the device.  Every vertex has a
  * row id d_ids[v] (any non-negative int32: not contiguous, may exceed V) and a column d_cols[v] in 0..n_cols-1; both are checked on the

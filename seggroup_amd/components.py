@@ -1,0 +1,401 @@
+"""Connected components of a scan on the GPU; scans without their floating pieces; pseudo instances that fall apart.
+
+A laser scan or a fused depth cloud carries specks of a few points away from every surface, a reconstructed mesh small floating patches.
+No click reaches them, so each goes down the unlabeled fallback and puts noise into some instance's pseudo label.  `components` labels
+every vertex with the lowest vertex index of its component (`sg_components_edges` / `_faces` / `_knn`: one hooking pass over the pairs on
+the GPU, integers only, the same bytes on every run; there is no other path).  The graph is an edge list, a mesh's faces, or a kNN table
+cut at a length -- the kNN graph as it is, not a radius graph: a point with more than k neighbours inside the length links to its k
+nearest only.
+
+    python -m seggroup_amd.components --scans DIR --out DIR (--min-verts M | --largest) [--pointcloud --knn {5,10,20} --max-edge R
+                                      --index {grid,brute}] [--scenes FILE] [--force] [--workers W] [--device D] [--report-only]
+        every scan directory of --scans -> a scan directory under --out without the small pieces, which every command of the project reads
+        as it is: <scene>_vh_clean_2.ply (the kept vertices in ascending raw index with their colours, the faces whose vertices are kept),
+        <scene>.clean.npz (kept, new_of_old, comp, the parameters), the segs.json taken at the kept vertices and the aggregation file when
+        the source has them; clean_report.json for the run.  A mesh uses its faces; a scan without faces (or --pointcloud) uses its kNN
+        graph and NEEDS --max-edge, in the scan's unit.  Results made on the cleaned scans go back to the raw ones with
+        `python -m seggroup_amd.transfer --from-scans CLEAN --to-scans RAW ...`: a kept vertex is its own nearest vertex at distance 0.
+    python -m seggroup_amd.components --fragments --scans DIR -n EXP --stage S [--layer final] [--root .] [--json OUT] [--max-edge R ...]
+        per scene the pseudo instances of results/EXP/<scene>/<stage>/pseudo_labels.sgl that are in more than one piece of the scan's own
+        graph, their piece sizes, and the share of the vertices outside their instance's largest piece; a report, no label file is touched
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import shutil
+import sys
+from typing import Optional
+
+import numpy as np
+
+from . import hip
+
+MAX_WORKERS = 16
+MAP_SUFFIX = ".clean.npz"
+REPORT_NAME = "clean_report.json"
+KNN_CHOICES = (5, 10, 20)
+
+
+def _shape2(a, cols, what):
+    shape = tuple(a.shape)
+    if len(shape) != 2 or (shape[1] != cols if cols else shape[1] < 2):
+        raise ValueError("components: %s must be [*, %s], not %r" % (what, cols or ">= 2", shape))
+    return int(shape[0]), int(shape[1])
+
+
+def _cut(max_edge) -> float:
+    r = math.inf if max_edge is None else float(max_edge)
+    if not r > 0.0:
+        raise ValueError("components: max_edge must be a length > 0 (None or inf: no cut), not %r" % (max_edge,))
+    return r
+
+
+def components(V: int, *, edges=None, faces=None, knn=None, xyz=None, max_edge=None, labels=None, device=None, stream=None):
+    """-> (comp int32 [V], size int32 [V], C): comp[v] = the lowest vertex index of v's component, size[v] = its vertex count (device
+    tensors), C = the number of components.  Exactly one of `edges` [E,2], `faces` [F,3], `knn` [V, k+1] (with `xyz` [V, >= 3]; a pair
+    counts when its fp32 d2 <= max_edge^2; max_edge=None: every pair).  `labels` [V]: a pair counts only when both ends hold the same
+    value.  NumPy arrays or tensors.  Anything else is a ValueError before a device call."""
+    V = int(V)
+    given = [n for n, a in (("edges", edges), ("faces", faces), ("knn", knn)) if a is not None]
+    if len(given) != 1:
+        raise ValueError("components: exactly one of edges, faces and knn is needed, not %s" % (given or "none"))
+    if V < 1:
+        raise ValueError("components: a graph needs at least one vertex")
+    if knn is None and (xyz is not None or max_edge is not None):
+        raise ValueError("components: xyz and max_edge belong to the knn form")
+    if edges is not None:
+        count, _ = _shape2(edges, 2, "edges")
+    elif faces is not None:
+        count, _ = _shape2(faces, 3, "faces")
+    else:
+        if xyz is None:
+            raise ValueError("components: the knn form needs xyz")
+        count, row = _shape2(knn, 0, "knn")
+        if len(tuple(xyz.shape)) != 2 or xyz.shape[1] < 3 or int(xyz.shape[0]) != V or count != V:
+            raise ValueError("components: the knn form needs knn [V, k+1] and xyz [V, >= 3] with V = %d" % V)
+        cut = _cut(max_edge)
+    if labels is not None and tuple(labels.shape) != (V,):
+        raise ValueError("components: labels must be [%d], not %r" % (V, tuple(labels.shape)))
+
+    import torch
+    from .oversegment import _on, _stream_ptr
+    from .prepare import _dev, _t, _ws
+    dev = _dev(device)
+    lib = hip.lib()
+    need = lib.sg_components_ws_bytes(V)
+    if need == 0:
+        raise hip.SgError(hip.SG_EUNSUP, "components: %d vertices; a graph holds at most 2^27" % V)
+    with torch.cuda.device(dev), _on(stream):
+        d_lab = None if labels is None else _t(labels, torch.int32, dev)
+        comp = torch.empty(V, dtype=torch.int32, device=dev)
+        size = torch.empty(V, dtype=torch.int32, device=dev)
+        ws = _ws(need, dev)
+        c = C.c_int(0)
+        tail = (hip.ptr(d_lab), comp.data_ptr(), size.data_ptr(), C.byref(c), ws.data_ptr(), ws.numel(), _stream_ptr(stream))
+        if edges is not None:
+            d_src = _t(edges, torch.int32, dev)
+            rc = lib.sg_components_edges(d_src.data_ptr() if count else None, count, V, *tail)
+        elif faces is not None:
+            d_src = _t(faces, torch.int32, dev)
+            rc = lib.sg_components_faces(d_src.data_ptr() if count else None, count, V, *tail)
+        else:
+            d_src, d_xyz = _t(knn, torch.int32, dev), _t(xyz, torch.float32, dev)
+            rc = lib.sg_components_knn(d_xyz.data_ptr(), int(d_xyz.shape[1]), d_src.data_ptr(), V, row, cut, *tail)
+        hip.check(rc)                                            # the call synchronised the stream
+    return comp, size, c.value
+
+
+def keep_mask(comp, size, min_verts: Optional[int] = None, largest: bool = False):
+    """-> bool [V]: the vertices of the components with size >= min_verts, or (largest=True) of the largest component alone, the one with
+    the lowest comp among equals.  Exactly one of the two; tensors give a tensor, arrays an array."""
+    if (min_verts is None) == (not largest):
+        raise ValueError("keep_mask: exactly one of min_verts and largest is needed")
+    if largest:
+        big = size == size.max()
+        return comp == comp[big].min()
+    if int(min_verts) < 1:
+        raise ValueError("keep_mask: min_verts must be at least 1")
+    return size >= int(min_verts)
+
+
+def clean_arrays(keep, faces):
+    """-> (kept int32 [M] ascending, new_of_old int32 [V], -1 where dropped, faces int32 [F',3]: the faces whose three vertices are kept,
+    renumbered, in their original order) as tensors on keep's device"""
+    import torch
+    keep = keep.to(torch.bool)
+    kept = torch.nonzero(keep).reshape(-1).to(torch.int32)
+    rank = torch.cumsum(keep.to(torch.int32), 0, dtype=torch.int32) - 1
+    new_of_old = torch.where(keep, rank, torch.full_like(rank, -1))
+    f = faces.to(device=keep.device, dtype=torch.long).reshape(-1, 3)
+    whole = keep[f].all(1)
+    return kept, new_of_old, new_of_old[f[whole]].reshape(-1, 3).to(torch.int32)
+
+
+def _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, what):
+    """-> (source name, keyword arguments of `components`) for a scan's own graph; max_edge is read on the kNN path only"""
+    from .prepare import pointcloud_knn
+    if pointcloud or faces.shape[0] == 0:
+        if max_edge is None:
+            raise ValueError(f"{what}: a scan without faces (or pointcloud=True) needs max_edge, in the scan's unit; a default would be a guess")
+        _cut(max_edge)
+        return "knn", dict(knn=pointcloud_knn(xyz, int(knn), index=index), xyz=xyz, max_edge=max_edge)
+    return "faces", dict(faces=faces)
+
+
+def _segs_name(scene: str) -> str:
+    from .oversegment import segs_json_name
+    return segs_json_name(scene)
+
+
+def clean_scan(scene_path: str, out_dir: str, min_verts: Optional[int] = None, largest: bool = False, pointcloud: bool = False, knn: int = 10,
+               max_edge: Optional[float] = None, index: str = "grid", force: bool = False, device=None, stream=None,
+               report_only: bool = False) -> Optional[dict]:
+    """One scan directory -> <out_dir>/<scene>/ without the small pieces (see the module's doc); -> its entry of clean_report.json, or
+    None when the cleaned PLY was there already (never overwritten without `force`).  `report_only`: the entry alone, nothing written."""
+    import torch
+    from .prepare import _scene_name, mesh_arrays, read_ply, write_ply
+    if (min_verts is None) == (not largest):
+        raise ValueError("clean_scan: exactly one of min_verts and largest is needed")
+    hip.knn_index(index)
+    scene = _scene_name(scene_path)
+    dst = os.path.join(out_dir, scene)
+    ply_out = os.path.join(dst, scene + "_vh_clean_2.ply")
+    if not report_only and os.path.exists(ply_out) and not force:
+        return None
+    xyz, rgb, faces = mesh_arrays(read_ply(os.path.join(scene_path, scene + "_vh_clean_2.ply")))
+    source, graph = _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, scene)
+    v = int(xyz.shape[0])
+    d_comp, d_size, n_comp = components(v, device=device, stream=stream, **graph)
+    with torch.cuda.device(d_comp.device):
+        d_keep = keep_mask(d_comp, d_size, min_verts, largest)
+        d_kept, d_new, d_faces = clean_arrays(d_keep, torch.from_numpy(faces).to(d_comp.device))
+        roots = d_comp == torch.arange(v, dtype=torch.int32, device=d_comp.device)
+        sizes = torch.sort(d_size[roots], descending=True)[0]
+        kept_components = int((roots & d_keep).sum())
+        kept, new_of_old, new_faces, comp = d_kept.cpu().numpy(), d_new.cpu().numpy(), d_faces.cpu().numpy(), d_comp.cpu().numpy()
+        largest_sizes = sizes[:10].cpu().tolist()
+    entry = {"V": v, "M": int(kept.shape[0]), "components": int(n_comp), "kept_components": kept_components, "largest_sizes": largest_sizes,
+             "source": source, "F": int(faces.shape[0]), "kept_F": int(new_faces.shape[0])}
+    segs = os.path.join(scene_path, _segs_name(scene))
+    doc = None
+    if os.path.exists(segs):
+        with open(segs) as f:
+            doc = json.load(f)
+        ids = np.asarray(doc["segIndices"], dtype=np.int64)
+        if ids.shape[0] != v:
+            raise ValueError(f"{segs}: {ids.shape[0]} segIndices for {v} vertices")
+        doc["segIndices"] = ids[kept].tolist()
+        before, after = np.unique(ids), np.unique(ids[kept])
+        entry.update(source_segments=int(before.shape[0]), kept_segments=int(after.shape[0]), lost_segments=np.setdiff1d(before, after).tolist())
+    if report_only:
+        return entry
+    os.makedirs(dst, exist_ok=True)
+    write_ply(ply_out, xyz[kept], rgb[kept], new_faces)
+    np.savez(os.path.join(dst, scene + MAP_SUFFIX), kept=kept, new_of_old=new_of_old, comp=comp, min_verts=np.int32(-1 if min_verts is None else min_verts),
+             largest=np.bool_(largest), source=np.str_(source), knn=np.int32(knn if source == "knn" else 0),
+             max_edge=np.float32(np.inf if max_edge is None else max_edge))
+    if doc is not None:
+        with open(os.path.join(dst, _segs_name(scene)), "w") as f:
+            json.dump(doc, f)
+    agg = os.path.join(scene_path, scene + ".aggregation.json")
+    if os.path.exists(agg):
+        shutil.copyfile(agg, os.path.join(dst, scene + ".aggregation.json"))
+    return entry
+
+
+def _scan_names(scans_dir: str):
+    return sorted(d for d in os.listdir(scans_dir) if os.path.exists(os.path.join(scans_dir, d, d + "_vh_clean_2.ply")))
+
+
+def _threads(scenes, workers, dev, fn):
+    """fn(scene, stream) over the scenes on threads with a stream each -> [(scene, result)] in the scenes' order"""
+    import concurrent.futures
+    import threading
+
+    import torch
+    workers = max(1, min(int(workers), MAX_WORKERS, max(len(scenes), 1)))
+    local = threading.local()
+
+    def one(scene):
+        if not hasattr(local, "stream"):
+            with torch.cuda.device(dev):
+                local.stream = torch.cuda.Stream(device=dev)
+        return scene, fn(scene, local.stream)
+
+    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
+        return list(pool.map(one, scenes))
+
+
+def clean_scans(scans_dir: str, out_dir: str, min_verts: Optional[int] = None, largest: bool = False, pointcloud: bool = False, knn: int = 10,
+                max_edge: Optional[float] = None, index: str = "grid", scenes=None, force: bool = False, workers: int = 4, device=None,
+                report_only: bool = False):
+    """Every scan directory under `scans_dir` (or the named ones) -> (report {scene: entry}, skipped scene names); writes
+    <out_dir>/clean_report.json.  Workers are threads, each with its own stream."""
+    from .prepare import _dev
+    if (min_verts is None) == (not largest):
+        raise ValueError("clean_scans: exactly one of min_verts and largest is needed")
+    dev = _dev(device)
+    if scenes is None:
+        scenes = _scan_names(scans_dir)
+    done = _threads(scenes, workers, dev, lambda scene, stream: clean_scan(os.path.join(scans_dir, scene), out_dir, min_verts, largest, pointcloud,
+                                                                           knn, max_edge, index, force, device=dev, stream=stream,
+                                                                           report_only=report_only))
+    report = {scene: entry for scene, entry in done if entry is not None}
+    skipped = [scene for scene, entry in done if entry is None]
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, REPORT_NAME), "w") as f:
+        json.dump({"min_verts": min_verts, "largest": bool(largest), "pointcloud": bool(pointcloud), "knn": int(knn),
+                   "max_edge": None if max_edge is None else float(max_edge), "index": index, "report_only": bool(report_only),
+                   "scenes": report, "skipped": skipped}, f, indent=1, sort_keys=True)
+        f.write("\n")
+    return report, skipped
+
+
+# ---- pseudo instances that fall apart -------------------------------------------------------------------------------------------------
+def fragments(labels, V: int, **graph) -> dict:
+    """The label-filtered components of a graph (`graph`: the source keywords of `components`) -> dict(instances, fragmented,
+    outside_largest, outside_share, pieces {label: sizes, largest first} of the labels in more than one piece).  Every value of
+    `labels` counts as an instance."""
+    import torch
+    comp, _, _ = components(V, labels=labels, **graph)
+    with torch.cuda.device(comp.device):
+        lab = torch.as_tensor(np.asarray(labels) if not isinstance(labels, torch.Tensor) else labels).to(device=comp.device, dtype=torch.int64)
+        key, count = torch.unique(torch.stack([lab, comp.to(torch.int64)], 1), dim=0, return_counts=True)
+        key, count = key.cpu().numpy(), count.cpu().numpy()
+    inst, first, pieces_per = np.unique(key[:, 0], return_index=True, return_counts=True)
+    pieces, outside = {}, 0
+    for lb, at, n in zip(inst.tolist(), first.tolist(), pieces_per.tolist()):
+        if n > 1:
+            sizes = sorted(count[at:at + n].tolist(), reverse=True)
+            pieces[int(lb)] = sizes
+            outside += sum(sizes[1:])
+    return {"V": int(V), "instances": int(inst.shape[0]), "fragmented": len(pieces), "outside_largest": int(outside),
+            "outside_share": outside / float(V), "pieces": pieces}
+
+
+def fragments_scene(scene_path: str, exp: str, stage: str, layer: str = "final", root: str = ".", pointcloud: bool = False, knn: int = 10,
+                    max_edge: Optional[float] = None, index: str = "grid", device=None, stream=None) -> dict:
+    """`fragments` of one scene's `<layer>.ins` vector on the scan's own graph (its faces, or its kNN graph cut at max_edge)"""
+    from . import pseudo_labels
+    from .prepare import _scene_name, mesh_arrays, read_ply
+    scene = _scene_name(scene_path)
+    lab = pseudo_labels.load(os.path.join(root, "results", exp, scene, stage)).vector(layer + ".ins")
+    xyz, _, faces = mesh_arrays(read_ply(os.path.join(scene_path, scene + "_vh_clean_2.ply")))
+    if lab.shape[0] != xyz.shape[0]:
+        raise ValueError(f"{scene}: {lab.shape[0]} labels for {xyz.shape[0]} vertices")
+    source, graph = _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, scene)
+    out = fragments(lab, int(xyz.shape[0]), device=device, stream=stream, **graph)
+    out["source"] = source
+    out["pieces"] = {str(k): v for k, v in out["pieces"].items()}
+    return out
+
+
+def fragments_scans(scans_dir: str, exp: str, stage: str, layer: str = "final", root: str = ".", scenes=None, workers: int = 4, device=None,
+                    **graph) -> dict:
+    from .prepare import _dev
+    dev = _dev(device)
+    if scenes is None:
+        base = os.path.join(root, "results", exp)
+        scenes = [s for s in _scan_names(scans_dir) if os.path.isdir(os.path.join(base, s, stage))]
+    return dict(_threads(scenes, workers, dev, lambda scene, stream: fragments_scene(os.path.join(scans_dir, scene), exp, stage, layer, root,
+                                                                                     device=dev, stream=stream, **graph)))
+
+
+def _scene_list(path):
+    if not path:
+        return None
+    with open(path) as f:
+        return [ln.strip() for ln in f if ln.strip()]
+
+
+def _positive(text):
+    r = float(text)
+    if not (r > 0.0 and math.isfinite(r)):
+        raise argparse.ArgumentTypeError("a finite length > 0 is needed, not %s" % text)
+    return r
+
+
+def _needs_max_edge(scans_dir, scenes, pointcloud):
+    from .oversegment import _declared_faces
+    if pointcloud:
+        return "--pointcloud"
+    for s in scenes:
+        if _declared_faces(os.path.join(scans_dir, s, s + "_vh_clean_2.ply")) == 0:
+            return "%s has no faces and" % s
+    return None
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m seggroup_amd.components", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--scans", required=True, help="directory of scan directories (<scene>/<scene>_vh_clean_2.ply)")
+    ap.add_argument("--out", default=None, help="where the cleaned scan directories and clean_report.json go")
+    ap.add_argument("--min-verts", type=int, default=None, help="keep the components with at least this many vertices")
+    ap.add_argument("--largest", action="store_true", help="keep the largest component alone")
+    ap.add_argument("--pointcloud", action="store_true", help="use the kNN graph even where the scan has faces")
+    ap.add_argument("--knn", type=int, default=10, choices=KNN_CHOICES, help="neighbours per point of the kNN graph")
+    ap.add_argument("--max-edge", type=_positive, default=None, help="kNN graph: the longest pair that counts, in the scan's unit (no default)")
+    ap.add_argument("--index", default="grid", choices=sorted(hip.KNN_INDEX), help="kNN graph: the neighbour search")
+    ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
+    ap.add_argument("--force", action="store_true", help="overwrite existing cleaned scans")
+    ap.add_argument("--report-only", action="store_true", help="write clean_report.json and no scan")
+    ap.add_argument("--workers", type=int, default=4, help=f"threads, each with its own stream (at most {MAX_WORKERS})")
+    ap.add_argument("--device", default=None)
+    ap.add_argument("--fragments", action="store_true", help="report the pseudo instances that are in more than one piece")
+    ap.add_argument("-n", "--exp_name", default=None, help="--fragments: name of the experiment")
+    ap.add_argument("--stage", default="epoch_last", help="--fragments: the export directory's name")
+    ap.add_argument("--layer", default="final", help="--fragments: final or layer_1 .. layer_4")
+    ap.add_argument("--root", default=".", help="--fragments: directory holding results/ (default: CWD)")
+    ap.add_argument("--json", default=None, help="--fragments: write the report here as well")
+    a = ap.parse_args(argv)
+    if not 1 <= a.workers <= MAX_WORKERS:
+        ap.error(f"--workers must be in 1..{MAX_WORKERS}")
+    scenes = _scene_list(a.scenes)
+    if a.fragments:
+        if not a.exp_name:
+            ap.error("--fragments needs -n EXP")
+        if a.min_verts is not None or a.largest:
+            ap.error("--fragments is a report: --min-verts / --largest belong to cleaning")
+        names = scenes if scenes is not None else [s for s in _scan_names(a.scans)
+                                                   if os.path.isdir(os.path.join(a.root, "results", a.exp_name, s, a.stage))]
+        why = _needs_max_edge(a.scans, names, a.pointcloud)
+        if why and a.max_edge is None:
+            ap.error(f"{why} needs --max-edge R (the scan's unit; there is no default)")
+        if not why and a.max_edge is not None:
+            ap.error("--max-edge belongs to the kNN graph: every scan here is a mesh (--pointcloud ignores the faces)")
+        rep = fragments_scans(a.scans, a.exp_name, a.stage, a.layer, a.root, names, a.workers, a.device, pointcloud=a.pointcloud, knn=a.knn,
+                              max_edge=a.max_edge, index=a.index)
+        for scene, e in rep.items():
+            print("fragments", scene, e["instances"], "instances,", e["fragmented"], "in pieces,", "%.4f" % e["outside_share"], "outside")
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump({"exp": a.exp_name, "stage": a.stage, "layer": a.layer, "scenes": rep}, f, indent=1, sort_keys=True)
+                f.write("\n")
+        return 0
+    if not a.out:
+        ap.error("cleaning needs --out DIR")
+    if (a.min_verts is None) == (not a.largest):
+        ap.error("exactly one of --min-verts M and --largest is needed")
+    if a.min_verts is not None and a.min_verts < 1:
+        ap.error("--min-verts must be at least 1")
+    names = scenes if scenes is not None else _scan_names(a.scans)
+    why = _needs_max_edge(a.scans, names, a.pointcloud)
+    if why and a.max_edge is None:
+        ap.error(f"{why} needs --max-edge R (the scan's unit; there is no default)")
+    if not why and a.max_edge is not None:
+        ap.error("--max-edge belongs to the kNN graph: every scan here is a mesh (--pointcloud ignores the faces)")
+    report, skipped = clean_scans(a.scans, a.out, a.min_verts, a.largest, a.pointcloud, a.knn, a.max_edge, a.index, names, a.force, a.workers,
+                                  a.device, a.report_only)
+    for scene, e in report.items():
+        print("cleaned", scene, e["V"], "->", e["M"], "vertices,", e["components"], "->", e["kept_components"], "components")
+    for s in skipped:
+        print("skipped", s, "(cleaned scan exists; --force overwrites)")
+    print(f"{len(report)} {'reported' if a.report_only else 'written'}, {len(skipped)} skipped")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

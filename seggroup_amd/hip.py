@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("SEGGROUP_HIP_LIB") or os.path.join(_HERE, "libseggrou
 # parsers under ASan/UBSan).  It has no kernels, so only the host entry points bind; everything else raises on use.
 HOST_LIB_OVERRIDE = os.environ.get("SEGGROUP_HIP_HOST_LIB")
 
-SG_OK, SG_EINVAL, SG_EHIP, SG_ENOMEM, SG_ESTALL, SG_EUNSUP = 0, -1, -2, -3, -4, -5
+SG_OK, SG_EINVAL, SG_EHIP, SG_ENOMEM, SG_ESTALL, SG_EUNSUP, SG_EINTERNAL = 0, -1, -2, -3, -4, -5, -6
 MODE_INS_INFER, MODE_SEM_INFER = 0, 1
 COLOUR_SEMANTIC, COLOUR_INSTANCE, COLOUR_SEGMENT, COLOUR_GROUPING = 0, 1, 2, 3
 NUM_LABEL_VECTORS = 14
@@ -166,6 +166,13 @@ SIGNATURES = {
     "sg_nearest_point_grid_stage_name": (C.c_char_p, [_I]),
     "sg_nearest_point_grid_stats": (_I, [vp, _I]),
     "sg_nearest_point_grid_set_tuning": (_I, [_I, _I]),
+    "sg_components_ws_bytes": (_Z, [_I]),
+    "sg_components_edges": (_I, [vp, C.c_longlong, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_components_faces": (_I, [vp, _I, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_components_knn": (_I, [vp, _I, vp, _I, _I, C.c_float, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_components_set_timing": (_I, [_I]),
+    "sg_components_stage_times": (_I, [vp, _I]),
+    "sg_components_stage_name": (C.c_char_p, [_I]),
     "sg_segment_vote_ws_bytes": (_Z, [_I]),
     "sg_segment_rank": (_I, [vp, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_segment_vote": (_I, [vp, vp, _I, _I] + [vp] * 9 + [C.POINTER(C.c_int), vp, _Z, vp]),
