@@ -930,7 +930,7 @@ int sg_nearest_point_grid_set_tuning(int target_occupancy, int ring_limit);
  *                        (i, L[i][t]), t = 1..row-1 (entry 0 is skipped whatever it holds), that have j != i and d2 <= r2, where
  *                        d = p_j - p_i, d2 = (d0*d0 + d1*d1) + d2*d2 and r2 = max_edge * max_edge, fp32, each operation rounded once.
  *                        max_edge = +inf admits every pair.  Points are rows of `stride` >= 3 floats.  This is the kNN graph cut at a
- *                        length, not a radius graph.
+ *                        length, not a radius graph (that one is sg_components_radius below).
  * d_label (may be NULL) int32 [V]: a pair counts only when both ends hold the same value (any value).
  *   d_comp [V] = the lowest vertex index of the vertex's component; d_size [V] (may be NULL) = the component's vertex count, at every
  *   vertex; *h_C = the number of components = #{v : d_comp[v] == v}.  Integers only: the same bytes on every run.  E = 0 and F = 0 are
@@ -950,6 +950,37 @@ int sg_components_knn(const float* d_points, int stride, const int32_t* d_knn, i
 int sg_components_set_timing(int on);
 int sg_components_stage_times(float* h_us, int cap);
 const char* sg_components_stage_name(int i);
+
+/* The radius graph on the exact grid index: every pair of points i != j with d2 <= r2, where d = p_j - p_i,
+ * d2 = (d0*d0 + d1*d1) + d2*d2 and r2 = radius * radius, fp32, each operation rounded once -- sg_components_knn's pair predicate over ALL
+ * pairs of the cloud, not over a kNN table.  Coincident points are neighbours.  Points are rows of `stride` >= 3 floats,
+ * 1 <= N <= SG_MAX_GRID_POINTS.  No adjacency is written; two results are computed inside the search:
+ *   sg_radius_count_grid   d_count int32 [N]: the number of j that pass for i (the radius outlier filter's figure; below 2^24).
+ *   sg_components_radius   the connected components of that graph: d_comp, d_size (may be NULL) and *h_C exactly as sg_components_edges
+ *                          leaves them; d_label (may be NULL) int32 [N] keeps only the pairs whose ends hold the same value.
+ * The index is sg_pointcloud_knn_grid's (box, cells, sort, dense table).  A query reads the block of Chebyshev radius R round its cell,
+ * R the smallest block that no passing point can lie outside of for the cell edge in use, computed on the host and the same for every
+ * query: no queue, no fallback.  cell = 0: the library picks the edge just large enough for R = 1 and enlarges it only until the grid
+ * fits the table; cell > 0 forces it and may give R > 1.  Integers only: the same bytes on every run, for every cell edge and stream.
+ * SG_EINVAL (before the first HIP call): a null pointer, stride < 3, N < 1, a radius that is not finite and positive or whose fp32 square
+ *   is not finite or below 2^-100, a cell edge that is negative or not finite; (on the device, one flag word, the library stays usable) a
+ *   coordinate that is not finite.  SG_ENOMEM: a workspace below sg_radius_grid_ws_bytes(N) (0 outside the envelope; one size serves both
+ *   entry points).  SG_EUNSUP: N above SG_MAX_GRID_POINTS; an extent of the cloud that is not finite; a forced cell that needs R > 16, that
+ *   gives an axis 2^21 cells or more, or more cells than the dense table's max(2^22, 4 N) -- the message says which.  SG_EINTERNAL: a chase
+ *   ran out of its 2 N + 4 steps, which no input can cause.
+ * Synchronises the stream twice (the box; the end).  Stage times by events, as sg_overseg_set_timing: room for 7 floats (box, cells, sort,
+ * table, init, search, finish).  sg_radius_grid_stats: the calling thread's last call of either entry point -> h[0..2] cells per axis,
+ *   h[3] occupied cells, h[4] the largest cell, h[5] the bits of the fp32 cell edge, h[6] R, h[7] pair tests evaluated, h[8] pairs passed
+ *   (ordered pairs: the sum of the counts; h[7] and h[8] are counted in timed calls only). */
+size_t sg_radius_grid_ws_bytes(int N);         /* 0 when N < 1 or N > SG_MAX_GRID_POINTS */
+int sg_radius_count_grid(const float* d_points, int stride, int N, float radius, float cell, int32_t* d_count, void* d_ws, size_t ws_bytes,
+                         void* stream);
+int sg_components_radius(const float* d_points, int stride, int N, float radius, float cell, const int32_t* d_label, int32_t* d_comp,
+                         int32_t* d_size, int* h_C, void* d_ws, size_t ws_bytes, void* stream);
+int sg_radius_grid_set_timing(int on);
+int sg_radius_grid_stage_times(float* h_us, int cap);
+const char* sg_radius_grid_stage_name(int i);
+int sg_radius_grid_stats(int64_t* h, int cap);
 
 /* Segment vote: what re-keying a scan's annotations onto another over-segmentation needs on the device.  Every vertex has a
  * row id d_ids[v] (any non-negative int32: not contiguous, may exceed V) and a column d_cols[v] in 0..n_cols-1; both are checked on the

@@ -5,17 +5,25 @@ No click reaches them, so each goes down the unlabeled fallback and puts noise i
 every vertex with the lowest vertex index of its component (`sg_components_edges` / `_faces` / `_knn`: one hooking pass over the pairs on
 the GPU, integers only, the same bytes on every run; there is no other path).  The graph is an edge list, a mesh's faces, or a kNN table
 cut at a length -- the kNN graph as it is, not a radius graph: a point with more than k neighbours inside the length links to its k
-nearest only.
+nearest only -- or the radius graph itself: every pair of points at most `radius` apart, searched on the grid index
+(`sg_components_radius`), with the number of neighbours inside the radius per point as a by-product (`neighbour_counts`,
+`sg_radius_count_grid`: the radius outlier filter).
 
     python -m seggroup_amd.components --scans DIR --out DIR (--min-verts M | --largest) [--pointcloud --knn {5,10,20} --max-edge R
                                       --index {grid,brute}] [--scenes FILE] [--force] [--workers W] [--device D] [--report-only]
+                                      [--radius R [--min-neighbours M]]
         every scan directory of --scans -> a scan directory under --out without the small pieces, which every command of the project reads
         as it is: <scene>_vh_clean_2.ply (the kept vertices in ascending raw index with their colours, the faces whose vertices are kept),
         <scene>.clean.npz (kept, new_of_old, comp, the parameters), the segs.json taken at the kept vertices and the aggregation file when
         the source has them; clean_report.json for the run.  A mesh uses its faces; a scan without faces (or --pointcloud) uses its kNN
         graph and NEEDS --max-edge, in the scan's unit.  Results made on the cleaned scans go back to the raw ones with
         `python -m seggroup_amd.transfer --from-scans CLEAN --to-scans RAW ...`: a kept vertex is its own nearest vertex at distance 0.
-    python -m seggroup_amd.components --fragments --scans DIR -n EXP --stage S [--layer final] [--root .] [--json OUT] [--max-edge R ...]
+        --radius R (a scan without faces, or --pointcloud; instead of --max-edge): the radius graph over all points.  --min-neighbours M
+        (needs --radius; --min-verts / --largest are then optional): a vertex is kept only if at least M points lie within R of it AND,
+        when a size rule is given too, its component in the radius graph over ALL points passes that rule -- one pass, nothing is
+        recomputed on the survivors.  <scene>.clean.npz then holds `count`, clean_report.json the radius, R, the cell edge and the
+        vertices dropped by each rule.
+    python -m seggroup_amd.components --fragments --scans DIR -n EXP --stage S [--layer final] [--root .] [--json OUT] [--max-edge R | --radius R ...]
         per scene the pseudo instances of results/EXP/<scene>/<stage>/pseudo_labels.sgl that are in more than one piece of the scan's own
         graph, their piece sizes, and the share of the vertices outside their instance's largest piece; a report, no label file is touched
 """
@@ -54,20 +62,79 @@ def _cut(max_edge) -> float:
     return r
 
 
-def components(V: int, *, edges=None, faces=None, knn=None, xyz=None, max_edge=None, labels=None, device=None, stream=None):
+def _radius(radius) -> float:
+    r = float(radius)
+    if not (r > 0.0 and math.isfinite(r)):
+        raise ValueError("components: radius must be a finite length > 0, not %r" % (radius,))
+    return r
+
+
+def _cloud(xyz, what):
+    shape = tuple(xyz.shape)
+    if len(shape) != 2 or shape[1] < 3 or shape[0] < 1:
+        raise ValueError("%s: xyz must be [N >= 1, >= 3], not %r" % (what, shape))
+    if shape[0] > hip.MAX_GRID_POINTS:
+        raise hip.SgError(hip.SG_EUNSUP, "%s: %d points; the grid path holds at most 2^24" % (what, shape[0]))
+    return int(shape[0])
+
+
+def radius_stats() -> dict:
+    """the calling thread's last radius call (`components(radius=)`, `neighbour_counts`): cells per axis, occupied cells, the largest cell,
+    the cell edge, the ring count R of the block a query reads; pair tests and pairs passed are counted in timed calls only"""
+    h = (C.c_int64 * 9)()
+    hip.check(hip.lib().sg_radius_grid_stats(h, 9))
+    return {"cells": [int(h[0]), int(h[1]), int(h[2])], "occupied": int(h[3]), "largest_cell": int(h[4]),
+            "cell": float(np.array([h[5]], np.uint32).view(np.float32)[0]), "R": int(h[6]), "pair_tests": int(h[7]), "pairs_passed": int(h[8])}
+
+
+def neighbour_counts(xyz, radius, cell=0.0, device=None, stream=None):
+    """-> int32 [N] (a device tensor): per point the number of OTHER points whose fp32 d2 <= radius^2, coincident points
+    included -- the radius outlier filter's figure.  `cell`: the grid's forced edge, 0 or None for the library's choice; it cannot change
+    a result."""
+    r, c = _radius(radius), hip.knn_cell(cell)
+    n = _cloud(xyz, "neighbour_counts")
+    import torch
+    from .oversegment import _on, _stream_ptr
+    from .prepare import _dev, _t, _ws
+    dev = _dev(device)
+    lib = hip.lib()
+    with torch.cuda.device(dev), _on(stream):
+        d_xyz = _t(xyz, torch.float32, dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        ws = _ws(lib.sg_radius_grid_ws_bytes(n), dev)
+        hip.check(lib.sg_radius_count_grid(d_xyz.data_ptr(), int(d_xyz.shape[1]), n, r, c, count.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           _stream_ptr(stream)))
+    return count
+
+
+def components(V: int, *, edges=None, faces=None, knn=None, radius=None, xyz=None, max_edge=None, labels=None, cell=0.0, device=None,
+               stream=None):
     """-> (comp int32 [V], size int32 [V], C): comp[v] = the lowest vertex index of v's component, size[v] = its vertex count (device
     tensors), C = the number of components.  Exactly one of `edges` [E,2], `faces` [F,3], `knn` [V, k+1] (with `xyz` [V, >= 3]; a pair
     counts when its fp32 d2 <= max_edge^2; max_edge=None: every pair).  `labels` [V]: a pair counts only when both ends hold the same
-    value.  NumPy arrays or tensors.  Anything else is a ValueError before a device call."""
+    value.  NumPy arrays or tensors.  A fourth source, `radius` (with `xyz` [V, >= 3]; `cell`: the grid's forced edge, 0 for the
+    library's choice): the radius graph, every pair of points whose fp32 d2 <= radius^2.  Anything else is a ValueError
+    before a device call."""
     V = int(V)
-    given = [n for n, a in (("edges", edges), ("faces", faces), ("knn", knn)) if a is not None]
+    given = [n for n, a in (("edges", edges), ("faces", faces), ("knn", knn), ("radius", radius)) if a is not None]
     if len(given) != 1:
-        raise ValueError("components: exactly one of edges, faces and knn is needed, not %s" % (given or "none"))
+        raise ValueError("components: exactly one of edges, faces, knn and radius is needed, not %s" % (given or "none"))
     if V < 1:
         raise ValueError("components: a graph needs at least one vertex")
-    if knn is None and (xyz is not None or max_edge is not None):
-        raise ValueError("components: xyz and max_edge belong to the knn form")
-    if edges is not None:
+    if knn is None and radius is None and xyz is not None:
+        raise ValueError("components: xyz belongs to the knn and radius forms")
+    if knn is None and max_edge is not None:
+        raise ValueError("components: max_edge belongs to the knn form")
+    grid_cell = hip.knn_cell(cell)
+    if radius is None and grid_cell != 0.0:
+        raise ValueError("components: cell belongs to the radius form")
+    if radius is not None:
+        if xyz is None:
+            raise ValueError("components: the radius form needs xyz")
+        if _cloud(xyz, "components") != V:
+            raise ValueError("components: the radius form needs xyz [V, >= 3] with V = %d" % V)
+        reach = _radius(radius)
+    elif edges is not None:
         count, _ = _shape2(edges, 2, "edges")
     elif faces is not None:
         count, _ = _shape2(faces, 3, "faces")
@@ -86,7 +153,7 @@ def components(V: int, *, edges=None, faces=None, knn=None, xyz=None, max_edge=N
     from .prepare import _dev, _t, _ws
     dev = _dev(device)
     lib = hip.lib()
-    need = lib.sg_components_ws_bytes(V)
+    need = lib.sg_radius_grid_ws_bytes(V) if radius is not None else lib.sg_components_ws_bytes(V)
     if need == 0:
         raise hip.SgError(hip.SG_EUNSUP, "components: %d vertices; a graph holds at most 2^27" % V)
     with torch.cuda.device(dev), _on(stream):
@@ -96,7 +163,10 @@ def components(V: int, *, edges=None, faces=None, knn=None, xyz=None, max_edge=N
         ws = _ws(need, dev)
         c = C.c_int(0)
         tail = (hip.ptr(d_lab), comp.data_ptr(), size.data_ptr(), C.byref(c), ws.data_ptr(), ws.numel(), _stream_ptr(stream))
-        if edges is not None:
+        if radius is not None:
+            d_xyz = _t(xyz, torch.float32, dev)
+            rc = lib.sg_components_radius(d_xyz.data_ptr(), int(d_xyz.shape[1]), V, reach, grid_cell, *tail)
+        elif edges is not None:
             d_src = _t(edges, torch.int32, dev)
             rc = lib.sg_components_edges(d_src.data_ptr() if count else None, count, V, *tail)
         elif faces is not None:
@@ -135,9 +205,16 @@ def clean_arrays(keep, faces):
     return kept, new_of_old, new_of_old[f[whole]].reshape(-1, 3).to(torch.int32)
 
 
-def _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, what):
-    """-> (source name, keyword arguments of `components`) for a scan's own graph; max_edge is read on the kNN path only"""
+def _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, what, radius=None):
+    """-> (source name, keyword arguments of `components`) for a scan's own graph; max_edge is read on the kNN path only, radius takes
+    its place (the radius graph)"""
     from .prepare import pointcloud_knn
+    if radius is not None:
+        if max_edge is not None:
+            raise ValueError(f"{what}: radius and max_edge are two different graphs; give one")
+        if not (pointcloud or faces.shape[0] == 0):
+            raise ValueError(f"{what}: radius belongs to a scan without faces (or pointcloud=True); a mesh uses its faces")
+        return "radius", dict(radius=_radius(radius), xyz=xyz)
     if pointcloud or faces.shape[0] == 0:
         if max_edge is None:
             raise ValueError(f"{what}: a scan without faces (or pointcloud=True) needs max_edge, in the scan's unit; a default would be a guess")
@@ -153,13 +230,15 @@ def _segs_name(scene: str) -> str:
 
 def clean_scan(scene_path: str, out_dir: str, min_verts: Optional[int] = None, largest: bool = False, pointcloud: bool = False, knn: int = 10,
                max_edge: Optional[float] = None, index: str = "grid", force: bool = False, device=None, stream=None,
-               report_only: bool = False) -> Optional[dict]:
+               report_only: bool = False, radius: Optional[float] = None, min_neighbours: Optional[int] = None) -> Optional[dict]:
     """One scan directory -> <out_dir>/<scene>/ without the small pieces (see the module's doc); -> its entry of clean_report.json, or
-    None when the cleaned PLY was there already (never overwritten without `force`).  `report_only`: the entry alone, nothing written."""
+    None when the cleaned PLY was there already (never overwritten without `force`).  `report_only`: the entry alone, nothing written.
+    `radius` (a scan without faces, or pointcloud=True): the radius graph in place of the kNN graph.  `min_neighbours` (needs `radius`;
+    min_verts / largest are then optional): keep a vertex only if that many points lie within `radius` of it and its component in the
+    radius graph over ALL points passes the size rule, when one is given."""
     import torch
     from .prepare import _scene_name, mesh_arrays, read_ply, write_ply
-    if (min_verts is None) == (not largest):
-        raise ValueError("clean_scan: exactly one of min_verts and largest is needed")
+    _check_rules("clean_scan", min_verts, largest, radius, min_neighbours)
     hip.knn_index(index)
     scene = _scene_name(scene_path)
     dst = os.path.join(out_dir, scene)
@@ -167,19 +246,31 @@ def clean_scan(scene_path: str, out_dir: str, min_verts: Optional[int] = None, l
     if not report_only and os.path.exists(ply_out) and not force:
         return None
     xyz, rgb, faces = mesh_arrays(read_ply(os.path.join(scene_path, scene + "_vh_clean_2.ply")))
-    source, graph = _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, scene)
+    source, graph = _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, scene, radius)
     v = int(xyz.shape[0])
     d_comp, d_size, n_comp = components(v, device=device, stream=stream, **graph)
-    with torch.cuda.device(d_comp.device):
-        d_keep = keep_mask(d_comp, d_size, min_verts, largest)
+    stats = radius_stats() if source == "radius" else None
+    d_count = None if min_neighbours is None else neighbour_counts(xyz, radius, device=d_comp.device, stream=stream)
+    with torch.cuda.device(d_comp.device):                       # both calls synchronised their stream
+        sized = min_verts is not None or largest
+        d_keep = keep_mask(d_comp, d_size, min_verts, largest) if sized else torch.ones(v, dtype=torch.bool, device=d_comp.device)
+        by_size = int((~d_keep).sum())
+        if d_count is not None:
+            d_dense = d_count >= int(min_neighbours)
+            by_count = int((~d_dense).sum())
+            d_keep = d_keep & d_dense
         d_kept, d_new, d_faces = clean_arrays(d_keep, torch.from_numpy(faces).to(d_comp.device))
         roots = d_comp == torch.arange(v, dtype=torch.int32, device=d_comp.device)
         sizes = torch.sort(d_size[roots], descending=True)[0]
-        kept_components = int((roots & d_keep).sum())
+        kept_components = int((roots & d_keep).sum()) if d_count is None else int(torch.unique(d_comp[d_keep]).numel())
         kept, new_of_old, new_faces, comp = d_kept.cpu().numpy(), d_new.cpu().numpy(), d_faces.cpu().numpy(), d_comp.cpu().numpy()
         largest_sizes = sizes[:10].cpu().tolist()
     entry = {"V": v, "M": int(kept.shape[0]), "components": int(n_comp), "kept_components": kept_components, "largest_sizes": largest_sizes,
              "source": source, "F": int(faces.shape[0]), "kept_F": int(new_faces.shape[0])}
+    if stats is not None:
+        entry.update(radius=float(radius), R=stats["R"], cell=stats["cell"], dropped={"size": by_size})
+        if d_count is not None:
+            entry["dropped"]["min_neighbours"] = by_count
     segs = os.path.join(scene_path, _segs_name(scene))
     doc = None
     if os.path.exists(segs):
@@ -195,9 +286,14 @@ def clean_scan(scene_path: str, out_dir: str, min_verts: Optional[int] = None, l
         return entry
     os.makedirs(dst, exist_ok=True)
     write_ply(ply_out, xyz[kept], rgb[kept], new_faces)
+    extra = {}
+    if source == "radius":
+        extra.update(radius=np.float32(radius), min_neighbours=np.int32(-1 if min_neighbours is None else min_neighbours))
+    if d_count is not None:
+        extra["count"] = d_count.cpu().numpy()
     np.savez(os.path.join(dst, scene + MAP_SUFFIX), kept=kept, new_of_old=new_of_old, comp=comp, min_verts=np.int32(-1 if min_verts is None else min_verts),
              largest=np.bool_(largest), source=np.str_(source), knn=np.int32(knn if source == "knn" else 0),
-             max_edge=np.float32(np.inf if max_edge is None else max_edge))
+             max_edge=np.float32(np.inf if max_edge is None else max_edge), **extra)
     if doc is not None:
         with open(os.path.join(dst, _segs_name(scene)), "w") as f:
             json.dump(doc, f)
@@ -205,6 +301,19 @@ def clean_scan(scene_path: str, out_dir: str, min_verts: Optional[int] = None, l
     if os.path.exists(agg):
         shutil.copyfile(agg, os.path.join(dst, scene + ".aggregation.json"))
     return entry
+
+
+def _check_rules(who, min_verts, largest, radius, min_neighbours):
+    if min_neighbours is None:
+        if (min_verts is None) == (not largest):
+            raise ValueError(f"{who}: exactly one of min_verts and largest is needed")
+        return
+    if radius is None:
+        raise ValueError(f"{who}: min_neighbours counts the points within radius; radius is needed")
+    if int(min_neighbours) < 1:
+        raise ValueError(f"{who}: min_neighbours must be at least 1")
+    if min_verts is not None and largest:
+        raise ValueError(f"{who}: at most one of min_verts and largest")
 
 
 def _scan_names(scans_dir: str):
@@ -232,25 +341,28 @@ def _threads(scenes, workers, dev, fn):
 
 def clean_scans(scans_dir: str, out_dir: str, min_verts: Optional[int] = None, largest: bool = False, pointcloud: bool = False, knn: int = 10,
                 max_edge: Optional[float] = None, index: str = "grid", scenes=None, force: bool = False, workers: int = 4, device=None,
-                report_only: bool = False):
+                report_only: bool = False, radius: Optional[float] = None, min_neighbours: Optional[int] = None):
     """Every scan directory under `scans_dir` (or the named ones) -> (report {scene: entry}, skipped scene names); writes
     <out_dir>/clean_report.json.  Workers are threads, each with its own stream."""
     from .prepare import _dev
-    if (min_verts is None) == (not largest):
-        raise ValueError("clean_scans: exactly one of min_verts and largest is needed")
+    _check_rules("clean_scans", min_verts, largest, radius, min_neighbours)
     dev = _dev(device)
     if scenes is None:
         scenes = _scan_names(scans_dir)
     done = _threads(scenes, workers, dev, lambda scene, stream: clean_scan(os.path.join(scans_dir, scene), out_dir, min_verts, largest, pointcloud,
                                                                            knn, max_edge, index, force, device=dev, stream=stream,
-                                                                           report_only=report_only))
+                                                                           report_only=report_only, radius=radius,
+                                                                           min_neighbours=min_neighbours))
     report = {scene: entry for scene, entry in done if entry is not None}
     skipped = [scene for scene, entry in done if entry is None]
     os.makedirs(out_dir, exist_ok=True)
+    doc = {"min_verts": min_verts, "largest": bool(largest), "pointcloud": bool(pointcloud), "knn": int(knn),
+           "max_edge": None if max_edge is None else float(max_edge), "index": index, "report_only": bool(report_only),
+           "scenes": report, "skipped": skipped}
+    if radius is not None:
+        doc.update(radius=float(radius), min_neighbours=None if min_neighbours is None else int(min_neighbours))
     with open(os.path.join(out_dir, REPORT_NAME), "w") as f:
-        json.dump({"min_verts": min_verts, "largest": bool(largest), "pointcloud": bool(pointcloud), "knn": int(knn),
-                   "max_edge": None if max_edge is None else float(max_edge), "index": index, "report_only": bool(report_only),
-                   "scenes": report, "skipped": skipped}, f, indent=1, sort_keys=True)
+        json.dump(doc, f, indent=1, sort_keys=True)
         f.write("\n")
     return report, skipped
 
@@ -259,7 +371,7 @@ def clean_scans(scans_dir: str, out_dir: str, min_verts: Optional[int] = None, l
 def fragments(labels, V: int, **graph) -> dict:
     """The label-filtered components of a graph (`graph`: the source keywords of `components`) -> dict(instances, fragmented,
     outside_largest, outside_share, pieces {label: sizes, largest first} of the labels in more than one piece).  Every value of
-    `labels` counts as an instance."""
+    `labels` counts as an instance.  `radius=R, xyz=...` is the radius graph."""
     import torch
     comp, _, _ = components(V, labels=labels, **graph)
     with torch.cuda.device(comp.device):
@@ -278,8 +390,9 @@ def fragments(labels, V: int, **graph) -> dict:
 
 
 def fragments_scene(scene_path: str, exp: str, stage: str, layer: str = "final", root: str = ".", pointcloud: bool = False, knn: int = 10,
-                    max_edge: Optional[float] = None, index: str = "grid", device=None, stream=None) -> dict:
-    """`fragments` of one scene's `<layer>.ins` vector on the scan's own graph (its faces, or its kNN graph cut at max_edge)"""
+                    max_edge: Optional[float] = None, index: str = "grid", device=None, stream=None, radius: Optional[float] = None) -> dict:
+    """`fragments` of one scene's `<layer>.ins` vector on the scan's own graph (its faces, its kNN graph cut at max_edge, or its radius
+    graph)"""
     from . import pseudo_labels
     from .prepare import _scene_name, mesh_arrays, read_ply
     scene = _scene_name(scene_path)
@@ -287,7 +400,7 @@ def fragments_scene(scene_path: str, exp: str, stage: str, layer: str = "final",
     xyz, _, faces = mesh_arrays(read_ply(os.path.join(scene_path, scene + "_vh_clean_2.ply")))
     if lab.shape[0] != xyz.shape[0]:
         raise ValueError(f"{scene}: {lab.shape[0]} labels for {xyz.shape[0]} vertices")
-    source, graph = _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, scene)
+    source, graph = _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, scene, radius)
     out = fragments(lab, int(xyz.shape[0]), device=device, stream=stream, **graph)
     out["source"] = source
     out["pieces"] = {str(k): v for k, v in out["pieces"].items()}
@@ -329,6 +442,16 @@ def _needs_max_edge(scans_dir, scenes, pointcloud):
     return None
 
 
+def _radius_needs_clouds(ap, scans_dir, scenes, pointcloud):
+    """--radius is the graph of a scan without faces (or of --pointcloud): a mesh in the list is a parser error, not a silent switch"""
+    from .oversegment import _declared_faces
+    if pointcloud:
+        return
+    for s in scenes:
+        if _declared_faces(os.path.join(scans_dir, s, s + "_vh_clean_2.ply")) != 0:
+            ap.error(f"--radius belongs to a scan without faces: {s} is a mesh (--pointcloud ignores the faces)")
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m seggroup_amd.components", description=__doc__.split("\n\n")[0])
     ap.add_argument("--scans", required=True, help="directory of scan directories (<scene>/<scene>_vh_clean_2.ply)")
@@ -339,6 +462,9 @@ def main(argv=None) -> int:
     ap.add_argument("--knn", type=int, default=10, choices=KNN_CHOICES, help="neighbours per point of the kNN graph")
     ap.add_argument("--max-edge", type=_positive, default=None, help="kNN graph: the longest pair that counts, in the scan's unit (no default)")
     ap.add_argument("--index", default="grid", choices=sorted(hip.KNN_INDEX), help="kNN graph: the neighbour search")
+    ap.add_argument("--radius", type=_positive, default=None,
+                    help="the radius graph in place of the kNN graph: every pair of points at most this far apart, in the scan's unit")
+    ap.add_argument("--min-neighbours", type=int, default=None, help="with --radius: keep the vertices with at least this many points within the radius")
     ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
     ap.add_argument("--force", action="store_true", help="overwrite existing cleaned scans")
     ap.add_argument("--report-only", action="store_true", help="write clean_report.json and no scan")
@@ -354,20 +480,32 @@ def main(argv=None) -> int:
     if not 1 <= a.workers <= MAX_WORKERS:
         ap.error(f"--workers must be in 1..{MAX_WORKERS}")
     scenes = _scene_list(a.scenes)
+    if a.radius is not None and a.max_edge is not None:
+        ap.error("--radius and --max-edge are two different graphs: give one")
+    if a.min_neighbours is not None:
+        if a.radius is None:
+            ap.error("--min-neighbours counts the points within --radius R: --radius is needed")
+        if a.min_neighbours < 1:
+            ap.error("--min-neighbours must be at least 1")
     if a.fragments:
         if not a.exp_name:
             ap.error("--fragments needs -n EXP")
         if a.min_verts is not None or a.largest:
             ap.error("--fragments is a report: --min-verts / --largest belong to cleaning")
+        if a.min_neighbours is not None:
+            ap.error("--fragments is a report: --min-neighbours belongs to cleaning")
         names = scenes if scenes is not None else [s for s in _scan_names(a.scans)
                                                    if os.path.isdir(os.path.join(a.root, "results", a.exp_name, s, a.stage))]
         why = _needs_max_edge(a.scans, names, a.pointcloud)
-        if why and a.max_edge is None:
+        if a.radius is not None:
+            _radius_needs_clouds(ap, a.scans, names, a.pointcloud)
+        elif why and a.max_edge is None:
             ap.error(f"{why} needs --max-edge R (the scan's unit; there is no default)")
         if not why and a.max_edge is not None:
             ap.error("--max-edge belongs to the kNN graph: every scan here is a mesh (--pointcloud ignores the faces)")
+        graph = dict(radius=a.radius) if a.radius is not None else {}
         rep = fragments_scans(a.scans, a.exp_name, a.stage, a.layer, a.root, names, a.workers, a.device, pointcloud=a.pointcloud, knn=a.knn,
-                              max_edge=a.max_edge, index=a.index)
+                              max_edge=a.max_edge, index=a.index, **graph)
         for scene, e in rep.items():
             print("fragments", scene, e["instances"], "instances,", e["fragmented"], "in pieces,", "%.4f" % e["outside_share"], "outside")
         if a.json:
@@ -377,18 +515,23 @@ def main(argv=None) -> int:
         return 0
     if not a.out:
         ap.error("cleaning needs --out DIR")
-    if (a.min_verts is None) == (not a.largest):
+    if a.min_neighbours is None and (a.min_verts is None) == (not a.largest):
         ap.error("exactly one of --min-verts M and --largest is needed")
+    if a.min_verts is not None and a.largest:
+        ap.error("at most one of --min-verts M and --largest")
     if a.min_verts is not None and a.min_verts < 1:
         ap.error("--min-verts must be at least 1")
     names = scenes if scenes is not None else _scan_names(a.scans)
     why = _needs_max_edge(a.scans, names, a.pointcloud)
-    if why and a.max_edge is None:
+    if a.radius is not None:
+        _radius_needs_clouds(ap, a.scans, names, a.pointcloud)
+    elif why and a.max_edge is None:
         ap.error(f"{why} needs --max-edge R (the scan's unit; there is no default)")
     if not why and a.max_edge is not None:
         ap.error("--max-edge belongs to the kNN graph: every scan here is a mesh (--pointcloud ignores the faces)")
+    new = dict(radius=a.radius, min_neighbours=a.min_neighbours) if a.radius is not None else {}
     report, skipped = clean_scans(a.scans, a.out, a.min_verts, a.largest, a.pointcloud, a.knn, a.max_edge, a.index, names, a.force, a.workers,
-                                  a.device, a.report_only)
+                                  a.device, a.report_only, **new)
     for scene, e in report.items():
         print("cleaned", scene, e["V"], "->", e["M"], "vertices,", e["components"], "->", e["kept_components"], "components")
     for s in skipped:

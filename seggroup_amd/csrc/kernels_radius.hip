@@ -1,0 +1,351 @@
+// The radius graph on the exact grid index: every pair of points with  j != i  and  d2 <= r2 , d = p_j - p_i,
+// d2 = (d0*d0 + d1*d1) + d2*d2 in fp32 with every operation rounded once (the file is built without contraction), r2 = radius * radius
+// rounded once on the host -- 8j's pair predicate, over ALL pairs and not over a kNN table.  Two things are computed inside the search,
+// without an adjacency: count[i] = the pairs of i (sg_radius_count_grid) and the connected components of the graph (sg_components_radius,
+// 8j's outputs and conventions).
+//
+//   index     grid_index_device.h: box and finite check, cells on 8g's formula, radix sort, gather, dense table -- the grid kNN's (8h)
+//   R         the block of Chebyshev radius R round a query's cell holds every point that can pass: the smallest R with
+//             gap = fl(fl(R h) - slack) > 0  and  fl(fl(gap * gap) * (1 - 2^-9)) > r2  (8h item 3 bounds the axis gap of a point outside the
+//             block from below; 8k shows that the 2^-9 also pays for the roundings of d2).  Computed on the host, the same for every
+//             query; no queue and no fallback.  cell = 0: h just large enough for R = 1, enlarged only until the grid fits the table.
+//   search    k_radius_search<Visitor>: k_grid_search's shape.  One wave per 64 consecutive sorted points; the lanes of one cell form a
+//             group, taken in turn by ballot; the (2R+1)^2 row ranges of the block come from the table; candidates are staged through LDS
+//             in tiles of 256 (float4 + original index); each lane of the group tests its own query.  Nothing is indexed at run time.
+//   Count     a register counter, one plain vector store at the original row
+//   Hook      for a passing pair with original j > i (each edge once) and equal labels: 8j's hook (components_device.h) on the parent
+//             array; k_cc_init before, k_cc_flatten and k_cc_sizes after, as they are.  The hooks run inside a divergent wave loop; no lane
+//             waits for another, and the step budget bounds every lane's loop.
+#include <cmath>
+#include <cstring>
+
+#include "sg_common.h"
+#include "grid_index_device.h"
+#include "components_device.h"
+
+namespace {
+
+using sggrid::Grid;
+using sggrid::kGTile;
+using sggrid::kWave;
+
+constexpr int kMaxR = 16;
+constexpr int kNumStats = 9;
+constexpr float kMinR2 = 7.8886090522101181e-31f;       // 2^-100: below, squares underflow and the relative error bounds of 8k do not hold
+
+struct Tally {
+    unsigned long long evals, passed;       // pair tests evaluated, pairs passed (timed calls only)
+};
+
+__global__ void k_radius_init(Tally* __restrict__ t) { t->evals = 0ull; t->passed = 0ull; }
+
+struct CountVisitor {
+    int32_t* count;
+    __device__ __forceinline__ void pair(int, int) const {}
+    __device__ __forceinline__ void finish(int i, int n) const { count[i] = n; }
+};
+
+struct HookVisitor {
+    int* parent;
+    const int32_t* label;
+    sgcc::Misc* misc;
+    int V;
+    __device__ __forceinline__ void pair(int i, int j) const {
+        if (j > i && (!label || label[i] == label[j])) sgcc::hook(parent, i, j, V, misc);
+    }
+    __device__ __forceinline__ void finish(int, int) const {}
+};
+
+template <class Visitor>
+__global__ __launch_bounds__(kWave) void k_radius_search(const float4* __restrict__ spts, const int* __restrict__ sidx,
+                                                         const unsigned long long* __restrict__ skey, const int* __restrict__ start, Grid g, int N,
+                                                         float r2, Visitor vis, Tally* __restrict__ tally, int counting) {
+    __shared__ float4 tile[kGTile];
+    __shared__ int tidx[kGTile];
+    const int lane = threadIdx.x;
+    const int s = blockIdx.x * kWave + lane;
+    const bool live = s < N;
+    const int sl = live ? s : N - 1;
+    const float4 me = spts[sl];
+    const int mycell = (int)skey[sl];
+    const int orig = sidx[sl];
+    const int nx = g.nc[0], ny = g.nc[1], nz = g.nc[2], R = g.rmax;
+    bool done = !live;
+    int passed = 0;
+    unsigned int evals = 0u;
+    for (;;) {
+        const unsigned long long pending = __builtin_amdgcn_ballot_w64(!done);
+        if (pending == 0ull) break;
+        const int leader = __builtin_ctzll(pending);
+        const int gcell = __builtin_amdgcn_readfirstlane(__shfl(mycell, leader));
+        const bool ingroup = !done && mycell == gcell;
+        const int gx = gcell % nx, gy = (gcell / nx) % ny, gz = gcell / (nx * ny);
+        const int x0 = max(gx - R, 0), x1 = min(gx + R, nx - 1);
+        for (int z = max(gz - R, 0); z <= min(gz + R, nz - 1); ++z) {
+            for (int y = max(gy - R, 0); y <= min(gy + R, ny - 1); ++y) {
+                const int row = (z * ny + y) * nx;
+                const int a = start[row + x0], b = start[row + x1 + 1];          // one contiguous range of the sorted points
+                for (int c0 = a; c0 < b; c0 += kGTile) {
+                    __syncthreads();
+#pragma unroll
+                    for (int u = 0; u < kGTile / kWave; ++u) {
+                        const int e = c0 + u * kWave + lane;
+                        if (e < b) { tile[u * kWave + lane] = spts[e]; tidx[u * kWave + lane] = sidx[e]; }
+                    }
+                    __syncthreads();
+                    const int n = min(kGTile, b - c0);
+                    if (ingroup) {
+                        for (int t = 0; t < n; ++t) {
+                            const float4 c = tile[t];
+                            const int j = tidx[t];
+                            const float d0 = c.x - me.x, d1 = c.y - me.y, d2 = c.z - me.z;
+                            const float dd = (d0 * d0 + d1 * d1) + d2 * d2;
+                            if (j != orig && dd <= r2) {
+                                ++passed;
+                                vis.pair(orig, j);
+                            }
+                        }
+                        evals += (unsigned int)n;
+                    }
+                }
+            }
+        }
+        if (ingroup) done = true;
+    }
+    if (live) vis.finish(orig, passed);
+    if (counting) {
+        unsigned long long e = evals, p = live ? (unsigned long long)passed : 0ull;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) { e += __shfl_xor(e, off); p += __shfl_xor(p, off); }
+        if (lane == 0) { atomicAdd(&tally->evals, e); atomicAdd(&tally->passed, p); }
+    }
+}
+
+struct Plan {
+    sggrid::Plan grid;
+    Tally* tally;
+    sgcc::Misc* misc;
+    int* parent;
+    int* count;
+    bool ok;
+};
+
+Plan carve(void* d_ws, size_t ws_bytes, int N) {
+    Plan p{};
+    sg::Carver cv(d_ws, ws_bytes);
+    sggrid::carve(cv, p.grid, N);
+    p.tally = cv.take<Tally>(1);
+    p.misc = cv.take<sgcc::Misc>(1);
+    p.parent = cv.take<int>((size_t)N);
+    p.count = cv.take<int>((size_t)N);
+    p.ok = cv.ok;
+    return p;
+}
+
+constexpr int kStages = 7;
+const char* const kStageNames[kStages] = {"box", "cells", "sort", "table", "init", "search", "finish"};
+
+struct Session {
+    bool timing = false;
+    float stage_us[kStages];
+    int64_t stats[kNumStats];
+};
+thread_local Session t_ses;
+
+// the smallest block radius at cell edge h that no passing point can lie outside of; 0: above kMaxR
+int rings_for(float h, float slack, float r2) {
+    for (int r = 1; r <= kMaxR; ++r) {
+        const float gap = (float)r * h - slack;
+        const float lhs = (gap * gap) * sggrid::kShrink;
+        if (gap > 0.0f && lhs > r2) return r;
+    }
+    return 0;
+}
+
+struct Index {
+    Grid g;
+    const unsigned long long* skey;
+    const int* sidx;
+};
+
+// box, cells, sort, table: the grid kNN's stages with the cell edge decided by the radius.  Synchronises the stream once (the box).
+int build_index(const char* who, const float* d_points, int stride, int N, float radius, float r2, float cell, const Plan& p,
+                sgos::StageClock<kStages>& clock, hipStream_t st, Index* out) {
+    const sggrid::Plan& gp = p.grid;
+    const int nb = sg::cdiv(N, sggrid::kBlock);
+    sggrid::k_grid_init<<<1, 1, 0, st>>>(gp.misc);
+    k_radius_init<<<1, 1, 0, st>>>(p.tally);
+    sggrid::k_grid_box<<<std::min(nb, sggrid::kBoxBlocks), sggrid::kBlock, 0, st>>>(d_points, stride, N, gp.cand, gp.misc);
+    sggrid::Misc hm{};
+    SG_HIP(hipMemcpyAsync(&hm, gp.misc, sizeof(hm), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (hm.flag & 1) return sg::fail(SG_EINVAL, "%s: a coordinate is not finite", who);
+    clock.tick();
+    Grid& g = out->g;
+    g = Grid{};
+    float ext[3], emax = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        g.lo[a] = sggrid::unkey_host(hm.lo[a]);
+        ext[a] = sggrid::unkey_host(hm.hi[a]) - g.lo[a];
+        emax = std::max(emax, ext[a]);
+    }
+    if (!std::isfinite(emax)) return sg::fail(SG_EUNSUP, "%s: the extent of the cloud is not finite", who);
+    g.slack = std::ldexp(emax, -21);
+    const long long cap = sggrid::cell_cap(N);
+    long long total = 0;
+    if (cell > 0.0f) {
+        g.rmax = rings_for(cell, g.slack, r2);
+        if (g.rmax == 0)
+            return sg::fail(SG_EUNSUP, "%s: a cell of %g needs a block of more than %d rings for a radius of %g", who, (double)cell, kMaxR,
+                            (double)radius);
+        if (!sggrid::cells_of(ext, cell, g.nc, &total))
+            return sg::fail(SG_EUNSUP, "%s: cell too small for the cloud's extent (%g / %g is not below %g cells on an axis)", who, (double)emax,
+                            (double)cell, (double)sggrid::kCellLimit);
+        if (total > cap)
+            return sg::fail(SG_EUNSUP, "%s: a cell of %g gives %lld cells; the table of %d points holds %lld", who, (double)cell, total, N, cap);
+    } else {
+        // just large enough for one ring; a larger edge keeps one ring (gap grows with h)
+        cell = radius * 1.00390625f + g.slack;
+        for (int tries = 0; tries < 64 && rings_for(cell, g.slack, r2) != 1; ++tries) cell *= 1.0009765625f;
+        for (int tries = 0; tries < 400 && !(sggrid::cells_of(ext, cell, g.nc, &total) && total <= cap); ++tries) cell *= 1.25f;
+        if (!(sggrid::cells_of(ext, cell, g.nc, &total) && total <= cap)) cell = std::max(cell, emax);         // at most two cells per axis
+        g.rmax = rings_for(cell, g.slack, r2);
+        if (g.rmax != 1 || !std::isfinite(cell) || !sggrid::cells_of(ext, cell, g.nc, &total) || total > cap)
+            return sg::fail(SG_EINTERNAL, "%s: no cell edge for a radius of %g on an extent of %g", who, (double)radius, (double)emax);
+    }
+    g.h = cell;
+    g.ncells = (int)total;
+    sggrid::k_grid_cells<<<nb, sggrid::kBlock, 0, st>>>(gp.cand, N, g, gp.k0, gp.v0);
+    clock.tick();
+    sgsort::Lists<unsigned long long, int> L{};
+    L.kin[0] = gp.k0; L.kout[0] = gp.k1; L.vin[0] = gp.v0; L.vout[0] = gp.v1; L.hist[0] = gp.hist; L.n[0] = N;
+    sgsort::radix_sort<unsigned long long, int, true>(L, 1, 0, sggrid::bits_for_cells(g.ncells), st);
+    out->skey = L.kin[0] ? L.kin[0] : gp.k0;
+    out->sidx = L.vin[0] ? L.vin[0] : gp.v0;
+    sggrid::k_grid_gather<<<nb, sggrid::kBlock, 0, st>>>(gp.cand, out->sidx, N, gp.spts);
+    clock.tick();
+    sggrid::k_grid_table<<<sg::cdiv((long long)g.ncells + 1, sggrid::kBlock), sggrid::kBlock, 0, st>>>(out->skey, N, g.ncells, gp.start);
+    sggrid::k_grid_cellstats<<<sg::cdiv(g.ncells, sggrid::kBlock), sggrid::kBlock, 0, st>>>(gp.start, g.ncells, gp.misc);
+    clock.tick();
+    return SG_OK;
+}
+
+void leave_stats(const Grid& g, const sggrid::Misc& hm, const Tally& t) {
+    unsigned int hbits;
+    std::memcpy(&hbits, &g.h, 4);
+    int64_t* s = t_ses.stats;
+    s[0] = g.nc[0]; s[1] = g.nc[1]; s[2] = g.nc[2];
+    s[3] = hm.occupied; s[4] = hm.maxcell; s[5] = (int64_t)hbits;
+    s[6] = g.rmax; s[7] = (int64_t)t.evals; s[8] = (int64_t)t.passed;
+}
+
+// everything that is checked before the first HIP call
+int check_args(const char* who, const float* d_points, int stride, int N, float radius, float cell, const void* d_out, const void* d_ws,
+               size_t ws_bytes, float* r2) {
+    SG_REQUIRE(N >= 1, "%s: %d points", who, N);
+    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
+    SG_REQUIRE(d_points && d_out && d_ws, "%s: a null pointer", who);
+    SG_REQUIRE(stride >= 3, "%s: rows of at least 3 floats (%d)", who, stride);
+    SG_REQUIRE(std::isfinite(radius) && radius > 0.0f, "%s: the radius must be finite and positive (%g)", who, (double)radius);
+    *r2 = radius * radius;                       // one fp32 multiplication
+    SG_REQUIRE(std::isfinite(*r2) && *r2 >= kMinR2, "%s: the square of the radius must be finite and at least 2^-100 (radius %g)", who, (double)radius);
+    SG_REQUIRE(std::isfinite(cell) && cell >= 0.0f, "%s: the cell edge must be finite and positive, or 0 for the library's choice (%g)", who, (double)cell);
+    if (ws_bytes < sg_radius_grid_ws_bytes(N))
+        return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_radius_grid_ws_bytes(N));
+    return SG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sg_radius_grid_set_timing(int on) { t_ses.timing = on != 0; return SG_OK; }
+
+int sg_radius_grid_stage_times(float* h_us, int cap) {
+    SG_REQUIRE(h_us && cap >= kStages, "sg_radius_grid_stage_times: room for %d floats is needed", kStages);
+    for (int i = 0; i < kStages; ++i) h_us[i] = t_ses.stage_us[i];
+    return kStages;
+}
+
+const char* sg_radius_grid_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+
+int sg_radius_grid_stats(int64_t* h, int cap) {
+    SG_REQUIRE(h && cap >= kNumStats, "sg_radius_grid_stats: room for %d words is needed", kNumStats);
+    for (int i = 0; i < kNumStats; ++i) h[i] = t_ses.stats[i];
+    return kNumStats;
+}
+
+size_t sg_radius_grid_ws_bytes(int N) {
+    if (N < 1 || N > SG_MAX_GRID_POINTS) return 0;
+    return sggrid::plan_bytes(N) + sg::align_up(sizeof(Tally)) + sg::align_up(sizeof(sgcc::Misc)) + 2 * sg::align_up((size_t)N * 4);
+}
+
+int sg_radius_count_grid(const float* d_points, int stride, int N, float radius, float cell, int32_t* d_count, void* d_ws, size_t ws_bytes,
+                         void* stream) {
+    const char* who = "sg_radius_count_grid";
+    for (int i = 0; i < kNumStats; ++i) t_ses.stats[i] = 0;
+    float r2 = 0.0f;
+    if (const int rc = check_args(who, d_points, stride, N, radius, cell, d_count, d_ws, ws_bytes, &r2)) return rc;
+    const Plan p = carve(d_ws, ws_bytes, N);
+    if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_radius_grid_ws_bytes(N));
+    hipStream_t st = sg::as_stream(stream);
+    const int counting = t_ses.timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, t_ses.timing, t_ses.stage_us);
+    Index ix{};
+    if (const int rc = build_index(who, d_points, stride, N, radius, r2, cell, p, clock, st, &ix)) return rc;
+    clock.tick();                                // init: nothing to do
+    k_radius_search<CountVisitor><<<sg::cdiv(N, kWave), kWave, 0, st>>>(p.grid.spts, ix.sidx, ix.skey, p.grid.start, ix.g, N, r2,
+                                                                       CountVisitor{d_count}, p.tally, counting);
+    clock.tick();
+    sggrid::Misc hm{};
+    Tally ht{};
+    SG_HIP(hipMemcpyAsync(&hm, p.grid.misc, sizeof(hm), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipMemcpyAsync(&ht, p.tally, sizeof(ht), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    clock.tick();
+    SG_LAUNCH_CHECK();
+    leave_stats(ix.g, hm, ht);
+    return SG_OK;
+}
+
+int sg_components_radius(const float* d_points, int stride, int N, float radius, float cell, const int32_t* d_label, int32_t* d_comp,
+                         int32_t* d_size, int* h_C, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* who = "sg_components_radius";
+    for (int i = 0; i < kNumStats; ++i) t_ses.stats[i] = 0;
+    SG_REQUIRE(h_C, "%s: a null pointer", who);
+    *h_C = 0;
+    float r2 = 0.0f;
+    if (const int rc = check_args(who, d_points, stride, N, radius, cell, d_comp, d_ws, ws_bytes, &r2)) return rc;
+    const Plan p = carve(d_ws, ws_bytes, N);
+    if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_radius_grid_ws_bytes(N));
+    hipStream_t st = sg::as_stream(stream);
+    const int counting = t_ses.timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, t_ses.timing, t_ses.stage_us);
+    Index ix{};
+    if (const int rc = build_index(who, d_points, stride, N, radius, r2, cell, p, clock, st, &ix)) return rc;
+    const int nb = sg::cdiv(N, sgcc::kBlock);
+    sgcc::k_cc_init<<<nb, sgcc::kBlock, 0, st>>>(p.parent, p.count, N, p.misc);
+    clock.tick();
+    k_radius_search<HookVisitor><<<sg::cdiv(N, kWave), kWave, 0, st>>>(p.grid.spts, ix.sidx, ix.skey, p.grid.start, ix.g, N, r2,
+                                                                      HookVisitor{p.parent, d_label, p.misc, N}, p.tally, counting);
+    clock.tick();
+    sgcc::k_cc_flatten<<<nb, sgcc::kBlock, 0, st>>>(p.parent, N, d_comp, d_size ? p.count : nullptr, p.misc);
+    if (d_size) sgcc::k_cc_sizes<<<nb, sgcc::kBlock, 0, st>>>(d_comp, p.count, N, d_size);
+    sggrid::Misc hm{};
+    sgcc::Misc hc{};
+    Tally ht{};
+    SG_HIP(hipMemcpyAsync(&hm, p.grid.misc, sizeof(hm), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipMemcpyAsync(&hc, p.misc, sizeof(hc), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipMemcpyAsync(&ht, p.tally, sizeof(ht), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    clock.tick();
+    SG_LAUNCH_CHECK();
+    if (hc.flag & sgcc::kFlagBudget) return sg::fail(SG_EINTERNAL, "%s: a chase ran out of its %d steps", who, 2 * N + 4);
+    if (hc.roots < 1 || hc.roots > N) return sg::fail(SG_EINTERNAL, "%s: %d components from %d points", who, hc.roots, N);
+    *h_C = hc.roots;
+    leave_stats(ix.g, hm, ht);
+    return SG_OK;
+}
+
+}  // extern "C"

@@ -173,6 +173,13 @@ SIGNATURES = {
     "sg_components_set_timing": (_I, [_I]),
     "sg_components_stage_times": (_I, [vp, _I]),
     "sg_components_stage_name": (C.c_char_p, [_I]),
+    "sg_radius_grid_ws_bytes": (_Z, [_I]),
+    "sg_radius_count_grid": (_I, [vp, _I, _I, C.c_float, C.c_float, vp, vp, _Z, vp]),
+    "sg_components_radius": (_I, [vp, _I, _I, C.c_float, C.c_float, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_radius_grid_set_timing": (_I, [_I]),
+    "sg_radius_grid_stage_times": (_I, [vp, _I]),
+    "sg_radius_grid_stage_name": (C.c_char_p, [_I]),
+    "sg_radius_grid_stats": (_I, [vp, _I]),
     "sg_segment_vote_ws_bytes": (_Z, [_I]),
     "sg_segment_rank": (_I, [vp, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_segment_vote": (_I, [vp, vp, _I, _I] + [vp] * 9 + [C.POINTER(C.c_int), vp, _Z, vp]),

@@ -355,6 +355,9 @@ class Engine:
                 tid = self.lib.sg_engine_submit(self.handle, c_scenes, n, mode, c_res, wh, c_dirs, fm)
             else:
                 c_dbg = (C.c_void_p * n)(*[C.addressof(d) if d is not None else None for d in debug])
+                # the taps are copied on the groups' own non-blocking streams, which nothing orders behind the caller's stream: whatever the
+                # caller queued to prepare the tap buffers (a zero fill) must have run, or it lands on top of a small scene's taps
+                torch.cuda.current_stream().synchronize()
                 tid = self.lib.sg_engine_submit_debug(self.handle, c_scenes, n, mode, c_res, c_dbg, wh, c_dirs, fm)
         hip.check(tid)
         if wh is not None:
