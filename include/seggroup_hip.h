@@ -127,7 +127,10 @@ int sg_group_max_rows(const float* d_rows, int row_stride, int D, const int32_t*
                       int G, float* d_out, int out_stride, void* stream);
 
 /* a10 point->cluster max (model.py:793,834): rows are in member order, i.e. clusters are contiguous ranges and
- * d_cluster_of_pos is non-decreasing along the rows (sg_gather_members produces exactly that) */
+ * d_cluster_of_pos is non-decreasing along the rows (sg_gather_members produces exactly that).  Only D == 64.  Columns [0,64) of
+ * every one of the C output rows are written: a cluster without a row stays -inf.  The maximum is by VALUE over arbitrary rows
+ * (infinities, subnormals and both zeros included): the float max is an integer atomic on the bits, split on the value's sign
+ * bit, so -0.0 orders above every negative and below +0.0; a cluster holding both zeros returns either. */
 int sg_segment_max(const float* d_rows, int N, int D, const int32_t* d_cluster_of_pos,
                    float* d_out, int out_stride, int C, void* stream);
 

@@ -323,7 +323,8 @@ __device__ __forceinline__ void edgeconv_body(sg::gptr<const float> x9m, sg::gpt
         const gptr<float> row = ext + (size_t)__builtin_amdgcn_readfirstlane(c) * ext_stride;
         const unsigned off = 4u * (unsigned)ch;
         // (as statements: from C++ the compiler builds a 64-bit lane address whose zero high half it parks in scratch for the whole walk)
-        if (v >= 0.0f) asm volatile("global_atomic_smax %0, %1, %2" :: "v"(off), "v"(v), "s"(row) : "memory");
+        // split on the sign BIT: -0.0 has the bits of INT_MIN, which never wins a signed max; as an unsigned it orders correctly
+        if (__builtin_bit_cast(int, v) >= 0) asm volatile("global_atomic_smax %0, %1, %2" :: "v"(off), "v"(v), "s"(row) : "memory");
         else asm volatile("global_atomic_umin %0, %1, %2" :: "v"(off), "v"(v), "s"(row) : "memory");
     };
     for (int it = 0; it < walk_n; ++it) {

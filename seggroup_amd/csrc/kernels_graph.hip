@@ -248,8 +248,11 @@ __global__ void k_group_max_rows_b(const SlotCtx* __restrict__ cx) {
 }
 
 __device__ inline void atomic_max_float(float* addr, float v) {
-    // order-preserving integer view: non-negative floats compare as ints, negative floats reversed as uints
-    if (v >= 0.0f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
+    // order-preserving integer view: floats with a clear sign bit compare as ints, those with the sign bit set reversed as uints.
+    // The split is on the SIGN BIT, not on v >= 0: -0.0 has the bits of INT_MIN, which never wins a signed max (a maximum of exactly
+    // -0.0 came out as the next lower value, or as the -inf fill); as an unsigned it is the smallest of the negatives and orders
+    // correctly against every stored value ("signed zero in the float max").
+    if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
     else atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
 
