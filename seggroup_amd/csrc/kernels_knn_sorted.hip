@@ -981,21 +981,73 @@ __device__ __forceinline__ void cluster_knn_sorted_body(
     // phase B: every other segment of the cluster.  The segment descriptors (id, member offset, size, first chunk,
     // box) are staged kSlotBatch at a time in LDS by the whole workgroup: walking the list straight from global
     // memory costs two dependent round trips per segment and dominated the kernel for clusters of many segments.
-    for (int r0 = 1; r0 < nslots; r0 += kSlotBatch) {
-        const int nb = min(kSlotBatch, nslots - r0);
-        __syncthreads();                                      // previous batch fully consumed
-        for (int e = tid; e < nb; e += 64 * kSlices) {
-            const int slot = slot_of(r0 + e), sg = order[slot];
-            st_m[e] = seg_off[sg + 1] - seg_off[sg];
-            st_c0[e] = seg_chunk_off[sg];
-            st_d[e] = dst[slot];
-            if (kSeeded) st_pc[e] = seg_prevcl[sg];
-            const sg::gptr<const float4> bp = (sg::gptr<const float4>)(segbox + (size_t)sg * 8);
-            reinterpret_cast<float4*>(&st_box[e][0])[0] = bp[0];
-            reinterpret_cast<float4*>(&st_box[e][0])[1] = bp[1];
+    // One wave per tile: the staged segments are tested 32 AT ONCE, one per lane, before anybody walks them -- the pretest the chunk boxes of a
+    // big segment get in scan_segment, one level up.  At the bench's third layer a tile's cluster has ~57 segments and 47 of a tile's 54
+    // wave-uniform segment tests (LDS reads of the box, box_score_bound, list_key, 64-bit compare, ballot) answer "nobody needs it".
+    // Lane e holds segment e's box against the box of the tile's 64 queries: every gap is <= each lane's own gap and qw >= each lane's w, fp32
+    // subtraction, multiplication and addition of non-negative values round monotonically, so the value is >= every lane's box_score_bound();
+    // `weakest` is taken once per batch and thresholds only rise, so it is <= every lane's bound at the time of the exact test.  A segment
+    // some lane would accept therefore survives; the survivors go through scan_segment's exact per-lane test in the old order.  (NaN on
+    // either side survives too.)
+    // Seeded: when every query of the tile comes from ONE former cluster, its segments are dropped here as well (each lane's `ok` would be
+    // false); a tile that spans former clusters, and segments with no list (seg_prevcl = -1), are left to the per-lane flag.
+    if constexpr (kSlices == 1) {
+        static_assert(kSlotBatch <= 64, "one staged segment per lane");
+        int tile_prev = -1;
+        if constexpr (kSeeded) {
+            const int p0 = sgw::bcast(myprev, 0);
+            if (__all(!active || myprev == p0)) tile_prev = p0;
         }
-        __syncthreads();
-        for (int i = 0; i < nb; ++i) scan_segment(st_m[i], st_c0[i], st_d[i], &st_box[i][0], kSeeded ? st_pc[i] : -1, item, 0);
+        for (int r0 = 1; r0 < nslots; r0 += kSlotBatch) {
+            const int nb = min(kSlotBatch, nslots - r0);      // <= 32: one staged segment per lane
+            __syncthreads();                                  // previous batch fully consumed
+            // the weakest score any lane still accepts, decoded as score_bound() does (score bits below -inf's are "anything goes"); all lanes take part
+            const unsigned int o = list_score(best_thr());
+            float mine = INFINITY;
+            if (active) mine = o < 0x00800000u ? -INFINITY : __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+            const float weakest = sgw::wave_min(mine);
+            bool keep = false;
+            if (lane < nb) {
+                const int slot = slot_of(r0 + lane), sg = order[slot];
+                st_m[lane] = seg_off[sg + 1] - seg_off[sg];
+                st_c0[lane] = seg_chunk_off[sg];
+                st_d[lane] = dst[slot];
+                const int pc = kSeeded ? seg_prevcl[sg] : -1;
+                if (kSeeded) st_pc[lane] = pc;
+                const sg::gptr<const float4> bp = (sg::gptr<const float4>)(segbox + (size_t)sg * 8);
+                const float4 b0 = bp[0], b1 = bp[1];
+                reinterpret_cast<float4*>(&st_box[lane][0])[0] = b0;
+                reinterpret_cast<float4*>(&st_box[lane][0])[1] = b1;
+                const float gx = fmaxf(fmaxf(b0.x - qhi[0], qlo[0] - b0.w), 0.f);
+                const float gy = fmaxf(fmaxf(b0.y - qhi[1], qlo[1] - b1.x), 0.f);
+                const float gz = fmaxf(fmaxf(b0.z - qhi[2], qlo[2] - b1.y), 0.f);
+                keep = !(-((gx * gx + gy * gy) + gz * gz) * 0.999999f + 9.6e-7f * (qw + b1.z) < weakest) && !(pc >= 0 && pc == tile_prev);
+            }
+            __syncthreads();
+            unsigned long long live = __ballot(keep);         // bit e = staged segment e: ascending slot order
+            while (live) {
+                const int i = __ffsll((unsigned long long)live) - 1;
+                live &= live - 1;
+                scan_segment(st_m[i], st_c0[i], st_d[i], &st_box[i][0], kSeeded ? st_pc[i] : -1, item, 0);
+            }
+        }
+    } else {
+        for (int r0 = 1; r0 < nslots; r0 += kSlotBatch) {
+            const int nb = min(kSlotBatch, nslots - r0);
+            __syncthreads();                                  // previous batch fully consumed
+            for (int e = tid; e < nb; e += 64 * kSlices) {
+                const int slot = slot_of(r0 + e), sg = order[slot];
+                st_m[e] = seg_off[sg + 1] - seg_off[sg];
+                st_c0[e] = seg_chunk_off[sg];
+                st_d[e] = dst[slot];
+                if (kSeeded) st_pc[e] = seg_prevcl[sg];
+                const sg::gptr<const float4> bp = (sg::gptr<const float4>)(segbox + (size_t)sg * 8);
+                reinterpret_cast<float4*>(&st_box[e][0])[0] = bp[0];
+                reinterpret_cast<float4*>(&st_box[e][0])[1] = bp[1];
+            }
+            __syncthreads();
+            for (int i = 0; i < nb; ++i) scan_segment(st_m[i], st_c0[i], st_d[i], &st_box[i][0], kSeeded ? st_pc[i] : -1, item, 0);
+        }
     }
     drain();
     const unsigned long long t3 = (dbg & 16) ? __builtin_readcyclecounter() : 0ull;
