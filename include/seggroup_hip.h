@@ -985,6 +985,40 @@ int sg_radius_grid_stage_times(float* h_us, int cap);
 const char* sg_radius_grid_stage_name(int i);
 int sg_radius_grid_stats(int64_t* h, int cap);
 
+/* The radius graph written down, and the point-cloud over-segmenter over it.
+ * sg_radius_neighbours_grid: the pairs of sg_radius_count_grid as lists in CSR form.  d_off int64 [N + 1] = the exclusive sum of the counts,
+ *   T = off[N]; d_idx int32 [T]: the row of i holds its neighbours in ASCENDING INDEX whatever the cell edge.  d_off and *h_T are always
+ *   written.  With T > capacity (capacity = 0 and d_idx = NULL is the query form) nothing is written to d_idx and the call returns SG_ENOMEM
+ *   with T in *h_T.  Order of a call: index, count, a 64-bit scan, T read back (one synchronisation), fill in search order, every row
+ *   ordered by rank (one wave per row; the work of a row is its length squared / 64).
+ *   Refusals before the first HIP call: sg_radius_count_grid's, a negative capacity, room at a null d_idx, a workspace below
+ *   sg_radius_neighbours_ws_bytes(N, capacity) (SG_ENOMEM), a capacity above SG_MAX_RADIUS_PAIRS (SG_EUNSUP).  T above SG_MAX_RADIUS_PAIRS is
+ *   SG_EUNSUP once T is known; the message names the two ways out: a smaller radius, or thinning the cloud first (sg_thin_*).  The cap keeps
+ *   E = T / 2, 2 E and every int the weight sort and sg_overseg_merge form from E below 2^31.
+ * sg_pointcloud_normals_csr: d_normals [N,3] from d_xyz [N,3] and such lists: the neighbourhood of i is i itself, then its row in stored
+ *   order; mean, covariance and eigenvector as sg_pointcloud_normals.  A caller's lists are checked on the device: an entry outside 0..N-1
+ *   or offsets that do not ascend from 0 to off[N] are SG_EINVAL, and nothing is read through them.  d_ws: sg_pointcloud_knn_ws_bytes(N).
+ * sg_pcseg_edges_radius / sg_pcseg_scan_radius: sg_pcseg_edges_indexed / sg_pcseg_scan_indexed over the radius graph: `radius`, `cell` and a
+ *   pair capacity (d_edges and d_w hold capacity / 2 edges) in place of k and index; d_off / d_idx may both be NULL.  *h_T as above; SG_ENOMEM
+ *   with T > capacity.  d_ws: sg_pcseg_ws_bytes_radius(N, capacity) (0 outside the envelope).
+ * Stage times by events, as sg_pcseg_set_timing: room for 13 floats (box, cells, sort, table, count, scan, fill, rows, normals, edges,
+ *   weights, weight_sort, gather; tools/time_pcseg_radius.py). */
+#define SG_MAX_RADIUS_PAIRS (1ll << 30)
+size_t sg_radius_neighbours_ws_bytes(int N, int64_t capacity);
+int sg_radius_neighbours_grid(const float* d_points, int stride, int N, float radius, float cell, int64_t capacity, int64_t* d_off,
+                              int32_t* d_idx, int64_t* h_T, void* d_ws, size_t ws_bytes, void* stream);
+int sg_pointcloud_normals_csr(const float* d_xyz, int N, const int64_t* d_off, const int32_t* d_idx, const float* h_viewpoint, float* d_normals,
+                              void* d_ws, size_t ws_bytes, void* stream);
+size_t sg_pcseg_ws_bytes_radius(int N, int64_t T);
+int sg_pcseg_edges_radius(const float* d_xyz, int N, float radius, float cell, int64_t capacity, const float* h_viewpoint, int64_t* d_off,
+                          int32_t* d_idx, float* d_normals, int32_t* d_edges, float* d_w, int* h_E, int64_t* h_T, void* d_ws, size_t ws_bytes,
+                          void* stream);
+int sg_pcseg_scan_radius(const float* d_xyz, int N, float radius, float cell, int64_t capacity, const float* h_viewpoint, float k_thresh,
+                         int seg_min_verts, int32_t* h_seg_indices, int64_t* h_T, void* d_ws, size_t ws_bytes, void* stream);
+int sg_pcseg_radius_set_timing(int on);
+int sg_pcseg_radius_stage_times(float* h_us, int cap);
+const char* sg_pcseg_radius_stage_name(int i);
+
 /* Segment vote: what re-keying a scan's annotations onto another over-segmentation needs on the device.  Every vertex has a
  * row id d_ids[v] (any non-negative int32: not contiguous, may exceed V) and a column d_cols[v] in 0..n_cols-1; both are checked on the
  * device (SG_EINVAL).  Rows come out in ascending id order, *h_R of them; every output needs room for V entries.

@@ -107,6 +107,36 @@ def neighbour_counts(xyz, radius, cell=0.0, device=None, stream=None):
     return count
 
 
+def radius_neighbours(xyz, radius, cell=0.0, device=None, stream=None):
+    """-> (indptr int64 [N + 1], indices int32 [T]) device tensors: the radius graph of `neighbour_counts` written down in CSR form
+    (DESIGN.md 8l).  The row of i, indices[indptr[i]:indptr[i + 1]], holds every OTHER point whose fp32 d2 <= radius^2 in ascending
+    index; `cell` cannot change a byte.  Two calls of the library: one that counts (T is not known before), one that fills."""
+    r, c = _radius(radius), hip.knn_cell(cell)
+    n = _cloud(xyz, "radius_neighbours")
+    import torch
+    from .oversegment import _on, _stream_ptr
+    from .prepare import _dev, _t, _ws
+    dev = _dev(device)
+    lib = hip.lib()
+    with torch.cuda.device(dev), _on(stream):
+        d_xyz = _t(xyz, torch.float32, dev)
+        stride = int(d_xyz.shape[1])
+        indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        total = C.c_int64(0)
+        ws = _ws(lib.sg_radius_neighbours_ws_bytes(n, 0), dev)
+        rc = lib.sg_radius_neighbours_grid(d_xyz.data_ptr(), stride, n, r, c, 0, indptr.data_ptr(), None, C.byref(total), ws.data_ptr(),
+                                           ws.numel(), _stream_ptr(stream))
+        if rc != hip.SG_ENOMEM or total.value <= 0:          # the query form answers SG_ENOMEM with T whenever there is a pair
+            hip.check(rc)
+        t = int(total.value)
+        indices = torch.empty(t, dtype=torch.int32, device=dev)
+        if t:
+            ws = _ws(lib.sg_radius_neighbours_ws_bytes(n, t), dev)
+            hip.check(lib.sg_radius_neighbours_grid(d_xyz.data_ptr(), stride, n, r, c, t, indptr.data_ptr(), indices.data_ptr(), C.byref(total),
+                                                    ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+    return indptr, indices
+
+
 def components(V: int, *, edges=None, faces=None, knn=None, radius=None, xyz=None, max_edge=None, labels=None, cell=0.0, device=None,
                stream=None):
     """-> (comp int32 [V], size int32 [V], C): comp[v] = the lowest vertex index of v's component, size[v] = its vertex count (device

@@ -11,6 +11,9 @@
 //   edges               (i, L[i][t]), t = 1..k, without the self pairs, as sorted unique pair keys: a < b in lexicographic order
 //   k_pc_weights        8d's weight after the two normals have been aligned (the viewpoint test may have fallen either way)
 //   sort + gather       8d's, the same code (overseg_device.h)
+//   radius graph        DESIGN.md 8l, sg_pcseg_edges_radius: the lists of sg_radius_neighbours_grid in place of the kNN table; k_pc_normals_csr
+//                       (neighbourhoods of variable length, the same Jacobi code: pcseg_normals_device.h), the upper halves of the rows as the
+//                       lexicographic edge list (k_pc_upper_counts, scan64_device.h, k_pc_edges_csr); weights, sort and gather as above
 //
 // Every fp32 operation is written op by op and rounded once (-ffp-contract=off; only + - * / sqrt and comparisons, the explicit FMAs of
 // pair_score aside), which tests/test_gpu_pcseg.py holds to the NumPy statement of the specification (tests/pcseg_ref.py) bit for bit.
@@ -20,16 +23,18 @@
 #include "sort_device.h"
 #include "cloud_knn_device.h"
 #include "overseg_device.h"
+#include "pcseg_normals_device.h"
+#include "scan64_device.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kSweeps = 5;          // after five sweeps every off-diagonal is exactly 0 on the measured clouds
+using sgpc::kSweeps;
 using sgcloud::kTile;
 
 struct Misc {
     int flag;                       // |= 1: a coordinate is not finite; |= 2: a list has an unfilled entry (scores not finite); |= 4: a
-                                    // caller's list names a point outside 0..N-1
+                                    // caller's list names a point outside 0..N-1; |= 8: the offsets of a caller's rows do not ascend from 0
     int count;                      // unique pair keys
     unsigned int lo[3], hi[3];      // the bounding box as sgos::weight_key words
     float view[3];
@@ -91,36 +96,6 @@ __global__ __launch_bounds__(kTile) void k_pc_knn(const float4* __restrict__ can
     if (unfilled) atomicOr(&m->flag, 2);
 }
 
-// one Jacobi rotation of the pair (p, q); r is the third index.  a_rp, a_rq: the two off-diagonals that share r; v_ip, v_iq: the columns
-// p and q of the accumulated rotation.  A pair whose off-diagonal is exactly 0 is skipped.
-__device__ __forceinline__ void rotate(float& app, float& aqq, float& apq, float& arp, float& arq, float& v0p, float& v0q, float& v1p,
-                                       float& v1q, float& v2p, float& v2q) {
-    if (apq == 0.0f) return;
-    const float theta = (aqq - app) / (2.0f * apq);
-    const float sgn = theta >= 0.0f ? 1.0f : -1.0f;
-    const float t = sgn / (__builtin_fabsf(theta) + __builtin_sqrtf(theta * theta + 1.0f));      // theta * theta = +inf gives t = 0
-    const float c = 1.0f / __builtin_sqrtf(t * t + 1.0f);
-    const float s = t * c;
-    const float h = t * apq;
-    app = app - h;
-    aqq = aqq + h;
-    apq = 0.0f;
-    const float rp = arp, rq = arq;
-    arp = c * rp - s * rq;
-    arq = s * rp + c * rq;
-    const float x0 = v0p, y0 = v0q, x1 = v1p, y1 = v1q, x2 = v2p, y2 = v2q;
-    v0p = c * x0 - s * y0; v0q = s * x0 + c * y0;
-    v1p = c * x1 - s * y1; v1q = s * x1 + c * y1;
-    v2p = c * x2 - s * y2; v2q = s * x2 + c * y2;
-}
-
-// c2 if b2, else c1 if b1, else c0
-__device__ __forceinline__ float pick(float c0, float c1, float c2, bool b1, bool b2) {
-    const unsigned int m1 = b1 ? ~0u : 0u, m2 = b2 ? ~0u : 0u;
-    const unsigned int lo = (__float_as_uint(c1) & m1) | (__float_as_uint(c0) & ~m1);
-    return __uint_as_float((__float_as_uint(c2) & m2) | (lo & ~m2));
-}
-
 // p: rows of `stride` floats, xyz first.  table [N,KK]: every point's list; an entry outside 0..N-1 (a caller's table) raises flag 4 and
 // counts as the point itself.
 template <int KK>
@@ -151,25 +126,99 @@ __global__ __launch_bounds__(kBlock) void k_pc_normals(const float* __restrict__
         a00 = a00 + qx * qx; a01 = a01 + qx * qy; a02 = a02 + qx * qz;
         a11 = a11 + qy * qy; a12 = a12 + qy * qz; a22 = a22 + qz * qz;
     }
-    // 4. cyclic Jacobi, pairs (0,1), (0,2), (1,2); v_rc = row r, column c of the accumulated rotation
-    float v00 = 1.0f, v01 = 0.0f, v02 = 0.0f, v10 = 0.0f, v11 = 1.0f, v12 = 0.0f, v20 = 0.0f, v21 = 0.0f, v22 = 1.0f;
-#pragma unroll 1
-    for (int sweep = 0; sweep < kSweeps; ++sweep) {
-        rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
-        rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
-        rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
-    }
-    // the column whose diagonal entry is smallest, the lowest index among equal entries
-    // (selected by masks: written as branches, the compiler turns the three candidates into a table in scratch)
-    const bool b1 = a11 < a00;
-    const float dm = b1 ? a11 : a00;
-    const bool b2 = a22 < dm;
-    float nx = pick(v00, v01, v02, b1, b2), ny = pick(v10, v11, v12, b1, b2), nz = pick(v20, v21, v22, b1, b2);
+    // 4. cyclic Jacobi and the column of the smallest diagonal entry (pcseg_normals_device.h)
+    float nx, ny, nz;
+    sgpc::smallest_eigenvector(a00, a01, a02, a11, a12, a22, nx, ny, nz);
     // 5. towards the viewpoint
     const float dx = m->view[0] - p[(size_t)i * stride], dy = m->view[1] - p[(size_t)i * stride + 1], dz = m->view[2] - p[(size_t)i * stride + 2];
     const float s = (nx * dx + ny * dy) + nz * dz;
     if (s < 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
     nrm[(size_t)i * 3] = nx; nrm[(size_t)i * 3 + 1] = ny; nrm[(size_t)i * 3 + 2] = nz;
+}
+
+
+// The normals over neighbourhoods of variable length: the neighbourhood of i is i itself, then its row
+// idx[off[i] .. off[i+1]) in stored order.  One thread per point, two passes over the row, every point gathered as the packed 16-byte
+// record of k_pc_pack; the sums are sequential by the statement.  The table is checked here: a row outside 0 <= lo <= hi <= off[N] (or
+// off[0] != 0) raises flag 8 and counts as empty, an entry outside 0..N-1 raises flag 4 and counts as the point itself -- nothing is
+// read through either.
+__global__ __launch_bounds__(kBlock) void k_pc_normals_csr(const float4* __restrict__ cand, int N, const int64_t* __restrict__ off,
+                                                           const int32_t* __restrict__ idx, Misc* __restrict__ m, float* __restrict__ nrm) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    const int64_t T = off[N];
+    int64_t lo = off[i], hi = off[i + 1];
+    if (!(lo >= 0 && lo <= hi && hi <= T) || (i == 0 && lo != 0)) { atomicOr(&m->flag, 8); lo = 0; hi = 0; }
+    const float4 me = cand[i];
+    // the mean: the sum in neighbourhood order from +0, divided by (float)m
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    sx = sx + me.x; sy = sy + me.y; sz = sz + me.z;
+    bool bad = false;
+    for (int64_t e = lo; e < hi; ++e) {
+        int j = idx[e];
+        if ((unsigned)j >= (unsigned)N) { bad = true; j = i; }
+        const float4 q = cand[j];
+        sx = sx + q.x; sy = sy + q.y; sz = sz + q.z;
+    }
+    if (bad) atomicOr(&m->flag, 4);
+    const float mm = (float)(hi - lo + 1);
+    const float mx = sx / mm, my = sy / mm, mz = sz / mm;
+    // the six covariance sums in the same order from +0, not normalised
+    float a00 = 0.0f, a01 = 0.0f, a02 = 0.0f, a11 = 0.0f, a12 = 0.0f, a22 = 0.0f;
+    {
+        const float qx = me.x - mx, qy = me.y - my, qz = me.z - mz;
+        a00 = a00 + qx * qx; a01 = a01 + qx * qy; a02 = a02 + qx * qz;
+        a11 = a11 + qy * qy; a12 = a12 + qy * qz; a22 = a22 + qz * qz;
+    }
+    for (int64_t e = lo; e < hi; ++e) {
+        int j = idx[e];
+        if ((unsigned)j >= (unsigned)N) j = i;
+        const float4 q = cand[j];
+        const float qx = q.x - mx, qy = q.y - my, qz = q.z - mz;
+        a00 = a00 + qx * qx; a01 = a01 + qx * qy; a02 = a02 + qx * qz;
+        a11 = a11 + qy * qy; a12 = a12 + qy * qz; a22 = a22 + qz * qz;
+    }
+    float nx, ny, nz;
+    sgpc::smallest_eigenvector(a00, a01, a02, a11, a12, a22, nx, ny, nz);
+    // towards the viewpoint
+    const float dx = m->view[0] - me.x, dy = m->view[1] - me.y, dz = m->view[2] - me.z;
+    const float s = (nx * dx + ny * dy) + nz * dz;
+    if (s < 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+    nrm[(size_t)i * 3] = nx; nrm[(size_t)i * 3 + 1] = ny; nrm[(size_t)i * 3 + 2] = nz;
+}
+
+// where the upper half of row i begins: the first entry above i of a row in ascending index (the library's own rows)
+__device__ __forceinline__ int64_t upper_begin(const int32_t* __restrict__ idx, int64_t lo, int64_t hi, int i) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (idx[mid] > i) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// up[i] = the entries of row i above i
+__global__ __launch_bounds__(kBlock) void k_pc_upper_counts(const int64_t* __restrict__ off, const int32_t* __restrict__ idx, int N,
+                                                            int32_t* __restrict__ up) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    const int64_t hi = off[i + 1];
+    up[i] = (int32_t)(hi - upper_begin(idx, off[i], hi, i));
+}
+
+// the pairs a < b in lexicographic order: one wave per row copies the row's upper half to adj [E,2] at eoff[i]; E: the room of adj
+__global__ __launch_bounds__(kBlock) void k_pc_edges_csr(const int64_t* __restrict__ off, const int32_t* __restrict__ idx, int N,
+                                                         const int64_t* __restrict__ eoff, int64_t E, int64_t* __restrict__ adj) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (i >= N) return;
+    const int64_t hi = off[i + 1];
+    const int64_t from = upper_begin(idx, off[i], hi, i);
+    const int64_t dst = eoff[i];
+    for (int64_t t = lane; t < hi - from; t += 64) {
+        if (dst + t >= E) break;
+        adj[(size_t)(dst + t) * 2] = (int64_t)i;
+        adj[(size_t)(dst + t) * 2 + 1] = (int64_t)idx[from + t];
+    }
 }
 
 // 6. pair key of (i, L[i][t]), t = 1..k, at i * k + t - 1: lo << 32 | hi; a self pair (coincident points) becomes ~0 and sorts to the end
@@ -399,6 +448,161 @@ int pcseg_scan(const char* who, const float* d_xyz, int N, int k, const float* h
     return sg_overseg_merge(h_edges.data(), h_w.data(), E, N, k_thresh, seg_min_verts, h_seg_indices);
 }
 
+// ---- the radius graph instead of the kNN graph ------------------------------------------------------------------------
+struct RPlan {                      // the workspace of one cloud at room for T pairs; E = T / 2
+    float4* cand;
+    Misc* misc;
+    int64_t *off, *eoff;            // [N + 1]
+    int32_t* idx;                   // [T]
+    int32_t* up;                    // [N]
+    long long* tsum;
+    int64_t* adj;                   // [E,2]
+    float* w;
+    unsigned int *k0, *k1;
+    int *v0, *v1;
+    int* hist;
+    float* vn;
+    int32_t* edges;
+    float* w_sorted;
+    char* lists;                    // sg_radius_neighbours_grid's workspace
+    size_t lists_bytes;
+    bool ok;
+};
+
+RPlan carve_radius(void* d_ws, size_t ws_bytes, int N, int64_t T) {
+    RPlan p{};
+    const size_t np = (size_t)std::max(N, 1), t = (size_t)std::max<int64_t>(T, 0), e = std::max<size_t>(t / 2, 1);
+    sg::Carver cv(d_ws, ws_bytes);
+    p.cand = cv.take<float4>(np);
+    p.misc = cv.take<Misc>(1);
+    p.off = cv.take<int64_t>(np + 1);
+    p.eoff = cv.take<int64_t>(np + 1);
+    p.idx = cv.take<int32_t>(std::max<size_t>(t, 1));
+    p.up = cv.take<int32_t>(np);
+    p.tsum = cv.take<long long>((size_t)sgscan::tiles_of((int)np) + 1);
+    p.adj = cv.take<int64_t>(e * 2);
+    p.w = cv.take<float>(e);
+    p.k0 = cv.take<unsigned int>(e);
+    p.k1 = cv.take<unsigned int>(e);
+    p.v0 = cv.take<int>(e);
+    p.v1 = cv.take<int>(e);
+    p.hist = cv.take<int>(sgsort::hist_ints((long long)e));
+    p.vn = cv.take<float>(np * 3);
+    p.edges = cv.take<int32_t>(e * 2);
+    p.w_sorted = cv.take<float>(e);
+    p.lists_bytes = sg_radius_neighbours_ws_bytes(N, T);
+    p.lists = cv.take<char>(p.lists_bytes);
+    p.ok = cv.ok && p.lists_bytes > 0;
+    return p;
+}
+
+size_t pcseg_ws_bytes_radius(int N, int64_t T) {
+    const size_t np = (size_t)N, t = (size_t)T, e = std::max<size_t>(t / 2, 1);
+    return sg::align_up(np * 16) + sg::align_up(sizeof(Misc)) + 2 * sg::align_up((np + 1) * 8) + sg::align_up(std::max<size_t>(t, 1) * 4) +
+           sg::align_up(np * 4) + sg::align_up(((size_t)sgscan::tiles_of(N) + 1) * 8) + sg::align_up(e * 16) + 5 * sg::align_up(e * 4) +
+           sg::align_up(sgsort::hist_ints((long long)e) * 4) + sg::align_up(np * 12) + sg::align_up(e * 8) + sg::align_up(e * 4) +
+           sg::align_up(sg_radius_neighbours_ws_bytes(N, T));
+}
+
+constexpr int kListStages = 8;      // box, cells, sort, table, count, scan, fill, rows: the lists' own (kernels_radius.hip)
+constexpr int kOwnStages = 5;
+constexpr int kRStages = kListStages + kOwnStages;
+const char* const kOwnStageNames[kOwnStages] = {"normals", "edges", "weights", "weight_sort", "gather"};
+thread_local bool t_rtiming = false;
+thread_local float t_rstage_us[kRStages];
+
+struct ListTiming {                 // the lists report their stages to this thread while one of these lives
+    bool on;
+    explicit ListTiming(bool o) : on(o) { if (on) sg::radius_lists_timing(true); }
+    ~ListTiming() { if (on) sg::radius_lists_timing(false); }
+};
+
+int pcseg_edges_radius(const char* who, const float* d_xyz, int N, float radius, float cell, int64_t capacity, const float* h_viewpoint,
+                       int64_t* d_off, int32_t* d_idx, float* d_normals, int32_t* d_edges, float* d_w, int* h_E, int64_t* h_T, void* d_ws,
+                       size_t ws_bytes, void* stream) {
+    if (!(d_xyz && d_normals && h_E && h_T && d_ws)) return sg::fail(SG_EINVAL, "%s: a null pointer", who);
+    *h_E = 0;
+    *h_T = 0;
+    SG_REQUIRE(N >= 1, "%s: %d points", who, N);
+    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
+    if (capacity > SG_MAX_RADIUS_PAIRS)
+        return sg::fail(SG_EUNSUP, "%s: room for %lld pairs; the lists hold at most %lld: take a smaller radius, or thin the cloud first", who,
+                        (long long)capacity, (long long)SG_MAX_RADIUS_PAIRS);
+    SG_REQUIRE(capacity >= 0 && (capacity < 2 || (d_edges && d_w)), "%s: room for %lld pairs at a null pointer", who, (long long)capacity);
+    SG_REQUIRE((d_off == nullptr) == (d_idx == nullptr) || capacity == 0, "%s: the caller's lists are both offsets and indices", who);
+    int rc = viewpoint_ok(who, h_viewpoint);
+    if (rc < 0) return rc;
+    const RPlan p = carve_radius(d_ws, ws_bytes, N, capacity);
+    if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, pcseg_ws_bytes_radius(N, capacity));
+    hipStream_t st = sg::as_stream(stream);
+    int64_t* off = d_off ? d_off : p.off;
+    int32_t* idx = d_idx ? d_idx : p.idx;
+    if (t_rtiming) for (int i = 0; i < kRStages; ++i) t_rstage_us[i] = 0.0f;
+    // the lists: every refusal of 8k and the pair cap are theirs
+    {
+        const ListTiming lt(t_rtiming);
+        rc = sg::radius_lists(who, d_xyz, 3, N, radius, cell, capacity, off, idx, h_T, p.lists, p.lists_bytes, stream);
+        if (t_rtiming) for (int i = 0; i < kListStages; ++i) t_rstage_us[i] = sg::radius_lists_stage_us()[i];
+    }
+    if (rc < 0) return rc;
+    const int64_t T = *h_T;
+    sgos::StageClock<kOwnStages> clock(st, t_rtiming, t_rstage_us + kListStages);
+    // normals over the rows
+    k_pc_init<<<1, 1, 0, st>>>(p.misc, h_viewpoint != nullptr, h_viewpoint ? h_viewpoint[0] : 0.0f, h_viewpoint ? h_viewpoint[1] : 0.0f,
+                               h_viewpoint ? h_viewpoint[2] : 0.0f);
+    k_pc_pack<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(d_xyz, 3, N, p.cand, p.misc);
+    if (!h_viewpoint) k_pc_view<<<1, 1, 0, st>>>(p.misc);
+    k_pc_normals_csr<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(p.cand, N, off, idx, p.misc, d_normals);
+    clock.tick();
+    // the pairs a < b in lexicographic order: the upper halves of the rows
+    k_pc_upper_counts<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(off, idx, N, p.up);
+    sgscan::exclusive_scan64(p.up, N, p.tsum, p.eoff, st);
+    int64_t E64 = 0;
+    int flag = 0;
+    SG_HIP(hipMemcpyAsync(&E64, p.eoff + N, 8, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipMemcpyAsync(&flag, &p.misc->flag, 4, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (flag & 1) return sg::fail(SG_EINVAL, "%s: a coordinate is not finite", who);
+    if (flag & (4 | 8)) return sg::fail(SG_EINTERNAL, "%s: the lists do not hold together (flag %d)", who, flag);
+    if (E64 * 2 != T) return sg::fail(SG_EINTERNAL, "%s: %lld upper entries in rows of %lld", who, (long long)E64, (long long)T);
+    const int E = (int)E64;                                  // T <= SG_MAX_RADIUS_PAIRS = 2^30: E <= 2^29
+    if (E > 0) k_pc_edges_csr<<<sg::cdiv(N, kBlock / 64), kBlock, 0, st>>>(off, idx, N, p.eoff, E64, p.adj);
+    clock.tick();
+    if (E == 0) { SG_LAUNCH_CHECK(); return SG_OK; }
+    k_pc_weights<<<sg::cdiv(E, kBlock), kBlock, 0, st>>>(p.adj, E, p.cand, d_normals, p.w, p.k0, p.v0);
+    clock.tick();
+    const int* order = sgos::sort_by_weight(p.k0, p.k1, p.v0, p.v1, p.hist, E, st);
+    clock.tick();
+    sgos::gather_edges(order, E, p.adj, p.w, d_edges, d_w, st);
+    clock.tick();
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    *h_E = E;
+    return SG_OK;
+}
+
+int pcseg_scan_radius(const char* who, const float* d_xyz, int N, float radius, float cell, int64_t capacity, const float* h_viewpoint,
+                      float k_thresh, int seg_min_verts, int32_t* h_seg_indices, int64_t* h_T, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!(d_xyz && h_seg_indices && h_T && d_ws)) return sg::fail(SG_EINVAL, "%s: a null pointer", who);
+    const RPlan p = carve_radius(d_ws, ws_bytes, std::max(N, 1), std::max<int64_t>(std::min<int64_t>(capacity, SG_MAX_RADIUS_PAIRS), 0));
+    if (N >= 1 && N <= SG_MAX_GRID_POINTS && capacity >= 0 && capacity <= SG_MAX_RADIUS_PAIRS && !p.ok)
+        return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, pcseg_ws_bytes_radius(N, capacity));
+    int E = 0;
+    const int rc = pcseg_edges_radius(who, d_xyz, N, radius, cell, capacity, h_viewpoint, nullptr, nullptr, p.vn, p.edges, p.w_sorted, &E, h_T,
+                                      d_ws, ws_bytes, stream);
+    if (rc < 0) return rc;
+    std::vector<int32_t> h_edges((size_t)E * 2);
+    std::vector<float> h_w((size_t)E);
+    if (E > 0) {
+        hipStream_t st = sg::as_stream(stream);
+        SG_HIP(hipMemcpyAsync(h_edges.data(), p.edges, (size_t)E * 8, hipMemcpyDeviceToHost, st));
+        SG_HIP(hipMemcpyAsync(h_w.data(), p.w_sorted, (size_t)E * 4, hipMemcpyDeviceToHost, st));
+        SG_HIP(hipStreamSynchronize(st));
+    }
+    return sg_overseg_merge(h_edges.data(), h_w.data(), E, N, k_thresh, seg_min_verts, h_seg_indices);
+}
+
 }  // namespace
 
 extern "C" {
@@ -488,6 +692,65 @@ int sg_pcseg_scan_indexed(const float* d_xyz, int N, int k, const float* h_viewp
                           int32_t* h_seg_indices, void* d_ws, size_t ws_bytes, void* stream) {
     return pcseg_scan("sg_pcseg_scan_indexed", d_xyz, N, k, h_viewpoint, index, cell, k_thresh, seg_min_verts, h_seg_indices, d_ws, ws_bytes,
                       stream);
+}
+
+int sg_pointcloud_normals_csr(const float* d_xyz, int N, const int64_t* d_off, const int32_t* d_idx, const float* h_viewpoint, float* d_normals,
+                              void* d_ws, size_t ws_bytes, void* stream) {
+    const char* who = "sg_pointcloud_normals_csr";
+    SG_REQUIRE(d_xyz && N > 0 && d_off && d_normals && d_ws, "%s: bad arguments", who);
+    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
+    const int rc = viewpoint_ok(who, h_viewpoint);
+    if (rc < 0) return rc;
+    sg::Carver cv(d_ws, ws_bytes);
+    float4* cand = cv.take<float4>(N);
+    Misc* misc = cv.take<Misc>(1);
+    if (!cv.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_pointcloud_knn_ws_bytes(N));
+    hipStream_t st = sg::as_stream(stream);
+    k_pc_init<<<1, 1, 0, st>>>(misc, h_viewpoint != nullptr, h_viewpoint ? h_viewpoint[0] : 0.0f, h_viewpoint ? h_viewpoint[1] : 0.0f,
+                               h_viewpoint ? h_viewpoint[2] : 0.0f);
+    k_pc_pack<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(d_xyz, 3, N, cand, misc);
+    if (!h_viewpoint) k_pc_view<<<1, 1, 0, st>>>(misc);
+    // d_idx may be null only where every row is empty; a row that is not then fails the check of its offsets against off[N]
+    k_pc_normals_csr<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(cand, N, d_off, d_idx, misc, d_normals);
+    int flag = 0;
+    SG_HIP(hipMemcpyAsync(&flag, &misc->flag, 4, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (flag & 1) return sg::fail(SG_EINVAL, "%s: a coordinate is not finite", who);
+    if (flag & 8) return sg::fail(SG_EINVAL, "%s: the offsets of the rows do not ascend from 0 to off[N]", who);
+    if (flag & 4) return sg::fail(SG_EINVAL, "%s: a row names a point outside 0..%d", who, N - 1);
+    return SG_OK;
+}
+
+size_t sg_pcseg_ws_bytes_radius(int N, int64_t T) {
+    if (N < 1 || N > SG_MAX_GRID_POINTS || T < 0 || T > SG_MAX_RADIUS_PAIRS) return 0;
+    return pcseg_ws_bytes_radius(N, T);
+}
+
+int sg_pcseg_edges_radius(const float* d_xyz, int N, float radius, float cell, int64_t capacity, const float* h_viewpoint, int64_t* d_off,
+                          int32_t* d_idx, float* d_normals, int32_t* d_edges, float* d_w, int* h_E, int64_t* h_T, void* d_ws, size_t ws_bytes,
+                          void* stream) {
+    return pcseg_edges_radius("sg_pcseg_edges_radius", d_xyz, N, radius, cell, capacity, h_viewpoint, d_off, d_idx, d_normals, d_edges, d_w, h_E,
+                              h_T, d_ws, ws_bytes, stream);
+}
+
+int sg_pcseg_scan_radius(const float* d_xyz, int N, float radius, float cell, int64_t capacity, const float* h_viewpoint, float k_thresh,
+                         int seg_min_verts, int32_t* h_seg_indices, int64_t* h_T, void* d_ws, size_t ws_bytes, void* stream) {
+    return pcseg_scan_radius("sg_pcseg_scan_radius", d_xyz, N, radius, cell, capacity, h_viewpoint, k_thresh, seg_min_verts, h_seg_indices, h_T,
+                             d_ws, ws_bytes, stream);
+}
+
+int sg_pcseg_radius_set_timing(int on) { t_rtiming = on != 0; return SG_OK; }
+
+int sg_pcseg_radius_stage_times(float* h_us, int cap) {
+    SG_REQUIRE(h_us && cap >= kRStages, "sg_pcseg_radius_stage_times: room for %d floats is needed", kRStages);
+    for (int i = 0; i < kRStages; ++i) h_us[i] = t_rstage_us[i];
+    return kRStages;
+}
+
+const char* sg_pcseg_radius_stage_name(int i) {
+    if (i >= 0 && i < kListStages) return sg::radius_lists_stage_name(i);
+    return i >= kListStages && i < kRStages ? kOwnStageNames[i - kListStages] : nullptr;
 }
 
 }  // extern "C"

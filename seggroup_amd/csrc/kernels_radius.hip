@@ -16,12 +16,16 @@
 //   Hook      for a passing pair with original j > i (each edge once) and equal labels: 8j's hook (components_device.h) on the parent
 //             array; k_cc_init before, k_cc_flatten and k_cc_sizes after, as they are.  The hooks run inside a divergent wave loop; no lane
 //             waits for another, and the step budget bounds every lane's loop.
+//   List      DESIGN.md 8l, sg_radius_neighbours_grid: the pairs written down in CSR form.  Count, a 64-bit exclusive scan (scan64_device.h),
+//             T read back, the same search again with the n-th passing pair of i stored at raw[off[i] + n], then k_rn_rows puts every row
+//             into ascending index (a rank sort, one wave per row) -- the stored order does not depend on the cell edge
 #include <cmath>
 #include <cstring>
 
 #include "sg_common.h"
 #include "grid_index_device.h"
 #include "components_device.h"
+#include "scan64_device.h"
 
 namespace {
 
@@ -41,7 +45,7 @@ __global__ void k_radius_init(Tally* __restrict__ t) { t->evals = 0ull; t->passe
 
 struct CountVisitor {
     int32_t* count;
-    __device__ __forceinline__ void pair(int, int) const {}
+    __device__ __forceinline__ void pair(int, int, int) const {}
     __device__ __forceinline__ void finish(int i, int n) const { count[i] = n; }
 };
 
@@ -50,9 +54,17 @@ struct HookVisitor {
     const int32_t* label;
     sgcc::Misc* misc;
     int V;
-    __device__ __forceinline__ void pair(int i, int j) const {
+    __device__ __forceinline__ void pair(int i, int j, int) const {
         if (j > i && (!label || label[i] == label[j])) sgcc::hook(parent, i, j, V, misc);
     }
+    __device__ __forceinline__ void finish(int, int) const {}
+};
+
+// the n-th passing pair of i goes to the n-th place of i's row, in search order (k_rn_rows orders the row afterwards)
+struct ListVisitor {
+    const int64_t* off;
+    int32_t* idx;
+    __device__ __forceinline__ void pair(int i, int j, int n) const { idx[off[i] + n] = j; }
     __device__ __forceinline__ void finish(int, int) const {}
 };
 
@@ -101,8 +113,8 @@ __global__ __launch_bounds__(kWave) void k_radius_search(const float4* __restric
                             const float d0 = c.x - me.x, d1 = c.y - me.y, d2 = c.z - me.z;
                             const float dd = (d0 * d0 + d1 * d1) + d2 * d2;
                             if (j != orig && dd <= r2) {
+                                vis.pair(orig, j, passed);
                                 ++passed;
-                                vis.pair(orig, j);
                             }
                         }
                         evals += (unsigned int)n;
@@ -118,6 +130,37 @@ __global__ __launch_bounds__(kWave) void k_radius_search(const float4* __restric
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) { e += __shfl_xor(e, off); p += __shfl_xor(p, off); }
         if (lane == 0) { atomicAdd(&tally->evals, e); atomicAdd(&tally->passed, p); }
+    }
+}
+
+
+// ---- the neighbour lists: off = the exclusive sum of count in 64 bits, the rows filled in search order, then ordered ----
+constexpr int kRowBlock = 256;                              // k_rn_rows: four rows per block, one wave each
+
+// One wave per row: raw[off[i] .. off[i+1]) in search order -> idx, the same entries in ascending index.  The entries of a row are
+// distinct, so an entry's place is the number of entries below it: the wave holds 64 of its own entries and passes the row by in chunks
+// of 64, each lane's chunk entry read across the wave.  A rank is below the row's length whatever the row holds: nothing is written
+// outside the row.  The work of a row is its length squared / 64 (the envelope).
+__global__ __launch_bounds__(kRowBlock) void k_rn_rows(const int64_t* __restrict__ off, const int32_t* __restrict__ raw, int N,
+                                                       int32_t* __restrict__ idx) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * (kRowBlock / 64) + (threadIdx.x >> 6);
+    if (i >= N) return;                                      // whole waves leave; there is no barrier below
+    const int64_t lo = off[i];
+    const int64_t len = off[i + 1] - lo;
+    const int32_t* __restrict__ row = raw + lo;
+    int32_t* __restrict__ out = idx + lo;
+    const int top = 0x7fffffff;                              // never below an entry
+    for (int64_t e0 = 0; e0 < len; e0 += 64) {
+        const bool mine_live = e0 + lane < len;
+        const int mine = mine_live ? row[e0 + lane] : top;
+        int64_t rank = 0;
+        for (int64_t c0 = 0; c0 < len; c0 += 64) {
+            const int c = c0 + lane < len ? row[c0 + lane] : top;
+#pragma unroll
+            for (int u = 0; u < 64; ++u) rank += __builtin_amdgcn_readlane(c, u) < mine ? 1 : 0;
+        }
+        if (mine_live) out[rank] = mine;
     }
 }
 
@@ -169,8 +212,9 @@ struct Index {
 };
 
 // box, cells, sort, table: the grid kNN's stages with the cell edge decided by the radius.  Synchronises the stream once (the box).
-int build_index(const char* who, const float* d_points, int stride, int N, float radius, float r2, float cell, const Plan& p,
-                sgos::StageClock<kStages>& clock, hipStream_t st, Index* out) {
+template <class Clock>
+int build_index(const char* who, const float* d_points, int stride, int N, float radius, float r2, float cell, const Plan& p, Clock& clock,
+                hipStream_t st, Index* out) {
     const sggrid::Plan& gp = p.grid;
     const int nb = sg::cdiv(N, sggrid::kBlock);
     sggrid::k_grid_init<<<1, 1, 0, st>>>(gp.misc);
@@ -256,9 +300,94 @@ int check_args(const char* who, const float* d_points, int stride, int N, float 
     return SG_OK;
 }
 
+// the lists' own stages (sg_pcseg_edges_radius reports them in front of its own)
+constexpr int kListStages = 8;
+const char* const kListStageNames[kListStages] = {"box", "cells", "sort", "table", "count", "scan", "fill", "rows"};
+thread_local bool t_list_timing = false;
+thread_local float t_list_us[kListStages];
+
+size_t lists_ws_bytes(int N, long long capacity) {
+    return sg_radius_grid_ws_bytes(N) + sg::align_up(((size_t)sgscan::tiles_of(N) + 1) * 8) + sg::align_up((size_t)capacity * 4);
+}
+
+const char* const kPairsWayOut = "take a smaller radius, or thin the cloud first";
+
 }  // namespace
 
+namespace sg {
+void radius_lists_timing(bool on) { t_list_timing = on; }
+const float* radius_lists_stage_us() { return t_list_us; }
+const char* radius_lists_stage_name(int i) { return i >= 0 && i < kListStages ? kListStageNames[i] : nullptr; }
+
+int radius_lists(const char* who, const float* d_points, int stride, int N, float radius, float cell, int64_t capacity, int64_t* d_off,
+                 int32_t* d_idx, int64_t* h_T, void* d_ws, size_t ws_bytes, void* stream) {
+    for (int i = 0; i < kNumStats; ++i) t_ses.stats[i] = 0;
+    SG_REQUIRE(h_T, "%s: a null pointer", who);
+    *h_T = 0;
+    float r2 = 0.0f;
+    if (const int rc = check_args(who, d_points, stride, N, radius, cell, d_off, d_ws, ws_bytes, &r2)) return rc;
+    SG_REQUIRE(capacity >= 0 && (capacity == 0 || d_idx), "%s: room for %lld pairs at a null pointer", who, (long long)capacity);
+    if (capacity > SG_MAX_RADIUS_PAIRS)
+        return sg::fail(SG_EUNSUP, "%s: room for %lld pairs; the lists hold at most %lld: %s", who, (long long)capacity,
+                        (long long)SG_MAX_RADIUS_PAIRS, kPairsWayOut);
+    if (ws_bytes < lists_ws_bytes(N, capacity))
+        return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, lists_ws_bytes(N, capacity));
+    const Plan p = carve(d_ws, ws_bytes, N);
+    const size_t base = sg_radius_grid_ws_bytes(N);
+    sg::Carver cv((char*)d_ws + base, ws_bytes - base);
+    const int nt = sgscan::tiles_of(N);
+    long long* tsum = cv.take<long long>((size_t)nt + 1);
+    int32_t* raw = cv.take<int32_t>((size_t)capacity);
+    if (!p.ok || !cv.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, lists_ws_bytes(N, capacity));
+    hipStream_t st = sg::as_stream(stream);
+    const int counting = t_list_timing ? 1 : 0;
+    sgos::StageClock<kListStages> clock(st, t_list_timing, t_list_us);
+    Index ix{};
+    if (const int rc = build_index(who, d_points, stride, N, radius, r2, cell, p, clock, st, &ix)) return rc;
+    k_radius_search<CountVisitor><<<sg::cdiv(N, kWave), kWave, 0, st>>>(p.grid.spts, ix.sidx, ix.skey, p.grid.start, ix.g, N, r2,
+                                                                       CountVisitor{p.count}, p.tally, counting);
+    clock.tick();
+    sgscan::exclusive_scan64(p.count, N, tsum, d_off, st);
+    int64_t T = 0;
+    sggrid::Misc hm{};
+    Tally ht{};
+    SG_HIP(hipMemcpyAsync(&T, d_off + N, 8, hipMemcpyDeviceToHost, st));
+    SG_HIP(hipMemcpyAsync(&hm, p.grid.misc, sizeof(hm), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipMemcpyAsync(&ht, p.tally, sizeof(ht), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    clock.tick();
+    SG_LAUNCH_CHECK();
+    if (T < 0 || T > (int64_t)N * (N - 1)) return sg::fail(SG_EINTERNAL, "%s: %lld pairs from %d points", who, (long long)T, N);
+    *h_T = T;
+    leave_stats(ix.g, hm, ht);
+    if (T > SG_MAX_RADIUS_PAIRS)
+        return sg::fail(SG_EUNSUP, "%s: %lld pairs; the lists hold at most %lld: %s", who, (long long)T, (long long)SG_MAX_RADIUS_PAIRS,
+                        kPairsWayOut);
+    if (T > capacity) return sg::fail(SG_ENOMEM, "%s: %lld pairs; the caller's lists hold %lld", who, (long long)T, (long long)capacity);
+    if (T > 0) {
+        k_radius_search<ListVisitor><<<sg::cdiv(N, kWave), kWave, 0, st>>>(p.grid.spts, ix.sidx, ix.skey, p.grid.start, ix.g, N, r2,
+                                                                          ListVisitor{d_off, raw}, p.tally, 0);
+        clock.tick();
+        k_rn_rows<<<sg::cdiv(N, kRowBlock / 64), kRowBlock, 0, st>>>(d_off, raw, N, d_idx);
+        clock.tick();
+    }
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    return SG_OK;
+}
+}  // namespace sg
+
 extern "C" {
+
+size_t sg_radius_neighbours_ws_bytes(int N, int64_t capacity) {
+    if (N < 1 || N > SG_MAX_GRID_POINTS || capacity < 0 || capacity > SG_MAX_RADIUS_PAIRS) return 0;
+    return lists_ws_bytes(N, capacity);
+}
+
+int sg_radius_neighbours_grid(const float* d_points, int stride, int N, float radius, float cell, int64_t capacity, int64_t* d_off,
+                              int32_t* d_idx, int64_t* h_T, void* d_ws, size_t ws_bytes, void* stream) {
+    return sg::radius_lists("sg_radius_neighbours_grid", d_points, stride, N, radius, cell, capacity, d_off, d_idx, h_T, d_ws, ws_bytes, stream);
+}
 
 int sg_radius_grid_set_timing(int on) { t_ses.timing = on != 0; return SG_OK; }
 

@@ -120,6 +120,14 @@ struct SdmaTicket { unsigned long long signal = 0; };
 int sdma_issue(void* dst, const void* src, size_t bytes, SdmaTicket* t);     // one copy, either direction between device and pinned host memory
 int sdma_wait(SdmaTicket* t);
 
+// the radius lists for callers inside the library (kernels_radius.hip): sg_radius_neighbours_grid under the caller's name; with timing on,
+// the calling thread's next call leaves its eight stage times (box .. rows) in radius_lists_stage_us()
+int radius_lists(const char* who, const float* d_points, int stride, int N, float radius, float cell, int64_t capacity, int64_t* d_off,
+                 int32_t* d_idx, int64_t* h_T, void* d_ws, size_t ws_bytes, void* stream);
+void radius_lists_timing(bool on);
+const float* radius_lists_stage_us();
+const char* radius_lists_stage_name(int i);
+
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 

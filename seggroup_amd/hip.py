@@ -26,6 +26,7 @@ KNN_INDEX = {"brute": KNN_BRUTE, "grid": KNN_GRID}
 MAX_GRID_POINTS = 1 << 24
 MAX_POINTS = 1 << 20
 MAX_CLOUD_POINTS = 1 << 27
+MAX_RADIUS_PAIRS = 1 << 30
 
 
 def knn_index(index) -> int:
@@ -180,6 +181,16 @@ SIGNATURES = {
     "sg_radius_grid_stage_times": (_I, [vp, _I]),
     "sg_radius_grid_stage_name": (C.c_char_p, [_I]),
     "sg_radius_grid_stats": (_I, [vp, _I]),
+    "sg_radius_neighbours_ws_bytes": (_Z, [_I, C.c_int64]),
+    "sg_radius_neighbours_grid": (_I, [vp, _I, _I, C.c_float, C.c_float, C.c_int64, vp, vp, C.POINTER(C.c_int64), vp, _Z, vp]),
+    "sg_pointcloud_normals_csr": (_I, [vp, _I, vp, vp, vp, vp, vp, _Z, vp]),
+    "sg_pcseg_ws_bytes_radius": (_Z, [_I, C.c_int64]),
+    "sg_pcseg_edges_radius": (_I, [vp, _I, C.c_float, C.c_float, C.c_int64, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int64),
+                                   vp, _Z, vp]),
+    "sg_pcseg_scan_radius": (_I, [vp, _I, C.c_float, C.c_float, C.c_int64, vp, C.c_float, _I, vp, C.POINTER(C.c_int64), vp, _Z, vp]),
+    "sg_pcseg_radius_set_timing": (_I, [_I]),
+    "sg_pcseg_radius_stage_times": (_I, [vp, _I]),
+    "sg_pcseg_radius_stage_name": (C.c_char_p, [_I]),
     "sg_segment_vote_ws_bytes": (_Z, [_I]),
     "sg_segment_rank": (_I, [vp, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_segment_vote": (_I, [vp, vp, _I, _I] + [vp] * 9 + [C.POINTER(C.c_int), vp, _Z, vp]),

@@ -21,7 +21,11 @@ every pair: the same lists bit for bit, hence the same segs.json, in a fraction 
 cloud is thinned first and the grid works on the representatives.
 
     python -m seggroup_amd.oversegment --scans DIR [--scenes LIST] [--k-thresh 0.01] [--seg-min-verts 20] [--force] [--workers 4]
-                                       [--pointcloud] [--knn {5,10,20}] [--viewpoint X Y Z] [--voxel H] [--index {brute,grid}]
+                                       [--pointcloud] [--knn {5,10,20}] [--viewpoint X Y Z] [--voxel H] [--index {brute,grid}] [--radius R]
+
+`radius=R` / `--radius R` (a scan without faces, or `--pointcloud`; instead of `--knn` and `--index`): the graph is the radius graph of
+the points, every pair at most R apart, and the normals are taken over those neighbourhoods -- for clouds that hold more than
+k points inside the neighbourhood scale, where the kNN graph has no edge out of a clump.
 """
 from __future__ import annotations
 
@@ -157,13 +161,77 @@ def knn_grid_stats() -> dict:
                 cell=float(np.array([h[5]], dtype=np.uint32).view(np.float32)[0]), max_ring=int(h[6]), fallback=int(h[7]), scores=int(h[8]))
 
 
-def pointcloud_edges(xyz, k: int = 10, viewpoint=None, device=None, stream=None, index: str = "brute", cell=None):
+def _radius_only(who, radius, k=10, index="brute", knn=None):
+    """`radius` selects the radius graph in place of the kNN graph: it goes with neither a neighbour count, nor a kNN index,
+    nor a caller's kNN table.  -> the radius as a float, or None"""
+    if radius is None:
+        return None
+    if int(k) != 10:
+        raise ValueError(f"{who}: radius and k = {int(k)} are two different graphs; give one")
+    if index != "brute":
+        raise ValueError(f"{who}: radius and index = {index!r} are two different graphs (the radius graph has its own grid); give one")
+    if knn is not None:
+        raise ValueError(f"{who}: radius and a kNN table are two different graphs; give one")
+    import math
+    r = float(radius)
+    if not (r > 0.0 and math.isfinite(r)):
+        raise ValueError(f"{who}: radius must be a finite length > 0, not {radius!r}")
+    return r
+
+
+def _query_pairs(lib, d_xyz, n, r, edge, dev, stream):
+    """-> T, the number of (ordered) pairs of the radius graph: the query form of sg_radius_neighbours_grid"""
+    import torch
+    from .prepare import _ws
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    total = C.c_int64(0)
+    ws = _ws(lib.sg_radius_neighbours_ws_bytes(n, 0), dev)
+    if ws.numel() == 0:                                        # outside the envelope: refused before anything is touched
+        hip.check(lib.sg_radius_neighbours_grid(None, 3, n, r, edge, 0, None, None, C.byref(total), None, 0, None))
+    rc = lib.sg_radius_neighbours_grid(d_xyz.data_ptr(), 3, n, r, edge, 0, off.data_ptr(), None, C.byref(total), ws.data_ptr(), ws.numel(),
+                                       _stream_ptr(stream))
+    if rc != hip.SG_ENOMEM or total.value <= 0:
+        hip.check(rc)
+    return int(total.value)
+
+
+def _pointcloud_edges_radius(xyz, r, viewpoint, device, stream, cell):
+    import torch
+    from .prepare import _dev, _ws
+    edge = hip.knn_cell(cell)
+    dev = _dev(device)
+    lib = hip.lib()
+    with torch.cuda.device(dev), _on(stream):
+        d_xyz, n = _cloud_tensor(xyz, dev)
+        t = _query_pairs(lib, d_xyz, n, r, edge, dev, stream)
+        indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        indices = torch.empty(max(t, 1), dtype=torch.int32, device=dev)
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        edges = torch.empty((max(t // 2, 1), 2), dtype=torch.int32, device=dev)
+        w = torch.empty(max(t // 2, 1), dtype=torch.float32, device=dev)
+        n_e, total = C.c_int(0), C.c_int64(0)
+        ws = _ws(lib.sg_pcseg_ws_bytes_radius(n, t), dev)
+        hip.check(lib.sg_pcseg_edges_radius(d_xyz.data_ptr(), n, r, edge, t, _viewpoint(viewpoint), indptr.data_ptr(), indices.data_ptr(),
+                                            nrm.data_ptr(), edges.data_ptr(), w.data_ptr(), C.byref(n_e), C.byref(total), ws.data_ptr(),
+                                            ws.numel(), _stream_ptr(stream)))
+        (stream.synchronize() if stream is not None else torch.cuda.synchronize())
+    return dict(indptr=indptr, indices=indices[:t], normals=nrm, edges=edges[:n_e.value], w=w[:n_e.value])
+
+
+def pointcloud_edges(xyz, k: int = 10, viewpoint=None, device=None, stream=None, index: str = "brute", cell=None, radius=None):
     """The device stages of one cloud -> dict(knn [N,k+1] i32, normals [N,3], edges [E,2] i32, w [E]) of device tensors:
     every point's k + 1 best-scoring points, the covariance normals turned towards the viewpoint (default: the centre of the bounding
     box), and the unique undirected kNN pairs a < b in ascending (w, a, b).  `index="grid"`: the lists come from the exact grid index
-    (`cell` forces its cell edge) -- the same bytes, up to 2^24 points."""
+    (`cell` forces its cell edge) -- the same bytes, up to 2^24 points.
+
+    `radius=R` (instead of `k` and `index`): the radius graph -> dict(indptr int64 [N+1], indices int32 [T], normals,
+    edges, w): every point's neighbours within R in ascending index, the normals over those neighbourhoods, the pairs a < b of the
+    graph in ascending (w, a, b).  `cell` forces the grid's cell edge and cannot change a byte."""
     import torch
     from .prepare import _dev, _ws
+    r = _radius_only("pointcloud_edges", radius, k, index)
+    if r is not None:
+        return _pointcloud_edges_radius(xyz, r, viewpoint, device, stream, cell)
     which, edge = hip.knn_index(index), hip.knn_cell(cell)
     dev = _dev(device)
     lib = hip.lib()
@@ -190,16 +258,37 @@ def pointcloud_edges(xyz, k: int = 10, viewpoint=None, device=None, stream=None,
     return dict(knn=knn, normals=nrm, edges=edges[:n_e.value], w=w[:n_e.value])
 
 
-def pointcloud_normals(xyz, k: int = 10, viewpoint=None, knn=None, device=None):
+def pointcloud_normals(xyz, k: int = 10, viewpoint=None, knn=None, device=None, radius=None, lists=None):
     """-> [N,3] f32 device tensor: per point the eigenvector of the smallest eigenvalue of its k + 1 nearest points' covariance, not
-    re-normalised, turned towards the viewpoint.  `knn`: a table of `prepare.pointcloud_knn` (made when not given)."""
+    re-normalised, turned towards the viewpoint.  `knn`: a table of `prepare.pointcloud_knn` (made when not given).
+
+    `radius=R` (instead of `k` and `knn`): the neighbourhood of a point is the point and every other point within R.
+    `lists=(indptr, indices)`: a caller's rows in place of `components.radius_neighbours(xyz, R)`; they are checked on the device."""
     import torch
     from .prepare import _dev, _t, _ws, pointcloud_knn
+    r = _radius_only("pointcloud_normals", radius, k, "brute", knn)
+    if lists is not None and r is None:
+        raise ValueError("pointcloud_normals: lists belong to the radius form")
     dev = _dev(device)
     lib = hip.lib()
     k = int(k)
     with torch.cuda.device(dev):
         d_xyz, n = _cloud_tensor(xyz, dev)
+        if r is not None:
+            if lists is None:
+                from .components import radius_neighbours
+                lists = radius_neighbours(d_xyz, r, device=dev)
+            indptr, indices = _t(lists[0], torch.int64, dev), _t(lists[1], torch.int32, dev)
+            if indptr.dim() != 1 or indptr.shape[0] != n + 1 or indices.dim() != 1:
+                raise ValueError("pointcloud_normals: lists are (indptr [N + 1], indices [T])")
+            if int(indptr[-1]) != indices.shape[0]:
+                raise ValueError("pointcloud_normals: indptr[N] = %d, and indices holds %d entries" % (int(indptr[-1]), indices.shape[0]))
+            nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            ws = _ws(lib.sg_pointcloud_knn_ws_bytes(n), dev)
+            hip.check(lib.sg_pointcloud_normals_csr(d_xyz.data_ptr(), n, indptr.data_ptr(), indices.data_ptr() if indices.numel() else None,
+                                                    _viewpoint(viewpoint), nrm.data_ptr(), ws.data_ptr(), ws.numel(), None))
+            torch.cuda.synchronize()
+            return nrm
         table = pointcloud_knn(d_xyz, k, device=dev) if knn is None else _t(knn, torch.int32, dev)
         if table.dim() != 2 or tuple(table.shape) != (n, k + 1):
             raise ValueError("pointcloud_normals: knn must be [N, k+1]")
@@ -212,7 +301,7 @@ def pointcloud_normals(xyz, k: int = 10, viewpoint=None, knn=None, device=None):
 
 
 def segment_pointcloud(xyz, k: int = 10, k_thresh: float = 0.01, seg_min_verts: int = 20, viewpoint=None, device=None,
-                       stream=None, voxel: Optional[float] = None, index: str = "brute", cell=None) -> np.ndarray:
+                       stream=None, voxel: Optional[float] = None, index: str = "brute", cell=None, radius=None) -> np.ndarray:
     """-> int32 [N]: seg_indices[i] = the lowest point index of i's segment, for a cloud without faces.
 
     `voxel`: thin the cloud on a grid of that edge first and segment the representatives with the same parameters -- the
@@ -221,9 +310,14 @@ def segment_pointcloud(xyz, k: int = 10, k_thresh: float = 0.01, seg_min_verts: 
     That is how a cloud above 2^20 points is segmented; a grid that leaves every point alone gives the un-thinned ids.
 
     `index="grid"`: the neighbour lists come from the exact grid index (`cell` forces its cell edge): the same ids, and a
-    cloud of up to 2^24 points is segmented at full resolution.  With `voxel` the grid works on the representatives."""
+    cloud of up to 2^24 points is segmented at full resolution.  With `voxel` the grid works on the representatives.
+
+    `radius=R` (instead of `k` and `index`): the graph is the radius graph -- every pair of points at most R apart, the
+    normals over those neighbourhoods.  That is the graph for a cloud with more than k points inside the neighbourhood scale (near the
+    scanner, overlapping sweeps, an unthinned cloud), where the kNN graph has no edge out of a clump.  `voxel` combines as with kNN."""
     import torch
     from .prepare import _dev, _ws
+    r = _radius_only("segment_pointcloud", radius, k, index)
     which, edge = hip.knn_index(index), hip.knn_cell(cell)
     dev = _dev(device)
     lib = hip.lib()
@@ -235,13 +329,20 @@ def segment_pointcloud(xyz, k: int = 10, k_thresh: float = 0.01, seg_min_verts: 
         rep, top, _ = thin_cloud(d_all, voxel, device=dev, stream=stream)
         with torch.cuda.device(dev), _on(stream):
             d_thin = d_all.index_select(0, rep.long())
-        seg_thin = segment_pointcloud(d_thin, k, k_thresh, seg_min_verts, viewpoint=viewpoint, device=dev, stream=stream, index=index, cell=cell)
+        seg_thin = segment_pointcloud(d_thin, k, k_thresh, seg_min_verts, viewpoint=viewpoint, device=dev, stream=stream, index=index, cell=cell,
+                                      radius=radius)
         rep_h = rep.cpu().numpy()
         return np.ascontiguousarray(rep_h[seg_thin[top.cpu().numpy()]], dtype=np.int32)
     with torch.cuda.device(dev), _on(stream):
         d_xyz, n = _cloud_tensor(xyz, dev)
         out = np.empty(n, dtype=np.int32)
-        if which == hip.KNN_GRID:
+        if r is not None:
+            t = _query_pairs(lib, d_xyz, n, r, edge, dev, stream)
+            total = C.c_int64(0)
+            ws = _ws(lib.sg_pcseg_ws_bytes_radius(n, t), dev)
+            hip.check(lib.sg_pcseg_scan_radius(d_xyz.data_ptr(), n, r, edge, t, _viewpoint(viewpoint), float(k_thresh), int(seg_min_verts),
+                                               out.ctypes.data, C.byref(total), ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+        elif which == hip.KNN_GRID:
             if n > hip.MAX_GRID_POINTS or lib.sg_pcseg_ws_bytes_indexed(n, k, which) == 0:      # refused before anything is allocated
                 hip.check(lib.sg_pointcloud_knn_grid(None, 3, n, k, edge, None, None, 0, None))
             ws = _ws(lib.sg_pcseg_ws_bytes_indexed(n, k, which), dev)
@@ -262,14 +363,16 @@ def write_segs_json(path: str, seg_indices, scene_id: str, k_thresh: float = 0.0
 
 def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int = 20, force: bool = False, device=None, stream=None,
                      plydata=None, pointcloud: bool = False, knn: int = 10, viewpoint=None, voxel: Optional[float] = None,
-                     index: str = "brute") -> Optional[str]:
+                     index: str = "brute", radius=None) -> Optional[str]:
     """Writes the scan's segs.json next to its mesh; -> the path, or None when the file was there already (never overwritten without
     `force`).  A scan without faces is segmented as a point cloud (`knn` neighbours, normals towards `viewpoint`); `pointcloud=True`
     does the same to a mesh, ignoring its faces.  `voxel`: the point-cloud path thins on that grid first (`segment_pointcloud`); on the
     mesh path it is an error, not ignored.  `index`: "brute" or "grid", the point-cloud path's neighbour search; on
-    the mesh path "grid" is an error as well."""
+    the mesh path "grid" is an error as well.  `radius`: the point-cloud path's graph is the radius graph instead of the
+    kNN graph; not with a non-default `knn` or `index`, and on the mesh path an error."""
     from .prepare import _scene_name, mesh_arrays, read_ply
     hip.knn_index(index)
+    _radius_only("oversegment_scan", radius, knn, index)
     name = _scene_name(scene_path)
     out = os.path.join(scene_path, segs_json_name(name, k_thresh))
     if os.path.exists(out) and not force:
@@ -278,7 +381,10 @@ def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int
         plydata = read_ply(os.path.join(scene_path, name + "_vh_clean_2.ply"))
     xyz, _, faces = mesh_arrays(plydata)
     if pointcloud or faces.shape[0] == 0:
-        seg = segment_pointcloud(xyz, knn, k_thresh, seg_min_verts, viewpoint=viewpoint, device=device, stream=stream, voxel=voxel, index=index)
+        seg = segment_pointcloud(xyz, knn, k_thresh, seg_min_verts, viewpoint=viewpoint, device=device, stream=stream, voxel=voxel, index=index,
+                                 radius=radius)
+    elif radius is not None:
+        raise ValueError(f"{name}: the radius graph belongs to the point-cloud path; this scan is a mesh (pass pointcloud=True to ignore its faces)")
     elif voxel is not None:
         raise ValueError(f"{name}: voxel thinning belongs to the point-cloud path; this scan is a mesh (pass pointcloud=True to ignore its faces)")
     elif index != "brute":
@@ -290,7 +396,8 @@ def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int
 
 
 def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_min_verts: int = 20, force: bool = False, workers: int = 4,
-                      device=None, pointcloud: bool = False, knn: int = 10, viewpoint=None, voxel: Optional[float] = None, index: str = "brute"):
+                      device=None, pointcloud: bool = False, knn: int = 10, viewpoint=None, voxel: Optional[float] = None, index: str = "brute",
+                      radius=None):
     """Every scan directory under `scans_dir` (or the named ones) -> (written paths, skipped scene names).  Workers are threads, each
     with its own stream and workspace: the host chain of one scan overlaps the device work of the next."""
     import concurrent.futures
@@ -299,6 +406,7 @@ def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_m
     import torch
     from .prepare import _dev
     hip.knn_index(index)
+    _radius_only("oversegment_scans", radius, knn, index)
     dev = _dev(device)
     if scenes is None:
         scenes = sorted(d for d in os.listdir(scans_dir) if os.path.exists(os.path.join(scans_dir, d, d + "_vh_clean_2.ply")))
@@ -310,7 +418,7 @@ def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_m
             with torch.cuda.device(dev):
                 local.stream = torch.cuda.Stream(device=dev)
         return scene, oversegment_scan(os.path.join(scans_dir, scene), k_thresh, seg_min_verts, force, device=dev, stream=local.stream,
-                                       pointcloud=pointcloud, knn=knn, viewpoint=viewpoint, voxel=voxel, index=index)
+                                       pointcloud=pointcloud, knn=knn, viewpoint=viewpoint, voxel=voxel, index=index, radius=radius)
 
     written, skipped = [], []
     with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
@@ -348,22 +456,36 @@ def main(argv=None) -> int:
                     help="the point-cloud path thins the cloud on a voxel grid of this edge first (needed above 2^20 points)")
     ap.add_argument("--index", default="brute", choices=("brute", "grid"),
                     help="neighbour search of the point-cloud path: every pair, or the exact grid index (the same lists; up to 2^24 points)")
+    ap.add_argument("--radius", type=float, default=None, metavar="R",
+                    help="the point-cloud path segments over the radius graph (every pair of points at most R apart) instead of the kNN graph")
     a = ap.parse_args(argv)
+    given = [t.split("=")[0] for t in (sys.argv[1:] if argv is None else argv)]
+    if a.radius is not None:
+        import math
+        if not (a.radius > 0.0 and math.isfinite(a.radius)):
+            ap.error("--radius must be a finite length > 0")
+        if any(t in ("--kn", "--knn") for t in given):                      # given explicitly, the default value included
+            ap.error("--radius and --knn are two different graphs: give one")
+        if any(len(t) > 2 and "--index".startswith(t) for t in given):
+            ap.error("--radius and --index are two different graphs (the radius graph has its own grid): give one")
     scenes = None
     if a.scenes:
         with open(a.scenes) as f:
             scenes = [ln.strip() for ln in f if ln.strip()]
-    if (a.voxel is not None or a.index != "brute") and not a.pointcloud:
+    if (a.voxel is not None or a.index != "brute" or a.radius is not None) and not a.pointcloud:
         names = scenes if scenes is not None else sorted(d for d in os.listdir(a.scans) if os.path.exists(os.path.join(a.scans, d, d + "_vh_clean_2.ply")))
         meshes = [s for s in names if _declared_faces(os.path.join(a.scans, s, s + "_vh_clean_2.ply")) > 0]
         if meshes and a.voxel is not None:
             ap.error("--voxel thins point clouds, and %s %s faces: add --pointcloud to ignore them" % (", ".join(meshes[:5]),
                                                                                                        "has" if len(meshes) == 1 else "have"))
+        if meshes and a.radius is not None:
+            ap.error("--radius is the graph of point clouds, and %s %s faces: add --pointcloud to ignore them" % (", ".join(meshes[:5]),
+                                                                                                             "has" if len(meshes) == 1 else "have"))
         if meshes:
             ap.error("--index grid indexes point clouds, and %s %s faces: add --pointcloud to ignore them" % (", ".join(meshes[:5]),
                                                                                                               "has" if len(meshes) == 1 else "have"))
     written, skipped = oversegment_scans(a.scans, scenes, a.k_thresh, a.seg_min_verts, a.force, a.workers, a.device, pointcloud=a.pointcloud,
-                                         knn=a.knn, viewpoint=a.viewpoint, voxel=a.voxel, index=a.index)
+                                         knn=a.knn, viewpoint=a.viewpoint, voxel=a.voxel, index=a.index, radius=a.radius)
     for p in written:
         print("wrote", p)
     for s in skipped:

@@ -339,11 +339,25 @@ def pointcloud_knn(pointcloud, k=10, device=None, index="brute", cell=None):
     return out
 
 
-def get_adj_from_cloud_scan(xyz, unmapper=None, k=10, device=None):
-    """A scan without faces: the point graph stands in for the mesh edges.  -> (adj, adj_resampled): get_adj_from_pointcloud(xyz, k), and
-    those rows mapped through the unmapper, per-row sorted and unique, rows with i == j dropped like get_adj_from_mesh drops them."""
+def get_adj_from_radius(xyz, radius, device=None):
+    """The radius graph of a cloud as the pairs a < b in lexicographic order -> [E, 2] LongTensor (CPU): the upper halves
+    of the rows of `components.radius_neighbours`."""
     import torch
-    raw = get_adj_from_pointcloud(xyz, k, device=device)
+    from .components import radius_neighbours
+    indptr, indices = radius_neighbours(xyz, radius, device=device)
+    n = indptr.shape[0] - 1
+    rows = torch.repeat_interleave(torch.arange(n, device=indptr.device), indptr[1:] - indptr[:-1])
+    cols = indices.long()
+    up = cols > rows
+    return torch.stack([rows[up], cols[up]], dim=1).cpu()
+
+
+def get_adj_from_cloud_scan(xyz, unmapper=None, k=10, device=None, radius=None):
+    """A scan without faces: the point graph stands in for the mesh edges.  -> (adj, adj_resampled): get_adj_from_pointcloud(xyz, k), and
+    those rows mapped through the unmapper, per-row sorted and unique, rows with i == j dropped like get_adj_from_mesh drops them.
+    `radius`: the raw list is the radius graph's (`get_adj_from_radius`) instead."""
+    import torch
+    raw = get_adj_from_pointcloud(xyz, k, device=device) if radius is None else get_adj_from_radius(xyz, radius, device=device)
     if unmapper is None:
         return raw, None
     un = torch.as_tensor(unmapper, dtype=torch.long).cpu()
@@ -410,10 +424,13 @@ def generate_seg_labels_and_ds_set(scene_path, root: str = ".", device=None):
                                     h_off.shape[0] - 1, h_pts.shape[0]))
 
 
-def generate_mesh_adjcency_pth(scene_name, plydata=None, root: str = ".", scene_path: Optional[str] = None, device=None, knn: int = 10):
+def generate_mesh_adjcency_pth(scene_name, plydata=None, root: str = ".", scene_path: Optional[str] = None, device=None, knn: int = 10,
+                               radius=None):
     """util.py:795-811: adj/mesh/raw/<s>/<s>.adj.pth and adj/mesh/resampled/<s>/<s>.adj.pth (skipped when both exist).  A scan without
-    faces gets the kNN graph of its points (`knn` neighbours) under the same names."""
+    faces gets the kNN graph of its points (`knn` neighbours) under the same names, or with `radius` the radius graph."""
     import torch
+    if radius is not None and int(knn) != 10:
+        raise ValueError("generate_mesh_adjcency_pth: radius and knn = %d are two different graphs; give one" % int(knn))
     p1 = os.path.join(root, "adj", "mesh", "raw", scene_name, scene_name + ".adj.pth")
     p2 = os.path.join(root, "adj", "mesh", "resampled", scene_name, scene_name + ".adj.pth")
     if os.path.exists(p1) and os.path.exists(p2):
@@ -424,7 +441,9 @@ def generate_mesh_adjcency_pth(scene_name, plydata=None, root: str = ".", scene_
         plydata = read_ply(os.path.join(scene_path, scene_name + "_vh_clean_2.ply"))
     unmapper = torch.load(os.path.join(root, "data", "resampled", scene_name, scene_name + ".unmap.pth"))
     if not has_faces(plydata):
-        adj, adj_resampled = get_adj_from_cloud_scan(mesh_arrays(plydata)[0], unmapper, knn, device=device)
+        adj, adj_resampled = get_adj_from_cloud_scan(mesh_arrays(plydata)[0], unmapper, knn, device=device, radius=radius)
+    elif radius is not None:
+        raise ValueError(f"{scene_name}: the radius graph belongs to a scan without faces; this scan is a mesh and uses its faces")
     else:
         adj, adj_resampled = get_adj_from_mesh(plydata, unmapper, device=device)
     for p, t in ((p1, adj), (p2, adj_resampled)):
@@ -438,24 +457,29 @@ from .labels import (generate_real_label_pth, generate_real_labels, generate_seg
 
 
 def prepare_scene(scene_path, item, num_points: int = 150000, root: str = ".", perm=None, device=None, label_style: Optional[str] = None,
-                  manual_label_path: Optional[str] = None, oversegment: bool = False, knn: int = 10, index: str = "brute"):
+                  manual_label_path: Optional[str] = None, oversegment: bool = False, knn: int = 10, index: str = "brute", radius=None):
     """What prepare_data.py:36-71 + prepare_weak_label.py:60-90 do for one scan: point cloud, mapper / unmapper, segment lists,
     mesh adjacency and -- with `label_style` and ScanNet's annotation files next to the mesh -- the ground-truth and weak-label
     files, i.e. every input of SegModel.forward.  `oversegment=True`: a scan without a segs.json gets one from its mesh first
     (oversegment.py, default parameters); an existing file is never overwritten.  A scan without faces (a point cloud) is segmented
     over the kNN graph of its points (`knn` neighbours), and that graph stands in for the mesh adjacency.  `index="grid"`: the
-    unsampled vertices' nearest sampled point comes from the exact grid index; the files are the same."""
+    unsampled vertices' nearest sampled point comes from the exact grid index; the files are the same.  `radius` (a scan
+    without faces): the over-segmentation and the adjacency files come from the radius graph instead of the kNN graph."""
     hip.knn_index(index)
+    if radius is not None and int(knn) != 10:
+        raise ValueError("prepare_scene: radius and knn = %d are two different graphs; give one" % int(knn))
     scene_name = _scene_name(scene_path)
     ply = read_ply(os.path.join(scene_path, scene_name + "_vh_clean_2.ply"))
+    if radius is not None and has_faces(ply):
+        raise ValueError(f"{scene_name}: the radius graph belongs to a scan without faces; this scan is a mesh and uses its faces")
     if oversegment:
         from .oversegment import oversegment_scan
-        oversegment_scan(scene_path, device=device, plydata=ply, knn=knn)
+        oversegment_scan(scene_path, device=device, plydata=ply, knn=knn, radius=radius)
     elif not has_faces(ply) and not os.path.exists(os.path.join(scene_path, scene_name + "_vh_clean_2.0.010000.segs.json")):
         raise ValueError(f"{scene_name}: a scan without faces and without a segs.json: pass oversegment=True to make one from the points")
     generate_pointcloud_pth(scene_path, item, num_points, ply, root=root, perm=perm, device=device, index=index)
     generate_seg_labels_and_ds_set(scene_path, root=root, device=device)
-    generate_mesh_adjcency_pth(scene_name, ply, root=root, device=device, knn=knn)
+    generate_mesh_adjcency_pth(scene_name, ply, root=root, device=device, knn=knn, radius=radius)
     if label_style is not None:
         generate_real_labels(scene_path, root=root)
         generate_real_label_pth(scene_path, root=root)
