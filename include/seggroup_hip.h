@@ -1101,11 +1101,19 @@ int sg_fps_general(const float* d_pts, int n, int dim, int k, int initial_idx, i
 int sg_knn_general(const float* d_x, int B, int C, int n, int k, int64_t* d_idx, void* stream);
 
 /* backward of sg_group_max_rows (aggregate_cluster_feature, model.py:278-288): the gradient of a group's maximum goes to its
- * first maximal row (torch.max), every other row of the group gets 0; d_grows rows of `grow_stride` floats */
+ * first maximal row (torch.max), every other row of the group gets 0; d_grows rows of `grow_stride` floats.
+ * Both backward maxima (this one and sg_segment_max_backward) compare BY VALUE, as torch.max does: -0.0 == +0.0, so of a
+ * {-0.0, +0.0} pair the FIRST row wins, as among any equal values (duplicates, rows that are all -inf).  A row id may be listed
+ * more than once in a group (sg_group_max_rows allows it): the row receives the gradient iff one of its positions is the first
+ * maximal position of the list, and a later position of the same row does not clear it (autograd of x[ids].max(0)).  The groups
+ * of one call share no row.  An empty group writes nothing, and a row in no group is NOT written: the caller zeroes d_grows
+ * where that matters. */
 int sg_group_max_rows_backward(const float* d_rows, int row_stride, int D, const int32_t* d_goff, const int32_t* d_gidx, int G,
                                const float* d_gout, int out_stride, float* d_grows, int grow_stride, void* stream);
-/* backward of sg_segment_max (model.py:793,834): rows [N,D] in member order, cluster c = rows [d_cl_off[c], d_cl_off[c+1]); the
- * gradient of a cluster's maximum goes to its first maximal row.  d_ws needs sg_segment_max_backward_ws_bytes(C, D). */
+/* backward of sg_segment_max (model.py:793,834): rows [N,D] in member order, cluster c = rows [d_cl_off[c], d_cl_off[c+1]) with
+ * d_cl_off[0] = 0 and d_cl_off[C] = N; the gradient of a cluster's maximum goes to its first maximal row, by value (above), whatever
+ * the order in which the blocks' atomics arrive.  Every other entry of d_grows [N,D] is set to 0, an empty cluster sends nothing;
+ * with C == 0 or N == 0 nothing is written.  d_ws needs sg_segment_max_backward_ws_bytes(C, D). */
 size_t sg_segment_max_backward_ws_bytes(int C, int D);
 int sg_segment_max_backward(const float* d_rows, int N, int D, const int32_t* d_cl_off, int C, const float* d_gout, int out_stride,
                             float* d_grows, void* d_ws, size_t ws_bytes, void* stream);

@@ -186,17 +186,22 @@ __global__ void k_group_max_backward(const float* __restrict__ rows, int row_str
             const float v = rows[(size_t)gidx[i] * row_stride + k];
             if (a < 0 || v > m) { m = v; a = i; }
         }
-        for (int i = lo; i < hi; ++i) grows[(size_t)gidx[i] * grow_stride + k] = i == a ? gout[(size_t)g * out_stride + k] : 0.f;
+        // a row id may be listed more than once (a hub): every position of the winner's ROW writes the gradient, so that a later
+        // position of that row cannot clear it (autograd of x[ids].max(0) leaves it there)
+        const int win = a < 0 ? -1 : gidx[a];
+        for (int i = lo; i < hi; ++i) grows[(size_t)gidx[i] * grow_stride + k] = gidx[i] == win ? gout[(size_t)g * out_stride + k] : 0.f;
     }
 }
 
 // ---- backward of the point -> cluster max (model.py:793,834): rows in member order, cluster c = rows [cl_off[c], cl_off[c+1]).
 // A floor or wall is one cluster of tens of thousands of rows, so the arg-max runs over ROWS in parallel: 64 rows per block and
 // one thread per column reduce to one key, then one atomicMax per (block, cluster, column) on
-//     key = order-preserving bits of the value << 32 | ~row          (largest value, FIRST row on ties, whatever the arrival order)
+//     key = order-preserving bits of the value << 32 | ~row          (largest value, FIRST row on ties, whatever the arrival order;
+//                                                                      -0.0 is folded to +0.0 first: the order is BY VALUE)
 // and a second kernel sends the cluster's gradient to the winning row (everything else was zeroed by a memset).
 __device__ __forceinline__ unsigned long long segmax_key(float v, int row) {
-    const unsigned int u = __float_as_uint(v);
+    unsigned int u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0u;                             // -0.0 == +0.0 by value: one key, so the FIRST zero row wins (torch.max)
     const unsigned int o = u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
     return ((unsigned long long)o << 32) | (unsigned int)(0xffffffffu - (unsigned int)row);
 }
@@ -337,11 +342,12 @@ __global__ void k_sgd_step(float* __restrict__ p, const float* __restrict__ g, f
 
 // torch.optim.Adam (train.py:98; betas 0.9 / 0.999, eps 1e-8, L2 weight decay added to the gradient), step = 1, 2, ...
 __global__ void k_adam_step(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int n, float lr, float wd,
-                            float beta1, float beta2, float eps, float bc1, float bc2_sqrt) {
+                            float beta1, float beta2, float om_beta1, float om_beta2, float eps, float bc1, float bc2_sqrt) {
+    // om_beta = 1 - beta rounded from float64 (torch rounds `value = 1 - beta2` the same way): 1.f - 0.999f is 1.3e-5 off 0.001
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float gg = g[i] + wd * p[i];
-        const float mi = beta1 * m[i] + (1.f - beta1) * gg;
-        const float vi = beta2 * v[i] + (1.f - beta2) * gg * gg;
+        const float mi = beta1 * m[i] + om_beta1 * gg;
+        const float vi = beta2 * v[i] + om_beta2 * gg * gg;
         m[i] = mi;
         v[i] = vi;
         p[i] = p[i] - (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
@@ -563,7 +569,8 @@ int sg_optimizer_adam(float* d_params, const float* d_grads, float* d_m, float* 
     if (n == 0) return SG_OK;
     const double b1 = 0.9, b2 = 0.999;
     const float bc1 = (float)(1.0 - std::pow(b1, step)), bc2s = (float)std::sqrt(1.0 - std::pow(b2, step));
-    k_adam_step<<<std::min(sg::cdiv(n, 256), 1024), 256, 0, sg::as_stream(stream)>>>(d_params, d_grads, d_m, d_v, n, lr, weight_decay, 0.9f, 0.999f, 1e-8f, bc1, bc2s);
+    k_adam_step<<<std::min(sg::cdiv(n, 256), 1024), 256, 0, sg::as_stream(stream)>>>(d_params, d_grads, d_m, d_v, n, lr, weight_decay, (float)b1, (float)b2,
+                                                                                     (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f, bc1, bc2s);
     SG_LAUNCH_CHECK();
     return SG_OK;
 }
