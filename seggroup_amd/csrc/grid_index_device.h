@@ -1,6 +1,12 @@
-// The exact grid index that the grid kNN, the two-cloud nearest point (8i) and the radius graph (8k) share: the box and the
-// finite check, the cells on 8g's formula, the sorted order, the dense table.  Every file that includes this gets its own copy of the
-// kernels (internal linkage); the entry points decide the cell edge and drive the stages.
+// The exact grid index that the grid kNN, the two-cloud nearest point (8i) and the radius graph (8k) share, and everything
+// round it that does not depend on who searches:
+//   kernels   the box and the finite check (overseg_device.h's box pieces), the cells on 8g's formula, the gather, the dense table, its stats
+//   host      measure (box, read-back, finite check, extents and slack), check_cell (the refusals of a caller's cell edge), bin and
+//             sort_cells (cells and the stable sort at one edge), finish_index (gather, table, stats), index_stats
+//   device    the search skeleton: pending_lanes and pick_group (the wave's next cell), stage_tile (a sorted range through LDS),
+//             wave_sum, search_epilogue
+// The entry points decide the cell edge and drive the stages: "measure, choose the edge, index".  Every file that includes this gets its
+// own copy of the kernels (internal linkage).
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -13,11 +19,12 @@
 namespace sggrid {
 namespace {
 
-constexpr int kBlock = 256;
+using sgos::bits_for_cells;
+using sgos::kCellLimit;
+
+constexpr int kBlock = sgos::kBoxBlock;
 constexpr int kWave = 64;                       // queries per block of the search: one wave
 constexpr int kGTile = 256;                     // candidates staged per LDS tile of the search
-constexpr int kBoxBlocks = 1024;
-constexpr float kCellLimit = 2097152.0f;        // 2^21 cells per axis, as in 8g
 constexpr int kMinCells = 1 << 22;              // the dense table holds max(2^22, 4 N) cells
 constexpr int kTargetOccupancy = 48;            // points per occupied cell the library aims at
 constexpr int kRingLimit = 8;
@@ -45,67 +52,35 @@ struct Grid {
     int rmax;
 };
 
-inline float unkey_host(unsigned int k) {
-    const unsigned int b = k & 0x80000000u ? k ^ 0x80000000u : ~k;
-    float f;
-    std::memcpy(&f, &b, 4);
-    return f;
-}
-
 __global__ void k_grid_init(Misc* __restrict__ m) {
     m->evals = 0ull;
     m->flag = 0; m->nq = 0; m->maxring = 0; m->heads = 0; m->occupied = 0; m->maxcell = 0; m->m2 = 0u;
     for (int a = 0; a < 3; ++a) { m->lo[a] = 0xffffffffu; m->hi[a] = 0u; }
 }
 
-// k_thin_box's shape (a fixed number of blocks, 7 atomics per block) with k_pc_pack's output
+// the box reduction of overseg_device.h with k_pc_pack's output: cand[i] = (x, y, z, |p|^2), and a seventh atomic per block for M2
 __global__ __launch_bounds__(kBlock) void k_grid_box(const float* __restrict__ p, int stride, int N, float4* __restrict__ cand,
                                                      Misc* __restrict__ m) {
-    __shared__ unsigned int s_lo[3][kBlock / 64], s_hi[3][kBlock / 64], s_m2[kBlock / 64];
-    unsigned int lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u}, m2 = 0u;
-    bool bad = false;
+    __shared__ unsigned int s_lo[3][sgos::kBoxWaves], s_hi[3][sgos::kBoxWaves], s_m2[sgos::kBoxWaves];
+    sgos::Box box;
+    unsigned int m2 = 0u;
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)N; i += (size_t)gridDim.x * kBlock) {
-        float c[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            c[a] = p[i * stride + a];
-            bad |= !sgos::finite_f32(c[a]);
-            const unsigned int key = sgos::weight_key(c[a]);
-            lo[a] = min(lo[a], key);
-            hi[a] = max(hi[a], key);
-        }
+        const float c[3] = {p[i * stride], p[i * stride + 1], p[i * stride + 2]};
+        sgos::box_take(box, c);
         const float4 v = sgcloud::with_norm(c[0], c[1], c[2]);
         cand[i] = v;
         m2 = max(m2, __float_as_uint(v.w));
     }
-    if (bad) atomicOr(&m->flag, 1);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    sgos::box_stage(box, &m->flag, s_lo, s_hi);
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = min(lo[a], (unsigned int)__shfl_xor((int)lo[a], off));
-            hi[a] = max(hi[a], (unsigned int)__shfl_xor((int)hi[a], off));
-        }
-        m2 = max(m2, (unsigned int)__shfl_xor((int)m2, off));
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_lo[a][wave] = lo[a]; s_hi[a][wave] = hi[a]; }
-        s_m2[wave] = m2;
-    }
+    for (int off = 32; off >= 1; off >>= 1) m2 = max(m2, (unsigned int)__shfl_xor((int)m2, off));
+    if ((threadIdx.x & 63) == 0) s_m2[threadIdx.x >> 6] = m2;
     __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        unsigned int l = s_lo[a][0], h = s_hi[a][0];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) { l = min(l, s_lo[a][w]); h = max(h, s_hi[a][w]); }
-        atomicMin(&m->lo[a], l);
-        atomicMax(&m->hi[a], h);
-    } else if (threadIdx.x == 3) {
+    sgos::box_commit(s_lo, s_hi, m->lo, m->hi);
+    if (threadIdx.x == 3) {
         unsigned int v = s_m2[0];
 #pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) v = max(v, s_m2[w]);
+        for (int w = 1; w < sgos::kBoxWaves; ++w) v = max(v, s_m2[w]);
         atomicMax(&m->m2, v);
     }
 }
@@ -176,11 +151,59 @@ __global__ __launch_bounds__(kBlock) void k_grid_cellstats(const int* __restrict
     }
 }
 
-int bits_for_cells(long long cells) {           // bits that hold 0..cells-1; none for one cell
-    int b = 0;
-    while (b < 62 && (1ll << b) < cells) ++b;
-    return b;
+// ---- the search skeleton: one wave per 64 queries in the order of their cell keys ----
+
+// The wave's next group: the lanes of the first pending lane's cell, and that cell's coordinates (wave-uniform).  A search loops
+//     while (const unsigned long long pending = pending_lanes(done)) { const Group grp = pick_group(g, pending, done, mycell); ... }
+// The group is returned by value and picked in one place of the loop: outputs through references cost k_grid_search<21> its occupancy, a
+// second inlined copy a hundred instructions (profiles/grid_builder_resources.md).
+struct Group {
+    bool in;                        // this lane belongs to the group
+    int x, y, z;
+};
+
+__device__ __forceinline__ unsigned long long pending_lanes(bool done) { return __builtin_amdgcn_ballot_w64(!done); }
+
+__device__ __forceinline__ Group pick_group(const Grid& g, unsigned long long pending, bool done, int mycell) {
+    const int leader = __builtin_ctzll(pending);
+    const int gcell = __builtin_amdgcn_readfirstlane(__shfl(mycell, leader));
+    const int nx = g.nc[0], ny = g.nc[1];
+    return Group{!done && mycell == gcell, gcell % nx, (gcell / nx) % ny, gcell / (nx * ny)};
 }
+
+// The sorted points [c0, min(c0 + kGTile, b)) into tile / tidx (float4 + original index) -> their number.  c0 and b are wave-uniform, so
+// every lane of the block (one wave) reaches both barriers: the first keeps the previous tile's readers apart from these stores, the
+// second the stores from the readers that follow.
+__device__ __forceinline__ int stage_tile(int c0, int b, const float4* __restrict__ spts, const int* __restrict__ sidx, float4* tile, int* tidx) {
+    const int lane = threadIdx.x;
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kGTile / kWave; ++u) {
+        const int e = c0 + u * kWave + lane;
+        if (e < b) { tile[u * kWave + lane] = spts[e]; tidx[u * kWave + lane] = sidx[e]; }
+    }
+    __syncthreads();
+    return min(kGTile, b - c0);
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// a ring search's leave: the wave's largest ring count of a settled query, and (timed calls) its pair scores
+__device__ __forceinline__ void search_epilogue(int myr, unsigned int evals, int counting, Misc* __restrict__ m) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) myr = max(myr, __shfl_xor(myr, off));
+    if (threadIdx.x == 0 && myr > 0) atomicMax(&m->maxring, myr);
+    if (counting) {
+        const unsigned long long e = wave_sum(evals);
+        if (threadIdx.x == 0) atomicAdd(&m->evals, e);
+    }
+}
+
+// ---- the host side ----
 
 long long cell_cap(int N) { return std::max<long long>(kMinCells, 4ll * N); }
 
@@ -233,6 +256,94 @@ bool cells_of(const float ext[3], float h, int nc[3], long long* total) {
         *total *= nc[a];
     }
     return true;
+}
+
+struct Measured {
+    Misc hm;                        // as the box left it
+    float ext[3], emax;             // the box's extents and the largest of them, E
+};
+
+struct Sorted {
+    const unsigned long long* key;
+    const int* idx;
+};
+
+struct Index {
+    Grid g;
+    const unsigned long long* skey;     // the candidates' sorted keys
+    const int* sidx;                    // and their original indices
+};
+
+// The stage "box" over the N candidates of `d_points`: the finite check, p.cand, the bounding box and M2.  With queries (d_q, U > 0)
+// they run over the UNION of the two clouds and q_pts receives the queries' (x, y, z, |q|^2).  Synchronises the stream once.
+// -> a fresh g with lo and slack; the caller chooses h and the rings.
+int measure(const char* who, const float* d_points, int stride, int N, const float* d_q, int qstride, int U, float4* q_pts, const Plan& p,
+            hipStream_t st, Grid* g, Measured* out) {
+    k_grid_init<<<1, 1, 0, st>>>(p.misc);
+    k_grid_box<<<std::min(sg::cdiv(N, kBlock), sgos::kBoxBlocks), kBlock, 0, st>>>(d_points, stride, N, p.cand, p.misc);
+    if (U > 0) k_grid_box<<<std::min(sg::cdiv(U, kBlock), sgos::kBoxBlocks), kBlock, 0, st>>>(d_q, qstride, U, q_pts, p.misc);
+    out->hm = Misc{};
+    SG_HIP(hipMemcpyAsync(&out->hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (out->hm.flag & 1) return sg::fail(SG_EINVAL, "%s: a coordinate is not finite", who);
+    *g = Grid{};
+    out->emax = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        g->lo[a] = sgos::unkey_host(out->hm.lo[a]);
+        out->ext[a] = sgos::unkey_host(out->hm.hi[a]) - g->lo[a];
+        out->emax = std::max(out->emax, out->ext[a]);
+    }
+    g->slack = std::ldexp(out->emax, -21);              // 8 u E, u = 2^-24
+    return SG_OK;
+}
+
+// a cell edge the caller chose: g.nc and the number of cells, or the refusal
+int check_cell(const char* who, const Measured& ms, float cell, int N, Grid* g, long long* total) {
+    if (!cells_of(ms.ext, cell, g->nc, total))
+        return sg::fail(SG_EUNSUP, "%s: cell too small for the cloud's extent (%g / %g is not below %g cells on an axis)", who, (double)ms.emax,
+                        (double)cell, (double)kCellLimit);
+    if (*total > cell_cap(N))
+        return sg::fail(SG_EUNSUP, "%s: a cell of %g gives %lld cells; the table of %d points holds %lld", who, (double)cell, *total, N,
+                        cell_cap(N));
+    return SG_OK;
+}
+
+// the cells at edge h (one that cells_of accepts): g.h, g.nc, g.ncells, and p.k0 / p.v0 = every candidate's key and index
+void bin(const Measured& ms, float h, const Plan& p, int N, hipStream_t st, Grid* g) {
+    long long total = 0;
+    g->h = h;
+    cells_of(ms.ext, h, g->nc, &total);
+    g->ncells = (int)total;
+    k_grid_cells<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(p.cand, N, *g, p.k0, p.v0);
+}
+
+// (key, index) of n points, stable by key over the bits a table of ncells uses -> where the sorted lists are
+Sorted sort_cells(unsigned long long* k0, unsigned long long* k1, int* v0, int* v1, int* hist, int n, int ncells, hipStream_t st) {
+    auto L = sgsort::one_list<unsigned long long, int>(k0, k1, v0, v1, hist, n);
+    sgsort::radix_sort<unsigned long long, int, true>(L, 1, 0, bits_for_cells(ncells), st);
+    return Sorted{L.kin[0], L.vin[0]};
+}
+
+// the rest of the stage "sort" (the points in sorted order) and the stage "table"
+template <class Clock>
+void finish_index(const Plan& p, const Sorted& s, int N, Clock& clock, hipStream_t st, Index* ix) {
+    const Grid& g = ix->g;
+    ix->skey = s.key;
+    ix->sidx = s.idx;
+    k_grid_gather<<<sg::cdiv(N, kBlock), kBlock, 0, st>>>(p.cand, s.idx, N, p.spts);
+    clock.tick();
+    k_grid_table<<<sg::cdiv((long long)g.ncells + 1, kBlock), kBlock, 0, st>>>(s.key, N, g.ncells, p.start);
+    k_grid_cellstats<<<sg::cdiv(g.ncells, kBlock), kBlock, 0, st>>>(p.start, g.ncells, p.misc);
+    clock.tick();
+}
+
+// the stats words every grid entry starts with: nc[0..2], occupied cells, the largest cell, the bits of h
+void index_stats(int64_t* s, const Grid& g, const Misc& hm) {
+    unsigned int hbits;
+    std::memcpy(&hbits, &g.h, 4);
+    s[0] = g.nc[0]; s[1] = g.nc[1]; s[2] = g.nc[2];
+    s[3] = hm.occupied; s[4] = hm.maxcell; s[5] = (int64_t)hbits;
 }
 
 }  // namespace

@@ -106,8 +106,7 @@ Plan carve(void* d_ws, size_t ws_bytes, int V) {
 // sg_components_set_timing(1): the calling thread's next calls bracket their stages with events (tools/time_components.py)
 constexpr int kStages = 4;
 const char* const kStageNames[kStages] = {"init", "hook", "flatten", "sizes"};
-thread_local bool t_timing = false;
-thread_local float t_stage_us[kStages];
+thread_local sgos::StageTimes<kStages> t_times;
 
 int check_tail(const char* who, int V, int32_t* d_comp, int* h_C, void* d_ws) {
     SG_REQUIRE(d_comp && h_C && d_ws, "%s: a null pointer", who);
@@ -123,7 +122,7 @@ int run(const char* who, const Graph& g, int V, int32_t* d_comp, int32_t* d_size
     SG_REQUIRE(p.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_components_ws_bytes(V));
     hipStream_t st = sg::as_stream(stream);
     const int nb = sg::cdiv(V, kBlock);
-    sgos::StageClock<kStages> clock(st, t_timing, t_stage_us);
+    sgos::StageClock<kStages> clock(st, t_times.timing, t_times.us);
     k_cc_init<<<nb, kBlock, 0, st>>>(p.parent, p.count, V, p.misc);
     clock.tick();
     if (g.count > 0) {
@@ -151,15 +150,9 @@ int run(const char* who, const Graph& g, int V, int32_t* d_comp, int32_t* d_size
 
 extern "C" {
 
-int sg_components_set_timing(int on) { t_timing = on != 0; return SG_OK; }
-
-int sg_components_stage_times(float* h_us, int cap) {
-    SG_REQUIRE(h_us && cap >= kStages, "sg_components_stage_times: room for %d floats is needed", kStages);
-    for (int i = 0; i < kStages; ++i) h_us[i] = t_stage_us[i];
-    return kStages;
-}
-
-const char* sg_components_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+int sg_components_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
+int sg_components_stage_times(float* h_us, int cap) { return t_times.copy("sg_components_stage_times", h_us, cap); }
+const char* sg_components_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
 
 size_t sg_components_ws_bytes(int V) {
     if (V < 1 || V > SG_MAX_CLOUD_POINTS) return 0;

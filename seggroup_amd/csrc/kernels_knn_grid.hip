@@ -23,8 +23,10 @@
 // of both clouds), the queries x are binned by the same formula and sorted by cell key, k_nearest_search walks the rings, and the queue is
 // finished by sg_nearest_point's own kernel.  Both entry points build their index through build_index.
 //
-// The index's own pieces (k_grid_box .. k_grid_cellstats, the Grid, the workspace plan) live in grid_index_device.h, which the radius graph
-// (kernels_radius.hip) includes as well; the search kernels, the cell-edge choice and the entry points are here.
+// The index's own pieces (k_grid_box .. k_grid_cellstats, the Grid, the workspace plan), the steps of its build and the search skeleton
+// (group pick, tile staging, the kernels' leave) live in grid_index_device.h, which the radius graph (kernels_radius.hip)
+// includes as well; the ring walk with its settled test, the cell-edge choice (fit, the probe, the occupancy correction) and the entry
+// points are here.
 #include <cmath>
 #include <cstring>
 
@@ -62,16 +64,8 @@ template <int KK>
 __device__ __forceinline__ void scan_range(int a, int b, bool active, const float4& me, const float4* __restrict__ spts,
                                            const int* __restrict__ sidx, float4* tile, int* tidx, float (&bs)[KK], int (&bi)[KK],
                                            unsigned int& evals) {
-    const int lane = threadIdx.x;
     for (int c0 = a; c0 < b; c0 += kGTile) {
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kGTile / kWave; ++u) {
-            const int e = c0 + u * kWave + lane;
-            if (e < b) { tile[u * kWave + lane] = spts[e]; tidx[u * kWave + lane] = sidx[e]; }
-        }
-        __syncthreads();
-        const int n = min(kGTile, b - c0);
+        const int n = stage_tile(c0, b, spts, sidx, tile, tidx);
         if (active) {
             for (int j = 0; j < n; ++j) insert<KK>(sgcloud::pair_score(me.x, me.y, me.z, me.w, tile[j]), tidx[j], bs, bi);
             evals += (unsigned int)n;
@@ -115,6 +109,36 @@ __device__ __forceinline__ bool ring_settles(const Grid& g, int gx, int gy, int 
     return all || (full && gap > 0.0f && lhs > rhs);
 }
 
+struct Walk {
+    bool queued;                    // the rings did not settle this lane's query: it goes to the queue
+    int ring;                       // the ring that settled it (0: none)
+    unsigned int evals;             // pair scores this lane evaluated
+};
+
+// The walk of one wave: its groups in turn, each ring by ring until all its lanes are settled or the ring limit is reached;
+// the list is left in bs / bi.  The counters are locals returned by value, as pick_group's are.
+template <int KK>
+__device__ __forceinline__ Walk ring_walk(const Grid& g, bool live, int mycell, const float4& me, const int* __restrict__ start,
+                                          const float4* __restrict__ spts, const int* __restrict__ sidx, float4* tile, int* tidx, float (&bs)[KK],
+                                          int (&bi)[KK]) {
+#pragma unroll
+    for (int t = 0; t < KK; ++t) { bs[t] = -INFINITY; bi[t] = 0x7fffffff; }
+    bool done = !live, queued = false;
+    int myr = 0;
+    unsigned int evals = 0u;
+    while (const unsigned long long pending = pending_lanes(done)) {
+        const Group grp = pick_group(g, pending, done, mycell);
+        for (int r = 1; r <= g.rmax; ++r) {
+            const bool act = grp.in && !done;
+            scan_ring<KK>(g, grp.x, grp.y, grp.z, r, start, act, me, spts, sidx, tile, tidx, bs, bi, evals);
+            if (act && ring_settles(g, grp.x, grp.y, grp.z, r, bs[KK - 1], bi[KK - 1] != 0x7fffffff)) { done = true; myr = r; }
+            if (__builtin_amdgcn_ballot_w64(grp.in && !done) == 0ull) break;
+        }
+        if (grp.in && !done) { done = true; queued = true; }
+    }
+    return Walk{queued, myr, evals};
+}
+
 template <int KK>
 __global__ __launch_bounds__(kWave) void k_grid_search(const float4* __restrict__ spts, const int* __restrict__ sidx,
                                                        const unsigned long long* __restrict__ skey, const int* __restrict__ start, Grid g, int N,
@@ -129,44 +153,16 @@ __global__ __launch_bounds__(kWave) void k_grid_search(const float4* __restrict_
     const int orig = sidx[sl];
     float bs[KK];
     int bi[KK];
-#pragma unroll
-    for (int t = 0; t < KK; ++t) { bs[t] = -INFINITY; bi[t] = 0x7fffffff; }
-    const int nx = g.nc[0], ny = g.nc[1];
-    bool done = !live, queued = false;
-    int myr = 0;
-    unsigned int evals = 0u;
-    for (;;) {
-        const unsigned long long pending = __builtin_amdgcn_ballot_w64(!done);
-        if (pending == 0ull) break;
-        const int leader = __builtin_ctzll(pending);
-        const int gcell = __builtin_amdgcn_readfirstlane(__shfl(mycell, leader));
-        const bool ingroup = !done && mycell == gcell;
-        const int gx = gcell % nx, gy = (gcell / nx) % ny, gz = gcell / (nx * ny);
-        for (int r = 1; r <= g.rmax; ++r) {
-            const bool act = ingroup && !done;
-            scan_ring<KK>(g, gx, gy, gz, r, start, act, me, spts, sidx, tile, tidx, bs, bi, evals);
-            if (act && ring_settles(g, gx, gy, gz, r, bs[KK - 1], bi[KK - 1] != 0x7fffffff)) { done = true; myr = r; }
-            if (__builtin_amdgcn_ballot_w64(ingroup && !done) == 0ull) break;
-        }
-        if (ingroup && !done) { done = true; queued = true; }
-    }
+    const Walk w = ring_walk<KK>(g, live, mycell, me, start, spts, sidx, tile, tidx, bs, bi);
     if (live) {
-        if (queued) {
+        if (w.queued) {
             queue[atomicAdd(&m->nq, 1)] = orig;
         } else {
 #pragma unroll
             for (int t = 0; t < KK; ++t) table[(size_t)orig * KK + t] = bi[t];
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) myr = max(myr, __shfl_xor(myr, off));
-    if (threadIdx.x == 0 && myr > 0) atomicMax(&m->maxring, myr);
-    if (counting) {
-        unsigned long long e = evals;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) e += __shfl_xor(e, off);
-        if (threadIdx.x == 0) atomicAdd(&m->evals, e);
-    }
+    search_epilogue(w.ring, w.evals, counting, m);
 }
 
 // the queued queries (original indices) against the whole cloud in original order: k_pc_knn for a compacted list
@@ -190,7 +186,7 @@ __global__ __launch_bounds__(kTile) void k_grid_fallback(const float4* __restric
 }
 
 // The two-cloud, one-entry form: one wave per 64 queries in the order of their cell keys; the lanes of one cell form a group
-// and share the staged candidate tiles exactly as in k_grid_search, the list is (best score, its original index).  A query whose block
+// and share the staged candidate tiles through k_grid_search's ring_walk, the list is (best score, its original index).  A query whose block
 // holds no candidate keeps -inf and is unsettled by construction.  The result goes to the query's ORIGINAL row; queries unsettled at the
 // ring limit are queued with their original index for k_nearest (kernels_prepare.hip).
 __global__ __launch_bounds__(kWave) void k_nearest_search(const float4* __restrict__ spts, const int* __restrict__ sidx, const int* __restrict__ start,
@@ -205,40 +201,14 @@ __global__ __launch_bounds__(kWave) void k_nearest_search(const float4* __restri
     const int orig = qsidx[sl];
     const float4 me = qpts[orig];
     const int mycell = (int)qskey[sl];
-    float bs[1] = {-INFINITY};
-    int bi[1] = {0x7fffffff};
-    const int nx = g.nc[0], ny = g.nc[1];
-    bool done = !live, queued = false;
-    int myr = 0;
-    unsigned int evals = 0u;
-    for (;;) {
-        const unsigned long long pending = __builtin_amdgcn_ballot_w64(!done);
-        if (pending == 0ull) break;
-        const int leader = __builtin_ctzll(pending);
-        const int gcell = __builtin_amdgcn_readfirstlane(__shfl(mycell, leader));
-        const bool ingroup = !done && mycell == gcell;
-        const int gx = gcell % nx, gy = (gcell / nx) % ny, gz = gcell / (nx * ny);
-        for (int r = 1; r <= g.rmax; ++r) {
-            const bool act = ingroup && !done;
-            scan_ring<1>(g, gx, gy, gz, r, start, act, me, spts, sidx, tile, tidx, bs, bi, evals);
-            if (act && ring_settles(g, gx, gy, gz, r, bs[0], bi[0] != 0x7fffffff)) { done = true; myr = r; }
-            if (__builtin_amdgcn_ballot_w64(ingroup && !done) == 0ull) break;
-        }
-        if (ingroup && !done) { done = true; queued = true; }
-    }
+    float bs[1];
+    int bi[1];
+    const Walk w = ring_walk<1>(g, live, mycell, me, start, spts, sidx, tile, tidx, bs, bi);
     if (live) {
-        if (queued) queue[atomicAdd(&m->nq, 1)] = orig;
+        if (w.queued) queue[atomicAdd(&m->nq, 1)] = orig;
         else out[orig] = (int64_t)bi[0];
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) myr = max(myr, __shfl_xor(myr, off));
-    if (threadIdx.x == 0 && myr > 0) atomicMax(&m->maxring, myr);
-    if (counting) {
-        unsigned long long e = evals;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) e += __shfl_xor(e, off);
-        if (threadIdx.x == 0) atomicAdd(&m->evals, e);
-    }
+    search_epilogue(w.ring, w.evals, counting, m);
 }
 
 // d2[u] = (dx*dx + dy*dy) + dz*dz with d = x[u] - y[idx[u]], every operation rounded once (the file is built without contraction)
@@ -285,18 +255,11 @@ const char* const kStageNames[kStages] = {"box", "probe", "cells", "sort", "tabl
 
 // what a thread asked for and what its last call left: one set per entry point (the kNN, the nearest point)
 struct Session {
-    bool timing = false;
-    float stage_us[kStages];
+    sgos::StageTimes<kStages> times;
     int64_t stats[kNumStats];
     int target = 0, ring_limit = 0;         // 0: the defaults
 };
 thread_local Session t_knn, t_nearest;
-
-int stage_times(const Session& s, const char* who, float* h_us, int cap) {
-    SG_REQUIRE(h_us && cap >= kStages, "%s: room for %d floats is needed", who, kStages);
-    for (int i = 0; i < kStages; ++i) h_us[i] = s.stage_us[i];
-    return kStages;
-}
 
 int stats_of(const Session& s, const char* who, int64_t* h, int cap) {
     SG_REQUIRE(h && cap >= kNumStats, "%s: room for %d words is needed", who, kNumStats);
@@ -313,52 +276,27 @@ int set_tuning(Session& s, const char* who, int target_occupancy, int ring_limit
 }
 
 void leave_stats(Session& s, const Grid& g, const Misc& hm, int nq, unsigned long long evals) {
-    unsigned int hbits;
-    std::memcpy(&hbits, &g.h, 4);
-    s.stats[0] = g.nc[0]; s.stats[1] = g.nc[1]; s.stats[2] = g.nc[2];
-    s.stats[3] = hm.occupied; s.stats[4] = hm.maxcell; s.stats[5] = (int64_t)hbits;
+    index_stats(s.stats, g, hm);
     s.stats[6] = hm.maxring; s.stats[7] = nq; s.stats[8] = (int64_t)evals;
 }
 
-struct Index {
-    Grid g;
-    const unsigned long long* skey;     // the candidates' sorted keys
-    const int* sidx;                    // and their original indices
-};
-
-// The stages box, probe, cells, sort and table over the N candidates of `d_points`: p.cand, p.spts, p.start and
-// the sorted keys / indices.  With queries (d_q, U > 0) the finite check, the box, E and M2 run over the UNION of the two clouds and
-// q_pts receives the queries' (x, y, z, |q|^2); the index itself holds the candidates only.  `brute`: the entry point that decides a cloud
-// whose score margin is not finite.
+// The stages box, probe, cells, sort and table over the N candidates of `d_points`, through grid_index_device.h's
+// steps: measure, the cell edge (the caller's, or the probe's below), bin, sort_cells, finish_index.  With queries (d_q, U > 0) the box
+// covers both clouds and q_pts receives the queries; the index itself holds the candidates only.  `brute`: the entry point that decides a
+// cloud whose score margin is not finite.
 int build_index(const char* who, const char* brute, const Session& ses, const float* d_points, int stride, int N, const float* d_q, int qstride,
                 int U, float4* q_pts, float cell, const Plan& p, sgos::StageClock<kStages>& clock, hipStream_t st, Index* out) {
     const int nb = sg::cdiv(N, kBlock);
-    // box
-    k_grid_init<<<1, 1, 0, st>>>(p.misc);
-    k_grid_box<<<std::min(nb, kBoxBlocks), kBlock, 0, st>>>(d_points, stride, N, p.cand, p.misc);
-    if (U > 0) k_grid_box<<<std::min(sg::cdiv(U, kBlock), kBoxBlocks), kBlock, 0, st>>>(d_q, qstride, U, q_pts, p.misc);
-    Misc hm{};
-    SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
-    SG_HIP(hipStreamSynchronize(st));
-    SG_LAUNCH_CHECK();
-    if (hm.flag & 1) return sg::fail(SG_EINVAL, "%s: a coordinate is not finite", who);
+    Grid& g = out->g;
+    Measured ms;
+    if (const int rc = measure(who, d_points, stride, N, d_q, qstride, U, q_pts, p, st, &g, &ms)) return rc;
     float m2;
-    std::memcpy(&m2, &hm.m2, 4);
-    const float delta = std::max(std::ldexp(m2, -19), std::ldexp(1.0f, -100));
-    if (!std::isfinite(4.0f * m2) || !std::isfinite(delta))
+    std::memcpy(&m2, &ms.hm.m2, 4);
+    g.delta = std::max(std::ldexp(m2, -19), std::ldexp(1.0f, -100));
+    if (!std::isfinite(4.0f * m2) || !std::isfinite(g.delta))
         return sg::fail(SG_EUNSUP, "%s: the coordinates are too large for the grid's score margin (max |p|^2 = %g); the brute-force path "
                                    "(%s) decides such a cloud", who, (double)m2, brute);
     clock.tick();
-    Grid& g = out->g;
-    g = Grid{};
-    float ext[3], emax = 0.0f;
-    for (int a = 0; a < 3; ++a) {
-        g.lo[a] = unkey_host(hm.lo[a]);
-        ext[a] = unkey_host(hm.hi[a]) - g.lo[a];
-        emax = std::max(emax, ext[a]);
-    }
-    g.delta = delta;
-    g.slack = std::ldexp(emax, -21);                    // 8 u E, u = 2^-24
     g.rmax = ses.ring_limit > 0 ? ses.ring_limit : kRingLimit;
     const long long cap = cell_cap(N);
     long long total = 0;
@@ -366,39 +304,24 @@ int build_index(const char* who, const char* brute, const Session& ses, const fl
     auto fit = [&](float h) {
         if (!(h > 0.0f) || !std::isfinite(h)) h = 1.0f;
         for (int tries = 0; tries < 400; ++tries) {
-            if (cells_of(ext, h, g.nc, &total) && total <= cap) return h;
+            if (cells_of(ms.ext, h, g.nc, &total) && total <= cap) return h;
             h *= 1.25f;
         }
-        return emax > 0.0f ? emax * 2.0f : 1.0f;        // one cell per axis
+        return ms.emax > 0.0f ? ms.emax * 2.0f : 1.0f;  // one cell per axis
     };
-    sgsort::Lists<unsigned long long, int> L{};
-    auto bin = [&](float h) {                           // cells and sort at edge h
-        g.h = h;
-        cells_of(ext, h, g.nc, &total);
-        g.ncells = (int)total;
-        k_grid_cells<<<nb, kBlock, 0, st>>>(p.cand, N, g, p.k0, p.v0);
-    };
-    auto sort = [&]() {
-        L = sgsort::Lists<unsigned long long, int>{};
-        L.kin[0] = p.k0; L.kout[0] = p.k1; L.vin[0] = p.v0; L.vout[0] = p.v1; L.hist[0] = p.hist; L.n[0] = N;
-        sgsort::radix_sort<unsigned long long, int, true>(L, 1, 0, bits_for_cells(g.ncells), st);
-    };
+    Sorted sorted{};
     bool binned = false;
     if (cell > 0.0f) {
-        if (!cells_of(ext, cell, g.nc, &total))
-            return sg::fail(SG_EUNSUP, "%s: cell too small for the cloud's extent (%g / %g is not below %g cells on an axis)", who, (double)emax,
-                            (double)cell, (double)kCellLimit);
-        if (total > cap)
-            return sg::fail(SG_EUNSUP, "%s: a cell of %g gives %lld cells; the table of %d points holds %lld", who, (double)cell, total, N, cap);
+        if (const int rc = check_cell(who, ms, cell, N, &g, &total)) return rc;
         clock.tick();
     } else {
         // first guess: the cloud as a surface of the box's half area (a line: its length), `target` points per cell
         const float target = (float)(ses.target > 0 ? ses.target : kTargetOccupancy);
-        const float area = ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2];
-        const float h0 = fit(std::max(std::sqrt(target * area / (float)N), target * emax / (float)N));
-        bin(h0);
-        sort();
-        k_grid_heads<<<nb, kBlock, 0, st>>>(L.kin[0], N, &p.misc->heads);
+        const float area = ms.ext[0] * ms.ext[1] + ms.ext[1] * ms.ext[2] + ms.ext[0] * ms.ext[2];
+        const float h0 = fit(std::max(std::sqrt(target * area / (float)N), target * ms.emax / (float)N));
+        bin(ms, h0, p, N, st, &g);
+        sorted = sort_cells(p.k0, p.k1, p.v0, p.v1, p.hist, N, g.ncells, st);
+        k_grid_heads<<<nb, kBlock, 0, st>>>(sorted.key, N, &p.misc->heads);
         int heads = 0;
         SG_HIP(hipMemcpyAsync(&heads, &p.misc->heads, 4, hipMemcpyDeviceToHost, st));
         SG_HIP(hipStreamSynchronize(st));
@@ -414,16 +337,10 @@ int build_index(const char* who, const char* brute, const Session& ses, const fl
         }
         clock.tick();
     }
-    if (!binned) bin(cell);
+    if (!binned) bin(ms, cell, p, N, st, &g);
     clock.tick();
-    if (!binned) sort();
-    out->skey = L.kin[0] ? L.kin[0] : p.k0;
-    out->sidx = L.vin[0] ? L.vin[0] : p.v0;
-    k_grid_gather<<<nb, kBlock, 0, st>>>(p.cand, out->sidx, N, p.spts);
-    clock.tick();
-    k_grid_table<<<sg::cdiv((long long)g.ncells + 1, kBlock), kBlock, 0, st>>>(out->skey, N, g.ncells, p.start);
-    k_grid_cellstats<<<sg::cdiv(g.ncells, kBlock), kBlock, 0, st>>>(p.start, g.ncells, p.misc);
-    clock.tick();
+    if (!binned) sorted = sort_cells(p.k0, p.k1, p.v0, p.v1, p.hist, N, g.ncells, st);
+    finish_index(p, sorted, N, clock, st, out);
     return SG_OK;
 }
 
@@ -442,9 +359,9 @@ void launch_fallback(const Plan& p, int N, int nq, int32_t* table, int counting,
 
 extern "C" {
 
-int sg_pointcloud_knn_grid_set_timing(int on) { t_knn.timing = on != 0; return SG_OK; }
-int sg_pointcloud_knn_grid_stage_times(float* h_us, int cap) { return stage_times(t_knn, "sg_pointcloud_knn_grid_stage_times", h_us, cap); }
-const char* sg_pointcloud_knn_grid_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+int sg_pointcloud_knn_grid_set_timing(int on) { t_knn.times.timing = on != 0; return SG_OK; }
+int sg_pointcloud_knn_grid_stage_times(float* h_us, int cap) { return t_knn.times.copy("sg_pointcloud_knn_grid_stage_times", h_us, cap); }
+const char* sg_pointcloud_knn_grid_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
 int sg_pointcloud_knn_grid_stats(int64_t* h, int cap) { return stats_of(t_knn, "sg_pointcloud_knn_grid_stats", h, cap); }
 int sg_pointcloud_knn_grid_set_tuning(int target_occupancy, int ring_limit) {
     return set_tuning(t_knn, "sg_pointcloud_knn_grid_set_tuning", target_occupancy, ring_limit);
@@ -468,8 +385,8 @@ int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, floa
     const Plan p = carve(d_ws, ws_bytes, N);
     if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_pointcloud_knn_grid_ws_bytes(N, k));
     hipStream_t st = sg::as_stream(stream);
-    const int counting = t_knn.timing ? 1 : 0;
-    sgos::StageClock<kStages> clock(st, t_knn.timing, t_knn.stage_us);
+    const int counting = t_knn.times.timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, t_knn.times.timing, t_knn.times.us);
     Index ix{};
     const int rc = build_index(who, "sg_pointcloud_knn", t_knn, d_points, stride, N, nullptr, 0, 0, nullptr, cell, p, clock, st, &ix);
     if (rc != SG_OK) return rc;
@@ -497,9 +414,9 @@ int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, floa
     return SG_OK;
 }
 
-int sg_nearest_point_grid_set_timing(int on) { t_nearest.timing = on != 0; return SG_OK; }
-int sg_nearest_point_grid_stage_times(float* h_us, int cap) { return stage_times(t_nearest, "sg_nearest_point_grid_stage_times", h_us, cap); }
-const char* sg_nearest_point_grid_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+int sg_nearest_point_grid_set_timing(int on) { t_nearest.times.timing = on != 0; return SG_OK; }
+int sg_nearest_point_grid_stage_times(float* h_us, int cap) { return t_nearest.times.copy("sg_nearest_point_grid_stage_times", h_us, cap); }
+const char* sg_nearest_point_grid_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
 int sg_nearest_point_grid_stats(int64_t* h, int cap) { return stats_of(t_nearest, "sg_nearest_point_grid_stats", h, cap); }
 int sg_nearest_point_grid_set_tuning(int target_occupancy, int ring_limit) {
     return set_tuning(t_nearest, "sg_nearest_point_grid_set_tuning", target_occupancy, ring_limit);
@@ -530,8 +447,8 @@ int sg_nearest_point_grid(const float* d_x, int x_stride, int U, const float* d_
     carve(cv, q, U);
     SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_nearest_point_grid_ws_bytes(U, N));
     hipStream_t st = sg::as_stream(stream);
-    const int counting = t_nearest.timing ? 1 : 0;
-    sgos::StageClock<kStages> clock(st, t_nearest.timing, t_nearest.stage_us);
+    const int counting = t_nearest.times.timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, t_nearest.times.timing, t_nearest.times.us);
     Index ix{};
     const int rc = build_index(who, "sg_nearest_point", t_nearest, d_y, y_stride, N, d_x, x_stride, U, q.pts, cell, p, clock, st, &ix);
     if (rc != SG_OK) return rc;
@@ -539,10 +456,8 @@ int sg_nearest_point_grid(const float* d_x, int x_stride, int U, const float* d_
     // the queries in the order of their cell keys: 64 consecutive ones are a wave's groups
     const int ub = sg::cdiv(U, kBlock);
     k_grid_cells<<<ub, kBlock, 0, st>>>(q.pts, U, g, q.k0, q.v0);
-    sgsort::Lists<unsigned long long, int> L{};
-    L.kin[0] = q.k0; L.kout[0] = q.k1; L.vin[0] = q.v0; L.vout[0] = q.v1; L.hist[0] = q.hist; L.n[0] = U;
-    sgsort::radix_sort<unsigned long long, int, true>(L, 1, 0, bits_for_cells(g.ncells), st);
-    k_nearest_search<<<sg::cdiv(U, kWave), kWave, 0, st>>>(p.spts, ix.sidx, p.start, g, q.pts, L.kin[0], L.vin[0], U, d_idx, q.queue, p.misc, counting);
+    const Sorted qs = sort_cells(q.k0, q.k1, q.v0, q.v1, q.hist, U, g.ncells, st);
+    k_nearest_search<<<sg::cdiv(U, kWave), kWave, 0, st>>>(p.spts, ix.sidx, p.start, g, q.pts, qs.key, qs.idx, U, d_idx, q.queue, p.misc, counting);
     clock.tick();
     Misc hm{};
     SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));

@@ -165,8 +165,7 @@ Plan carve(void* d_ws, size_t ws_bytes, int V, int F) {
 // sg_overseg_set_timing(1): the calling thread's next sg_overseg_edges calls bracket their stages with events (tools/time_overseg.py)
 constexpr int kStages = 8;
 const char* const kStageNames[kStages] = {"check", "face_normals", "incidence_sort", "vertex_normals", "edges", "weights", "weight_sort", "gather"};
-thread_local bool t_timing = false;
-thread_local float t_stage_us[kStages];
+thread_local sgos::StageTimes<kStages> t_times;
 
 using StageClock = sgos::StageClock<kStages>;
 
@@ -174,8 +173,7 @@ using StageClock = sgos::StageClock<kStages>;
 
 // the stages both segmenters share (overseg_device.h)
 const int* sgos::sort_by_weight(unsigned int* k0, unsigned int* k1, int* v0, int* v1, int* hist, int E, hipStream_t st) {
-    sgsort::Lists<unsigned int, int> W{};
-    W.kin[0] = k0; W.kout[0] = k1; W.vin[0] = v0; W.vout[0] = v1; W.hist[0] = hist; W.n[0] = E;
+    auto W = sgsort::one_list<unsigned int, int>(k0, k1, v0, v1, hist, E);
     sgsort::radix_sort<unsigned int, int, true>(W, 1, 0, 32, st);
     return W.vin[0];
 }
@@ -186,16 +184,10 @@ void sgos::gather_edges(const int* idx, int E, const int64_t* adj, const float* 
 
 extern "C" {
 
-int sg_overseg_set_timing(int on) { t_timing = on != 0; return SG_OK; }
-
+int sg_overseg_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
 // the stage times in microseconds of this thread's last timed sg_overseg_edges -> number of stages; names through sg_overseg_stage_name
-int sg_overseg_stage_times(float* h_us, int cap) {
-    SG_REQUIRE(h_us && cap >= kStages, "sg_overseg_stage_times: room for %d floats is needed", kStages);
-    for (int i = 0; i < kStages; ++i) h_us[i] = t_stage_us[i];
-    return kStages;
-}
-
-const char* sg_overseg_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+int sg_overseg_stage_times(float* h_us, int cap) { return t_times.copy("sg_overseg_stage_times", h_us, cap); }
+const char* sg_overseg_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
 
 size_t sg_overseg_ws_bytes(int V, int F) {
     const size_t n = (size_t)std::max(F, 1) * 3;
@@ -213,7 +205,7 @@ int sg_overseg_edges(const float* d_xyz, int V, const int32_t* d_faces, int F, f
     if (!p.ok) return sg::fail(SG_ENOMEM, "sg_overseg_edges: workspace too small (%zu < %zu)", ws_bytes, sg_overseg_ws_bytes(V, F));
     hipStream_t st = sg::as_stream(stream);
     const int n = 3 * F;
-    StageClock clock(st, t_timing, t_stage_us);
+    StageClock clock(st, t_times.timing, t_times.us);
     // 0. the inputs are the caller's: nothing reads through a face id before this check has passed
     SG_HIP(hipMemsetAsync(p.flag, 0, 4, st));
     k_os_check<<<sg::cdiv(3ll * std::max(V, F), kBlock), kBlock, 0, st>>>(d_xyz, V, d_faces, F, p.flag);
@@ -229,8 +221,7 @@ int sg_overseg_edges(const float* d_xyz, int V, const int32_t* d_faces, int F, f
     if (F > 0) {
         k_os_face_normals<<<sg::cdiv(F, kBlock), kBlock, 0, st>>>(d_xyz, d_faces, F, p.fn, p.k0, p.v0);
         clock.tick();
-        sgsort::Lists<unsigned int, int> L{};
-        L.kin[0] = p.k0; L.kout[0] = p.k1; L.vin[0] = p.v0; L.vout[0] = p.v1; L.hist[0] = p.hist; L.n[0] = n;
+        auto L = sgsort::one_list<unsigned int, int>(p.k0, p.k1, p.v0, p.v1, p.hist, n);
         sgsort::radix_sort<unsigned int, int, true>(L, 1, 0, bits_for((long long)V + 1), st);
         skey = L.kin[0];
         sface = L.vin[0];

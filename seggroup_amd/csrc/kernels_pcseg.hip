@@ -345,8 +345,7 @@ int viewpoint_ok(const char* who, const float* v) {
 // sg_pcseg_set_timing(1): the calling thread's next sg_pcseg_edges calls bracket their stages with events (tools/time_pcseg.py)
 constexpr int kStages = 7;
 const char* const kStageNames[kStages] = {"check", "knn", "normals", "edges", "weights", "weight_sort", "gather"};
-thread_local bool t_timing = false;
-thread_local float t_stage_us[kStages];
+thread_local sgos::StageTimes<kStages> t_times;
 
 
 size_t pcseg_ws_bytes(int N, int k, int index) {
@@ -369,7 +368,7 @@ int pcseg_edges(const char* who, const float* d_xyz, int N, int k, const float* 
     if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, pcseg_ws_bytes(N, k, index));
     hipStream_t st = sg::as_stream(stream);
     const int n = N * k;                                                       // N <= 2^24, k <= 20: below 2^31
-    sgos::StageClock<kStages> clock(st, t_timing, t_stage_us);
+    sgos::StageClock<kStages> clock(st, t_times.timing, t_times.us);
     // 0. the coordinates are the caller's
     k_pc_init<<<1, 1, 0, st>>>(p.misc, h_viewpoint != nullptr, h_viewpoint ? h_viewpoint[0] : 0.0f, h_viewpoint ? h_viewpoint[1] : 0.0f,
                                h_viewpoint ? h_viewpoint[2] : 0.0f);
@@ -393,8 +392,7 @@ int pcseg_edges(const char* who, const float* d_xyz, int N, int k, const float* 
     clock.tick();
     // 6. the unique undirected pairs a < b in lexicographic order
     k_pc_edge_keys<<<sg::cdiv(n, kBlock), kBlock, 0, st>>>(table, N, k, p.p0);
-    sgsort::Lists<unsigned long long, int> L{};
-    L.kin[0] = p.p0; L.kout[0] = p.p1; L.hist[0] = p.hist; L.n[0] = n;
+    auto L = sgsort::one_list<unsigned long long, int>(p.p0, p.p1, nullptr, nullptr, p.hist, n);
     const int field = std::min(32, bits_for((long long)N + 1) + 1);           // one bit more than an id carries: ~0 must come out last
     sgsort::radix_sort<unsigned long long, int, false>(L, 1, 0, field, st);
     sgsort::radix_sort<unsigned long long, int, false>(L, 1, 32, field, st);
@@ -508,8 +506,7 @@ constexpr int kListStages = 8;      // box, cells, sort, table, count, scan, fil
 constexpr int kOwnStages = 5;
 constexpr int kRStages = kListStages + kOwnStages;
 const char* const kOwnStageNames[kOwnStages] = {"normals", "edges", "weights", "weight_sort", "gather"};
-thread_local bool t_rtiming = false;
-thread_local float t_rstage_us[kRStages];
+thread_local sgos::StageTimes<kRStages> t_rtimes;       // the lists' stages in front, then this file's own
 
 struct ListTiming {                 // the lists report their stages to this thread while one of these lives
     bool on;
@@ -537,16 +534,16 @@ int pcseg_edges_radius(const char* who, const float* d_xyz, int N, float radius,
     hipStream_t st = sg::as_stream(stream);
     int64_t* off = d_off ? d_off : p.off;
     int32_t* idx = d_idx ? d_idx : p.idx;
-    if (t_rtiming) for (int i = 0; i < kRStages; ++i) t_rstage_us[i] = 0.0f;
+    if (t_rtimes.timing) for (int i = 0; i < kRStages; ++i) t_rtimes.us[i] = 0.0f;
     // the lists: every refusal of 8k and the pair cap are theirs
     {
-        const ListTiming lt(t_rtiming);
+        const ListTiming lt(t_rtimes.timing);
         rc = sg::radius_lists(who, d_xyz, 3, N, radius, cell, capacity, off, idx, h_T, p.lists, p.lists_bytes, stream);
-        if (t_rtiming) for (int i = 0; i < kListStages; ++i) t_rstage_us[i] = sg::radius_lists_stage_us()[i];
+        if (t_rtimes.timing) for (int i = 0; i < kListStages; ++i) t_rtimes.us[i] = sg::radius_lists_stage_us()[i];
     }
     if (rc < 0) return rc;
     const int64_t T = *h_T;
-    sgos::StageClock<kOwnStages> clock(st, t_rtiming, t_rstage_us + kListStages);
+    sgos::StageClock<kOwnStages> clock(st, t_rtimes.timing, t_rtimes.us + kListStages);
     // normals over the rows
     k_pc_init<<<1, 1, 0, st>>>(p.misc, h_viewpoint != nullptr, h_viewpoint ? h_viewpoint[0] : 0.0f, h_viewpoint ? h_viewpoint[1] : 0.0f,
                                h_viewpoint ? h_viewpoint[2] : 0.0f);
@@ -607,15 +604,9 @@ int pcseg_scan_radius(const char* who, const float* d_xyz, int N, float radius, 
 
 extern "C" {
 
-int sg_pcseg_set_timing(int on) { t_timing = on != 0; return SG_OK; }
-
-int sg_pcseg_stage_times(float* h_us, int cap) {
-    SG_REQUIRE(h_us && cap >= kStages, "sg_pcseg_stage_times: room for %d floats is needed", kStages);
-    for (int i = 0; i < kStages; ++i) h_us[i] = t_stage_us[i];
-    return kStages;
-}
-
-const char* sg_pcseg_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+int sg_pcseg_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
+int sg_pcseg_stage_times(float* h_us, int cap) { return t_times.copy("sg_pcseg_stage_times", h_us, cap); }
+const char* sg_pcseg_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
 
 size_t sg_pointcloud_knn_ws_bytes(int N) { return sg::align_up((size_t)std::max(N, 1) * 16) + sg::align_up(sizeof(Misc)); }
 
@@ -740,17 +731,10 @@ int sg_pcseg_scan_radius(const float* d_xyz, int N, float radius, float cell, in
                              d_ws, ws_bytes, stream);
 }
 
-int sg_pcseg_radius_set_timing(int on) { t_rtiming = on != 0; return SG_OK; }
-
-int sg_pcseg_radius_stage_times(float* h_us, int cap) {
-    SG_REQUIRE(h_us && cap >= kRStages, "sg_pcseg_radius_stage_times: room for %d floats is needed", kRStages);
-    for (int i = 0; i < kRStages; ++i) h_us[i] = t_rstage_us[i];
-    return kRStages;
-}
-
+int sg_pcseg_radius_set_timing(int on) { t_rtimes.timing = on != 0; return SG_OK; }
+int sg_pcseg_radius_stage_times(float* h_us, int cap) { return t_rtimes.copy("sg_pcseg_radius_stage_times", h_us, cap); }
 const char* sg_pcseg_radius_stage_name(int i) {
-    if (i >= 0 && i < kListStages) return sg::radius_lists_stage_name(i);
-    return i >= kListStages && i < kRStages ? kOwnStageNames[i - kListStages] : nullptr;
+    return i < kListStages ? sg::radius_lists_stage_name(i) : sgos::stage_name(kOwnStageNames, i - kListStages);
 }
 
 }  // extern "C"

@@ -372,8 +372,7 @@ int sg_segment_lists(const int32_t* d_seg_indices, int V, const int64_t* d_mappe
     using L32 = sgsort::Lists<unsigned int, int>;
     // 1. sorted unique raw ids (ids are non-negative in ScanNet: the sort is on the value's 32 bits)
     SG_HIP(hipMemcpyAsync(a, d_seg_indices, (size_t)V * 4, hipMemcpyDeviceToDevice, st));
-    L32 L{};
-    L.kin[0] = (const unsigned int*)a; L.kout[0] = (unsigned int*)b; L.hist[0] = hist; L.n[0] = V;
+    L32 L = sgsort::one_list<unsigned int, int>((const unsigned int*)a, (unsigned int*)b, nullptr, nullptr, hist, V);
     sgsort::radix_sort<unsigned int, int, false>(L, 1, 0, 32, st);
     const unsigned int* sorted = L.kin[0];
     int32_t* uniq = (int32_t*)L.kout[0];

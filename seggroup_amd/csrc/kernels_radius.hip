@@ -4,14 +4,16 @@
 // without an adjacency: count[i] = the pairs of i (sg_radius_count_grid) and the connected components of the graph (sg_components_radius,
 // 8j's outputs and conventions).
 //
-//   index     grid_index_device.h: box and finite check, cells on 8g's formula, radix sort, gather, dense table -- the grid kNN's (8h)
+//   index     grid_index_device.h: measure (box and finite check), bin (cells on 8g's formula), sort_cells, finish_index (gather, dense
+//             table) -- the grid kNN's (8h); the cell edge and the rings are chosen here (rings_for)
 //   R         the block of Chebyshev radius R round a query's cell holds every point that can pass: the smallest R with
 //             gap = fl(fl(R h) - slack) > 0  and  fl(fl(gap * gap) * (1 - 2^-9)) > r2  (8h item 3 bounds the axis gap of a point outside the
 //             block from below; 8k shows that the 2^-9 also pays for the roundings of d2).  Computed on the host, the same for every
 //             query; no queue and no fallback.  cell = 0: h just large enough for R = 1, enlarged only until the grid fits the table.
-//   search    k_radius_search<Visitor>: k_grid_search's shape.  One wave per 64 consecutive sorted points; the lanes of one cell form a
-//             group, taken in turn by ballot; the (2R+1)^2 row ranges of the block come from the table; candidates are staged through LDS
-//             in tiles of 256 (float4 + original index); each lane of the group tests its own query.  Nothing is indexed at run time.
+//   search    k_radius_search<Visitor>: k_grid_search's shape on the same pieces (pick_group, stage_tile, wave_sum).  One wave per 64
+//             consecutive sorted points; the lanes of one cell form a group, taken in turn by ballot; the (2R+1)^2 row ranges of the
+//             block come from the table; candidates are staged through LDS in tiles of 256 (float4 + original index); each lane of the
+//             group tests its own query.  Nothing is indexed at run time.
 //   Count     a register counter, one plain vector store at the original row
 //   Hook      for a passing pair with original j > i (each edge once) and equal labels: 8j's hook (components_device.h) on the parent
 //             array; k_cc_init before, k_cc_flatten and k_cc_sizes after, as they are.  The hooks run inside a divergent wave loop; no lane
@@ -30,6 +32,7 @@
 namespace {
 
 using sggrid::Grid;
+using sggrid::Index;
 using sggrid::kGTile;
 using sggrid::kWave;
 
@@ -85,28 +88,16 @@ __global__ __launch_bounds__(kWave) void k_radius_search(const float4* __restric
     bool done = !live;
     int passed = 0;
     unsigned int evals = 0u;
-    for (;;) {
-        const unsigned long long pending = __builtin_amdgcn_ballot_w64(!done);
-        if (pending == 0ull) break;
-        const int leader = __builtin_ctzll(pending);
-        const int gcell = __builtin_amdgcn_readfirstlane(__shfl(mycell, leader));
-        const bool ingroup = !done && mycell == gcell;
-        const int gx = gcell % nx, gy = (gcell / nx) % ny, gz = gcell / (nx * ny);
-        const int x0 = max(gx - R, 0), x1 = min(gx + R, nx - 1);
-        for (int z = max(gz - R, 0); z <= min(gz + R, nz - 1); ++z) {
-            for (int y = max(gy - R, 0); y <= min(gy + R, ny - 1); ++y) {
+    while (const unsigned long long pending = sggrid::pending_lanes(done)) {
+        const sggrid::Group grp = sggrid::pick_group(g, pending, done, mycell);
+        const int x0 = max(grp.x - R, 0), x1 = min(grp.x + R, nx - 1);
+        for (int z = max(grp.z - R, 0); z <= min(grp.z + R, nz - 1); ++z) {
+            for (int y = max(grp.y - R, 0); y <= min(grp.y + R, ny - 1); ++y) {
                 const int row = (z * ny + y) * nx;
                 const int a = start[row + x0], b = start[row + x1 + 1];          // one contiguous range of the sorted points
                 for (int c0 = a; c0 < b; c0 += kGTile) {
-                    __syncthreads();
-#pragma unroll
-                    for (int u = 0; u < kGTile / kWave; ++u) {
-                        const int e = c0 + u * kWave + lane;
-                        if (e < b) { tile[u * kWave + lane] = spts[e]; tidx[u * kWave + lane] = sidx[e]; }
-                    }
-                    __syncthreads();
-                    const int n = min(kGTile, b - c0);
-                    if (ingroup) {
+                    const int n = sggrid::stage_tile(c0, b, spts, sidx, tile, tidx);
+                    if (grp.in) {
                         for (int t = 0; t < n; ++t) {
                             const float4 c = tile[t];
                             const int j = tidx[t];
@@ -122,13 +113,11 @@ __global__ __launch_bounds__(kWave) void k_radius_search(const float4* __restric
                 }
             }
         }
-        if (ingroup) done = true;
+        if (grp.in) done = true;
     }
     if (live) vis.finish(orig, passed);
     if (counting) {
-        unsigned long long e = evals, p = live ? (unsigned long long)passed : 0ull;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { e += __shfl_xor(e, off); p += __shfl_xor(p, off); }
+        const unsigned long long e = sggrid::wave_sum(evals), p = sggrid::wave_sum(live ? (unsigned long long)passed : 0ull);
         if (lane == 0) { atomicAdd(&tally->evals, e); atomicAdd(&tally->passed, p); }
     }
 }
@@ -189,8 +178,7 @@ constexpr int kStages = 7;
 const char* const kStageNames[kStages] = {"box", "cells", "sort", "table", "init", "search", "finish"};
 
 struct Session {
-    bool timing = false;
-    float stage_us[kStages];
+    sgos::StageTimes<kStages> times;
     int64_t stats[kNumStats];
 };
 thread_local Session t_ses;
@@ -205,37 +193,19 @@ int rings_for(float h, float slack, float r2) {
     return 0;
 }
 
-struct Index {
-    Grid g;
-    const unsigned long long* skey;
-    const int* sidx;
-};
-
-// box, cells, sort, table: the grid kNN's stages with the cell edge decided by the radius.  Synchronises the stream once (the box).
+// box, cells, sort, table: grid_index_device.h's steps with the cell edge decided by the radius -- the caller's cell with as many rings
+// as it needs, or the smallest edge that one ring serves.  Synchronises the stream once (the box).
 template <class Clock>
 int build_index(const char* who, const float* d_points, int stride, int N, float radius, float r2, float cell, const Plan& p, Clock& clock,
                 hipStream_t st, Index* out) {
     const sggrid::Plan& gp = p.grid;
-    const int nb = sg::cdiv(N, sggrid::kBlock);
-    sggrid::k_grid_init<<<1, 1, 0, st>>>(gp.misc);
     k_radius_init<<<1, 1, 0, st>>>(p.tally);
-    sggrid::k_grid_box<<<std::min(nb, sggrid::kBoxBlocks), sggrid::kBlock, 0, st>>>(d_points, stride, N, gp.cand, gp.misc);
-    sggrid::Misc hm{};
-    SG_HIP(hipMemcpyAsync(&hm, gp.misc, sizeof(hm), hipMemcpyDeviceToHost, st));
-    SG_HIP(hipStreamSynchronize(st));
-    SG_LAUNCH_CHECK();
-    if (hm.flag & 1) return sg::fail(SG_EINVAL, "%s: a coordinate is not finite", who);
-    clock.tick();
     Grid& g = out->g;
-    g = Grid{};
-    float ext[3], emax = 0.0f;
-    for (int a = 0; a < 3; ++a) {
-        g.lo[a] = sggrid::unkey_host(hm.lo[a]);
-        ext[a] = sggrid::unkey_host(hm.hi[a]) - g.lo[a];
-        emax = std::max(emax, ext[a]);
-    }
+    sggrid::Measured ms;
+    if (const int rc = sggrid::measure(who, d_points, stride, N, nullptr, 0, 0, nullptr, gp, st, &g, &ms)) return rc;
+    clock.tick();
+    const float emax = ms.emax;
     if (!std::isfinite(emax)) return sg::fail(SG_EUNSUP, "%s: the extent of the cloud is not finite", who);
-    g.slack = std::ldexp(emax, -21);
     const long long cap = sggrid::cell_cap(N);
     long long total = 0;
     if (cell > 0.0f) {
@@ -243,44 +213,27 @@ int build_index(const char* who, const float* d_points, int stride, int N, float
         if (g.rmax == 0)
             return sg::fail(SG_EUNSUP, "%s: a cell of %g needs a block of more than %d rings for a radius of %g", who, (double)cell, kMaxR,
                             (double)radius);
-        if (!sggrid::cells_of(ext, cell, g.nc, &total))
-            return sg::fail(SG_EUNSUP, "%s: cell too small for the cloud's extent (%g / %g is not below %g cells on an axis)", who, (double)emax,
-                            (double)cell, (double)sggrid::kCellLimit);
-        if (total > cap)
-            return sg::fail(SG_EUNSUP, "%s: a cell of %g gives %lld cells; the table of %d points holds %lld", who, (double)cell, total, N, cap);
+        if (const int rc = sggrid::check_cell(who, ms, cell, N, &g, &total)) return rc;
     } else {
         // just large enough for one ring; a larger edge keeps one ring (gap grows with h)
         cell = radius * 1.00390625f + g.slack;
         for (int tries = 0; tries < 64 && rings_for(cell, g.slack, r2) != 1; ++tries) cell *= 1.0009765625f;
-        for (int tries = 0; tries < 400 && !(sggrid::cells_of(ext, cell, g.nc, &total) && total <= cap); ++tries) cell *= 1.25f;
-        if (!(sggrid::cells_of(ext, cell, g.nc, &total) && total <= cap)) cell = std::max(cell, emax);         // at most two cells per axis
+        for (int tries = 0; tries < 400 && !(sggrid::cells_of(ms.ext, cell, g.nc, &total) && total <= cap); ++tries) cell *= 1.25f;
+        if (!(sggrid::cells_of(ms.ext, cell, g.nc, &total) && total <= cap)) cell = std::max(cell, emax);      // at most two cells per axis
         g.rmax = rings_for(cell, g.slack, r2);
-        if (g.rmax != 1 || !std::isfinite(cell) || !sggrid::cells_of(ext, cell, g.nc, &total) || total > cap)
+        if (g.rmax != 1 || !std::isfinite(cell) || !sggrid::cells_of(ms.ext, cell, g.nc, &total) || total > cap)
             return sg::fail(SG_EINTERNAL, "%s: no cell edge for a radius of %g on an extent of %g", who, (double)radius, (double)emax);
     }
-    g.h = cell;
-    g.ncells = (int)total;
-    sggrid::k_grid_cells<<<nb, sggrid::kBlock, 0, st>>>(gp.cand, N, g, gp.k0, gp.v0);
+    sggrid::bin(ms, cell, gp, N, st, &g);
     clock.tick();
-    sgsort::Lists<unsigned long long, int> L{};
-    L.kin[0] = gp.k0; L.kout[0] = gp.k1; L.vin[0] = gp.v0; L.vout[0] = gp.v1; L.hist[0] = gp.hist; L.n[0] = N;
-    sgsort::radix_sort<unsigned long long, int, true>(L, 1, 0, sggrid::bits_for_cells(g.ncells), st);
-    out->skey = L.kin[0] ? L.kin[0] : gp.k0;
-    out->sidx = L.vin[0] ? L.vin[0] : gp.v0;
-    sggrid::k_grid_gather<<<nb, sggrid::kBlock, 0, st>>>(gp.cand, out->sidx, N, gp.spts);
-    clock.tick();
-    sggrid::k_grid_table<<<sg::cdiv((long long)g.ncells + 1, sggrid::kBlock), sggrid::kBlock, 0, st>>>(out->skey, N, g.ncells, gp.start);
-    sggrid::k_grid_cellstats<<<sg::cdiv(g.ncells, sggrid::kBlock), sggrid::kBlock, 0, st>>>(gp.start, g.ncells, gp.misc);
-    clock.tick();
+    const sggrid::Sorted sorted = sggrid::sort_cells(gp.k0, gp.k1, gp.v0, gp.v1, gp.hist, N, g.ncells, st);
+    sggrid::finish_index(gp, sorted, N, clock, st, out);
     return SG_OK;
 }
 
 void leave_stats(const Grid& g, const sggrid::Misc& hm, const Tally& t) {
-    unsigned int hbits;
-    std::memcpy(&hbits, &g.h, 4);
     int64_t* s = t_ses.stats;
-    s[0] = g.nc[0]; s[1] = g.nc[1]; s[2] = g.nc[2];
-    s[3] = hm.occupied; s[4] = hm.maxcell; s[5] = (int64_t)hbits;
+    sggrid::index_stats(s, g, hm);
     s[6] = g.rmax; s[7] = (int64_t)t.evals; s[8] = (int64_t)t.passed;
 }
 
@@ -303,8 +256,7 @@ int check_args(const char* who, const float* d_points, int stride, int N, float 
 // the lists' own stages (sg_pcseg_edges_radius reports them in front of its own)
 constexpr int kListStages = 8;
 const char* const kListStageNames[kListStages] = {"box", "cells", "sort", "table", "count", "scan", "fill", "rows"};
-thread_local bool t_list_timing = false;
-thread_local float t_list_us[kListStages];
+thread_local sgos::StageTimes<kListStages> t_list;
 
 size_t lists_ws_bytes(int N, long long capacity) {
     return sg_radius_grid_ws_bytes(N) + sg::align_up(((size_t)sgscan::tiles_of(N) + 1) * 8) + sg::align_up((size_t)capacity * 4);
@@ -315,9 +267,9 @@ const char* const kPairsWayOut = "take a smaller radius, or thin the cloud first
 }  // namespace
 
 namespace sg {
-void radius_lists_timing(bool on) { t_list_timing = on; }
-const float* radius_lists_stage_us() { return t_list_us; }
-const char* radius_lists_stage_name(int i) { return i >= 0 && i < kListStages ? kListStageNames[i] : nullptr; }
+void radius_lists_timing(bool on) { t_list.timing = on; }
+const float* radius_lists_stage_us() { return t_list.us; }
+const char* radius_lists_stage_name(int i) { return sgos::stage_name(kListStageNames, i); }
 
 int radius_lists(const char* who, const float* d_points, int stride, int N, float radius, float cell, int64_t capacity, int64_t* d_off,
                  int32_t* d_idx, int64_t* h_T, void* d_ws, size_t ws_bytes, void* stream) {
@@ -340,8 +292,8 @@ int radius_lists(const char* who, const float* d_points, int stride, int N, floa
     int32_t* raw = cv.take<int32_t>((size_t)capacity);
     if (!p.ok || !cv.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, lists_ws_bytes(N, capacity));
     hipStream_t st = sg::as_stream(stream);
-    const int counting = t_list_timing ? 1 : 0;
-    sgos::StageClock<kListStages> clock(st, t_list_timing, t_list_us);
+    const int counting = t_list.timing ? 1 : 0;
+    sgos::StageClock<kListStages> clock(st, t_list.timing, t_list.us);
     Index ix{};
     if (const int rc = build_index(who, d_points, stride, N, radius, r2, cell, p, clock, st, &ix)) return rc;
     k_radius_search<CountVisitor><<<sg::cdiv(N, kWave), kWave, 0, st>>>(p.grid.spts, ix.sidx, ix.skey, p.grid.start, ix.g, N, r2,
@@ -389,15 +341,9 @@ int sg_radius_neighbours_grid(const float* d_points, int stride, int N, float ra
     return sg::radius_lists("sg_radius_neighbours_grid", d_points, stride, N, radius, cell, capacity, d_off, d_idx, h_T, d_ws, ws_bytes, stream);
 }
 
-int sg_radius_grid_set_timing(int on) { t_ses.timing = on != 0; return SG_OK; }
-
-int sg_radius_grid_stage_times(float* h_us, int cap) {
-    SG_REQUIRE(h_us && cap >= kStages, "sg_radius_grid_stage_times: room for %d floats is needed", kStages);
-    for (int i = 0; i < kStages; ++i) h_us[i] = t_ses.stage_us[i];
-    return kStages;
-}
-
-const char* sg_radius_grid_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+int sg_radius_grid_set_timing(int on) { t_ses.times.timing = on != 0; return SG_OK; }
+int sg_radius_grid_stage_times(float* h_us, int cap) { return t_ses.times.copy("sg_radius_grid_stage_times", h_us, cap); }
+const char* sg_radius_grid_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
 
 int sg_radius_grid_stats(int64_t* h, int cap) {
     SG_REQUIRE(h && cap >= kNumStats, "sg_radius_grid_stats: room for %d words is needed", kNumStats);
@@ -419,8 +365,8 @@ int sg_radius_count_grid(const float* d_points, int stride, int N, float radius,
     const Plan p = carve(d_ws, ws_bytes, N);
     if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_radius_grid_ws_bytes(N));
     hipStream_t st = sg::as_stream(stream);
-    const int counting = t_ses.timing ? 1 : 0;
-    sgos::StageClock<kStages> clock(st, t_ses.timing, t_ses.stage_us);
+    const int counting = t_ses.times.timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, t_ses.times.timing, t_ses.times.us);
     Index ix{};
     if (const int rc = build_index(who, d_points, stride, N, radius, r2, cell, p, clock, st, &ix)) return rc;
     clock.tick();                                // init: nothing to do
@@ -449,8 +395,8 @@ int sg_components_radius(const float* d_points, int stride, int N, float radius,
     const Plan p = carve(d_ws, ws_bytes, N);
     if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_radius_grid_ws_bytes(N));
     hipStream_t st = sg::as_stream(stream);
-    const int counting = t_ses.timing ? 1 : 0;
-    sgos::StageClock<kStages> clock(st, t_ses.timing, t_ses.stage_us);
+    const int counting = t_ses.times.timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, t_ses.times.timing, t_ses.times.us);
     Index ix{};
     if (const int rc = build_index(who, d_points, stride, N, radius, r2, cell, p, clock, st, &ix)) return rc;
     const int nb = sg::cdiv(N, sgcc::kBlock);

@@ -16,6 +16,7 @@
 // Memory is O(V): there is no rows x columns table anywhere (seg_min_verts = 1 gives rows ~ V, and the second vote's columns are segments).
 #include "sg_common.h"
 #include "sort_device.h"
+#include "overseg_device.h"
 
 namespace {
 
@@ -168,37 +169,12 @@ Plan carve(void* d_ws, size_t ws_bytes, int V) {
     return p;
 }
 
-// sg_segment_vote_set_timing(1): the calling thread's next calls bracket their stages with events (tools/time_rekey.py); the same
-// arrangement as sg_overseg_set_timing
+// sg_segment_vote_set_timing(1): the calling thread's next calls bracket their stages with events (tools/time_rekey.py), through
+// overseg_device.h's StageTimes and StageClock
 constexpr int kStages = 7;
 const char* const kStageNames[kStages] = {"check", "rank_sort", "rank_unique", "pair_sort", "pair_unique", "arg_max", "vertex_gather"};
-thread_local bool t_timing = false;
-thread_local float t_stage_us[kStages];
-
-struct StageClock {
-    hipEvent_t ev[kStages + 1];
-    int made = 0, next = 0;
-    hipStream_t st;
-    explicit StageClock(hipStream_t s) : st(s) {
-        if (!t_timing) return;
-        for (int i = 0; i < kStages; ++i) t_stage_us[i] = 0.0f;
-        for (; made <= kStages; ++made)
-            if (hipEventCreate(&ev[made]) != hipSuccess) break;
-        if (made <= kStages) { drop(); return; }
-        tick();
-    }
-    void tick() { if (made && next <= kStages) (void)hipEventRecord(ev[next++], st); }     // the end of stage next - 1
-    void drop() { for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]); made = 0; }
-    ~StageClock() {
-        if (!made) return;
-        if (next > 1 && hipEventSynchronize(ev[next - 1]) == hipSuccess)
-            for (int i = 1; i < next; ++i) {
-                float ms = 0.0f;
-                if (hipEventElapsedTime(&ms, ev[i - 1], ev[i]) == hipSuccess) t_stage_us[i - 1] = ms * 1000.0f;
-            }
-        drop();
-    }
-};
+thread_local sgos::StageTimes<kStages> t_times;
+using StageClock = sgos::StageClock<kStages>;
 
 // stages 0-2: the check and the ranks.  -> *h_R rows; p.row_head holds the runs' starts
 int rank_stage(const char* who, const Plan& p, const int32_t* d_ids, const int32_t* d_cols, int V, int n_cols, int32_t* d_rank,
@@ -216,8 +192,7 @@ int rank_stage(const char* who, const Plan& p, const int32_t* d_ids, const int32
     unsigned int* k0 = reinterpret_cast<unsigned int*>(p.k0);
     unsigned int* k1 = reinterpret_cast<unsigned int*>(p.k1);
     k_rk_id_keys<<<sg::cdiv(V, kBlock), kBlock, 0, st>>>(d_ids, V, k0, p.v0);
-    sgsort::Lists<unsigned int, int> L{};
-    L.kin[0] = k0; L.kout[0] = k1; L.vin[0] = p.v0; L.vout[0] = p.v1; L.hist[0] = p.hist; L.n[0] = V;
+    auto L = sgsort::one_list<unsigned int, int>(k0, k1, p.v0, p.v1, p.hist, V);
     sgsort::radix_sort<unsigned int, int, true>(L, 1, 0, bits_for((long long)flag[1] + 1), st);
     clock.tick();
     // 2. the distinct ids, where their runs start, every vertex's rank
@@ -243,8 +218,7 @@ int pair_stages(const Plan& p, const int32_t* d_rank, const int32_t* d_cols, int
     K* k1 = reinterpret_cast<K*>(p.k1);
     K* pkey = reinterpret_cast<K*>(p.pkey);
     k_rk_pair_keys<K><<<sg::cdiv(V, kBlock), kBlock, 0, st>>>(d_rank, d_cols, V, cbits, k0, p.v0);
-    sgsort::Lists<K, int> L{};
-    L.kin[0] = k0; L.kout[0] = k1; L.vin[0] = p.v0; L.vout[0] = p.v1; L.hist[0] = p.hist; L.n[0] = V;
+    auto L = sgsort::one_list<K, int>(k0, k1, p.v0, p.v1, p.hist, V);
     sgsort::radix_sort<K, int, true>(L, 1, 0, rbits + cbits, st);
     clock.tick();
     sgsort::unique_sorted<K>(L.kin[0], V, pkey, p.phead, p.flag + 3, p.uniq, st);
@@ -268,15 +242,9 @@ constexpr int kMaxVertices = 1 << 30;
 
 extern "C" {
 
-int sg_segment_vote_set_timing(int on) { t_timing = on != 0; return SG_OK; }
-
-int sg_segment_vote_stage_times(float* h_us, int cap) {
-    SG_REQUIRE(h_us && cap >= kStages, "sg_segment_vote_stage_times: room for %d floats is needed", kStages);
-    for (int i = 0; i < kStages; ++i) h_us[i] = t_stage_us[i];
-    return kStages;
-}
-
-const char* sg_segment_vote_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+int sg_segment_vote_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
+int sg_segment_vote_stage_times(float* h_us, int cap) { return t_times.copy("sg_segment_vote_stage_times", h_us, cap); }
+const char* sg_segment_vote_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
 
 size_t sg_segment_vote_ws_bytes(int V) {
     const size_t n = (size_t)std::max(V, 1);
@@ -291,7 +259,7 @@ int sg_segment_rank(const int32_t* d_ids, int V, int32_t* d_rank, int32_t* d_row
     const Plan p = carve(d_ws, ws_bytes, V);
     if (!p.ok) return sg::fail(SG_ENOMEM, "sg_segment_rank: workspace too small (%zu < %zu)", ws_bytes, sg_segment_vote_ws_bytes(V));
     hipStream_t st = sg::as_stream(stream);
-    StageClock clock(st);
+    StageClock clock(st, t_times.timing, t_times.us);
     return rank_stage("sg_segment_rank", p, d_ids, nullptr, V, 1, d_rank, d_row_ids, d_row_count, h_R, clock, st);
 }
 
@@ -305,7 +273,7 @@ int sg_segment_vote(const int32_t* d_ids, const int32_t* d_cols, int V, int n_co
     const Plan p = carve(d_ws, ws_bytes, V);
     if (!p.ok) return sg::fail(SG_ENOMEM, "sg_segment_vote: workspace too small (%zu < %zu)", ws_bytes, sg_segment_vote_ws_bytes(V));
     hipStream_t st = sg::as_stream(stream);
-    StageClock clock(st);
+    StageClock clock(st, t_times.timing, t_times.us);
     int R = 0;
     const int rc = rank_stage("sg_segment_vote", p, d_ids, d_cols, V, n_cols, d_rank, d_row_ids, d_row_count, &R, clock, st);
     if (rc < 0) return rc;

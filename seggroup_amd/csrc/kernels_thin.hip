@@ -2,7 +2,8 @@
 // stands for it.  The front end of the point-cloud over-segmenter for clouds above SG_MAX_POINTS: the segmenter works on the thinned cloud,
 // its ids go back to every point through the map.
 //
-//   k_thin_box          coordinates finite (one flag word), the cloud's bounding box (order-free min / max on k_pc_pack's integer keys)
+//   k_thin_box          coordinates finite (one flag word), the cloud's bounding box (order-free min / max on k_pc_pack's integer keys):
+//                       the box pieces of overseg_device.h, which k_grid_box (grid_index_device.h) is made of as well
 //   k_thin_keys         per point its cell, the voxel key (c2, c1, c0 packed over exactly the bits the box needs) and the bits of d2
 //   sort                stable radix sort of (key, index) over the key's bits in use (sort_device.h)
 //   k_thin_argmin       run heads -> voxel numbers (sort_device.h's head flags and scan); per voxel a 64-bit atomicMin of
@@ -20,9 +21,12 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kBoxBlocks = 1024;                // blocks of the box kernel: four per CU
-constexpr float kCellLimit = 2097152.0f;       // 2^21 cells per axis: three axes share a 63-bit key
+using sgos::bits_for_cells;
+using sgos::kBoxBlocks;
+using sgos::kCellLimit;
+using sgos::unkey_host;
+
+constexpr int kBlock = sgos::kBoxBlock;
 
 struct Misc {
     int flag;                       // |= 1: a coordinate is not finite
@@ -36,56 +40,23 @@ struct Grid {                       // what the host derives from the box
     int shift1, shift2;             // key = c0 | c1 << shift1 | c2 << shift2
 };
 
-inline float unkey_host(unsigned int k) {
-    const unsigned int b = k & 0x80000000u ? k ^ 0x80000000u : ~k;
-    float f;
-    std::memcpy(&f, &b, 4);
-    return f;
-}
-
 __global__ void k_thin_init(Misc* __restrict__ m) {
     m->flag = 0;
     m->count = 0;
     for (int a = 0; a < 3; ++a) { m->lo[a] = 0xffffffffu; m->hi[a] = 0u; }
 }
 
-// A fixed number of blocks walks the cloud: every thread keeps its own minima and maxima, a wave folds them by shuffles, the block's waves
-// meet in LDS, and three threads of the block go to memory -- 6 atomics per block, 6 * kBoxBlocks per call whatever N is.  (One atomic per
-// wave and axis, as k_pc_pack has them, was 85 % of this call at 1 M points: 100,000 atomics on six words.)
+// the box reduction of overseg_device.h as it is: kBoxBlocks blocks, 6 atomics per block
 __global__ __launch_bounds__(kBlock) void k_thin_box(const float* __restrict__ p, int stride, int N, Misc* __restrict__ m) {
-    __shared__ unsigned int s_lo[3][kBlock / 64], s_hi[3][kBlock / 64];
-    unsigned int lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-    bool bad = false;
+    __shared__ unsigned int s_lo[3][sgos::kBoxWaves], s_hi[3][sgos::kBoxWaves];
+    sgos::Box box;
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)N; i += (size_t)gridDim.x * kBlock) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float c = p[i * stride + a];
-            bad |= !sgos::finite_f32(c);
-            const unsigned int key = sgos::weight_key(c);
-            lo[a] = min(lo[a], key);
-            hi[a] = max(hi[a], key);
-        }
+        const float c[3] = {p[i * stride], p[i * stride + 1], p[i * stride + 2]};
+        sgos::box_take(box, c);
     }
-    if (bad) atomicOr(&m->flag, 1);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            lo[a] = min(lo[a], (unsigned int)__shfl_xor((int)lo[a], off));
-            hi[a] = max(hi[a], (unsigned int)__shfl_xor((int)hi[a], off));
-        }
-        if (lane == 0) { s_lo[a][wave] = lo[a]; s_hi[a][wave] = hi[a]; }
-    }
+    sgos::box_stage(box, &m->flag, s_lo, s_hi);
     __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        unsigned int l = s_lo[a][0], h = s_hi[a][0];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) { l = min(l, s_lo[a][w]); h = max(h, s_hi[a][w]); }
-        atomicMin(&m->lo[a], l);
-        atomicMax(&m->hi[a], h);
-    }
+    sgos::box_commit(s_lo, s_hi, m->lo, m->hi);
 }
 
 // 8g steps 2-4 for point i: key[i], idx[i] = i, d2[i] (the bits of a non-negative float or +inf: ascending as unsigned)
@@ -163,12 +134,6 @@ __global__ __launch_bounds__(kBlock) void k_thin_map(const int* __restrict__ vox
     thin_of_point[i] = pos[r] + tile_sum[r / sgsort::kTile];
 }
 
-int bits_for_cells(unsigned int cells) {        // bits that hold 0..cells-1; none for one cell
-    int b = 0;
-    while (b < 32 && (1ull << b) < (unsigned long long)cells) ++b;
-    return b;
-}
-
 struct Plan {
     Misc* misc;
     unsigned long long *k0, *k1;    // voxel keys
@@ -204,22 +169,15 @@ Plan carve(void* d_ws, size_t ws_bytes, int N) {
 // sg_cloud_thin_set_timing(1): the calling thread's next sg_cloud_thin calls bracket their stages with events (tools/time_thin.py)
 constexpr int kStages = 6;
 const char* const kStageNames[kStages] = {"check_box", "keys", "sort", "representatives", "compact", "map"};
-thread_local bool t_timing = false;
-thread_local float t_stage_us[kStages];
+thread_local sgos::StageTimes<kStages> t_times;
 
 }  // namespace
 
 extern "C" {
 
-int sg_cloud_thin_set_timing(int on) { t_timing = on != 0; return SG_OK; }
-
-int sg_cloud_thin_stage_times(float* h_us, int cap) {
-    SG_REQUIRE(h_us && cap >= kStages, "sg_cloud_thin_stage_times: room for %d floats is needed", kStages);
-    for (int i = 0; i < kStages; ++i) h_us[i] = t_stage_us[i];
-    return kStages;
-}
-
-const char* sg_cloud_thin_stage_name(int i) { return i >= 0 && i < kStages ? kStageNames[i] : nullptr; }
+int sg_cloud_thin_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
+int sg_cloud_thin_stage_times(float* h_us, int cap) { return t_times.copy("sg_cloud_thin_stage_times", h_us, cap); }
+const char* sg_cloud_thin_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
 
 size_t sg_cloud_thin_ws_bytes(int N) {
     if (N < 1 || N > SG_MAX_CLOUD_POINTS) return 0;
@@ -239,7 +197,7 @@ int sg_cloud_thin(const float* d_points, int stride, int N, float voxel, int32_t
     SG_REQUIRE(p.ok, "sg_cloud_thin: workspace too small (%zu < %zu)", ws_bytes, sg_cloud_thin_ws_bytes(N));
     hipStream_t st = sg::as_stream(stream);
     const int nb = sg::cdiv(N, kBlock);
-    sgos::StageClock<kStages> clock(st, t_timing, t_stage_us);
+    sgos::StageClock<kStages> clock(st, t_times.timing, t_times.us);
     // 1. the coordinates are the caller's; the box
     k_thin_init<<<1, 1, 0, st>>>(p.misc);
     k_thin_box<<<std::min(nb, kBoxBlocks), kBlock, 0, st>>>(d_points, stride, N, p.misc);
@@ -269,8 +227,7 @@ int sg_cloud_thin(const float* d_points, int stride, int N, float voxel, int32_t
     k_thin_keys<<<nb, kBlock, 0, st>>>(d_points, stride, N, g, p.k0, p.v0, p.d2);
     clock.tick();
     // 3. stable by voxel key: inside a run the indices ascend
-    sgsort::Lists<unsigned long long, int> L{};
-    L.kin[0] = p.k0; L.kout[0] = p.k1; L.vin[0] = p.v0; L.vout[0] = p.v1; L.hist[0] = p.hist; L.n[0] = N;
+    auto L = sgsort::one_list<unsigned long long, int>(p.k0, p.k1, p.v0, p.v1, p.hist, N);
     sgsort::radix_sort<unsigned long long, int, true>(L, 1, 0, key_bits, st);
     clock.tick();
     // 5. the representatives

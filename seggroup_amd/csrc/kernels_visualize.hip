@@ -168,8 +168,7 @@ __global__ __launch_bounds__(kBlock) void k_vis_vector_colours(const int32_t* __
 // ascending distinct values of keys[0..n) -> distinct, their number -> *d_count.  a = the keys, b = a second buffer of n
 int sort_unique_keys(uint32_t* a, uint32_t* b, int n, uint32_t* distinct, int* hist, int* scratch, int* d_count, hipStream_t st) {
     using L32 = sgsort::Lists<unsigned int, int>;
-    L32 L{};
-    L.kin[0] = a; L.kout[0] = b; L.hist[0] = hist; L.n[0] = n;
+    L32 L = sgsort::one_list<unsigned int, int>(a, b, nullptr, nullptr, hist, n);
     sgsort::radix_sort<unsigned int, int, false>(L, 1, 0, 32, st);
     sgsort::unique_sorted<unsigned int>(L.kin[0], n, distinct, nullptr, d_count, scratch, st);
     SG_LAUNCH_CHECK();

@@ -32,6 +32,14 @@ struct Lists {                                  // up to two lists sorted side b
     int n[2];
 };
 
+// a single list of n items: keys k0 with the second buffer k1, values v0 / v1 (null for a keys-only sort)
+template <class K, class V>
+Lists<K, V> one_list(const K* k0, K* k1, const V* v0, V* v1, int* hist, int n) {
+    Lists<K, V> L{};
+    L.kin[0] = k0; L.kout[0] = k1; L.vin[0] = v0; L.vout[0] = v1; L.hist[0] = hist; L.n[0] = n;
+    return L;
+}
+
 template <class K>
 __device__ __forceinline__ unsigned digit_of(K k, int shift) { return (unsigned)(k >> shift) & (kRadix - 1); }
 
