@@ -25,12 +25,6 @@ OVERLAPS = np.append(np.arange(0.5, 0.95, 0.05), 0.25)      # the thresholds as 
 DEFAULT_GT_CAP = 256          # ground-truth ids per scene the first call's workspace allows for (ScanNet scenes hold a few dozen)
 
 
-def _check(rc: int) -> int:
-    if rc == hip.SG_EINVAL:
-        raise ValueError(hip.lib().sg_last_error().decode("utf-8", "replace"))
-    return hip.check(rc)
-
-
 def gt_ids(gt: np.ndarray) -> np.ndarray:
     """[V] int64 ground-truth ids of a [V,2] (sem, ins) array; refuses what would be miscounted."""
     gt = np.asarray(gt)
@@ -117,7 +111,7 @@ def _run(call, ws_bytes, B, n_first, v_total, device, gt_cap):
         if rc == hip.SG_ENOMEM and counts[:, 0].max() > gt_cap:
             gt_cap = int(counts[:, 0].max())
             continue
-        _check(rc)
+        hip.check_arg(rc)
         return counts, h_gt, h_first, h_trip
     raise RuntimeError("sg_ap_contingency: ground-truth list did not fit twice")
 
@@ -204,7 +198,7 @@ def fold(cont: Contingency, ins_row: np.ndarray, sem_row: np.ndarray) -> Record:
     match = np.zeros((max(T, 1), 2), np.int32)
     gtrec = np.zeros((max(G, 1), 3), np.int32)
     n = np.zeros(3, np.int64)
-    _check(hip.lib().sg_ap_fold(cont.triples.ctypes.data, T, cont.first_vertex.ctypes.data, n_slots, cont.gt.ctypes.data, G, ins_row.ctypes.data,
+    hip.check_arg(hip.lib().sg_ap_fold(cont.triples.ctypes.data, T, cont.first_vertex.ctypes.data, n_slots, cont.gt.ctypes.data, G, ins_row.ctypes.data,
                                 sem_row.ctypes.data, n_row, pred.ctypes.data, pred.shape[0], match.ctypes.data, match.shape[0],
                                 gtrec.ctypes.data, gtrec.shape[0], n.ctypes.data))
     return Record(pred[:n[0]].copy(), match[:n[1]].copy(), gtrec[:n[2]].copy())
@@ -224,7 +218,7 @@ def match(rec: Record, conf: Optional[np.ndarray] = None, overlaps: np.ndarray =
     cap = max(n * (Gv + M + P), 1)
     y_score, y_true = np.zeros(cap, np.float64), np.zeros(cap, np.uint8)
     y_off, info = np.zeros(len(CLASS_LABELS) * n + 1, np.int64), np.zeros((len(CLASS_LABELS) * n, 3), np.int32)
-    _check(hip.lib().sg_ap_match(rec.pred.ctypes.data, P, rec.match.ctypes.data, M, rec.gtrec.ctypes.data, Gv, None if c is None else c.ctypes.data,
+    hip.check_arg(hip.lib().sg_ap_match(rec.pred.ctypes.data, P, rec.match.ctypes.data, M, rec.gtrec.ctypes.data, Gv, None if c is None else c.ctypes.data,
                                  ov.ctypes.data, n, y_score.ctypes.data, y_true.ctypes.data, cap, y_off.ctypes.data, info.ctypes.data))
     return Matches(y_true[:y_off[-1]], y_score[:y_off[-1]], y_off, info)
 

@@ -40,9 +40,10 @@ from typing import Optional
 
 import numpy as np
 
-from . import hip
+from . import hip, pseudo_labels, scans
+from .device import device_tensor, on_stream, stream_ptr, torch_device, workspace
+from .prepare import mesh_arrays, pointcloud_knn, read_ply, write_ply
 
-MAX_WORKERS = 16
 MAP_SUFFIX = ".clean.npz"
 REPORT_NAME = "clean_report.json"
 KNN_CHOICES = (5, 10, 20)
@@ -81,10 +82,9 @@ def _cloud(xyz, what):
 def radius_stats() -> dict:
     """the calling thread's last radius call (`components(radius=)`, `neighbour_counts`): cells per axis, occupied cells, the largest cell,
     the cell edge, the ring count R of the block a query reads; pair tests and pairs passed are counted in timed calls only"""
-    h = (C.c_int64 * 9)()
-    hip.check(hip.lib().sg_radius_grid_stats(h, 9))
-    return {"cells": [int(h[0]), int(h[1]), int(h[2])], "occupied": int(h[3]), "largest_cell": int(h[4]),
-            "cell": float(np.array([h[5]], np.uint32).view(np.float32)[0]), "R": int(h[6]), "pair_tests": int(h[7]), "pairs_passed": int(h[8])}
+    stats = hip.grid_stats("radius_grid", ("R", "pair_tests", "pairs_passed"), slots=9)
+    stats["cells"] = list(stats["cells"])
+    return stats
 
 
 def neighbour_counts(xyz, radius, cell=0.0, device=None, stream=None):
@@ -94,17 +94,31 @@ def neighbour_counts(xyz, radius, cell=0.0, device=None, stream=None):
     r, c = _radius(radius), hip.knn_cell(cell)
     n = _cloud(xyz, "neighbour_counts")
     import torch
-    from .oversegment import _on, _stream_ptr
-    from .prepare import _dev, _t, _ws
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    with torch.cuda.device(dev), _on(stream):
-        d_xyz = _t(xyz, torch.float32, dev)
+    with torch.cuda.device(dev), on_stream(stream):
+        d_xyz = device_tensor(xyz, torch.float32, dev)
         count = torch.empty(n, dtype=torch.int32, device=dev)
-        ws = _ws(lib.sg_radius_grid_ws_bytes(n), dev)
+        ws = workspace(lib.sg_radius_grid_ws_bytes(n), dev)
         hip.check(lib.sg_radius_count_grid(d_xyz.data_ptr(), int(d_xyz.shape[1]), n, r, c, count.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           _stream_ptr(stream)))
+                                           stream_ptr(stream)))
     return count
+
+
+def radius_pairs(d_xyz, n, r, c, dev, stream):
+    """The query form of sg_radius_neighbours_grid over a device cloud [n, >= 3] -> (T, the number of (ordered) pairs of the radius graph,
+    which is not known before; the rows' offsets int64 [n + 1]).  The library answers SG_ENOMEM with T whenever there is a pair.  The
+    caller holds the device and the stream (`on_stream`)."""
+    import torch
+    lib = hip.lib()
+    indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    total = C.c_int64(0)
+    ws = workspace(lib.sg_radius_neighbours_ws_bytes(n, 0), dev)
+    rc = lib.sg_radius_neighbours_grid(d_xyz.data_ptr(), int(d_xyz.shape[1]), n, r, c, 0, indptr.data_ptr(), None, C.byref(total), ws.data_ptr(),
+                                       ws.numel(), stream_ptr(stream))
+    if rc != hip.SG_ENOMEM or total.value <= 0:
+        hip.check(rc)
+    return int(total.value), indptr
 
 
 def radius_neighbours(xyz, radius, cell=0.0, device=None, stream=None):
@@ -114,26 +128,16 @@ def radius_neighbours(xyz, radius, cell=0.0, device=None, stream=None):
     r, c = _radius(radius), hip.knn_cell(cell)
     n = _cloud(xyz, "radius_neighbours")
     import torch
-    from .oversegment import _on, _stream_ptr
-    from .prepare import _dev, _t, _ws
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    with torch.cuda.device(dev), _on(stream):
-        d_xyz = _t(xyz, torch.float32, dev)
-        stride = int(d_xyz.shape[1])
-        indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        total = C.c_int64(0)
-        ws = _ws(lib.sg_radius_neighbours_ws_bytes(n, 0), dev)
-        rc = lib.sg_radius_neighbours_grid(d_xyz.data_ptr(), stride, n, r, c, 0, indptr.data_ptr(), None, C.byref(total), ws.data_ptr(),
-                                           ws.numel(), _stream_ptr(stream))
-        if rc != hip.SG_ENOMEM or total.value <= 0:          # the query form answers SG_ENOMEM with T whenever there is a pair
-            hip.check(rc)
-        t = int(total.value)
+    with torch.cuda.device(dev), on_stream(stream):
+        d_xyz = device_tensor(xyz, torch.float32, dev)
+        t, indptr = radius_pairs(d_xyz, n, r, c, dev, stream)
         indices = torch.empty(t, dtype=torch.int32, device=dev)
         if t:
-            ws = _ws(lib.sg_radius_neighbours_ws_bytes(n, t), dev)
-            hip.check(lib.sg_radius_neighbours_grid(d_xyz.data_ptr(), stride, n, r, c, t, indptr.data_ptr(), indices.data_ptr(), C.byref(total),
-                                                    ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+            ws = workspace(lib.sg_radius_neighbours_ws_bytes(n, t), dev)
+            hip.check(lib.sg_radius_neighbours_grid(d_xyz.data_ptr(), int(d_xyz.shape[1]), n, r, c, t, indptr.data_ptr(), indices.data_ptr(),
+                                                    C.byref(C.c_int64(0)), ws.data_ptr(), ws.numel(), stream_ptr(stream)))
     return indptr, indices
 
 
@@ -179,31 +183,29 @@ def components(V: int, *, edges=None, faces=None, knn=None, radius=None, xyz=Non
         raise ValueError("components: labels must be [%d], not %r" % (V, tuple(labels.shape)))
 
     import torch
-    from .oversegment import _on, _stream_ptr
-    from .prepare import _dev, _t, _ws
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
     need = lib.sg_radius_grid_ws_bytes(V) if radius is not None else lib.sg_components_ws_bytes(V)
     if need == 0:
         raise hip.SgError(hip.SG_EUNSUP, "components: %d vertices; a graph holds at most 2^27" % V)
-    with torch.cuda.device(dev), _on(stream):
-        d_lab = None if labels is None else _t(labels, torch.int32, dev)
+    with torch.cuda.device(dev), on_stream(stream):
+        d_lab = None if labels is None else device_tensor(labels, torch.int32, dev)
         comp = torch.empty(V, dtype=torch.int32, device=dev)
         size = torch.empty(V, dtype=torch.int32, device=dev)
-        ws = _ws(need, dev)
+        ws = workspace(need, dev)
         c = C.c_int(0)
-        tail = (hip.ptr(d_lab), comp.data_ptr(), size.data_ptr(), C.byref(c), ws.data_ptr(), ws.numel(), _stream_ptr(stream))
+        tail = (hip.ptr(d_lab), comp.data_ptr(), size.data_ptr(), C.byref(c), ws.data_ptr(), ws.numel(), stream_ptr(stream))
         if radius is not None:
-            d_xyz = _t(xyz, torch.float32, dev)
+            d_xyz = device_tensor(xyz, torch.float32, dev)
             rc = lib.sg_components_radius(d_xyz.data_ptr(), int(d_xyz.shape[1]), V, reach, grid_cell, *tail)
         elif edges is not None:
-            d_src = _t(edges, torch.int32, dev)
+            d_src = device_tensor(edges, torch.int32, dev)
             rc = lib.sg_components_edges(d_src.data_ptr() if count else None, count, V, *tail)
         elif faces is not None:
-            d_src = _t(faces, torch.int32, dev)
+            d_src = device_tensor(faces, torch.int32, dev)
             rc = lib.sg_components_faces(d_src.data_ptr() if count else None, count, V, *tail)
         else:
-            d_src, d_xyz = _t(knn, torch.int32, dev), _t(xyz, torch.float32, dev)
+            d_src, d_xyz = device_tensor(knn, torch.int32, dev), device_tensor(xyz, torch.float32, dev)
             rc = lib.sg_components_knn(d_xyz.data_ptr(), int(d_xyz.shape[1]), d_src.data_ptr(), V, row, cut, *tail)
         hip.check(rc)                                            # the call synchronised the stream
     return comp, size, c.value
@@ -238,7 +240,6 @@ def clean_arrays(keep, faces):
 def _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, what, radius=None):
     """-> (source name, keyword arguments of `components`) for a scan's own graph; max_edge is read on the kNN path only, radius takes
     its place (the radius graph)"""
-    from .prepare import pointcloud_knn
     if radius is not None:
         if max_edge is not None:
             raise ValueError(f"{what}: radius and max_edge are two different graphs; give one")
@@ -253,11 +254,6 @@ def _scan_graph(xyz, faces, pointcloud, knn, max_edge, index, what, radius=None)
     return "faces", dict(faces=faces)
 
 
-def _segs_name(scene: str) -> str:
-    from .oversegment import segs_json_name
-    return segs_json_name(scene)
-
-
 def clean_scan(scene_path: str, out_dir: str, min_verts: Optional[int] = None, largest: bool = False, pointcloud: bool = False, knn: int = 10,
                max_edge: Optional[float] = None, index: str = "grid", force: bool = False, device=None, stream=None,
                report_only: bool = False, radius: Optional[float] = None, min_neighbours: Optional[int] = None) -> Optional[dict]:
@@ -267,10 +263,9 @@ def clean_scan(scene_path: str, out_dir: str, min_verts: Optional[int] = None, l
     min_verts / largest are then optional): keep a vertex only if that many points lie within `radius` of it and its component in the
     radius graph over ALL points passes the size rule, when one is given."""
     import torch
-    from .prepare import _scene_name, mesh_arrays, read_ply, write_ply
     _check_rules("clean_scan", min_verts, largest, radius, min_neighbours)
     hip.knn_index(index)
-    scene = _scene_name(scene_path)
+    scene = scans.scene_name(scene_path)
     dst = os.path.join(out_dir, scene)
     ply_out = os.path.join(dst, scene + "_vh_clean_2.ply")
     if not report_only and os.path.exists(ply_out) and not force:
@@ -301,7 +296,7 @@ def clean_scan(scene_path: str, out_dir: str, min_verts: Optional[int] = None, l
         entry.update(radius=float(radius), R=stats["R"], cell=stats["cell"], dropped={"size": by_size})
         if d_count is not None:
             entry["dropped"]["min_neighbours"] = by_count
-    segs = os.path.join(scene_path, _segs_name(scene))
+    segs = os.path.join(scene_path, scans.segs_json_name(scene))
     doc = None
     if os.path.exists(segs):
         with open(segs) as f:
@@ -325,7 +320,7 @@ def clean_scan(scene_path: str, out_dir: str, min_verts: Optional[int] = None, l
              largest=np.bool_(largest), source=np.str_(source), knn=np.int32(knn if source == "knn" else 0),
              max_edge=np.float32(np.inf if max_edge is None else max_edge), **extra)
     if doc is not None:
-        with open(os.path.join(dst, _segs_name(scene)), "w") as f:
+        with open(os.path.join(dst, scans.segs_json_name(scene)), "w") as f:
             json.dump(doc, f)
     agg = os.path.join(scene_path, scene + ".aggregation.json")
     if os.path.exists(agg):
@@ -346,43 +341,19 @@ def _check_rules(who, min_verts, largest, radius, min_neighbours):
         raise ValueError(f"{who}: at most one of min_verts and largest")
 
 
-def _scan_names(scans_dir: str):
-    return sorted(d for d in os.listdir(scans_dir) if os.path.exists(os.path.join(scans_dir, d, d + "_vh_clean_2.ply")))
-
-
-def _threads(scenes, workers, dev, fn):
-    """fn(scene, stream) over the scenes on threads with a stream each -> [(scene, result)] in the scenes' order"""
-    import concurrent.futures
-    import threading
-
-    import torch
-    workers = max(1, min(int(workers), MAX_WORKERS, max(len(scenes), 1)))
-    local = threading.local()
-
-    def one(scene):
-        if not hasattr(local, "stream"):
-            with torch.cuda.device(dev):
-                local.stream = torch.cuda.Stream(device=dev)
-        return scene, fn(scene, local.stream)
-
-    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
-        return list(pool.map(one, scenes))
-
-
 def clean_scans(scans_dir: str, out_dir: str, min_verts: Optional[int] = None, largest: bool = False, pointcloud: bool = False, knn: int = 10,
                 max_edge: Optional[float] = None, index: str = "grid", scenes=None, force: bool = False, workers: int = 4, device=None,
                 report_only: bool = False, radius: Optional[float] = None, min_neighbours: Optional[int] = None):
     """Every scan directory under `scans_dir` (or the named ones) -> (report {scene: entry}, skipped scene names); writes
     <out_dir>/clean_report.json.  Workers are threads, each with its own stream."""
-    from .prepare import _dev
     _check_rules("clean_scans", min_verts, largest, radius, min_neighbours)
-    dev = _dev(device)
+    dev = torch_device(device)
     if scenes is None:
-        scenes = _scan_names(scans_dir)
-    done = _threads(scenes, workers, dev, lambda scene, stream: clean_scan(os.path.join(scans_dir, scene), out_dir, min_verts, largest, pointcloud,
-                                                                           knn, max_edge, index, force, device=dev, stream=stream,
-                                                                           report_only=report_only, radius=radius,
-                                                                           min_neighbours=min_neighbours))
+        scenes = scans.scan_names(scans_dir)
+    done = scans.map_scans(scenes, workers, dev, lambda scene, stream: clean_scan(os.path.join(scans_dir, scene), out_dir, min_verts, largest,
+                                                                                  pointcloud, knn, max_edge, index, force, device=dev,
+                                                                                  stream=stream, report_only=report_only, radius=radius,
+                                                                                  min_neighbours=min_neighbours))
     report = {scene: entry for scene, entry in done if entry is not None}
     skipped = [scene for scene, entry in done if entry is None]
     os.makedirs(out_dir, exist_ok=True)
@@ -391,9 +362,7 @@ def clean_scans(scans_dir: str, out_dir: str, min_verts: Optional[int] = None, l
            "scenes": report, "skipped": skipped}
     if radius is not None:
         doc.update(radius=float(radius), min_neighbours=None if min_neighbours is None else int(min_neighbours))
-    with open(os.path.join(out_dir, REPORT_NAME), "w") as f:
-        json.dump(doc, f, indent=1, sort_keys=True)
-        f.write("\n")
+    scans.write_report(os.path.join(out_dir, REPORT_NAME), doc)
     return report, skipped
 
 
@@ -423,9 +392,7 @@ def fragments_scene(scene_path: str, exp: str, stage: str, layer: str = "final",
                     max_edge: Optional[float] = None, index: str = "grid", device=None, stream=None, radius: Optional[float] = None) -> dict:
     """`fragments` of one scene's `<layer>.ins` vector on the scan's own graph (its faces, its kNN graph cut at max_edge, or its radius
     graph)"""
-    from . import pseudo_labels
-    from .prepare import _scene_name, mesh_arrays, read_ply
-    scene = _scene_name(scene_path)
+    scene = scans.scene_name(scene_path)
     lab = pseudo_labels.load(os.path.join(root, "results", exp, scene, stage)).vector(layer + ".ins")
     xyz, _, faces = mesh_arrays(read_ply(os.path.join(scene_path, scene + "_vh_clean_2.ply")))
     if lab.shape[0] != xyz.shape[0]:
@@ -439,20 +406,12 @@ def fragments_scene(scene_path: str, exp: str, stage: str, layer: str = "final",
 
 def fragments_scans(scans_dir: str, exp: str, stage: str, layer: str = "final", root: str = ".", scenes=None, workers: int = 4, device=None,
                     **graph) -> dict:
-    from .prepare import _dev
-    dev = _dev(device)
+    dev = torch_device(device)
     if scenes is None:
         base = os.path.join(root, "results", exp)
-        scenes = [s for s in _scan_names(scans_dir) if os.path.isdir(os.path.join(base, s, stage))]
-    return dict(_threads(scenes, workers, dev, lambda scene, stream: fragments_scene(os.path.join(scans_dir, scene), exp, stage, layer, root,
-                                                                                     device=dev, stream=stream, **graph)))
-
-
-def _scene_list(path):
-    if not path:
-        return None
-    with open(path) as f:
-        return [ln.strip() for ln in f if ln.strip()]
+        scenes = [s for s in scans.scan_names(scans_dir) if os.path.isdir(os.path.join(base, s, stage))]
+    return dict(scans.map_scans(scenes, workers, dev, lambda scene, stream: fragments_scene(os.path.join(scans_dir, scene), exp, stage, layer, root,
+                                                                                            device=dev, stream=stream, **graph)))
 
 
 def _positive(text):
@@ -463,22 +422,20 @@ def _positive(text):
 
 
 def _needs_max_edge(scans_dir, scenes, pointcloud):
-    from .oversegment import _declared_faces
     if pointcloud:
         return "--pointcloud"
     for s in scenes:
-        if _declared_faces(os.path.join(scans_dir, s, s + "_vh_clean_2.ply")) == 0:
+        if scans.declared_faces(os.path.join(scans_dir, s, s + "_vh_clean_2.ply")) == 0:
             return "%s has no faces and" % s
     return None
 
 
 def _radius_needs_clouds(ap, scans_dir, scenes, pointcloud):
     """--radius is the graph of a scan without faces (or of --pointcloud): a mesh in the list is a parser error, not a silent switch"""
-    from .oversegment import _declared_faces
     if pointcloud:
         return
     for s in scenes:
-        if _declared_faces(os.path.join(scans_dir, s, s + "_vh_clean_2.ply")) != 0:
+        if scans.declared_faces(os.path.join(scans_dir, s, s + "_vh_clean_2.ply")) != 0:
             ap.error(f"--radius belongs to a scan without faces: {s} is a mesh (--pointcloud ignores the faces)")
 
 
@@ -498,7 +455,7 @@ def main(argv=None) -> int:
     ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
     ap.add_argument("--force", action="store_true", help="overwrite existing cleaned scans")
     ap.add_argument("--report-only", action="store_true", help="write clean_report.json and no scan")
-    ap.add_argument("--workers", type=int, default=4, help=f"threads, each with its own stream (at most {MAX_WORKERS})")
+    scans.add_workers_argument(ap)
     ap.add_argument("--device", default=None)
     ap.add_argument("--fragments", action="store_true", help="report the pseudo instances that are in more than one piece")
     ap.add_argument("-n", "--exp_name", default=None, help="--fragments: name of the experiment")
@@ -507,9 +464,8 @@ def main(argv=None) -> int:
     ap.add_argument("--root", default=".", help="--fragments: directory holding results/ (default: CWD)")
     ap.add_argument("--json", default=None, help="--fragments: write the report here as well")
     a = ap.parse_args(argv)
-    if not 1 <= a.workers <= MAX_WORKERS:
-        ap.error(f"--workers must be in 1..{MAX_WORKERS}")
-    scenes = _scene_list(a.scenes)
+    scans.check_workers(ap, a.workers)
+    scenes = scans.scene_list(a.scenes)
     if a.radius is not None and a.max_edge is not None:
         ap.error("--radius and --max-edge are two different graphs: give one")
     if a.min_neighbours is not None:
@@ -524,7 +480,7 @@ def main(argv=None) -> int:
             ap.error("--fragments is a report: --min-verts / --largest belong to cleaning")
         if a.min_neighbours is not None:
             ap.error("--fragments is a report: --min-neighbours belongs to cleaning")
-        names = scenes if scenes is not None else [s for s in _scan_names(a.scans)
+        names = scenes if scenes is not None else [s for s in scans.scan_names(a.scans)
                                                    if os.path.isdir(os.path.join(a.root, "results", a.exp_name, s, a.stage))]
         why = _needs_max_edge(a.scans, names, a.pointcloud)
         if a.radius is not None:
@@ -539,9 +495,7 @@ def main(argv=None) -> int:
         for scene, e in rep.items():
             print("fragments", scene, e["instances"], "instances,", e["fragmented"], "in pieces,", "%.4f" % e["outside_share"], "outside")
         if a.json:
-            with open(a.json, "w") as f:
-                json.dump({"exp": a.exp_name, "stage": a.stage, "layer": a.layer, "scenes": rep}, f, indent=1, sort_keys=True)
-                f.write("\n")
+            scans.write_report(a.json, {"exp": a.exp_name, "stage": a.stage, "layer": a.layer, "scenes": rep})
         return 0
     if not a.out:
         ap.error("cleaning needs --out DIR")
@@ -551,7 +505,7 @@ def main(argv=None) -> int:
         ap.error("at most one of --min-verts M and --largest")
     if a.min_verts is not None and a.min_verts < 1:
         ap.error("--min-verts must be at least 1")
-    names = scenes if scenes is not None else _scan_names(a.scans)
+    names = scenes if scenes is not None else scans.scan_names(a.scans)
     why = _needs_max_edge(a.scans, names, a.pointcloud)
     if a.radius is not None:
         _radius_needs_clouds(ap, a.scans, names, a.pointcloud)

@@ -8,6 +8,8 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
+import struct
+import types
 from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -410,6 +412,54 @@ def check(rc: int) -> int:
     if rc < 0:
         raise SgError(rc, lib().sg_last_error().decode("utf-8", "replace"))
     return rc
+
+
+def check_arg(rc: int) -> int:
+    """check, with SG_EINVAL (a bad file, label or argument) raised as ValueError."""
+    if rc == SG_EINVAL:
+        raise ValueError(lib().sg_last_error().decode("utf-8", "replace"))
+    return check(rc)
+
+
+def grid_stats(family: str, tail, slots: int = 16) -> dict:
+    """The record sg_<family>_stats leaves of the calling thread's last grid call, read into `slots` int64s: cells per axis, occupied
+    cells, the largest cell and the cell edge (fp32 bits) in every family, then the three counters the family names in `tail`."""
+    h = (C.c_int64 * slots)()
+    check(getattr(lib(), f"sg_{family}_stats")(h, slots))
+    out = dict(cells=(int(h[0]), int(h[1]), int(h[2])), occupied=int(h[3]), largest_cell=int(h[4]),
+               cell=struct.unpack("<f", struct.pack("<I", h[5]))[0])
+    out.update(zip(tail, (int(h[6]), int(h[7]), int(h[8]))))
+    return out
+
+
+STAGE_FAMILIES = ("overseg", "pcseg", "cloud_thin", "pointcloud_knn_grid", "nearest_point_grid", "components", "radius_grid", "pcseg_radius",
+                  "segment_vote")
+
+
+@contextlib.contextmanager
+def stage_timer(family: str):
+    """The calling thread's stage timer of one of STAGE_FAMILIES, on inside the block and off after it whatever happens:
+
+        with hip.stage_timer("pcseg") as t:
+            call(); rows.append(t.read())        # microseconds per stage of the last timed call, one per name in t.names
+    """
+    l = lib()
+    set_timing, times, name = (getattr(l, f"sg_{family}_{f}") for f in ("set_timing", "stage_times", "stage_name"))
+    names = []
+    while name(len(names)) is not None:
+        names.append(name(len(names)).decode())
+    buf = (C.c_float * len(names))()
+
+    def read():
+        if check(times(buf, len(names))) != len(names):
+            raise RuntimeError(f"sg_{family}_stage_times: {len(names)} stages have a name, and another number came back")
+        return list(buf)
+
+    check(set_timing(1))
+    try:
+        yield types.SimpleNamespace(names=names, read=read)
+    finally:
+        check(set_timing(0))
 
 
 def require_device() -> None:

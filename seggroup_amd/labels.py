@@ -17,11 +17,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from . import hip
-
-
-def _scene_name(scene_path: str) -> str:
-    return os.path.split(scene_path[:-1] if scene_path.endswith("/") else scene_path)[-1]
+from . import hip, scans
 
 
 def _write_txt(path: str, values) -> None:
@@ -42,7 +38,7 @@ def load_labels(label_path):
     raise SystemExit(1)
 
 
-def load_seg_labels(label_file):
+def load_seg_labels(label_file):                               # util.py:95-100
     with open(label_file, 'r') as f:
         return json.load(f)["segIndices"]
 
@@ -71,7 +67,7 @@ def load_aggregation(aggregation_file, mapper):
 def generate_real_labels(scene_path, root: str = "."):
     """util.py:129-170: label/real/raw/<s>/<s>.{ins,sem}.txt -- per vertex, 0 = unlabeled"""
     scene_path = scene_path[:-1] if scene_path.endswith('/') else scene_path
-    name = _scene_name(scene_path)
+    name = scans.scene_name(scene_path)
     seg = np.asarray(load_seg_labels(os.path.join(scene_path, name + '_vh_clean_2.0.010000.segs.json')), dtype=np.int64)
     mapper = read_label_mapper(os.path.join('/'.join(scene_path.split('/')[:-2]), 'scannetv2-labels.combined.tsv'))
     seg2ins, seg2sem = load_aggregation(os.path.join(scene_path, name + '.aggregation.json'), mapper)
@@ -125,7 +121,7 @@ def generate_weak_labels(scene_path, plydata=None, label_style='manual', manual_
     """util.py:268-427: label/seg/<style>/raw/<s>/<s>.{ins,sem}.txt (-1 = no click on the vertex's segment) ->
     (labeled vertices, vertices, clicked segments, segments, instances)"""
     scene_path = scene_path[:-1] if scene_path.endswith('/') else scene_path
-    name = _scene_name(scene_path)
+    name = scans.scene_name(scene_path)
     raw = os.path.join(root, 'label', 'real', 'raw', name)
     ins_labels = np.array(load_labels(os.path.join(raw, name + '.ins.txt')))
     sem_labels = np.array(load_labels(os.path.join(raw, name + '.sem.txt')))
@@ -199,7 +195,7 @@ def generate_weak_labels(scene_path, plydata=None, label_style='manual', manual_
 def generate_real_label_pth(scene_path, root: str = "."):
     """util.py:697-729: label/real/raw/<s>/<s>.label.pth = LongTensor [V,2] (sem, ins), 0 = unlabeled"""
     import torch
-    name = _scene_name(scene_path)
+    name = scans.scene_name(scene_path)
     raw = os.path.join(root, 'label', 'real', 'raw', name)
     ins = np.array(load_labels(os.path.join(raw, name + '.ins.txt')), dtype=np.int64)
     sem = np.array(load_labels(os.path.join(raw, name + '.sem.txt')), dtype=np.int64)

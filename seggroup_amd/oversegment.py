@@ -37,32 +37,17 @@ from typing import Optional
 
 import numpy as np
 
-from . import hip
-
-MAX_WORKERS = 16
-
-
-def segs_json_name(scene_name: str, k_thresh: float = 0.01) -> str:
-    return "%s_vh_clean_2.%f.segs.json" % (scene_name, float(np.float32(k_thresh)))
-
-
-def _stream_ptr(stream):
-    return None if stream is None else stream.cuda_stream
-
-
-def _on(stream):
-    """The caller's stream as torch's current one (uploads, allocations and the library's launches share it), behind whatever the
-    current stream has queued."""
-    import torch
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-    return torch.cuda.stream(stream)
+from . import hip, scans
+from .components import radius_neighbours, radius_pairs
+from .device import device_cloud, device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
+from .prepare import mesh_arrays, pointcloud_knn, read_ply
+from .scans import segs_json_name  # noqa: F401  (the name is made here; every reader of a scan tree finds it in scans.py)
+from .thin import thin_cloud
 
 
 def _mesh_tensors(xyz, faces, dev):
     import torch
-    from .prepare import _t
-    d_xyz, d_f = _t(xyz, torch.float32, dev), _t(faces, torch.int32, dev)
+    d_xyz, d_f = device_tensor(xyz, torch.float32, dev), device_tensor(faces, torch.int32, dev)
     if d_xyz.dim() != 2 or d_xyz.shape[1] != 3 or d_f.dim() != 2 or d_f.shape[1] != 3:
         raise ValueError("oversegment: xyz must be [V,3] and faces [F,3]")
     if d_xyz.shape[0] < 1:
@@ -74,21 +59,20 @@ def device_edges(xyz, faces, device=None, stream=None, want_face_normals: bool =
     """The device stages of one mesh -> dict(face_normals [F,3] | None, normals [V,3], edges [E,2] i32, w [E]) of device tensors:
     the unique undirected edges in ascending (w, a, b)."""
     import torch
-    from .prepare import _dev, _ws
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    with torch.cuda.device(dev), _on(stream):
+    with torch.cuda.device(dev), on_stream(stream):
         d_xyz, d_f, v, f = _mesh_tensors(xyz, faces, dev)
         fn = torch.empty((f, 3), dtype=torch.float32, device=dev) if want_face_normals else None
         nrm = torch.empty((v, 3), dtype=torch.float32, device=dev)
         edges = torch.empty((max(3 * f, 1), 2), dtype=torch.int32, device=dev)
         w = torch.empty(max(3 * f, 1), dtype=torch.float32, device=dev)
-        ws = _ws(lib.sg_overseg_ws_bytes(v, f), dev)
+        ws = workspace(lib.sg_overseg_ws_bytes(v, f), dev)
         n_e = C.c_int(0)
         hip.check(lib.sg_overseg_edges(d_xyz.data_ptr(), v, d_f.data_ptr() if f else None, f, fn.data_ptr() if fn is not None and f else None,
                                        nrm.data_ptr(), edges.data_ptr(), w.data_ptr(), C.byref(n_e), ws.data_ptr(), ws.numel(),
-                                       _stream_ptr(stream)))
-        (stream.synchronize() if stream is not None else torch.cuda.synchronize())
+                                       stream_ptr(stream)))
+        sync(stream)
     return dict(face_normals=fn, normals=nrm, edges=edges[:n_e.value], w=w[:n_e.value])
 
 
@@ -118,27 +102,19 @@ def merge_edges(edges, w, num_vertices: int, k_thresh: float = 0.01, seg_min_ver
 def segment_mesh(xyz, faces, k_thresh: float = 0.01, seg_min_verts: int = 20, device=None, stream=None) -> np.ndarray:
     """-> int32 [V]: seg_indices[v] = the lowest vertex index of v's segment (non-contiguous ids, like ScanNet's)."""
     import torch
-    from .prepare import _dev, _ws
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    with torch.cuda.device(dev), _on(stream):
+    with torch.cuda.device(dev), on_stream(stream):
         d_xyz, d_f, v, f = _mesh_tensors(xyz, faces, dev)
         out = np.empty(v, dtype=np.int32)
-        ws = _ws(lib.sg_overseg_ws_bytes(v, f), dev)
+        ws = workspace(lib.sg_overseg_ws_bytes(v, f), dev)
         hip.check(lib.sg_overseg_scan(d_xyz.data_ptr(), v, d_f.data_ptr() if f else None, f, float(k_thresh), int(seg_min_verts),
-                                      out.ctypes.data if v else None, ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+                                      out.ctypes.data if v else None, ws.data_ptr(), ws.numel(), stream_ptr(stream)))
     return out
 
 
 def _cloud_tensor(xyz, dev):
-    import torch
-    from .prepare import _t
-    d_xyz = _t(xyz, torch.float32, dev)
-    if d_xyz.dim() != 2 or d_xyz.shape[1] != 3:
-        raise ValueError("oversegment: xyz must be [N,3]")
-    if d_xyz.shape[0] < 1:
-        raise ValueError("oversegment: a cloud needs at least one point")
-    return d_xyz, int(d_xyz.shape[0])
+    return device_cloud(xyz, dev, "oversegment", exact=True)
 
 
 def _viewpoint(viewpoint):
@@ -155,10 +131,7 @@ def knn_grid_stats() -> dict:
     """What the calling thread's last grid-indexed kNN did: cells per axis, occupied cells, the largest cell, the cell edge
     used, the largest ring count of a query the rings settled, the queries finished against the whole cloud, and the pair scores
     evaluated (counted in timed calls only)."""
-    h = (C.c_int64 * 16)()
-    hip.check(hip.lib().sg_pointcloud_knn_grid_stats(h, 16))
-    return dict(cells=(int(h[0]), int(h[1]), int(h[2])), occupied=int(h[3]), largest_cell=int(h[4]),
-                cell=float(np.array([h[5]], dtype=np.uint32).view(np.float32)[0]), max_ring=int(h[6]), fallback=int(h[7]), scores=int(h[8]))
+    return hip.grid_stats("pointcloud_knn_grid", ("max_ring", "fallback", "scores"))
 
 
 def _radius_only(who, radius, k=10, index="brute", knn=None):
@@ -179,43 +152,21 @@ def _radius_only(who, radius, k=10, index="brute", knn=None):
     return r
 
 
-def _query_pairs(lib, d_xyz, n, r, edge, dev, stream):
-    """-> T, the number of (ordered) pairs of the radius graph: the query form of sg_radius_neighbours_grid"""
-    import torch
-    from .prepare import _ws
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    total = C.c_int64(0)
-    ws = _ws(lib.sg_radius_neighbours_ws_bytes(n, 0), dev)
-    if ws.numel() == 0:                                        # outside the envelope: refused before anything is touched
-        hip.check(lib.sg_radius_neighbours_grid(None, 3, n, r, edge, 0, None, None, C.byref(total), None, 0, None))
-    rc = lib.sg_radius_neighbours_grid(d_xyz.data_ptr(), 3, n, r, edge, 0, off.data_ptr(), None, C.byref(total), ws.data_ptr(), ws.numel(),
-                                       _stream_ptr(stream))
-    if rc != hip.SG_ENOMEM or total.value <= 0:
-        hip.check(rc)
-    return int(total.value)
-
-
-def _pointcloud_edges_radius(xyz, r, viewpoint, device, stream, cell):
-    import torch
-    from .prepare import _dev, _ws
-    edge = hip.knn_cell(cell)
-    dev = _dev(device)
+def _graph_source(what, d_xyz, n, k, which, edge, r, dev, stream):
+    """The three graphs a cloud is segmented over -- brute-force kNN, grid kNN, radius -- stated once for sg_pcseg_edges* and
+    sg_pcseg_scan* (`what`: "edges" or "scan").  Every entry point reads (xyz, n, *head, viewpoint, *mid, its outputs, *tail, ws,
+    ws_bytes, stream).  -> (the entry point, head, mid, tail, workspace bytes, T: the radius graph's pair count, 0 for kNN).  A cloud
+    outside the grid's envelope is refused here, in the library's words, before anything is allocated."""
     lib = hip.lib()
-    with torch.cuda.device(dev), _on(stream):
-        d_xyz, n = _cloud_tensor(xyz, dev)
-        t = _query_pairs(lib, d_xyz, n, r, edge, dev, stream)
-        indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        indices = torch.empty(max(t, 1), dtype=torch.int32, device=dev)
-        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        edges = torch.empty((max(t // 2, 1), 2), dtype=torch.int32, device=dev)
-        w = torch.empty(max(t // 2, 1), dtype=torch.float32, device=dev)
-        n_e, total = C.c_int(0), C.c_int64(0)
-        ws = _ws(lib.sg_pcseg_ws_bytes_radius(n, t), dev)
-        hip.check(lib.sg_pcseg_edges_radius(d_xyz.data_ptr(), n, r, edge, t, _viewpoint(viewpoint), indptr.data_ptr(), indices.data_ptr(),
-                                            nrm.data_ptr(), edges.data_ptr(), w.data_ptr(), C.byref(n_e), C.byref(total), ws.data_ptr(),
-                                            ws.numel(), _stream_ptr(stream)))
-        (stream.synchronize() if stream is not None else torch.cuda.synchronize())
-    return dict(indptr=indptr, indices=indices[:t], normals=nrm, edges=edges[:n_e.value], w=w[:n_e.value])
+    if r is not None:
+        t = radius_pairs(d_xyz, n, r, edge, dev, stream)[0]
+        return getattr(lib, f"sg_pcseg_{what}_radius"), (r, edge, t), (), (C.byref(C.c_int64(0)),), lib.sg_pcseg_ws_bytes_radius(n, t), t
+    if which == hip.KNN_GRID:
+        need = lib.sg_pcseg_ws_bytes_indexed(n, k, which) if n <= hip.MAX_GRID_POINTS else 0
+        if need == 0:
+            hip.check(lib.sg_pointcloud_knn_grid(None, 3, n, k, edge, None, None, 0, None))
+        return getattr(lib, f"sg_pcseg_{what}_indexed"), (k,), (which, edge), (), need, 0
+    return getattr(lib, f"sg_pcseg_{what}"), (k,), (), (), lib.sg_pcseg_ws_bytes(n, k), 0
 
 
 def pointcloud_edges(xyz, k: int = 10, viewpoint=None, device=None, stream=None, index: str = "brute", cell=None, radius=None):
@@ -228,34 +179,30 @@ def pointcloud_edges(xyz, k: int = 10, viewpoint=None, device=None, stream=None,
     edges, w): every point's neighbours within R in ascending index, the normals over those neighbourhoods, the pairs a < b of the
     graph in ascending (w, a, b).  `cell` forces the grid's cell edge and cannot change a byte."""
     import torch
-    from .prepare import _dev, _ws
     r = _radius_only("pointcloud_edges", radius, k, index)
-    if r is not None:
-        return _pointcloud_edges_radius(xyz, r, viewpoint, device, stream, cell)
     which, edge = hip.knn_index(index), hip.knn_cell(cell)
-    dev = _dev(device)
-    lib = hip.lib()
+    dev = torch_device(device)
     k = int(k)
-    with torch.cuda.device(dev), _on(stream):
+    with torch.cuda.device(dev), on_stream(stream):
         d_xyz, n = _cloud_tensor(xyz, dev)
-        if which == hip.KNN_GRID:
-            if n > hip.MAX_GRID_POINTS or lib.sg_pcseg_ws_bytes_indexed(n, k, which) == 0:      # refused before anything is allocated
-                hip.check(lib.sg_pointcloud_knn_grid(None, 3, n, k, edge, None, None, 0, None))
-        knn = torch.empty((n, k + 1), dtype=torch.int32, device=dev)
-        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        edges = torch.empty((max(n * k, 1), 2), dtype=torch.int32, device=dev)
-        w = torch.empty(max(n * k, 1), dtype=torch.float32, device=dev)
-        n_e = C.c_int(0)
-        if which == hip.KNN_GRID:
-            ws = _ws(lib.sg_pcseg_ws_bytes_indexed(n, k, which), dev)
-            hip.check(lib.sg_pcseg_edges_indexed(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), which, edge, knn.data_ptr(), nrm.data_ptr(),
-                                                 edges.data_ptr(), w.data_ptr(), C.byref(n_e), ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+        call, head, mid, tail, need, t = _graph_source("edges", d_xyz, n, k, which, edge, r, dev, stream)
+        if r is not None:                                           # the rows of the graph: CSR lists, or the kNN table
+            rows = dict(indptr=torch.empty(n + 1, dtype=torch.int64, device=dev), indices=torch.empty(max(t, 1), dtype=torch.int32, device=dev))
+            cap = max(t // 2, 1)
         else:
-            ws = _ws(lib.sg_pcseg_ws_bytes(n, k), dev)
-            hip.check(lib.sg_pcseg_edges(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), knn.data_ptr(), nrm.data_ptr(), edges.data_ptr(),
-                                         w.data_ptr(), C.byref(n_e), ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
-        (stream.synchronize() if stream is not None else torch.cuda.synchronize())
-    return dict(knn=knn, normals=nrm, edges=edges[:n_e.value], w=w[:n_e.value])
+            rows = dict(knn=torch.empty((n, k + 1), dtype=torch.int32, device=dev))
+            cap = max(n * k, 1)
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        edges = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+        w = torch.empty(cap, dtype=torch.float32, device=dev)
+        n_e = C.c_int(0)
+        ws = workspace(need, dev)
+        hip.check(call(d_xyz.data_ptr(), n, *head, _viewpoint(viewpoint), *mid, *[x.data_ptr() for x in rows.values()], nrm.data_ptr(),
+                       edges.data_ptr(), w.data_ptr(), C.byref(n_e), *tail, ws.data_ptr(), ws.numel(), stream_ptr(stream)))
+        sync(stream)
+    if r is not None:
+        rows["indices"] = rows["indices"][:t]
+    return dict(rows, normals=nrm, edges=edges[:n_e.value], w=w[:n_e.value])
 
 
 def pointcloud_normals(xyz, k: int = 10, viewpoint=None, knn=None, device=None, radius=None, lists=None):
@@ -265,38 +212,36 @@ def pointcloud_normals(xyz, k: int = 10, viewpoint=None, knn=None, device=None, 
     `radius=R` (instead of `k` and `knn`): the neighbourhood of a point is the point and every other point within R.
     `lists=(indptr, indices)`: a caller's rows in place of `components.radius_neighbours(xyz, R)`; they are checked on the device."""
     import torch
-    from .prepare import _dev, _t, _ws, pointcloud_knn
     r = _radius_only("pointcloud_normals", radius, k, "brute", knn)
     if lists is not None and r is None:
         raise ValueError("pointcloud_normals: lists belong to the radius form")
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
     k = int(k)
     with torch.cuda.device(dev):
         d_xyz, n = _cloud_tensor(xyz, dev)
         if r is not None:
             if lists is None:
-                from .components import radius_neighbours
                 lists = radius_neighbours(d_xyz, r, device=dev)
-            indptr, indices = _t(lists[0], torch.int64, dev), _t(lists[1], torch.int32, dev)
+            indptr, indices = device_tensor(lists[0], torch.int64, dev), device_tensor(lists[1], torch.int32, dev)
             if indptr.dim() != 1 or indptr.shape[0] != n + 1 or indices.dim() != 1:
                 raise ValueError("pointcloud_normals: lists are (indptr [N + 1], indices [T])")
             if int(indptr[-1]) != indices.shape[0]:
                 raise ValueError("pointcloud_normals: indptr[N] = %d, and indices holds %d entries" % (int(indptr[-1]), indices.shape[0]))
             nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            ws = _ws(lib.sg_pointcloud_knn_ws_bytes(n), dev)
+            ws = workspace(lib.sg_pointcloud_knn_ws_bytes(n), dev)
             hip.check(lib.sg_pointcloud_normals_csr(d_xyz.data_ptr(), n, indptr.data_ptr(), indices.data_ptr() if indices.numel() else None,
                                                     _viewpoint(viewpoint), nrm.data_ptr(), ws.data_ptr(), ws.numel(), None))
-            torch.cuda.synchronize()
+            sync(None)
             return nrm
-        table = pointcloud_knn(d_xyz, k, device=dev) if knn is None else _t(knn, torch.int32, dev)
+        table = pointcloud_knn(d_xyz, k, device=dev) if knn is None else device_tensor(knn, torch.int32, dev)
         if table.dim() != 2 or tuple(table.shape) != (n, k + 1):
             raise ValueError("pointcloud_normals: knn must be [N, k+1]")
         nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        ws = _ws(lib.sg_pointcloud_knn_ws_bytes(n), dev)
+        ws = workspace(lib.sg_pointcloud_knn_ws_bytes(n), dev)
         hip.check(lib.sg_pointcloud_normals(d_xyz.data_ptr(), n, table.data_ptr(), k, _viewpoint(viewpoint), nrm.data_ptr(), ws.data_ptr(),
                                             ws.numel(), None))
-        torch.cuda.synchronize()
+        sync(None)
     return nrm
 
 
@@ -316,42 +261,27 @@ def segment_pointcloud(xyz, k: int = 10, k_thresh: float = 0.01, seg_min_verts: 
     normals over those neighbourhoods.  That is the graph for a cloud with more than k points inside the neighbourhood scale (near the
     scanner, overlapping sweeps, an unthinned cloud), where the kNN graph has no edge out of a clump.  `voxel` combines as with kNN."""
     import torch
-    from .prepare import _dev, _ws
     r = _radius_only("segment_pointcloud", radius, k, index)
     which, edge = hip.knn_index(index), hip.knn_cell(cell)
-    dev = _dev(device)
-    lib = hip.lib()
+    dev = torch_device(device)
     k = int(k)
     if voxel is not None:
-        from .thin import thin_cloud
-        with torch.cuda.device(dev), _on(stream):
+        with torch.cuda.device(dev), on_stream(stream):
             d_all = _cloud_tensor(xyz, dev)[0]
         rep, top, _ = thin_cloud(d_all, voxel, device=dev, stream=stream)
-        with torch.cuda.device(dev), _on(stream):
+        with torch.cuda.device(dev), on_stream(stream):
             d_thin = d_all.index_select(0, rep.long())
         seg_thin = segment_pointcloud(d_thin, k, k_thresh, seg_min_verts, viewpoint=viewpoint, device=dev, stream=stream, index=index, cell=cell,
                                       radius=radius)
         rep_h = rep.cpu().numpy()
         return np.ascontiguousarray(rep_h[seg_thin[top.cpu().numpy()]], dtype=np.int32)
-    with torch.cuda.device(dev), _on(stream):
+    with torch.cuda.device(dev), on_stream(stream):
         d_xyz, n = _cloud_tensor(xyz, dev)
         out = np.empty(n, dtype=np.int32)
-        if r is not None:
-            t = _query_pairs(lib, d_xyz, n, r, edge, dev, stream)
-            total = C.c_int64(0)
-            ws = _ws(lib.sg_pcseg_ws_bytes_radius(n, t), dev)
-            hip.check(lib.sg_pcseg_scan_radius(d_xyz.data_ptr(), n, r, edge, t, _viewpoint(viewpoint), float(k_thresh), int(seg_min_verts),
-                                               out.ctypes.data, C.byref(total), ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
-        elif which == hip.KNN_GRID:
-            if n > hip.MAX_GRID_POINTS or lib.sg_pcseg_ws_bytes_indexed(n, k, which) == 0:      # refused before anything is allocated
-                hip.check(lib.sg_pointcloud_knn_grid(None, 3, n, k, edge, None, None, 0, None))
-            ws = _ws(lib.sg_pcseg_ws_bytes_indexed(n, k, which), dev)
-            hip.check(lib.sg_pcseg_scan_indexed(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), which, edge, float(k_thresh), int(seg_min_verts),
-                                                out.ctypes.data, ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
-        else:
-            ws = _ws(lib.sg_pcseg_ws_bytes(n, k), dev)
-            hip.check(lib.sg_pcseg_scan(d_xyz.data_ptr(), n, k, _viewpoint(viewpoint), float(k_thresh), int(seg_min_verts), out.ctypes.data,
-                                        ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
+        call, head, mid, tail, need, _ = _graph_source("scan", d_xyz, n, k, which, edge, r, dev, stream)
+        ws = workspace(need, dev)
+        hip.check(call(d_xyz.data_ptr(), n, *head, _viewpoint(viewpoint), *mid, float(k_thresh), int(seg_min_verts), out.ctypes.data, *tail,
+                       ws.data_ptr(), ws.numel(), stream_ptr(stream)))
     return out
 
 
@@ -370,10 +300,9 @@ def oversegment_scan(scene_path: str, k_thresh: float = 0.01, seg_min_verts: int
     mesh path it is an error, not ignored.  `index`: "brute" or "grid", the point-cloud path's neighbour search; on
     the mesh path "grid" is an error as well.  `radius`: the point-cloud path's graph is the radius graph instead of the
     kNN graph; not with a non-default `knn` or `index`, and on the mesh path an error."""
-    from .prepare import _scene_name, mesh_arrays, read_ply
     hip.knn_index(index)
     _radius_only("oversegment_scan", radius, knn, index)
-    name = _scene_name(scene_path)
+    name = scans.scene_name(scene_path)
     out = os.path.join(scene_path, segs_json_name(name, k_thresh))
     if os.path.exists(out) and not force:
         return None
@@ -400,43 +329,15 @@ def oversegment_scans(scans_dir: str, scenes=None, k_thresh: float = 0.01, seg_m
                       radius=None):
     """Every scan directory under `scans_dir` (or the named ones) -> (written paths, skipped scene names).  Workers are threads, each
     with its own stream and workspace: the host chain of one scan overlaps the device work of the next."""
-    import concurrent.futures
-    import threading
-
-    import torch
-    from .prepare import _dev
     hip.knn_index(index)
     _radius_only("oversegment_scans", radius, knn, index)
-    dev = _dev(device)
+    dev = torch_device(device)
     if scenes is None:
-        scenes = sorted(d for d in os.listdir(scans_dir) if os.path.exists(os.path.join(scans_dir, d, d + "_vh_clean_2.ply")))
-    workers = max(1, min(int(workers), MAX_WORKERS, max(len(scenes), 1)))
-    local = threading.local()
-
-    def one(scene):
-        if not hasattr(local, "stream"):
-            with torch.cuda.device(dev):
-                local.stream = torch.cuda.Stream(device=dev)
-        return scene, oversegment_scan(os.path.join(scans_dir, scene), k_thresh, seg_min_verts, force, device=dev, stream=local.stream,
-                                       pointcloud=pointcloud, knn=knn, viewpoint=viewpoint, voxel=voxel, index=index, radius=radius)
-
-    written, skipped = [], []
-    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
-        for scene, path in pool.map(one, scenes):
-            (written.append(path) if path is not None else skipped.append(scene))
-    return written, skipped
-
-
-def _declared_faces(ply_path: str) -> int:
-    """the face count a PLY's header declares (0 without a face element); the body is not read"""
-    with open(ply_path, "rb") as f:
-        for _ in range(256):
-            tok = f.readline().split()
-            if not tok or tok[0] == b"end_header":
-                break
-            if len(tok) == 3 and tok[0] == b"element" and tok[1] == b"face":
-                return int(tok[2])
-    return 0
+        scenes = scans.scan_names(scans_dir)
+    done = scans.map_scans(scenes, workers, dev, lambda scene, stream: oversegment_scan(
+        os.path.join(scans_dir, scene), k_thresh, seg_min_verts, force, device=dev, stream=stream, pointcloud=pointcloud, knn=knn,
+        viewpoint=viewpoint, voxel=voxel, index=index, radius=radius))
+    return [path for _, path in done if path is not None], [scene for scene, path in done if path is None]
 
 
 def main(argv=None) -> int:
@@ -446,7 +347,7 @@ def main(argv=None) -> int:
     ap.add_argument("--k-thresh", type=float, default=0.01)
     ap.add_argument("--seg-min-verts", type=int, default=20)
     ap.add_argument("--force", action="store_true", help="overwrite existing segs.json files")
-    ap.add_argument("--workers", type=int, default=4, help=f"threads, each with its own stream (at most {MAX_WORKERS})")
+    scans.add_workers_argument(ap)
     ap.add_argument("--device", default=None)
     ap.add_argument("--pointcloud", action="store_true", help="segment every scan as a point cloud (a scan without faces always is); faces are ignored")
     ap.add_argument("--knn", type=int, default=10, choices=(5, 10, 20), help="neighbours per point of the point-cloud path")
@@ -468,13 +369,10 @@ def main(argv=None) -> int:
             ap.error("--radius and --knn are two different graphs: give one")
         if any(len(t) > 2 and "--index".startswith(t) for t in given):
             ap.error("--radius and --index are two different graphs (the radius graph has its own grid): give one")
-    scenes = None
-    if a.scenes:
-        with open(a.scenes) as f:
-            scenes = [ln.strip() for ln in f if ln.strip()]
+    scenes = scans.scene_list(a.scenes)
     if (a.voxel is not None or a.index != "brute" or a.radius is not None) and not a.pointcloud:
-        names = scenes if scenes is not None else sorted(d for d in os.listdir(a.scans) if os.path.exists(os.path.join(a.scans, d, d + "_vh_clean_2.ply")))
-        meshes = [s for s in names if _declared_faces(os.path.join(a.scans, s, s + "_vh_clean_2.ply")) > 0]
+        names = scenes if scenes is not None else scans.scan_names(a.scans)
+        meshes = [s for s in names if scans.declared_faces(os.path.join(a.scans, s, s + "_vh_clean_2.ply")) > 0]
         if meshes and a.voxel is not None:
             ap.error("--voxel thins point clouds, and %s %s faces: add --pointcloud to ignore them" % (", ".join(meshes[:5]),
                                                                                                        "has" if len(meshes) == 1 else "have"))

@@ -20,15 +20,17 @@ the aggregation and click files in the first place -- stays out of scope.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
-import json
 import os
 from typing import Optional
 
 import numpy as np
 
-from . import hip
+from . import hip, scans
+from .device import device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
+# the annotation-derived label producers of the same reference file (util.py:76-170, 224-427, 697-768) live in labels.py
+from .labels import (generate_real_label_pth, generate_real_labels, generate_seg_adjacency_matrix, generate_weak_label_pth,  # noqa: F401
+                     generate_weak_labels, group_adjacency_segs, load_aggregation, load_labels, load_seg_labels, read_label_mapper)
 
 
 # ---- minimal PLY (binary little endian; ScanNet's `_vh_clean_2.ply`) ---------------------------------------------
@@ -134,38 +136,12 @@ def mesh_arrays(plydata):
     return np.ascontiguousarray(xyz), np.ascontiguousarray(rgb), np.ascontiguousarray(faces)
 
 
-def load_seg_labels(label_file):                               # util.py:95-100
-    with open(label_file, "r") as f:
-        return json.load(f)["segIndices"]
-
-
-# ---- device plumbing --------------------------------------------------------------------------------------------
-def _dev(device=None):
-    import torch
-    hip.require_device()
-    return torch.device(device if device is not None else "cuda")
-
-
-def _ws(nbytes, dev):
-    import torch
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-
-
-def _t(a, dtype, dev):
-    import torch
-    if isinstance(a, torch.Tensor):
-        return a.to(device=dev, dtype=dtype).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype)
-
-
+# ---- device calls -----------------------------------------------------------------------------------------------
 def nearest_grid_stats() -> dict:
     """What the calling thread's last grid-indexed nearest-point search did: cells per axis, occupied cells and the largest
     cell of the candidates' index, the cell edge used, the largest ring count of a query the rings settled, the queries finished against
     every candidate, and the pair scores evaluated (counted in timed calls only)."""
-    h = (C.c_int64 * 16)()
-    hip.check(hip.lib().sg_nearest_point_grid_stats(h, 16))
-    return dict(cells=(int(h[0]), int(h[1]), int(h[2])), occupied=int(h[3]), largest_cell=int(h[4]),
-                cell=float(np.array([h[5]], dtype=np.uint32).view(np.float32)[0]), max_ring=int(h[6]), fallback=int(h[7]), scores=int(h[8]))
+    return hip.grid_stats("nearest_point_grid", ("max_ring", "fallback", "scores"))
 
 
 def nearest_point_grid(x, y, cell=None, device=None, stream=None, want_d2=True):
@@ -174,23 +150,23 @@ def nearest_point_grid(x, y, cell=None, device=None, stream=None, want_d2=True):
     (a performance knob: the result does not depend on it)."""
     import torch
     edge = hip.knn_cell(cell)
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    with torch.cuda.device(dev), (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
-        dx, dy = _t(x, torch.float32, dev), _t(y, torch.float32, dev)
+    with torch.cuda.device(dev), on_stream(stream):
+        dx, dy = device_tensor(x, torch.float32, dev), device_tensor(y, torch.float32, dev)
         if dx.dim() != 2 or dy.dim() != 2 or dx.shape[1] < 3 or dy.shape[1] < 3:
             raise ValueError("nearest_point_grid: x and y must be [*, >= 3]")
         u, n = int(dx.shape[0]), int(dy.shape[0])
-        sp = stream.cuda_stream if stream is not None else None
+        sp = stream_ptr(stream)
         need = lib.sg_nearest_point_grid_ws_bytes(u, n)
         if need == 0:                                               # outside the envelope: the library says why, nothing is allocated
             hip.check(lib.sg_nearest_point_grid(None, int(dx.shape[1]), u, None, int(dy.shape[1]), n, edge, None, None, None, 0, sp))
         idx = torch.empty(u, dtype=torch.int64, device=dev)
         d2 = torch.empty(u, dtype=torch.float32, device=dev) if want_d2 else None
-        ws = _ws(need, dev)
+        ws = workspace(need, dev)
         hip.check(lib.sg_nearest_point_grid(dx.data_ptr(), int(dx.shape[1]), u, dy.data_ptr(), int(dy.shape[1]), n, edge, idx.data_ptr(),
                                             d2.data_ptr() if want_d2 else None, ws.data_ptr(), ws.numel(), sp))
-        (stream.synchronize() if stream is not None else torch.cuda.current_stream(dev).synchronize())
+        sync(stream)
     return idx, d2
 
 
@@ -201,15 +177,15 @@ def get_unmapper(x, y, device=None, index="brute", cell=None):
     which, edge = hip.knn_index(index), hip.knn_cell(cell)
     if which == hip.KNN_GRID:
         return nearest_point_grid(x, y, cell=edge, device=device, want_d2=False)[0]
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    dx, dy = _t(x, torch.float32, dev), _t(y, torch.float32, dev)
+    dx, dy = device_tensor(x, torch.float32, dev), device_tensor(y, torch.float32, dev)
     out = torch.empty(dx.shape[0], dtype=torch.int64, device=dev)
-    ws = _ws(lib.sg_nearest_point_ws_bytes(dy.shape[0]), dev)
+    ws = workspace(lib.sg_nearest_point_ws_bytes(dy.shape[0]), dev)
     with torch.cuda.device(dev):
         hip.check(lib.sg_nearest_point(dx.data_ptr(), dx.shape[0], dy.data_ptr(), dy.shape[1], dy.shape[0], out.data_ptr(), ws.data_ptr(),
                                        ws.numel(), None))
-        torch.cuda.synchronize()
+        sync(None)
     return out
 
 
@@ -219,9 +195,9 @@ def sample_points(xyz, rgb, mapper, device=None, index="brute"):
     unmapper."""
     import torch
     which = hip.knn_index(index)
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    d_xyz, d_rgb, d_map = _t(xyz, torch.float32, dev), _t(rgb, torch.uint8, dev), _t(mapper, torch.int64, dev)
+    d_xyz, d_rgb, d_map = device_tensor(xyz, torch.float32, dev), device_tensor(rgb, torch.uint8, dev), device_tensor(mapper, torch.int64, dev)
     v, n = d_xyz.shape[0], d_map.shape[0]
     if which == hip.KNN_GRID:
         # the gather and the unmapper of the sampled vertices are index work (the last occurrence of a vertex in the mapper wins);
@@ -235,33 +211,33 @@ def sample_points(xyz, rgb, mapper, device=None, index="brute"):
         return pcl, unmap, int(missing.numel())
     pcl = torch.empty((n, 6), dtype=torch.float32, device=dev)
     unmap = torch.empty(v, dtype=torch.int64, device=dev)
-    ws = _ws(lib.sg_prep_sample_ws_bytes(v, n), dev)
+    ws = workspace(lib.sg_prep_sample_ws_bytes(v, n), dev)
     miss = C.c_int(0)
     with torch.cuda.device(dev):
         hip.check(lib.sg_prep_sample_points(d_xyz.data_ptr(), d_rgb.data_ptr(), v, d_map.data_ptr(), n, pcl.data_ptr(), unmap.data_ptr(),
                                             C.byref(miss), ws.data_ptr(), ws.numel(), None))
-        torch.cuda.synchronize()
+        sync(None)
     return pcl, unmap, miss.value
 
 
 def mesh_adjacency(faces, unmapper=None, num_vertices: Optional[int] = None, device=None):
     """The compute of get_adj_from_mesh: -> (adj [E,2] i64, adj_resampled [E',2] i64 or None), device tensors."""
     import torch
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    d_f = _t(faces, torch.int32, dev)
+    d_f = device_tensor(faces, torch.int32, dev)
     f = d_f.shape[0]
-    d_un = _t(unmapper, torch.int64, dev) if unmapper is not None else None
+    d_un = device_tensor(unmapper, torch.int64, dev) if unmapper is not None else None
     v = int(num_vertices if num_vertices is not None else (d_un.shape[0] if d_un is not None else int(d_f.max().item()) + 1 if f else 1))
     raw = torch.empty((max(3 * f, 1), 2), dtype=torch.int64, device=dev)
     res = torch.empty((max(3 * f, 1), 2), dtype=torch.int64, device=dev) if d_un is not None else None
-    ws = _ws(lib.sg_mesh_adjacency_ws_bytes(f), dev)
+    ws = workspace(lib.sg_mesh_adjacency_ws_bytes(f), dev)
     n_raw, n_res = C.c_int(0), C.c_int(0)
     with torch.cuda.device(dev):
         hip.check(lib.sg_mesh_adjacency(d_f.data_ptr(), f, d_un.data_ptr() if d_un is not None else None, v, raw.data_ptr(), C.byref(n_raw),
                                         res.data_ptr() if res is not None else None, C.byref(n_res) if res is not None else None,
                                         ws.data_ptr(), ws.numel(), None))
-        torch.cuda.synchronize()
+        sync(None)
     return raw[:n_raw.value], (res[:n_res.value] if res is not None else None)
 
 
@@ -269,19 +245,19 @@ def segment_lists(seg_indices, mapper, device=None):
     """The compute of generate_seg_labels_and_ds_set: -> (raw_label [V] i32, seg_points [Np] i32, seg_off [G+1] i32) device
     tensors: groups in ascending compacted-id order, members ascending."""
     import torch
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    d_seg, d_map = _t(seg_indices, torch.int32, dev), _t(mapper, torch.int64, dev)
+    d_seg, d_map = device_tensor(seg_indices, torch.int32, dev), device_tensor(mapper, torch.int64, dev)
     v, n = d_seg.shape[0], d_map.shape[0]
     raw = torch.empty(v, dtype=torch.int32, device=dev)
     pts = torch.empty(n, dtype=torch.int32, device=dev)
     off = torch.empty(min(v, n) + 1, dtype=torch.int32, device=dev)
-    ws = _ws(lib.sg_segment_lists_ws_bytes(v, n), dev)
+    ws = workspace(lib.sg_segment_lists_ws_bytes(v, n), dev)
     counts = (C.c_int * 2)()
     with torch.cuda.device(dev):
         hip.check(lib.sg_segment_lists(d_seg.data_ptr(), v, d_map.data_ptr(), n, raw.data_ptr(), pts.data_ptr(), off.data_ptr(), counts,
                                        ws.data_ptr(), ws.numel(), None))
-        torch.cuda.synchronize()
+        sync(None)
     return raw, pts, off[:counts[1] + 1]
 
 
@@ -296,16 +272,16 @@ def get_adj_from_pointcloud(pointcloud, k=10, device=None):
     """util.py:814-834 (optional in the reference: nothing calls it): the kNN graph of the cloud as a per-row sorted, unique
     [*, 2] LongTensor (CPU, like the reference's).  Equal scores rank by ascending index (torch.topk leaves that open)."""
     import torch
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    pts = _t(pointcloud, torch.float32, dev)
+    pts = device_tensor(pointcloud, torch.float32, dev)
     n, stride = int(pts.shape[0]), int(pts.shape[1])
     out = torch.empty((n * int(k), 2), dtype=torch.int64, device=dev)
-    ws = _ws(lib.sg_pointcloud_adjacency_ws_bytes(n, int(k)), dev)
+    ws = workspace(lib.sg_pointcloud_adjacency_ws_bytes(n, int(k)), dev)
     cnt = C.c_int(0)
     with torch.cuda.device(dev):
         hip.check(lib.sg_pointcloud_adjacency(pts.data_ptr(), stride, n, int(k), out.data_ptr(), C.byref(cnt), ws.data_ptr(), ws.numel(), None))
-        torch.cuda.synchronize()
+        sync(None)
     return out[:cnt.value].cpu()
 
 
@@ -316,9 +292,9 @@ def pointcloud_knn(pointcloud, k=10, device=None, index="brute", cell=None):
     performance knob: the table does not depend on it)."""
     import torch
     which, edge = hip.knn_index(index), hip.knn_cell(cell)
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    pts = _t(pointcloud, torch.float32, dev)
+    pts = device_tensor(pointcloud, torch.float32, dev)
     if pts.dim() != 2 or pts.shape[1] < 3:
         raise ValueError("pointcloud_knn: the cloud must be [N, >= 3]")
     n, stride = int(pts.shape[0]), int(pts.shape[1])
@@ -326,16 +302,16 @@ def pointcloud_knn(pointcloud, k=10, device=None, index="brute", cell=None):
         if n > hip.MAX_GRID_POINTS:                                 # refused before anything is allocated
             hip.check(lib.sg_pointcloud_knn_grid(None, stride, n, int(k), edge, None, None, 0, None))
         out = torch.empty((n, int(k) + 1), dtype=torch.int32, device=dev)
-        ws = _ws(lib.sg_pointcloud_knn_grid_ws_bytes(n, int(k)), dev)
+        ws = workspace(lib.sg_pointcloud_knn_grid_ws_bytes(n, int(k)), dev)
         with torch.cuda.device(dev):
             hip.check(lib.sg_pointcloud_knn_grid(pts.data_ptr(), stride, n, int(k), edge, out.data_ptr(), ws.data_ptr(), ws.numel(), None))
-            torch.cuda.synchronize()
+            sync(None)
         return out
     out = torch.empty((n, int(k) + 1), dtype=torch.int32, device=dev)
-    ws = _ws(lib.sg_pointcloud_knn_ws_bytes(n), dev)
+    ws = workspace(lib.sg_pointcloud_knn_ws_bytes(n), dev)
     with torch.cuda.device(dev):
         hip.check(lib.sg_pointcloud_knn(pts.data_ptr(), stride, n, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), None))
-        torch.cuda.synchronize()
+        sync(None)
     return out
 
 
@@ -368,10 +344,6 @@ def get_adj_from_cloud_scan(xyz, unmapper=None, k=10, device=None, radius=None):
 
 
 # ---- the reference's file-producing functions -------------------------------------------------------------------------
-def _scene_name(scene_path: str) -> str:
-    return os.path.split(scene_path[:-1] if scene_path.endswith("/") else scene_path)[-1]
-
-
 def make_mapper(num_vertices: int, num_points: int, perm=None):
     """util.py:664-676.  `perm` replaces the `torch.randperm(V)` draw (pass one for reproducible output)."""
     import torch
@@ -389,7 +361,7 @@ def make_mapper(num_vertices: int, num_points: int, perm=None):
 def generate_pointcloud_pth(scene_path, item, num_points, plydata=None, root: str = ".", perm=None, device=None, index: str = "brute"):
     """util.py:633-693: `.pcl.pth` f32 [num_points,6], `.info.pth`, `.map.pth`, `.unmap.pth` under data/resampled/<scene>/."""
     import torch
-    scene_name = _scene_name(scene_path)
+    scene_name = scans.scene_name(scene_path)
     if plydata is None:
         plydata = read_ply(os.path.join(scene_path, scene_name + "_vh_clean_2.ply"))
     xyz, rgb, _ = mesh_arrays(plydata)
@@ -406,7 +378,7 @@ def generate_pointcloud_pth(scene_path, item, num_points, plydata=None, root: st
 def generate_seg_labels_and_ds_set(scene_path, root: str = ".", device=None):
     """util.py:174-220: label/real/raw/<s>/<s>.seg.txt and label/real/resampled/<s>/<s>.seg.json."""
     import torch
-    scene_name = _scene_name(scene_path)
+    scene_name = scans.scene_name(scene_path)
     seg = np.asarray(load_seg_labels(os.path.join(scene_path, scene_name + "_vh_clean_2.0.010000.segs.json")), dtype=np.int64)
     if seg.size and seg.min() < 0:
         raise ValueError("segIndices must be non-negative")
@@ -451,11 +423,6 @@ def generate_mesh_adjcency_pth(scene_name, plydata=None, root: str = ".", scene_
         torch.save(t, p)
 
 
-# the annotation-derived label producers of the same reference file (util.py:76-170, 224-427, 697-768) live in labels.py
-from .labels import (generate_real_label_pth, generate_real_labels, generate_seg_adjacency_matrix, generate_weak_label_pth,  # noqa: E402,F401
-                     generate_weak_labels, group_adjacency_segs, load_aggregation, load_labels, read_label_mapper)
-
-
 def prepare_scene(scene_path, item, num_points: int = 150000, root: str = ".", perm=None, device=None, label_style: Optional[str] = None,
                   manual_label_path: Optional[str] = None, oversegment: bool = False, knn: int = 10, index: str = "brute", radius=None):
     """What prepare_data.py:36-71 + prepare_weak_label.py:60-90 do for one scan: point cloud, mapper / unmapper, segment lists,
@@ -468,7 +435,7 @@ def prepare_scene(scene_path, item, num_points: int = 150000, root: str = ".", p
     hip.knn_index(index)
     if radius is not None and int(knn) != 10:
         raise ValueError("prepare_scene: radius and knn = %d are two different graphs; give one" % int(knn))
-    scene_name = _scene_name(scene_path)
+    scene_name = scans.scene_name(scene_path)
     ply = read_ply(os.path.join(scene_path, scene_name + "_vh_clean_2.ply"))
     if radius is not None and has_faces(ply):
         raise ValueError(f"{scene_name}: the radius graph belongs to a scan without faces; this scan is a mesh and uses its faces")

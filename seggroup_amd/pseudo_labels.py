@@ -20,13 +20,6 @@ SGL_NAME = "pseudo_labels.sgl"
 INS_NVEC, SEM_NVEC = hip.NUM_LABEL_VECTORS, 6
 
 
-def _check(rc: int) -> int:
-    """hip.check, with SG_EINVAL (a bad file or argument) raised as ValueError."""
-    if rc == hip.SG_EINVAL:
-        raise ValueError(hip.lib().sg_last_error().decode("utf-8", "replace"))
-    return hip.check(rc)
-
-
 def sgl_path(path_or_dir: str) -> str:
     return os.path.join(path_or_dir, SGL_NAME) if os.path.isdir(path_or_dir) else path_or_dir
 
@@ -38,14 +31,14 @@ def write(path_or_dir: str, tables: np.ndarray, seg_of_vertex: np.ndarray) -> st
     sov = np.ascontiguousarray(seg_of_vertex, dtype=np.int32)
     if tab.ndim != 2:
         raise ValueError("tables must be [nvec, S]")
-    _check(hip.lib().sg_write_sgl(path.encode(), tab.ctypes.data, tab.shape[0], tab.shape[1], sov.ctypes.data, sov.shape[0]))
+    hip.check_arg(hip.lib().sg_write_sgl(path.encode(), tab.ctypes.data, tab.shape[0], tab.shape[1], sov.ctypes.data, sov.shape[0]))
     return path
 
 
 def read_header(path_or_dir: str) -> Dict[str, int]:
     """{version, nvec, S, V, sov_width} of a `.sgl` file (sizes checked against the file's length; the CRC is checked by `load`)."""
     info = (C.c_int * 5)()
-    _check(hip.lib().sg_read_sgl_header(sgl_path(path_or_dir).encode(), info))
+    hip.check_arg(hip.lib().sg_read_sgl_header(sgl_path(path_or_dir).encode(), info))
     return dict(zip(("version", "nvec", "S", "V", "sov_width"), list(info)))
 
 
@@ -93,7 +86,7 @@ def load(path_or_dir: str) -> PseudoLabels:
     h = read_header(path)
     tab = np.empty((h["nvec"], h["S"]), dtype=np.int32)
     sov = np.empty(h["V"], dtype=np.int32)
-    _check(hip.lib().sg_read_sgl(path.encode(), tab.ctypes.data, tab.size, sov.ctypes.data if h["V"] else None, sov.size))
+    hip.check_arg(hip.lib().sg_read_sgl(path.encode(), tab.ctypes.data, tab.size, sov.ctypes.data if h["V"] else None, sov.size))
     return PseudoLabels(tab, sov, path=path)
 
 

@@ -27,9 +27,11 @@ from typing import Optional
 
 import numpy as np
 
-from . import hip
+from . import hip, scans
+from .device import device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
+from .oversegment import segment_mesh, write_segs_json
+from .prepare import load_seg_labels, mesh_arrays, read_ply
 
-MAX_WORKERS = 16
 SEGS_SUFFIX = "_vh_clean_2.0.010000.segs.json"        # the one name every reader opens, whatever the parameters inside
 ROW_FIELDS = ("row_ids", "row_count", "winner", "winner_count", "distinct", "tied", "first_vertex")
 
@@ -55,12 +57,11 @@ class Vote:
 # ---- device side ----------------------------------------------------------------------------------------------------------------------
 def _ids(a, dev, what):
     import torch
-    from .prepare import _t
     if not isinstance(a, torch.Tensor):
         a = np.asarray(a)
         if a.dtype.kind not in "iu" or (a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31)):
             raise ValueError(f"rekey: {what} must be integers that fit int32")
-    t = _t(a, torch.int32, dev).reshape(-1)
+    t = device_tensor(a, torch.int32, dev).reshape(-1)
     if t.shape[0] < 1:
         raise ValueError(f"rekey: {what} is empty")
     return t
@@ -69,19 +70,17 @@ def _ids(a, dev, what):
 def rank_ids(ids, device=None, stream=None):
     """-> (rank [V], row_ids [R], row_count [R]) int32 device tensors: the distinct ids ascending and every vertex's position among them."""
     import torch
-    from .oversegment import _on, _stream_ptr
-    from .prepare import _dev, _ws
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    with torch.cuda.device(dev), _on(stream):
+    with torch.cuda.device(dev), on_stream(stream):
         d_ids = _ids(ids, dev, "the ids")
         v = int(d_ids.shape[0])
         out = torch.empty((3, v), dtype=torch.int32, device=dev)
-        ws = _ws(lib.sg_segment_vote_ws_bytes(v), dev)
+        ws = workspace(lib.sg_segment_vote_ws_bytes(v), dev)
         n_r = C.c_int(0)
         hip.check(lib.sg_segment_rank(d_ids.data_ptr(), v, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), C.byref(n_r), ws.data_ptr(),
-                                      ws.numel(), _stream_ptr(stream)))
-        (stream.synchronize() if stream is not None else torch.cuda.synchronize())
+                                      ws.numel(), stream_ptr(stream)))
+        sync(stream)
     return out[0], out[1, :n_r.value], out[2, :n_r.value]
 
 
@@ -89,11 +88,9 @@ def vote(row_ids, cols, n_cols: int, device=None, stream=None) -> Vote:
     """Per distinct row id the column most of its vertices hold (ties: the lowest column) -> `Vote` of device tensors.  `row_ids` are any
     non-negative int32 values, `cols` lie in 0..n_cols-1; both are checked on the device (`hip.SgError`, SG_EINVAL)."""
     import torch
-    from .oversegment import _on, _stream_ptr
-    from .prepare import _dev, _ws
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    with torch.cuda.device(dev), _on(stream):
+    with torch.cuda.device(dev), on_stream(stream):
         d_ids, d_cols = _ids(row_ids, dev, "the row ids"), _ids(cols, dev, "the columns")
         v = int(d_ids.shape[0])
         if d_cols.shape[0] != v:
@@ -101,12 +98,12 @@ def vote(row_ids, cols, n_cols: int, device=None, stream=None) -> Vote:
         if not 1 <= int(n_cols) < 2 ** 31:
             raise ValueError("rekey.vote: n_cols must be in 1..2^31-1")
         out = torch.empty((9, v), dtype=torch.int32, device=dev)
-        ws = _ws(lib.sg_segment_vote_ws_bytes(v), dev)
+        ws = workspace(lib.sg_segment_vote_ws_bytes(v), dev)
         n_r = C.c_int(0)
         # rank, vertex_winner, then the row fields in ROW_FIELDS order
         hip.check(lib.sg_segment_vote(d_ids.data_ptr(), d_cols.data_ptr(), v, int(n_cols), *[out[i].data_ptr() for i in range(9)], C.byref(n_r),
-                                      ws.data_ptr(), ws.numel(), _stream_ptr(stream)))
-        (stream.synchronize() if stream is not None else torch.cuda.synchronize())
+                                      ws.data_ptr(), ws.numel(), stream_ptr(stream)))
+        sync(stream)
     r = n_r.value
     return Vote(rank=out[0], vertex_winner=out[1], **{f: out[2 + i, :r] for i, f in enumerate(ROW_FIELDS)})
 
@@ -237,9 +234,7 @@ def rekey_arrays(src_seg, new_seg, aggregation: dict, manual: Optional[dict] = N
     """The whole re-keying of one scan from arrays: three device calls (ranks of the source ids, the vote of the new segments over the
     groups, and -- with clicks -- the vote of the source segments over the new ones), everything else on the host."""
     import torch
-    from .oversegment import _on
-    from .prepare import _dev
-    dev = _dev(device)
+    dev = torch_device(device)
     with torch.cuda.device(dev):
         d_src, d_new = _ids(src_seg, dev, "src_seg"), _ids(new_seg, dev, "new_seg")
         if d_src.shape != d_new.shape:
@@ -247,10 +242,10 @@ def rekey_arrays(src_seg, new_seg, aggregation: dict, manual: Optional[dict] = N
         src_rank, src_ids, _ = rank_ids(d_src, device=dev, stream=stream)
         h_src_ids = src_ids.cpu().numpy()
         table = group_table(aggregation, scene_name, h_src_ids)
-        with _on(stream):
+        with on_stream(stream):
             grp = torch.from_numpy(table).to(dev)[src_rank.long()].contiguous()         # the gather through the per-rank table
         nv = vote(d_new, grp, reached_groups(aggregation, scene_name) + 1, device=dev, stream=stream)
-        with _on(stream):
+        with on_stream(stream):
             before = int((grp != 0).sum())
             after = int((nv.vertex_winner != 0).sum())
             unchanged = int((nv.vertex_winner == grp).sum())
@@ -300,9 +295,8 @@ def rekey_scan(scene_path: str, out_root: str, new_seg=None, k_thresh: float = 0
     segs.json under the name every reader opens, <s>.aggregation.json, out_root/scannetv2-labels.combined.tsv and -- with
     `manual_label_path` -- out_root/manual_label/<s>.json.  Every file is written under a temporary name and renamed; nothing that
     exists is overwritten without `force`; an `out_root` whose scans directory is the source's is refused."""
-    from .prepare import _scene_name, load_seg_labels, mesh_arrays, read_ply
     scene_path = scene_path[:-1] if scene_path.endswith("/") else scene_path
-    name = _scene_name(scene_path)
+    name = scans.scene_name(scene_path)
     src_scans = os.path.dirname(os.path.abspath(scene_path))
     out_scans = os.path.join(out_root, "scans")
     if os.path.realpath(out_scans) == os.path.realpath(src_scans):
@@ -328,7 +322,6 @@ def rekey_scan(scene_path: str, out_root: str, new_seg=None, k_thresh: float = 0
         tsv = f.read()
     segs_bytes = None
     if new_seg is None:
-        from .oversegment import segment_mesh
         xyz, _, faces = mesh_arrays(read_ply(mesh))
         new_arr = segment_mesh(xyz, faces, k_thresh, seg_min_verts, device=device, stream=stream)
     elif isinstance(new_seg, (str, os.PathLike)):
@@ -350,7 +343,6 @@ def rekey_scan(scene_path: str, out_root: str, new_seg=None, k_thresh: float = 0
     if segs_bytes is not None:
         _write_bytes(targets["segs"], segs_bytes)
     elif new_seg is None:
-        from .oversegment import write_segs_json
         write_segs_json(targets["segs"], new_arr, name, k_thresh, seg_min_verts)
     else:
         _write_bytes(targets["segs"], _json_bytes({"params": {}, "sceneId": name, "segIndices": [int(s) for s in new_arr]}))
@@ -378,27 +370,16 @@ def rekey_scans(scans_dir: str, out_root: str, scenes=None, new_segs_from: Optio
                 workers: int = 4, device=None):
     """Every annotated scan directory under `scans_dir` (or the named ones) -> (reports in scene order, their totals).  Workers are threads,
     each with its own stream, as in `oversegment_scans`."""
-    import concurrent.futures
-    import threading
-
-    import torch
-    from .prepare import _dev
-    dev = _dev(device)
+    dev = torch_device(device)
     if scenes is None:
-        scenes = sorted(d for d in os.listdir(scans_dir) if os.path.exists(os.path.join(scans_dir, d, d + ".aggregation.json")))
-    workers = max(1, min(int(workers), MAX_WORKERS, max(len(scenes), 1)))
-    local = threading.local()
+        scenes = scans.scan_names(scans_dir, ".aggregation.json")
 
-    def one(scene):
-        if not hasattr(local, "stream"):
-            with torch.cuda.device(dev):
-                local.stream = torch.cuda.Stream(device=dev)
+    def one(scene, stream):
         new_seg = _new_segs_file(new_segs_from, scene) if new_segs_from else None
         return rekey_scan(os.path.join(scans_dir, scene), out_root, new_seg, k_thresh, seg_min_verts, manual_label_path, force, copy_mesh,
-                          device=dev, stream=local.stream)
+                          device=dev, stream=stream)
 
-    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
-        reports = list(pool.map(one, scenes))
+    reports = [report for _, report in scans.map_scans(scenes, workers, dev, one)]
     return reports, total_report(reports)
 
 
@@ -424,7 +405,7 @@ def main(argv=None) -> int:
     ap.add_argument("--manual_label_path", default=None, help="directory of the click files (<scene>.json)")
     ap.add_argument("--force", action="store_true", help="overwrite existing files")
     ap.add_argument("--copy-mesh", action="store_true", help="copy the meshes instead of linking them")
-    ap.add_argument("--workers", type=int, default=4, help=f"threads, each with its own stream (at most {MAX_WORKERS})")
+    scans.add_workers_argument(ap)
     ap.add_argument("--report", default=None, help="where the report goes (default: <out>/rekey_report.json)")
     ap.add_argument("--device", default=None)
     a = ap.parse_args(argv)
@@ -433,11 +414,7 @@ def main(argv=None) -> int:
     for d in (a.scans, a.new_segs_from, a.manual_label_path):
         if d is not None and not os.path.isdir(d):
             ap.error(f"{d} is not a directory")
-    scenes = None
-    if a.scenes:
-        with open(a.scenes) as f:
-            scenes = [ln.strip() for ln in f if ln.strip()]
-    reports, total = rekey_scans(a.scans, a.out, scenes, a.new_segs_from, 0.01 if a.k_thresh is None else a.k_thresh,
+    reports, total = rekey_scans(a.scans, a.out, scans.scene_list(a.scenes), a.new_segs_from, 0.01 if a.k_thresh is None else a.k_thresh,
                                  20 if a.seg_min_verts is None else a.seg_min_verts, a.manual_label_path, a.force, a.copy_mesh, a.workers,
                                  a.device)
     for r in reports:

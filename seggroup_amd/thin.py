@@ -27,9 +27,10 @@ from typing import Optional
 
 import numpy as np
 
-from . import hip
+from . import hip, pseudo_labels, scans
+from .device import device_cloud, on_stream, stream_ptr, sync, torch_device, workspace
+from .prepare import mesh_arrays, read_ply, write_ply
 
-MAX_WORKERS = 16
 MAP_SUFFIX = ".thin.npz"
 REPORT_NAME = "thin_report.json"
 
@@ -38,29 +39,23 @@ def thin_cloud(xyz, voxel: float, device=None, stream=None):
     """-> (rep int32 [M], thin_of_point int32 [N], lo float32 [3]) device tensors: rep = the representatives' indices, ascending;
     rep[thin_of_point[i]] stands for point i; lo = the corner of the grid.  xyz: [N, >= 3] rows, xyz first (NumPy or tensor)."""
     import torch
-    from .oversegment import _on, _stream_ptr
-    from .prepare import _dev, _t, _ws
-    dev = _dev(device)
+    dev = torch_device(device)
     lib = hip.lib()
-    with torch.cuda.device(dev), _on(stream):
-        d_xyz = _t(xyz, torch.float32, dev)
-        if d_xyz.dim() != 2 or d_xyz.shape[1] < 3:
-            raise ValueError("thin_cloud: xyz must be [N, >= 3]")
-        n, stride = int(d_xyz.shape[0]), int(d_xyz.shape[1])
-        if n < 1:
-            raise ValueError("thin_cloud: a cloud needs at least one point")
+    with torch.cuda.device(dev), on_stream(stream):
+        d_xyz, n = device_cloud(xyz, dev, "thin_cloud")
+        stride = int(d_xyz.shape[1])
         need = lib.sg_cloud_thin_ws_bytes(n)
         if need == 0:
             raise hip.SgError(hip.SG_EUNSUP, "thin_cloud: %d points; a cloud holds at most 2^27" % n)
         rep = torch.empty(n, dtype=torch.int32, device=dev)
         top = torch.empty(n, dtype=torch.int32, device=dev)
-        ws = _ws(need, dev)
+        ws = workspace(need, dev)
         m, lo = C.c_int(0), (C.c_float * 3)()
         hip.check(lib.sg_cloud_thin(d_xyz.data_ptr(), stride, n, float(voxel), rep.data_ptr(), top.data_ptr(), C.byref(m), lo, ws.data_ptr(),
-                                    ws.numel(), _stream_ptr(stream)))
+                                    ws.numel(), stream_ptr(stream)))
         rep = rep[:m.value].clone()
         d_lo = torch.tensor(list(lo), dtype=torch.float32, device=dev)
-        (stream.synchronize() if stream is not None else torch.cuda.current_stream(dev).synchronize())
+        sync(stream)
     return rep, top, d_lo
 
 
@@ -80,7 +75,6 @@ def lift(values, thin_of_point):
 
 def lift_sgl(src: str, dst: str, thin_of_point) -> str:
     """A `pseudo_labels.sgl` made on a thinned scan -> one for the raw scan: the same tables, seg_of_vertex[thin_of_point], the raw V."""
-    from . import pseudo_labels
     lab = pseudo_labels.load(src)
     top = np.asarray(thin_of_point.cpu() if hasattr(thin_of_point, "cpu") else thin_of_point).reshape(-1)
     if top.size and (int(top.min()) < 0 or int(top.max()) >= lab.V):
@@ -95,16 +89,10 @@ def load_map(maps_dir: str, scene: str):
         return {k: z[k] for k in ("rep", "thin_of_point", "voxel", "lo")}
 
 
-def _segs_name(scene: str) -> str:
-    from .oversegment import segs_json_name
-    return segs_json_name(scene)
-
-
 def thin_scan(scene_path: str, out_dir: str, voxel: float, force: bool = False, device=None, stream=None) -> Optional[dict]:
     """One scan directory -> <out_dir>/<scene>/ (see the module's doc); -> its entry of thin_report.json, or None when the thinned
     PLY was there already (never overwritten without `force`)."""
-    from .prepare import _scene_name, mesh_arrays, read_ply, write_ply
-    scene = _scene_name(scene_path)
+    scene = scans.scene_name(scene_path)
     dst = os.path.join(out_dir, scene)
     ply_out = os.path.join(dst, scene + "_vh_clean_2.ply")
     if os.path.exists(ply_out) and not force:
@@ -119,7 +107,7 @@ def thin_scan(scene_path: str, out_dir: str, voxel: float, force: bool = False, 
     entry = {"V": int(xyz.shape[0]), "M": int(rep.shape[0]), "voxel": float(h),
              "cells": [int(np.floor((xyz[:, a].max() - lo[a]) / h)) + 1 for a in range(3)],
              "largest_voxel": int(np.bincount(top, minlength=rep.shape[0]).max())}
-    segs = os.path.join(scene_path, _segs_name(scene))
+    segs = os.path.join(scene_path, scans.segs_json_name(scene))
     if os.path.exists(segs):
         with open(segs) as f:
             doc = json.load(f)
@@ -127,7 +115,7 @@ def thin_scan(scene_path: str, out_dir: str, voxel: float, force: bool = False, 
         if ids.shape[0] != xyz.shape[0]:
             raise ValueError(f"{segs}: {ids.shape[0]} segIndices for {xyz.shape[0]} vertices")
         doc["segIndices"] = ids[rep].tolist()
-        with open(os.path.join(dst, _segs_name(scene)), "w") as f:
+        with open(os.path.join(dst, scans.segs_json_name(scene)), "w") as f:
             json.dump(doc, f)
         before, after = np.unique(ids), np.unique(ids[rep])
         entry.update(source_segments=int(before.shape[0]), kept_segments=int(after.shape[0]),
@@ -138,48 +126,44 @@ def thin_scan(scene_path: str, out_dir: str, voxel: float, force: bool = False, 
     return entry
 
 
-def _scan_names(scans_dir: str):
-    return sorted(d for d in os.listdir(scans_dir) if os.path.exists(os.path.join(scans_dir, d, d + "_vh_clean_2.ply")))
-
-
 def thin_scans(scans_dir: str, out_dir: str, voxel: float, scenes=None, force: bool = False, workers: int = 4, device=None):
     """Every scan directory under `scans_dir` (or the named ones) -> (report {scene: entry}, skipped scene names); writes
     <out_dir>/thin_report.json.  Workers are threads, each with its own stream."""
-    import concurrent.futures
-    import threading
-
-    import torch
-    from .prepare import _dev
-    dev = _dev(device)
+    dev = torch_device(device)
     if scenes is None:
-        scenes = _scan_names(scans_dir)
-    workers = max(1, min(int(workers), MAX_WORKERS, max(len(scenes), 1)))
-    local = threading.local()
-
-    def one(scene):
-        if not hasattr(local, "stream"):
-            with torch.cuda.device(dev):
-                local.stream = torch.cuda.Stream(device=dev)
-        return scene, thin_scan(os.path.join(scans_dir, scene), out_dir, voxel, force, device=dev, stream=local.stream)
-
-    report, skipped = {}, []
-    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
-        for scene, entry in pool.map(one, scenes):
-            if entry is None:
-                skipped.append(scene)
-            else:
-                report[scene] = entry
+        scenes = scans.scan_names(scans_dir)
+    done = scans.map_scans(scenes, workers, dev, lambda scene, stream: thin_scan(os.path.join(scans_dir, scene), out_dir, voxel, force, device=dev,
+                                                                                 stream=stream))
+    report = {scene: entry for scene, entry in done if entry is not None}
+    skipped = [scene for scene, entry in done if entry is None]
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, REPORT_NAME), "w") as f:
-        json.dump({"voxel": float(np.float32(voxel)), "scenes": report, "skipped": skipped}, f, indent=1, sort_keys=True)
-        f.write("\n")
+    scans.write_report(os.path.join(out_dir, REPORT_NAME), {"voxel": float(np.float32(voxel)), "scenes": report, "skipped": skipped})
     return report, skipped
+
+
+def lift_stage(src: str, dst: str, index_map, n_src: int, verb: str = "lift", unit: str = "thinned points"):
+    """The files of one export directory through a gather map: pseudo_labels.sgl and every .npy vector of `src`, each of `n_src` values
+    on its leading axis, -> the same names under `dst` with index_map.shape[0] values; -> the files written.  `verb` and `unit` word the
+    errors for the caller's map."""
+    os.makedirs(dst, exist_ok=True)
+    files = []
+    if os.path.isfile(os.path.join(src, pseudo_labels.SGL_NAME)):
+        files.append(lift_sgl(os.path.join(src, pseudo_labels.SGL_NAME), os.path.join(dst, pseudo_labels.SGL_NAME), index_map))
+    for name in sorted(os.listdir(src)):
+        if name.endswith(".npy"):
+            vec = np.load(os.path.join(src, name))
+            if vec.shape[0] != n_src:
+                raise ValueError(f"{src}/{name}: {vec.shape[0]} values for {n_src} {unit}")
+            np.save(os.path.join(dst, name), lift(vec, index_map))
+            files.append(os.path.join(dst, name))
+    if not files:
+        raise FileNotFoundError(f"{src}: neither {pseudo_labels.SGL_NAME} nor .npy vectors (.txt is not read: {verb} the .sgl and run expand)")
+    return files
 
 
 def lift_results(exp: str, stage: str, maps_dir: str, out_root: str, root: str = ".", scenes=None):
     """results/<exp>/<scene>/<stage>/ under `root` -> the lifted files under <out_root>/results/<exp>/<scene>/<stage>/ for every scene
     (default: every scene of the experiment that has a map); -> [(scene, files written)].  Needs no GPU."""
-    from . import pseudo_labels
     base = os.path.join(root, "results", exp)
     if scenes is None:
         scenes = sorted(s for s in os.listdir(base) if os.path.exists(os.path.join(maps_dir, s, s + MAP_SUFFIX)))
@@ -189,29 +173,8 @@ def lift_results(exp: str, stage: str, maps_dir: str, out_root: str, root: str =
         if not os.path.isdir(src):
             raise FileNotFoundError(f"{src}: no such export directory")
         top = load_map(maps_dir, scene)["thin_of_point"]
-        dst = os.path.join(out_root, "results", exp, scene, stage)
-        os.makedirs(dst, exist_ok=True)
-        files = []
-        if os.path.isfile(os.path.join(src, pseudo_labels.SGL_NAME)):
-            files.append(lift_sgl(os.path.join(src, pseudo_labels.SGL_NAME), os.path.join(dst, pseudo_labels.SGL_NAME), top))
-        for name in sorted(os.listdir(src)):
-            if name.endswith(".npy"):
-                vec = np.load(os.path.join(src, name))
-                if vec.shape[0] != int(top.max()) + 1:
-                    raise ValueError(f"{src}/{name}: {vec.shape[0]} values for {int(top.max()) + 1} thinned points")
-                np.save(os.path.join(dst, name), lift(vec, top))
-                files.append(os.path.join(dst, name))
-        if not files:
-            raise FileNotFoundError(f"{src}: neither {pseudo_labels.SGL_NAME} nor .npy vectors (.txt is not read: lift the .sgl and run expand)")
-        done.append((scene, files))
+        done.append((scene, lift_stage(src, os.path.join(out_root, "results", exp, scene, stage), top, int(top.max()) + 1 if top.size else 0)))
     return done
-
-
-def _scene_list(path):
-    if not path:
-        return None
-    with open(path) as f:
-        return [ln.strip() for ln in f if ln.strip()]
 
 
 def main(argv=None) -> int:
@@ -222,7 +185,7 @@ def main(argv=None) -> int:
     ap.add_argument("--voxel", type=float, default=None, help="edge of the voxel grid, in the scan's unit")
     ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
     ap.add_argument("--force", action="store_true", help="overwrite existing thinned scans")
-    ap.add_argument("--workers", type=int, default=4, help=f"threads, each with its own stream (at most {MAX_WORKERS})")
+    scans.add_workers_argument(ap)
     ap.add_argument("--device", default=None)
     ap.add_argument("-n", "--exp_name", default=None, help="--lift: name of the experiment")
     ap.add_argument("--stage", default="epoch_last", help="--lift: the export directory's name")
@@ -232,16 +195,15 @@ def main(argv=None) -> int:
     if a.lift:
         if not a.exp_name or not a.maps:
             ap.error("--lift needs -n EXP and --maps THINNED_SCANS")
-        done = lift_results(a.exp_name, a.stage, a.maps, a.out, a.root, _scene_list(a.scenes))
+        done = lift_results(a.exp_name, a.stage, a.maps, a.out, a.root, scans.scene_list(a.scenes))
         for scene, files in done:
             print("lifted", scene, len(files), "files")
         print(f"{len(done)} scenes lifted")
         return 0
     if not a.scans or a.voxel is None:
         ap.error("thinning needs --scans DIR and --voxel H")
-    if not 1 <= a.workers <= MAX_WORKERS:
-        ap.error(f"--workers must be in 1..{MAX_WORKERS}")
-    report, skipped = thin_scans(a.scans, a.out, a.voxel, _scene_list(a.scenes), a.force, a.workers, a.device)
+    scans.check_workers(ap, a.workers)
+    report, skipped = thin_scans(a.scans, a.out, a.voxel, scans.scene_list(a.scenes), a.force, a.workers, a.device)
     for scene, e in report.items():
         print("thinned", scene, e["V"], "->", e["M"])
     for s in skipped:

@@ -20,15 +20,16 @@ own those).
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
-from . import hip
-from .thin import MAX_WORKERS, _scan_names, _scene_list
-from .thin import lift as transfer                                   # transfer(values, nearest): values[nearest] on the leading axis
+from . import hip, scans
+from .device import device_tensor, torch_device
+from .prepare import get_unmapper, mesh_arrays, nearest_point_grid, read_ply
+from .thin import lift_stage
+from .thin import lift as transfer                                  # transfer(values, nearest): values[nearest] on the leading axis
 from .thin import lift_sgl as transfer_sgl                           # transfer_sgl(src, dst, nearest): a .sgl for the target geometry
 
 MAP_SUFFIX = ".transfer.npz"
@@ -41,7 +42,6 @@ def nearest_vertex(src_xyz, dst_xyz, index: str = "grid", cell=None, device=None
     get_unmapper(dst_xyz, src_xyz), d2 = (dx*dx + dy*dy) + dz*dz of the pair in fp32.  `index="brute"` scores every pair
     (sg_nearest_point: at most 2^20 source vertices); `cell` forces the grid's cell edge, which cannot change the result."""
     import torch
-    from .prepare import _dev, _t, get_unmapper, nearest_point_grid
     which, edge = hip.knn_index(index), hip.knn_cell(cell)
     n_src = int(src_xyz.shape[0])
     if which == hip.KNN_BRUTE and n_src > hip.MAX_POINTS:
@@ -49,9 +49,9 @@ def nearest_vertex(src_xyz, dst_xyz, index: str = "grid", cell=None, device=None
                          "(index='grid')" % (n_src, hip.MAX_POINTS))
     if which == hip.KNN_GRID:
         return nearest_point_grid(dst_xyz, src_xyz, cell=edge, device=device, stream=stream)
-    dev = _dev(device)
+    dev = torch_device(device)
     with torch.cuda.device(dev):
-        d_src, d_dst = _t(src_xyz, torch.float32, dev)[:, :3], _t(dst_xyz, torch.float32, dev)[:, :3]
+        d_src, d_dst = device_tensor(src_xyz, torch.float32, dev)[:, :3], device_tensor(dst_xyz, torch.float32, dev)[:, :3]
         nearest = get_unmapper(d_dst.contiguous(), d_src.contiguous(), device=dev)
         d = d_dst - d_src.index_select(0, nearest)
         d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
@@ -59,7 +59,6 @@ def nearest_vertex(src_xyz, dst_xyz, index: str = "grid", cell=None, device=None
 
 
 def _scan_xyz(scans_dir: str, scene: str):
-    from .prepare import mesh_arrays, read_ply
     return mesh_arrays(read_ply(os.path.join(scans_dir, scene, scene + "_vh_clean_2.ply")))[0]
 
 
@@ -67,7 +66,6 @@ def transfer_scene(scene: str, from_scans: str, to_scans: str, exp: str, stage: 
                    device=None, stream=None):
     """One scene: results/<exp>/<scene>/<stage>/ under `root`, made on <from_scans>/<scene>, -> the same files for <to_scans>/<scene>
     under <out_root>/results/...; -> (its entry of transfer_report.json, the files written)."""
-    from . import pseudo_labels
     src_dir = os.path.join(root, "results", exp, scene, stage)
     if not os.path.isdir(src_dir):
         raise FileNotFoundError(f"{src_dir}: no such export directory")
@@ -75,19 +73,7 @@ def transfer_scene(scene: str, from_scans: str, to_scans: str, exp: str, stage: 
     d_near, d_d2 = nearest_vertex(src_xyz, dst_xyz, index=index, device=device, stream=stream)
     nearest, d2 = d_near.cpu().numpy(), d_d2.cpu().numpy()
     dst_dir = os.path.join(out_root, "results", exp, scene, stage)
-    os.makedirs(dst_dir, exist_ok=True)
-    files = []
-    if os.path.isfile(os.path.join(src_dir, pseudo_labels.SGL_NAME)):
-        files.append(transfer_sgl(os.path.join(src_dir, pseudo_labels.SGL_NAME), os.path.join(dst_dir, pseudo_labels.SGL_NAME), nearest))
-    for name in sorted(os.listdir(src_dir)):
-        if name.endswith(".npy"):
-            vec = np.load(os.path.join(src_dir, name))
-            if vec.shape[0] != src_xyz.shape[0]:
-                raise ValueError(f"{src_dir}/{name}: {vec.shape[0]} values for {src_xyz.shape[0]} source vertices")
-            np.save(os.path.join(dst_dir, name), transfer(vec, nearest))
-            files.append(os.path.join(dst_dir, name))
-    if not files:
-        raise FileNotFoundError(f"{src_dir}: neither {pseudo_labels.SGL_NAME} nor .npy vectors (.txt is not read: transfer the .sgl and run expand)")
+    files = lift_stage(src_dir, dst_dir, nearest, int(src_xyz.shape[0]), "transfer", "source vertices")
     np.savez(os.path.join(dst_dir, scene + MAP_SUFFIX), nearest=nearest, d2=d2)
     dist = np.sqrt(d2.astype(np.float64))
     entry = {"source_V": int(src_xyz.shape[0]), "target_V": int(dst_xyz.shape[0]), "max_distance": float(dist.max()) if dist.size else 0.0,
@@ -100,14 +86,9 @@ def transfer_results(from_scans: str, to_scans: str, exp: str, stage: str, out_r
                      index: str = "grid", device=None):
     """Every scene of `from_scans` (or the named ones) that both trees hold -> (report {scene: entry}, missing {scene: why}); writes
     <out_root>/transfer_report.json.  Workers are threads, each with its own stream."""
-    import concurrent.futures
-    import threading
-
-    import torch
-    from .prepare import _dev
     hip.knn_index(index)
-    dev = _dev(device)
-    have_src, have_dst = set(_scan_names(from_scans)), set(_scan_names(to_scans))
+    dev = torch_device(device)
+    have_src, have_dst = set(scans.scan_names(from_scans)), set(scans.scan_names(to_scans))
     if scenes is None:
         scenes = sorted(have_src | have_dst)
     missing = {}
@@ -119,23 +100,10 @@ def transfer_results(from_scans: str, to_scans: str, exp: str, stage: str, out_r
             missing[s] = "no scan under --to-scans"
         else:
             todo.append(s)
-    workers = max(1, min(int(workers), MAX_WORKERS, max(len(todo), 1)))
-    local = threading.local()
-
-    def one(scene):
-        if not hasattr(local, "stream"):
-            with torch.cuda.device(dev):
-                local.stream = torch.cuda.Stream(device=dev)
-        return scene, transfer_scene(scene, from_scans, to_scans, exp, stage, out_root, root, index, device=dev, stream=local.stream)[0]
-
-    report = {}
-    with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
-        for scene, entry in pool.map(one, todo):
-            report[scene] = entry
+    report = dict(scans.map_scans(todo, workers, dev, lambda scene, stream: transfer_scene(scene, from_scans, to_scans, exp, stage, out_root, root,
+                                                                                           index, device=dev, stream=stream)[0]))
     os.makedirs(out_root, exist_ok=True)
-    with open(os.path.join(out_root, REPORT_NAME), "w") as f:
-        json.dump({"experiment": exp, "stage": stage, "index": index, "scenes": report, "missing": missing}, f, indent=1, sort_keys=True)
-        f.write("\n")
+    scans.write_report(os.path.join(out_root, REPORT_NAME), {"experiment": exp, "stage": stage, "index": index, "scenes": report, "missing": missing})
     return report, missing
 
 
@@ -148,14 +116,13 @@ def main(argv=None) -> int:
     ap.add_argument("--out", required=True, help="the root that receives results/ and transfer_report.json")
     ap.add_argument("--root", default=".", help="directory holding results/ (default: CWD)")
     ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
-    ap.add_argument("--workers", type=int, default=4, help=f"threads, each with its own stream (at most {MAX_WORKERS})")
+    scans.add_workers_argument(ap)
     ap.add_argument("--index", choices=sorted(hip.KNN_INDEX), default="grid", help="grid: the exact grid index; brute: every pair (at most 2^20 source vertices)")
     ap.add_argument("--device", default=None)
     a = ap.parse_args(argv)
-    if not 1 <= a.workers <= MAX_WORKERS:
-        ap.error(f"--workers must be in 1..{MAX_WORKERS}")
+    scans.check_workers(ap, a.workers)
     try:
-        report, missing = transfer_results(a.from_scans, a.to_scans, a.exp_name, a.stage, a.out, a.root, _scene_list(a.scenes), a.workers,
+        report, missing = transfer_results(a.from_scans, a.to_scans, a.exp_name, a.stage, a.out, a.root, scans.scene_list(a.scenes), a.workers,
                                            a.index, a.device)
     except ValueError as e:
         if "--index grid" not in str(e):

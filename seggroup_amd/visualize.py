@@ -40,13 +40,6 @@ VECTOR_TYPES = [TYPES[{"seg": "segment", "ins": "instance", "sem": "semantic"}[n
 VECTOR_SHUFFLED = [n in ("layer_2.seg", "layer_3.seg", "layer_4.seg") for n in hip.LABEL_NAMES]
 
 
-def _check(rc: int) -> int:
-    """hip.check, with SG_EINVAL (a bad file, label or argument) raised as ValueError."""
-    if rc == hip.SG_EINVAL:
-        raise ValueError(hip.lib().sg_last_error().decode("utf-8", "replace"))
-    return hip.check(rc)
-
-
 def _device(device=None):
     import torch
     hip.require_device()
@@ -79,7 +72,7 @@ class PlySource:
 def ply_plan(path: str) -> dict:
     """sg_ply_plan: where the vertex block of a binary little-endian PLY file sits and which bytes of a vertex are its colour."""
     plan = (C.c_longlong * 10)()
-    _check(hip.lib().sg_ply_plan(os.fsencode(path), plan))
+    hip.check_arg(hip.lib().sg_ply_plan(os.fsencode(path), plan))
     keys = ("vertex_offset", "V", "stride", "red", "green", "blue", "tail_offset", "tail_bytes", "file_bytes", "header_bytes")
     return dict(zip(keys, [int(x) for x in plan]))
 
@@ -165,7 +158,7 @@ def dilate_labels(labels: np.ndarray, adj: np.ndarray) -> np.ndarray:
     indptr = np.zeros(V + 1, dtype=np.int64)
     np.cumsum(np.bincount(src, minlength=V), out=indptr[1:])
     indices = np.ascontiguousarray(dst[order], dtype=np.int32)
-    _check(hip.lib().sg_dilate_labels(lab.ctypes.data, V, indptr.ctypes.data, indices.ctypes.data if indices.size else None))
+    hip.check_arg(hip.lib().sg_dilate_labels(lab.ctypes.data, V, indptr.ctypes.data, indices.ctypes.data if indices.size else None))
     return lab
 
 
@@ -204,9 +197,9 @@ def colour_vector(labels, label_type, shuffle: bool = False, second=None, mult: 
     with torch.cuda.device(dev):
         st = _stream_ptr()
         count = C.c_int(0)
-        _check(lib.sg_colour_vector_unique(lab.data_ptr(), V, t, C.byref(count), ws.data_ptr(), ws_bytes, st))
+        hip.check_arg(lib.sg_colour_vector_unique(lab.data_ptr(), V, t, C.byref(count), ws.data_ptr(), ws_bytes, st))
         pos = draw_positions(count.value, rng) if (shuffle and t == hip.COLOUR_SEGMENT) else None
-        _check(lib.sg_colour_vector_apply(lab.data_ptr(), V, t, None if sec is None else sec.data_ptr(), count.value,
+        hip.check_arg(lib.sg_colour_vector_apply(lab.data_ptr(), V, t, None if sec is None else sec.data_ptr(), count.value,
                                           None if pos is None else pos.ctypes.data, int(mult), out.data_ptr(), ws.data_ptr(), ws_bytes, st))
     return out[:V]
 
@@ -228,7 +221,7 @@ def colour_tables(tables, seg_of_vertex, types: Sequence[int], shuffled: Optiona
     out = torch.empty((nvec, S + 1), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         st = _stream_ptr()
-        _check(lib.sg_colour_tables_unique(tables.data_ptr(), nvec, S, seg_of_vertex.data_ptr(), sov_width, V, ty, counts, ws.data_ptr(), ws_bytes, st))
+        hip.check_arg(lib.sg_colour_tables_unique(tables.data_ptr(), nvec, S, seg_of_vertex.data_ptr(), sov_width, V, ty, counts, ws.data_ptr(), ws_bytes, st))
         perm_off = np.full(nvec, -1, dtype=np.int64)
         perms: List[np.ndarray] = []
         at = 0
@@ -240,7 +233,7 @@ def colour_tables(tables, seg_of_vertex, types: Sequence[int], shuffled: Optiona
                 at += counts[r]
         perm = np.concatenate(perms) if perms else np.zeros(1, np.int32)
         sr = None if sem_rows is None else (C.c_int * nvec)(*[int(x) for x in sem_rows])
-        _check(lib.sg_colour_tables_apply(tables.data_ptr(), nvec, S, ty, sr, counts, perm.ctypes.data, perm_off.ctypes.data, out.data_ptr(),
+        hip.check_arg(lib.sg_colour_tables_apply(tables.data_ptr(), nvec, S, ty, sr, counts, perm.ctypes.data, perm_off.ctypes.data, out.data_ptr(),
                                           ws.data_ptr(), ws_bytes, st))
     return out
 
@@ -261,7 +254,7 @@ def vertex_records(src_dev, V: int, stride: int, offsets: Sequence[int], cidx, r
     if cidx.shape[1] < (S + 1 if seg_of_vertex is not None else V):
         raise ValueError("the colour table is narrower than the scene")
     with torch.cuda.device(dev):
-        _check(lib.sg_ply_vertex_records_device(src_dev.data_ptr(), V, stride, offsets[0], offsets[1], offsets[2],
+        hip.check_arg(lib.sg_ply_vertex_records_device(src_dev.data_ptr(), V, stride, offsets[0], offsets[1], offsets[2],
                                                 None if seg_of_vertex is None else seg_of_vertex.data_ptr(), sov_width, S, cidx.data_ptr(), ld,
                                                 len(rows), (C.c_int * len(rows))(*rows), out.data_ptr(), _stream_ptr()))
     return out[:, :V * stride]
@@ -290,9 +283,9 @@ def write_plys(src: PlySource, blocks: np.ndarray, paths: Sequence[str], writer=
     for i, p in enumerate(paths):
         os.makedirs(os.path.dirname(os.path.dirname(os.path.abspath(p))), exist_ok=True)
         b = blocks[i]
-        _check(lib.sg_writer_submit_ply(w, os.fsencode(p), src.head, len(src.head), b.ctypes.data, b.size, src.tail, len(src.tail), tag))
+        hip.check_arg(lib.sg_writer_submit_ply(w, os.fsencode(p), src.head, len(src.head), b.ctypes.data, b.size, src.tail, len(src.tail), tag))
     if flush:
-        _check(lib.sg_writer_flush(w))
+        hip.check_arg(lib.sg_writer_flush(w))
 
 
 # ---- the reference's two functions ----------------------------------------------------------------------------------------------------

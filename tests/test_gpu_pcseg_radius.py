@@ -136,7 +136,7 @@ def test_the_cell_edge_cannot_change_a_byte():
 def test_capacity_protocol(sg_lib):
     import torch
     from seggroup_amd import hip
-    from seggroup_amd.prepare import _ws
+    from seggroup_amd.device import workspace as _ws
     xyz, _, ref, _ = Q.case("room_dup")
     n, want_t = xyz.shape[0], int(ref["off"][-1])
     d_x = torch.from_numpy(xyz).to(DEV)

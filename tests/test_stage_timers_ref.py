@@ -38,3 +38,37 @@ def test_one_contract_for_every_family(sg_lib, family):
     assert name(-1) is None and name(n) is None
     assert tuple(name(i) for i in range(n)) == tuple(s.encode() for s in names)
     assert getattr(sg_lib, f"sg_{family}_set_timing")(0) == hip.SG_OK
+
+
+class _Recorded:
+    """the library, with every sg_*_set_timing call written down"""
+
+    def __init__(self, lib):
+        self._lib, self.switched = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.endswith("_set_timing"):
+            return fn
+        return lambda on: (self.switched.append((name, on)), fn(on))[1]
+
+
+def test_the_reader_covers_the_nine_families():
+    assert sorted(hip.STAGE_FAMILIES) == sorted(FAMILIES)
+
+
+@pytest.mark.parametrize("family", sorted(FAMILIES))
+def test_reader_names_values_and_switch(sg_lib, family, monkeypatch):
+    rec = _Recorded(sg_lib)
+    monkeypatch.setattr(hip, "lib", lambda: rec)
+    switch = f"sg_{family}_set_timing"
+    with hip.stage_timer(family) as t:
+        assert rec.switched == [(switch, 1)]
+        assert tuple(t.names) == FAMILIES[family]
+        us = t.read()
+        assert len(us) == len(FAMILIES[family]) and all(isinstance(u, float) for u in us)
+    assert rec.switched == [(switch, 1), (switch, 0)]
+    with pytest.raises(KeyError, match="inside the block"):
+        with hip.stage_timer(family):
+            raise KeyError("inside the block")
+    assert rec.switched == [(switch, 1), (switch, 0)] * 2            # off again after the exception, which is passed on

@@ -57,10 +57,7 @@ def measure(label, num_vertices, launch, pairs, source_bytes, host_pairs, repeat
     ws = torch.empty(lib.sg_components_ws_bytes(num_vertices), dtype=torch.uint8, device="cuda")
     c = C.c_int(0)
     tail = (None, comp.data_ptr(), size.data_ptr(), C.byref(c), ws.data_ptr(), ws.numel(), None)
-    buf = (C.c_float * 8)()
-    n_stages = lib.sg_components_stage_times(buf, 8)
-    names = [lib.sg_components_stage_name(i).decode() for i in range(n_stages)]
-    launch(lib, tail)                                            # warm-up
+    launch(lib, tail)                                           # warm-up
     torch.cuda.synchronize()
     ms = []
     for _ in range(repeats):
@@ -70,14 +67,13 @@ def measure(label, num_vertices, launch, pairs, source_bytes, host_pairs, repeat
         e1.record()
         e1.synchronize()
         ms.append(e0.elapsed_time(e1))
-    hip.check(lib.sg_components_set_timing(1))
     rows = []
-    for _ in range(3):
-        launch(lib, tail)
-        assert lib.sg_components_stage_times(buf, 8) == n_stages
-        rows.append(list(buf)[:n_stages])
-    hip.check(lib.sg_components_set_timing(0))
-    us = np.median(np.asarray(rows), 0)
+    with hip.stage_timer("components") as timer:
+        for _ in range(3):
+            launch(lib, tail)
+            rows.append(timer.read())
+    names = timer.names
+    us =np.median(np.asarray(rows), 0)
     a, b = host_pairs()
     want, which, host_s = host_answer(num_vertices, a, b)
     got = comp.cpu().numpy()

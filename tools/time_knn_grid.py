@@ -42,9 +42,6 @@ class Bench:
         self.knn = {w: torch.empty((n, k + 1), dtype=torch.int32, device="cuda") for w in ("brute", "grid") if w == "grid" or self.brute_ok}
         self.ws = torch.empty(lib.sg_pcseg_ws_bytes_indexed(n, k, hip.KNN_GRID), dtype=torch.uint8, device="cuda")
         self.n_e = C.c_int(0)
-        self.buf = (C.c_float * 8)()
-        self.names = [lib.sg_pcseg_stage_name(i).decode() for i in range(lib.sg_pcseg_stage_times(self.buf, 8))]
-        self.gnames = [lib.sg_pointcloud_knn_grid_stage_name(i).decode() for i in range(lib.sg_pointcloud_knn_grid_stage_times(self.buf, 8))]
 
     def call(self, which):
         lib, hip = self.lib, self.hip
@@ -56,26 +53,22 @@ class Bench:
         self.torch.cuda.synchronize()
         return time.perf_counter() - t0
 
-    def timed(self, which):
-        """-> (knn stage us, all stages us, wall ms)"""
+    def timed(self, which, timer):
+        """-> (knn stage us, all stages us, wall ms); `timer`: the pcseg family's, on"""
         wall = self.call(which)
-        n = self.lib.sg_pcseg_stage_times(self.buf, 8)
-        us = list(self.buf)[:n]
-        return us[self.names.index("knn")], float(sum(us)), wall * 1e3
+        us = timer.read()
+        return us[timer.names.index("knn")], float(sum(us)), wall * 1e3
 
     def grid_detail(self, iters):
         from seggroup_amd import oversegment
-        lib, hip = self.lib, self.hip
-        hip.check(lib.sg_pointcloud_knn_grid_set_timing(1))
         rows = []
-        for _ in range(iters):
-            self.call("grid")
-            n = lib.sg_pointcloud_knn_grid_stage_times(self.buf, 8)
-            rows.append(list(self.buf)[:n])
-        st = oversegment.knn_grid_stats()
-        hip.check(lib.sg_pointcloud_knn_grid_set_timing(0))
+        with self.hip.stage_timer("pointcloud_knn_grid") as timer:
+            for _ in range(iters):
+                self.call("grid")
+                rows.append(timer.read())
+            st = oversegment.knn_grid_stats()
         us = np.median(np.asarray(rows), 0)
-        return {nm: round(float(u), 1) for nm, u in zip(self.gnames, us)}, st
+        return {nm: round(float(u), 1) for nm, u in zip(timer.names, us)}, st
 
 
 def spread(v, digits=1):
@@ -89,12 +82,11 @@ def measure(label, xyz, k, iters):
     paths = ["brute", "grid"] if b.brute_ok else ["grid"]
     for w in paths:
         b.call(w)                                               # warm-up
-    hip.check(lib.sg_pcseg_set_timing(1))
     rec = {w: [] for w in paths}
-    for _ in range(iters):
-        for w in paths:                                         # alternating
-            rec[w].append(b.timed(w))
-    hip.check(lib.sg_pcseg_set_timing(0))
+    with hip.stage_timer("pcseg") as timer:
+        for _ in range(iters):
+            for w in paths:                                     # alternating
+                rec[w].append(b.timed(w, timer))
     out = dict(cloud=label, N=b.N, k=k, E=int(b.n_e.value))
     for w in paths:
         r = np.asarray(rec[w])
@@ -120,16 +112,16 @@ def sweep(b, iters):
     lib, hip = b.lib, b.hip
     from seggroup_amd import oversegment
     rows = []
-    hip.check(lib.sg_pcseg_set_timing(1))
-    for target, limit in [(t, 0) for t in (8, 16, 32, 48, 64, 96, 160)] + [(0, r) for r in (1, 2, 4, 8, 16)]:
-        hip.check(lib.sg_pointcloud_knn_grid_set_tuning(target, limit))
-        b.call("grid")
-        us = [b.timed("grid")[0] for _ in range(iters)]
-        st = oversegment.knn_grid_stats()
-        rows.append(dict(target_occupancy=target or "default", ring_limit=limit or "default", knn_stage_us=spread(us), cell=round(st["cell"], 5),
-                         occupied=st["occupied"], largest_cell=st["largest_cell"], max_ring=st["max_ring"], fallback=st["fallback"]))
-    hip.check(lib.sg_pointcloud_knn_grid_set_tuning(0, 0))
-    hip.check(lib.sg_pcseg_set_timing(0))
+    with hip.stage_timer("pcseg") as timer:
+        for target, limit in [(t, 0) for t in (8, 16, 32, 48, 64, 96, 160)] + [(0, r) for r in (1, 2, 4, 8, 16)]:
+            hip.check(lib.sg_pointcloud_knn_grid_set_tuning(target, limit))
+            b.call("grid")
+            us = [b.timed("grid", timer)[0] for _ in range(iters)]
+            st = oversegment.knn_grid_stats()
+            rows.append(dict(target_occupancy=target or "default", ring_limit=limit or "default", knn_stage_us=spread(us),
+                             cell=round(st["cell"], 5), occupied=st["occupied"], largest_cell=st["largest_cell"], max_ring=st["max_ring"],
+                             fallback=st["fallback"]))
+        hip.check(lib.sg_pointcloud_knn_grid_set_tuning(0, 0))
     return rows
 
 

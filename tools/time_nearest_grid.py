@@ -44,8 +44,6 @@ class Bench:
         self.d2 = torch.empty(self.U, dtype=torch.float32, device="cuda")
         self.ws = torch.empty(max(self.lib.sg_nearest_point_grid_ws_bytes(self.U, self.N), self.lib.sg_nearest_point_ws_bytes(self.N)),
                               dtype=torch.uint8, device="cuda")
-        self.buf = (C.c_float * 8)()
-        self.names = [self.lib.sg_nearest_point_grid_stage_name(i).decode() for i in range(7)]
 
     def call(self, which):
         """-> (device us between two events, host wall ms)"""
@@ -66,16 +64,13 @@ class Bench:
 
     def grid_detail(self, iters):
         from seggroup_amd import prepare
-        lib, hip = self.lib, self.hip
-        hip.check(lib.sg_nearest_point_grid_set_timing(1))
         rows = []
-        for _ in range(iters):
-            self.call("grid")
-            n = lib.sg_nearest_point_grid_stage_times(self.buf, 8)
-            rows.append(list(self.buf)[:n])
-        st = prepare.nearest_grid_stats()
-        hip.check(lib.sg_nearest_point_grid_set_timing(0))
-        return {nm: round(float(u), 1) for nm, u in zip(self.names, np.median(np.asarray(rows), 0))}, st
+        with self.hip.stage_timer("nearest_point_grid") as timer:
+            for _ in range(iters):
+                self.call("grid")
+                rows.append(timer.read())
+            st = prepare.nearest_grid_stats()
+        return {nm: round(float(u), 1) for nm, u in zip(timer.names, np.median(np.asarray(rows), 0))}, st
 
 
 def measure(label, x, y, iters, brute):

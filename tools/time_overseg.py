@@ -55,8 +55,6 @@ def measure(w, h, iters):
     wts = torch.empty(3 * F, dtype=torch.float32, device="cuda")
     ws = torch.empty(lib.sg_overseg_ws_bytes(V, F), dtype=torch.uint8, device="cuda")
     n_e = C.c_int(0)
-    ns = lib.sg_overseg_stage_times
-    names = [lib.sg_overseg_stage_name(i).decode() for i in range(8)]
 
     def device_call():
         hip.check(lib.sg_overseg_edges(d_xyz.data_ptr(), V, d_f.data_ptr(), F, None, nrm.data_ptr(), edges.data_ptr(), wts.data_ptr(), C.byref(n_e),
@@ -64,17 +62,15 @@ def measure(w, h, iters):
     for _ in range(3):
         device_call()
     torch.cuda.synchronize()
-    hip.check(lib.sg_overseg_set_timing(1))
     rows, wall = [], []
-    buf = (C.c_float * 8)()
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        device_call()
-        torch.cuda.synchronize()
-        wall.append(time.perf_counter() - t0)
-        assert ns(buf, 8) == 8
-        rows.append(list(buf))
-    hip.check(lib.sg_overseg_set_timing(0))
+    with hip.stage_timer("overseg") as timer:
+        for _ in range(iters):
+            t0 = time.perf_counter()
+            device_call()
+            torch.cuda.synchronize()
+            wall.append(time.perf_counter() - t0)
+            rows.append(timer.read())
+    names = timer.names
     E = n_e.value
     us = np.median(np.asarray(rows), 0)
     nbytes = stage_bytes(V, F, E)

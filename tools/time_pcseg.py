@@ -34,25 +34,21 @@ def measure(w, h, k, iters):
     wts = torch.empty(N * k, dtype=torch.float32, device="cuda")
     ws = torch.empty(lib.sg_pcseg_ws_bytes(N, k), dtype=torch.uint8, device="cuda")
     n_e = C.c_int(0)
-    buf = (C.c_float * 8)()
-    n_stages = lib.sg_pcseg_stage_times(buf, 8)
-    names = [lib.sg_pcseg_stage_name(i).decode() for i in range(n_stages)]
 
     def device_call():
         hip.check(lib.sg_pcseg_edges(d_xyz.data_ptr(), N, k, None, None, nrm.data_ptr(), edges.data_ptr(), wts.data_ptr(), C.byref(n_e), ws.data_ptr(),
                                      ws.numel(), None))
     device_call()
     torch.cuda.synchronize()
-    hip.check(lib.sg_pcseg_set_timing(1))
     rows, wall = [], []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        device_call()
-        torch.cuda.synchronize()
-        wall.append(time.perf_counter() - t0)
-        assert lib.sg_pcseg_stage_times(buf, 8) == n_stages
-        rows.append(list(buf)[:n_stages])
-    hip.check(lib.sg_pcseg_set_timing(0))
+    with hip.stage_timer("pcseg") as timer:
+        for _ in range(iters):
+            t0 = time.perf_counter()
+            device_call()
+            torch.cuda.synchronize()
+            wall.append(time.perf_counter() - t0)
+            rows.append(timer.read())
+    names = timer.names
     E = n_e.value
     us = np.median(np.asarray(rows), 0)
     total = float(us.sum())

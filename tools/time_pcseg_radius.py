@@ -66,12 +66,12 @@ def parent_route(d_x, repeats):
 
 def measure(label, xyz, radius, repeats, max_pairs):
     import torch
-    from seggroup_amd import hip, oversegment
+    from seggroup_amd import components, hip, oversegment
     lib = hip.lib()
     n = xyz.shape[0]
     d_x = torch.from_numpy(xyz).cuda()
     out = dict(cloud=label, N=int(n), radius=radius)
-    t_pairs = oversegment._query_pairs(lib, d_x, n, radius, 0.0, "cuda:0", None)
+    t_pairs = components.radius_pairs(d_x, n, radius, 0.0, "cuda:0", None)[0]
     need = int(lib.sg_pcseg_ws_bytes_radius(n, t_pairs))
     out.update(T=int(t_pairs), E=int(t_pairs // 2), workspace_bytes=need, parent_knn10_grid=parent_route(d_x, min(repeats, 3)))
     if t_pairs > max_pairs:
@@ -92,16 +92,13 @@ def measure(label, xyz, radius, repeats, max_pairs):
                                             edges.data_ptr(), w.data_ptr(), C.byref(n_e), C.byref(total), ws.data_ptr(), ws.numel(), None))
 
     out.update(run=True, edges_call_ms=timed(call, repeats))
-    buf = (C.c_float * 13)()
-    names = [lib.sg_pcseg_radius_stage_name(i).decode() for i in range(13)]
-    hip.check(lib.sg_pcseg_radius_set_timing(1))
     rows = []
-    for _ in range(3):
-        call()
-        assert lib.sg_pcseg_radius_stage_times(buf, 13) == 13
-        rows.append(list(buf))
-    hip.check(lib.sg_pcseg_radius_set_timing(0))
-    us = np.median(np.asarray(rows), 0)
+    with hip.stage_timer("pcseg_radius") as timer:
+        for _ in range(3):
+            call()
+            rows.append(timer.read())
+    names = timer.names
+    us =np.median(np.asarray(rows), 0)
     length = (off[1:] - off[:-1])
     out.update(stages_us={nm: round(float(u), 1) for nm, u in zip(names, us)}, mean_row=round(float(length.double().mean()), 2),
                max_row=int(length.max()), sum_row_squared_over_64=float((length.double() ** 2).sum() / 64.0))

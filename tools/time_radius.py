@@ -88,16 +88,12 @@ def measure(label, xyz, radius, repeats, host_pairs):
         hip.check(lib.sg_radius_count_grid(d_x.data_ptr(), 3, n, radius, 0.0, cnt.data_ptr(), ws.data_ptr(), ws.numel(), None))
 
     out = dict(cloud=label, N=int(n), radius=radius, components_ms=timed(components, repeats), count_ms=timed(count, repeats))
-    buf, h = (C.c_float * 8)(), (C.c_int64 * 9)()
-    names = [lib.sg_radius_grid_stage_name(i).decode() for i in range(7)]
-    hip.check(lib.sg_radius_grid_set_timing(1))
     rows = []
-    for _ in range(3):
-        components()
-        assert lib.sg_radius_grid_stage_times(buf, 8) == 7 and lib.sg_radius_grid_stats(h, 9) == 9
-        rows.append(list(buf)[:7])
-    hip.check(lib.sg_radius_grid_set_timing(0))
-    stats = M.radius_stats()
+    with hip.stage_timer("radius_grid") as timer:
+        for _ in range(3):
+            components()
+            rows.append(timer.read())
+    names, stats = timer.names, M.radius_stats()
     us = np.median(np.asarray(rows), 0)
     got = comp.cpu().numpy()
     sizes = np.sort(np.bincount(got)[np.unique(got)])[::-1]

@@ -33,8 +33,6 @@ def time_vote(ids, cols, n_cols, iters):
     out = torch.empty((9, v), dtype=torch.int32, device="cuda")
     ws = torch.empty(lib.sg_segment_vote_ws_bytes(v), dtype=torch.uint8, device="cuda")
     n_r = C.c_int(0)
-    n_st = 7
-    names = [lib.sg_segment_vote_stage_name(i).decode() for i in range(n_st)]
 
     def call():
         hip.check(lib.sg_segment_vote(d_ids.data_ptr(), d_cols.data_ptr(), v, n_cols, *[out[i].data_ptr() for i in range(9)], C.byref(n_r),
@@ -42,17 +40,15 @@ def time_vote(ids, cols, n_cols, iters):
     for _ in range(3):
         call()
     torch.cuda.synchronize()
-    hip.check(lib.sg_segment_vote_set_timing(1))
-    buf = (C.c_float * n_st)()
     rows, wall = [], []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        call()
-        torch.cuda.synchronize()
-        wall.append(time.perf_counter() - t0)
-        assert lib.sg_segment_vote_stage_times(buf, n_st) == n_st
-        rows.append(list(buf))
-    hip.check(lib.sg_segment_vote_set_timing(0))
+    with hip.stage_timer("segment_vote") as timer:
+        for _ in range(iters):
+            t0 = time.perf_counter()
+            call()
+            torch.cuda.synchronize()
+            wall.append(time.perf_counter() - t0)
+            rows.append(timer.read())
+    names = timer.names
     host = []
     for _ in range(3):
         t0 = time.perf_counter()

@@ -38,26 +38,22 @@ def measure(label, xyz, voxel, iters):
     top = torch.empty(n, dtype=torch.int32, device="cuda")
     ws = torch.empty(lib.sg_cloud_thin_ws_bytes(n), dtype=torch.uint8, device="cuda")
     m = C.c_int(0)
-    buf = (C.c_float * 8)()
-    n_stages = lib.sg_cloud_thin_stage_times(buf, 8)
-    names = [lib.sg_cloud_thin_stage_name(i).decode() for i in range(n_stages)]
 
     def device_call():
         hip.check(lib.sg_cloud_thin(d_xyz.data_ptr(), 3, n, float(voxel), rep.data_ptr(), top.data_ptr(), C.byref(m), None, ws.data_ptr(),
                                     ws.numel(), None))
     device_call()
     torch.cuda.synchronize()
-    hip.check(lib.sg_cloud_thin_set_timing(1))
     rows, wall = [], []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        device_call()
-        torch.cuda.synchronize()
-        wall.append(time.perf_counter() - t0)
-        assert lib.sg_cloud_thin_stage_times(buf, 8) == n_stages
-        rows.append(list(buf)[:n_stages])
-    hip.check(lib.sg_cloud_thin_set_timing(0))
-    us = np.median(np.asarray(rows), 0)
+    with hip.stage_timer("cloud_thin") as timer:
+        for _ in range(iters):
+            t0 = time.perf_counter()
+            device_call()
+            torch.cuda.synchronize()
+            wall.append(time.perf_counter() - t0)
+            rows.append(timer.read())
+    names = timer.names
+    us =np.median(np.asarray(rows), 0)
     total = float(us.sum())
     stages = {nm: dict(us=round(float(u), 1), share=round(float(u) / total, 4)) for nm, u in zip(names, us)}
     t0 = time.perf_counter()
