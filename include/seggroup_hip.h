@@ -1047,6 +1047,33 @@ int sg_rekey_clicks(const int32_t* h_src_seg, const int32_t* h_new_seg, int V, c
                     const int32_t* h_row_first, int R, const int32_t* h_new_ids, int S, const int64_t* h_click_seg,
                     const int64_t* h_click_point, int n, int32_t* h_out_seg, int32_t* h_out_point, int32_t* h_out_how);
 
+/* Segment graph of a scan: the scan's edge list contracted through the per-vertex segment number, with counts.  d_adj holds
+ * the rows of <scene>.adj.pth (int64 [E,2], 16-byte aligned), d_seg the segment number of every vertex: 0..S-1, negative = no segment.  For
+ * every row (u, v) let a = d_seg[u], b = d_seg[v]; the row counts when a >= 0, b >= 0 and a != b.  d_pairs = the distinct
+ * (min(a,b), max(a,b)) in ascending lexicographic order, d_cross[i] = the number of rows behind pair i (duplicate rows and both
+ * orientations each count), *h_P = the number of pairs.  Rows (u, u) and rows inside one segment are dropped; E = 0 gives P = 0.  d_pairs
+ * needs room for E rows of 2, d_cross for E words.  Integers only: the same bytes on every run and every stream.
+ * Refused before the first HIP call: SG_EINVAL for null pointers, E < 0, S < 1, V < 1; SG_EUNSUP for S > 2^20 or E >= 2^31 (and later
+ * for more than 2^30 crossing rows); SG_ENOMEM for a workspace below sg_segment_graph_ws_bytes(E, S) (0 outside those limits).
+ * Refused from the device (one flag word): SG_EINVAL for a vertex index outside 0..V-1 or a segment number >= S; nothing is read
+ * through either.  Sort-based (csrc/kernels_seggraph.hip): O(E) memory, where sg_contract_point_edges keeps S * S bits and no counts.
+ * Synchronises the stream twice: after the key pass (flag word, crossing rows) and at the end (pairs).
+ * sg_click_clusters (host, no GPU needed): the clusters of every instance's segments over that graph, in the list order and member order of
+ *   the reference's group_adjacency_segs.  h_pairs: P rows (a, b), a < b, strictly ascending; h_seg_ins[s] = the instance of segment s,
+ *   <= 0 = in no cluster.  Instances are visited in ascending value, inside one its segments in ascending number; segment s opens the
+ *   list [s], and every list that holds a neighbour t < s of the same instance (ascending t) is appended to it whole.  -> *h_C clusters in
+ *   the order their first (= highest) segments were visited: members h_cl_members[h_cl_off[c] .. h_cl_off[c+1]), instance h_cl_ins[c].
+ *   Room: h_cl_off [S+1], h_cl_members [S], h_cl_ins [S].  The arrays are untrusted (SG_EINVAL). */
+size_t sg_segment_graph_ws_bytes(long long E, int S);
+int sg_segment_graph(const int64_t* d_adj, long long E, const int32_t* d_seg, int V, int S, int32_t* d_pairs, int32_t* d_cross, long long* h_P,
+                     void* d_ws, size_t ws_bytes, void* stream);
+/* Stage times of sg_segment_graph by events (tools/time_clicks.py), as sg_overseg_set_timing: room for 4 floats. */
+int sg_segment_graph_set_timing(int on);
+int sg_segment_graph_stage_times(float* h_us, int cap);
+const char* sg_segment_graph_stage_name(int i);
+int sg_click_clusters(const int32_t* h_pairs, long long P, const int32_t* h_seg_ins, int S, int32_t* h_cl_off, int32_t* h_cl_members,
+                      int32_t* h_cl_ins, int* h_C);
+
 /* =============================================================================================
  * Training step, operator level: the train-mode tail of SegModel.forward + its backward, and the backward
  * of every operator in front of it (group max, point->cluster max, GCN, EdgeConv MLP2 / MLP3, MLP1); further down the whole step

@@ -200,6 +200,12 @@ SIGNATURES = {
     "sg_segment_vote_stage_times": (_I, [vp, _I]),
     "sg_segment_vote_stage_name": (C.c_char_p, [_I]),
     "sg_rekey_clicks": (_I, [vp, vp, _I, vp, vp, vp, _I, vp, _I, vp, vp, _I, vp, vp, vp]),
+    "sg_segment_graph_ws_bytes": (_Z, [C.c_longlong, _I]),
+    "sg_segment_graph": (_I, [vp, C.c_longlong, vp, _I, _I, vp, vp, C.POINTER(C.c_longlong), vp, _Z, vp]),
+    "sg_segment_graph_set_timing": (_I, [_I]),
+    "sg_segment_graph_stage_times": (_I, [vp, _I]),
+    "sg_segment_graph_stage_name": (C.c_char_p, [_I]),
+    "sg_click_clusters": (_I, [vp, C.c_longlong, vp, _I, vp, vp, vp, C.POINTER(C.c_int)]),
     "sg_train_tail_ws_bytes": (_Z, [_I, _I]),
     "sg_train_tail_forward": (_I, [vp, _I, vp, _I, vp, vp, vp, vp, vp, vp, _Z, vp]),
     "sg_train_tail_backward": (_I, [_I, _I, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, _Z, vp]),

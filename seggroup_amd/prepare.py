@@ -17,11 +17,18 @@ needs ScanNet's annotation files.  The over-segmentation (`<scene>_vh_clean_2.0.
 start from is read from the scan directory; `prepare_scene(..., oversegment=True)` makes a missing one from the mesh
 first (oversegment.py), and rekey.py carries a scan's annotation files over to such a segmentation.  Only annotating a scan -- making
 the aggregation and click files in the first place -- stays out of scope.
+
+    python -m seggroup_amd.prepare --data_root D [--scenes FILE] [--root OUT] [--num_points 150000]
+           [--label_style manual|maxseg|mainseg|rand] [--manual_label_path P] [--main_num M] [--anno_num A]
+           [--seg-graph scan|dense] [--seed N] [--oversegment] [--knn K | --radius R] [--index brute|grid] [--workers W]
+
+runs `prepare_scene` over <D>/scans/<scene>: the reference's prepare_data.py and prepare_weak_label.py in one pass.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 from typing import Optional
 
 import numpy as np
@@ -30,7 +37,7 @@ from . import hip, scans
 from .device import device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
 # the annotation-derived label producers of the same reference file (util.py:76-170, 224-427, 697-768) live in labels.py
 from .labels import (generate_real_label_pth, generate_real_labels, generate_seg_adjacency_matrix, generate_weak_label_pth,  # noqa: F401
-                     generate_weak_labels, group_adjacency_segs, load_aggregation, load_labels, load_seg_labels, read_label_mapper)
+                     generate_weak_labels, group_adjacency_segs, load_aggregation, load_labels, load_seg_labels, read_label_mapper, weak_style_dir)
 
 
 # ---- minimal PLY (binary little endian; ScanNet's `_vh_clean_2.ply`) ---------------------------------------------
@@ -424,14 +431,17 @@ def generate_mesh_adjcency_pth(scene_name, plydata=None, root: str = ".", scene_
 
 
 def prepare_scene(scene_path, item, num_points: int = 150000, root: str = ".", perm=None, device=None, label_style: Optional[str] = None,
-                  manual_label_path: Optional[str] = None, oversegment: bool = False, knn: int = 10, index: str = "brute", radius=None):
+                  manual_label_path: Optional[str] = None, oversegment: bool = False, knn: int = 10, index: str = "brute", radius=None,
+                  main_num: int = -1, anno_num: int = 1, seg_graph="dense", rng=None):
     """What prepare_data.py:36-71 + prepare_weak_label.py:60-90 do for one scan: point cloud, mapper / unmapper, segment lists,
     mesh adjacency and -- with `label_style` and ScanNet's annotation files next to the mesh -- the ground-truth and weak-label
     files, i.e. every input of SegModel.forward.  `oversegment=True`: a scan without a segs.json gets one from its mesh first
     (oversegment.py, default parameters); an existing file is never overwritten.  A scan without faces (a point cloud) is segmented
     over the kNN graph of its points (`knn` neighbours), and that graph stands in for the mesh adjacency.  `index="grid"`: the
     unsampled vertices' nearest sampled point comes from the exact grid index; the files are the same.  `radius` (a scan
-    without faces): the over-segmentation and the adjacency files come from the radius graph instead of the kNN graph."""
+    without faces): the over-segmentation and the adjacency files come from the radius graph instead of the kNN graph.
+    `main_num`, `anno_num`, `seg_graph` and `rng` go to `generate_weak_labels`.  -> what it returned (labeled vertices,
+    vertices, clicked segments, segments, instances), or None without `label_style`."""
     hip.knn_index(index)
     if radius is not None and int(knn) != 10:
         raise ValueError("prepare_scene: radius and knn = %d are two different graphs; give one" % int(knn))
@@ -447,8 +457,117 @@ def prepare_scene(scene_path, item, num_points: int = 150000, root: str = ".", p
     generate_pointcloud_pth(scene_path, item, num_points, ply, root=root, perm=perm, device=device, index=index)
     generate_seg_labels_and_ds_set(scene_path, root=root, device=device)
     generate_mesh_adjcency_pth(scene_name, ply, root=root, device=device, knn=knn, radius=radius)
-    if label_style is not None:
-        generate_real_labels(scene_path, root=root)
-        generate_real_label_pth(scene_path, root=root)
-        generate_weak_labels(scene_path, ply, label_style=label_style, manual_label_path=manual_label_path, root=root)
-        generate_weak_label_pth(scene_name, label_style, root=root)
+    if label_style is None:
+        return None
+    generate_real_labels(scene_path, root=root)
+    generate_real_label_pth(scene_path, root=root)
+    ret = generate_weak_labels(scene_path, ply, label_style=label_style, manual_label_path=manual_label_path, main_num=main_num,
+                               anno_num=anno_num, root=root, seg_graph=seg_graph, rng=rng, device=device)
+    generate_weak_label_pth(scene_name, weak_style_dir(label_style, main_num, anno_num), root=root)
+    return ret
+
+
+# ---- the dataset-level command: the reference's prepare_data.py and prepare_weak_label.py over a tree of scans -----------------------
+REPORT_NAME = "prepare_report.json"
+LABEL_STYLES = ("manual", "maxseg", "mainseg", "rand")
+
+
+def scene_rng(seed: int, scene: str):
+    """the RandomState a scene's mapper permutation and clicks are drawn from: a function of the seed and the scene's name alone, so the
+    tree depends neither on --workers nor on the order of the scenes"""
+    import zlib
+    return np.random.RandomState(zlib.crc32(("%d/%s" % (int(seed), scene)).encode()))
+
+
+def summary_lines(rets, scenes: int):
+    """prepare_weak_label.py:116-132 over the per-scene return values; the two per-scene averages are over `scenes`"""
+    lp, ap_, ls, as_, ins = (sum(int(r[i]) for r in rets) for i in range(5))
+    return ["Average labeled points of weak label in all points: %.2f%%" % (lp / ap_ * 100),
+            "Average labeled segments of weak label in all segments: %.2f%%" % (ls / as_ * 100),
+            "Average real labeled points in all points: %.4f%%" % (ls / ap_ * 100),
+            "Average instance number per scene: %.2f" % (ins / scenes),
+            "Average labeled segment number per scene: %.2f" % (ls / scenes)]
+
+
+def prepare_scans(data_root: str, scenes=None, root: str = ".", num_points: int = 150000, label_style: Optional[str] = None,
+                  manual_label_path: Optional[str] = None, main_num: int = -1, anno_num: int = 1, seg_graph: str = "scan", seed: int = 0,
+                  oversegment: bool = False, knn: int = 10, radius=None, index: str = "brute", workers: int = 4, device=None):
+    """`prepare_scene` over <data_root>/scans/<scene> for every named scene (default: every scan directory) on threads ->
+    [(scene, return value of generate_weak_labels or None)] in the scenes' order; writes <root>/prepare_report.json.  `item` is a
+    scene's position in the list; its permutation and its clicks come from `scene_rng(seed, scene)`."""
+    dev = torch_device(device)
+    scans_dir = os.path.join(data_root, "scans")
+    if scenes is None:
+        scenes = scans.scan_names(scans_dir)
+    item_of = {scene: i for i, scene in enumerate(scenes)}
+
+    def say(line):                                                   # one write per line: the threads' lines do not interleave
+        sys.stdout.write(line + "\n")
+        sys.stdout.flush()
+
+    def one(scene, stream):
+        item = item_of[scene]
+        say("[%04d/%d] Dealing with %s..." % (item, len(scenes), scene))
+        rng = scene_rng(seed, scene)
+        scene_path = os.path.join(scans_dir, scene)
+        perm = rng.permutation(scans.declared_count(os.path.join(scene_path, scene + scans.PLY_SUFFIX), b"vertex"))
+        ret = prepare_scene(scene_path, item, num_points, root=root, perm=perm, device=dev, label_style=label_style,
+                            manual_label_path=manual_label_path, oversegment=oversegment, knn=knn, index=index, radius=radius,
+                            main_num=main_num, anno_num=anno_num, seg_graph=seg_graph, rng=rng)
+        say("[%04d/%d] Finish %s!" % (item, len(scenes), scene))
+        return ret
+
+    done = scans.map_scans(list(scenes), workers, dev, one)
+    os.makedirs(root, exist_ok=True)
+    doc = {"num_points": int(num_points), "label_style": label_style, "main_num": int(main_num), "anno_num": int(anno_num),
+           "seg_graph": seg_graph if label_style not in (None, "manual") else None, "seed": int(seed),
+           "scenes": {scene: (None if ret is None else dict(zip(("labeled_points", "points", "labeled_segments", "segments", "instances"),
+                                                               (int(x) for x in ret)))) for scene, ret in done}}
+    scans.write_report(os.path.join(root, REPORT_NAME), doc)
+    return done
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m seggroup_amd.prepare",
+                                 description="Every input of SegModel.forward for a tree of ScanNet scans: what the reference's "
+                                             "prepare_data.py and prepare_weak_label.py write, in one pass.")
+    ap.add_argument("--data_root", required=True, help="the dataset's root: scans are <data_root>/scans/<scene>")
+    ap.add_argument("--scenes", default=None, help="text file with one scene name per line (default: every scan directory)")
+    ap.add_argument("--root", default=".", help="where data/, label/ and adj/ go (default: CWD)")
+    ap.add_argument("--num_points", type=int, default=150000, help="points to sample per scan")
+    ap.add_argument("--label_style", default=None, choices=LABEL_STYLES, help="also write ground truth and weak labels of this style")
+    ap.add_argument("--manual_label_path", default=None, help="directory of manual click files (only for manual)")
+    ap.add_argument("--main_num", type=int, default=-1, help="main segments to consider (only for mainseg)")
+    ap.add_argument("--anno_num", type=int, default=1, help="annotations per instance (only for maxseg and mainseg)")
+    ap.add_argument("--seg-graph", dest="seg_graph", default="scan", choices=("scan", "dense"),
+                    help="simulated clicks: the scan's own graph contracted on the GPU, or the reference's dense matrix over the faces")
+    ap.add_argument("--seed", type=int, default=0, help="every scene draws from RandomState(crc32('<seed>/<scene>'))")
+    ap.add_argument("--oversegment", action="store_true", help="make a missing segs.json from the scan first")
+    graph = ap.add_mutually_exclusive_group()
+    graph.add_argument("--knn", type=int, default=None, help="a scan without faces: neighbours of its point graph (default 10)")
+    graph.add_argument("--radius", type=float, default=None, help="a scan without faces: the radius graph instead of the kNN graph")
+    ap.add_argument("--index", default="brute", choices=tuple(hip.KNN_INDEX), help="nearest sampled point: brute force or the grid index")
+    scans.add_workers_argument(ap)
+    ap.add_argument("--device", default=None)
+    a = ap.parse_args(argv)
+    if a.label_style == "manual" and a.manual_label_path is None:
+        ap.error("--label_style manual needs --manual_label_path")
+    if a.label_style == "mainseg" and (a.main_num < 1 or a.anno_num > a.main_num):
+        ap.error("--label_style mainseg needs --main_num >= 1 and --anno_num <= --main_num")
+    if a.num_points < 1 or a.anno_num < 1:
+        ap.error("--num_points and --anno_num must be at least 1")
+    scans.check_workers(ap, a.workers)
+    done = prepare_scans(a.data_root, scans.scene_list(a.scenes), a.root, a.num_points, a.label_style, a.manual_label_path, a.main_num,
+                         a.anno_num, a.seg_graph, a.seed, a.oversegment, 10 if a.knn is None else a.knn, a.radius, a.index, a.workers,
+                         a.device)
+    if a.label_style is not None and done:
+        print()
+        for line in summary_lines([ret for _, ret in done], len(done)):
+            print(line)
+    print("\nFinish all!\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -26,16 +26,21 @@ def scan_names(scans_dir: str, marker: str = PLY_SUFFIX):
     return sorted(d for d in os.listdir(scans_dir) if os.path.exists(os.path.join(scans_dir, d, d + marker)))
 
 
-def declared_faces(ply_path: str) -> int:
-    """the face count a PLY's header declares (0 without a face element); the body is not read"""
+def declared_count(ply_path: str, element: bytes) -> int:
+    """the count a PLY's header declares for `element` (0 without that element); the body is not read"""
     with open(ply_path, "rb") as f:
         for _ in range(256):
             tok = f.readline().split()
             if not tok or tok[0] == b"end_header":
                 break
-            if len(tok) == 3 and tok[0] == b"element" and tok[1] == b"face":
+            if len(tok) == 3 and tok[0] == b"element" and tok[1] == element:
                 return int(tok[2])
     return 0
+
+
+def declared_faces(ply_path: str) -> int:
+    """the face count a PLY's header declares (0 without a face element); the body is not read"""
+    return declared_count(ply_path, b"face")
 
 
 def scene_list(path):
