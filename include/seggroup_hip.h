@@ -924,6 +924,40 @@ const char* sg_nearest_point_grid_stage_name(int i);
 int sg_nearest_point_grid_stats(int64_t* h, int cap);
 int sg_nearest_point_grid_set_tuning(int target_occupancy, int ring_limit);
 
+/* Exact k nearest candidates of every query between two clouds: row u of d_knn [U, k] holds the k rows of d_y
+ * [N, y_stride >= 3] with the largest pair score against the query row u of d_x [U, x_stride >= 3] (|q|^2 formed as (x*x + y*y) + z*z), in
+ * descending score, the lower candidate index first among equal scores, original indices, int32: the first k columns of a stable descending
+ * sort of the query's full score row, so column 0 is sg_nearest_point_grid's d_idx.  d_d2 [U, k] (may be NULL) receives
+ * (dx*dx + dy*dy) + dz*dz of d = x[u] - y[knn[u][t]], each operation rounded once.  The search is sg_nearest_point_grid's with a list of k
+ * entries: the same index over the candidates, the box, the largest extent and max|p|^2 over the union of both clouds, the queries sorted by
+ * cell, and a query is settled when its list is full and  Lb > delta - s_kth .  Queries unsettled at the ring limit are finished against
+ * every candidate in original order, so neither the cell edge nor the ring limit nor the stream can change a result.
+ *   k in {5, 10, 20} (else SG_EUNSUP); 0 <= U <= SG_MAX_CLOUD_POINTS and U * k below 2^31 (above: SG_EUNSUP); k <= N <= SG_MAX_GRID_POINTS
+ *   (N < k: SG_EINVAL, above: SG_EUNSUP); U = 0 is SG_OK and touches nothing.  SG_EINVAL: null pointers, a stride below 3, U < 0, a cell
+ *   edge that is negative or not finite, a workspace below sg_cloud_knn_cross_grid_ws_bytes(U, N, k) (0 outside the envelope) -- all before
+ *   the first device call --, a coordinate of either cloud that is not finite (found on the device by the box stage).  SG_EUNSUP:
+ *   4 * max|p|^2 or delta not finite, a forced cell outside the table, as sg_nearest_point_grid.
+ * Synchronises the stream like sg_nearest_point_grid.  Stage times, statistics (the same seven stages and nine words) and tuning per calling
+ * thread, as above. */
+size_t sg_cloud_knn_cross_grid_ws_bytes(int U, int N, int k);
+int sg_cloud_knn_cross_grid(const float* d_x, int x_stride, int U, const float* d_y, int y_stride, int N, int k, float cell, int32_t* d_knn,
+                            float* d_d2, void* d_ws, size_t ws_bytes, void* stream);
+int sg_cloud_knn_cross_grid_set_timing(int on);
+int sg_cloud_knn_cross_grid_stage_times(float* h_us, int cap);
+const char* sg_cloud_knn_cross_grid_stage_name(int i);
+int sg_cloud_knn_cross_grid_stats(int64_t* h, int cap);
+int sg_cloud_knn_cross_grid_set_tuning(int target_occupancy, int ring_limit);
+
+/* The most frequent value among each row's neighbours.  Row u of d_knn [U, k] is j_0 .. j_{k-1}, indices into d_label [N];
+ * c(t) = the number of s with label[j_s] == label[j_t], t* = the smallest t that maximises c.  d_winner[u] = label[j_t*]; d_rep[u] = j_t*,
+ * the nearest neighbour that holds the winner (among equally frequent values the one met first in the list wins); d_count[u] = c(t*);
+ * d_tied[u] = 1 when some t has c(t) == c(t*) and another label, else 0.  d_count and d_tied may be NULL.  Any int32 is a label; labels are
+ * compared by equality only; integers throughout, so every run writes the same bytes.
+ *   1 <= k <= 32, U >= 0 (0: SG_OK, nothing touched), N >= 1, else SG_EINVAL.  An entry of d_knn outside 0..N-1: SG_EINVAL after the
+ *   call's one stream synchronisation (that row's outputs are not written). */
+int sg_knn_vote(const int32_t* d_knn, int U, int k, const int32_t* d_label, int N, int32_t* d_winner, int32_t* d_rep, int32_t* d_count,
+                int32_t* d_tied, void* stream);
+
 /* Connected components of a scan's graph.  Vertices 0..V-1, 1 <= V <= SG_MAX_CLOUD_POINTS; the undirected graph comes from
  * one of three sources:
  *   sg_components_edges  d_edges int32 [E,2], 0 <= E < 2^30: a row (a, a) is a no-op, duplicates and both orientations are allowed, no order

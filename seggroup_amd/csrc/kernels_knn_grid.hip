@@ -23,6 +23,10 @@
 // of both clouds), the queries x are binned by the same formula and sorted by cell key, k_nearest_search walks the rings, and the queue is
 // finished by sg_nearest_point's own kernel.  Both entry points build their index through build_index.
 //
+// sg_cloud_knn_cross_grid is the two-cloud form with a list of k entries: the index and the sorted queries of 8i, the walk
+// and the `full` condition of 8h (k_cross_search), the queue finished by sgcloud::top_scores over every candidate (k_cross_fallback), the
+// squared distances per list entry (k_cross_d2).  sg_knn_vote is the majority vote over such rows (k_knn_vote): integers only.
+//
 // The index's own pieces (k_grid_box .. k_grid_cellstats, the Grid, the workspace plan), the steps of its build and the search skeleton
 // (group pick, tile staging, the kernels' leave) live in grid_index_device.h, which the radius graph (kernels_radius.hip)
 // includes as well; the ring walk with its settled test, the cell-edge choice (fit, the probe, the occupancy correction) and the entry
@@ -223,6 +227,112 @@ __global__ __launch_bounds__(kBlock) void k_nearest_d2(const float* __restrict__
     d2[u] = (dx * dx + dy * dy) + dz * dz;
 }
 
+// The two-cloud form with a list of KK = k entries: k_nearest_search's wave -- 64 queries in the order of their cell keys,
+// the groups sharing the staged candidate tiles -- with k_grid_search's list.  A list that is not full is unsettled (ring_settles takes
+// `full`), so a query whose block holds fewer than k candidates walks on; row orig of knn receives the list, original candidate indices.
+template <int KK>
+__global__ __launch_bounds__(kWave) void k_cross_search(const float4* __restrict__ spts, const int* __restrict__ sidx, const int* __restrict__ start,
+                                                        Grid g, const float4* __restrict__ qpts, const unsigned long long* __restrict__ qskey,
+                                                        const int* __restrict__ qsidx, int U, int32_t* __restrict__ knn, int* __restrict__ queue,
+                                                        Misc* __restrict__ m, int counting) {
+    __shared__ float4 tile[kGTile];
+    __shared__ int tidx[kGTile];
+    const int s = blockIdx.x * kWave + threadIdx.x;
+    const bool live = s < U;
+    const int sl = live ? s : U - 1;
+    const int orig = qsidx[sl];
+    const float4 me = qpts[orig];
+    const int mycell = (int)qskey[sl];
+    float bs[KK];
+    int bi[KK];
+    const Walk w = ring_walk<KK>(g, live, mycell, me, start, spts, sidx, tile, tidx, bs, bi);
+    if (live) {
+        if (w.queued) {
+            queue[atomicAdd(&m->nq, 1)] = orig;
+        } else {
+#pragma unroll
+            for (int t = 0; t < KK; ++t) knn[(size_t)orig * KK + t] = bi[t];
+        }
+    }
+    search_epilogue(w.ring, w.evals, counting, m);
+}
+
+// the queued queries (original rows of qpts) against every candidate in original order: k_grid_fallback for two clouds.  N >= KK, so the
+// list is full; the clamp only keeps a row inside the cloud whatever happens.
+template <int KK>
+__global__ __launch_bounds__(kTile) void k_cross_fallback(const float4* __restrict__ cand, int N, const float4* __restrict__ qpts, int U,
+                                                          const int* __restrict__ queue, int nq, int32_t* __restrict__ knn, Misc* __restrict__ m,
+                                                          int counting) {
+    __shared__ float4 tile[kTile];
+    const int u = blockIdx.x * kTile + threadIdx.x;
+    const bool live = u < nq;
+    const int q = live ? queue[u] : 0;
+    const bool sane = (unsigned)q < (unsigned)U;
+    const float4 me = qpts[sane ? q : 0];
+    float bs[KK];
+    int bi[KK];
+    sgcloud::top_scores<KK>(cand, N, me, tile, bs, bi);
+    if (live && sane) {
+#pragma unroll
+        for (int t = 0; t < KK; ++t) knn[(size_t)q * KK + t] = bi[t] < N ? bi[t] : N - 1;
+    }
+    if (counting && threadIdx.x == 0) atomicAdd(&m->evals, (unsigned long long)min(kTile, nq - blockIdx.x * kTile) * (unsigned long long)N);
+}
+
+// d2[u][t] = (dx*dx + dy*dy) + dz*dz with d = x[u] - y[knn[u][t]]: k_nearest_d2 per list entry, one thread each (total = U k < 2^31)
+__global__ __launch_bounds__(kBlock) void k_cross_d2(const float* __restrict__ x, int xs, const float* __restrict__ y, int ys, int N, int k,
+                                                     int total, const int32_t* __restrict__ knn, float* __restrict__ d2) {
+    const long long e = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= (long long)total) return;
+    const int u = (int)(e / k);
+    const int j = knn[e];
+    if ((unsigned)j >= (unsigned)N) { d2[e] = INFINITY; return; }
+    const float dx = x[(size_t)u * xs] - y[(size_t)j * ys], dy = x[(size_t)u * xs + 1] - y[(size_t)j * ys + 1];
+    const float dz = x[(size_t)u * xs + 2] - y[(size_t)j * ys + 2];
+    d2[e] = (dx * dx + dy * dy) + dz * dz;
+}
+
+// The vote over a row of neighbours: one thread per row, the row's labels in registers (KC >= k slots, the loops unrolled
+// over them), k^2 equality compares.  c(t) = the entries that carry entry t's label; the first t with the largest c wins.  A later t with
+// the same count and another label marks a tie; a strictly larger count clears it (nothing earlier reaches it).  An index outside 0..N-1
+// sets the flag and leaves the row unwritten.
+template <int KC>
+__global__ __launch_bounds__(kBlock) void k_knn_vote(const int32_t* __restrict__ knn, int U, int k, const int32_t* __restrict__ label, int N,
+                                                     int32_t* __restrict__ winner, int32_t* __restrict__ rep, int32_t* __restrict__ count,
+                                                     int32_t* __restrict__ tied, int* __restrict__ flag) {
+    const long long u = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (u >= (long long)U) return;
+    const int32_t* row = knn + (size_t)u * k;
+    int lab[KC];
+    bool bad = false;
+#pragma unroll
+    for (int t = 0; t < KC; ++t) {
+        lab[t] = 0;
+        if (t < k) {
+            const int j = row[t];
+            const bool ok = (unsigned)j < (unsigned)N;
+            bad |= !ok;
+            lab[t] = label[ok ? j : 0];
+        }
+    }
+    if (bad) { atomicOr(flag, 1); return; }
+    int best = 0, bestc = 0, bestlab = 0, tie = 0;
+#pragma unroll
+    for (int t = 0; t < KC; ++t) {
+        if (t < k) {
+            int c = 0;
+#pragma unroll
+            for (int s = 0; s < KC; ++s) c += (s < k && lab[s] == lab[t]) ? 1 : 0;
+            if (c > bestc) { bestc = c; best = t; bestlab = lab[t]; tie = 0; }
+            else if (c == bestc && lab[t] != bestlab) tie = 1;
+        }
+    }
+    winner[u] = bestlab;
+    rep[u] = row[best];
+    if (count) count[u] = bestc;
+    if (tied) tied[u] = tie;
+}
+
 
 // the queries of the two-cloud search: (x, y, z, |q|^2) in original order, their cell keys and the sort's buffers, the queue
 struct QueryPlan {
@@ -253,13 +363,13 @@ size_t query_plan_bytes(int U) {
 constexpr int kStages = 7;
 const char* const kStageNames[kStages] = {"box", "probe", "cells", "sort", "table", "search", "fallback"};
 
-// what a thread asked for and what its last call left: one set per entry point (the kNN, the nearest point)
+// what a thread asked for and what its last call left: one set per entry point (the kNN, the nearest point, the two-cloud kNN)
 struct Session {
     sgos::StageTimes<kStages> times;
     int64_t stats[kNumStats];
     int target = 0, ring_limit = 0;         // 0: the defaults
 };
-thread_local Session t_knn, t_nearest;
+thread_local Session t_knn, t_nearest, t_cross;
 
 int stats_of(const Session& s, const char* who, int64_t* h, int cap) {
     SG_REQUIRE(h && cap >= kNumStats, "%s: room for %d words is needed", who, kNumStats);
@@ -353,6 +463,16 @@ void launch_search(const Plan& p, const unsigned long long* skey, const int* sid
 template <int KK>
 void launch_fallback(const Plan& p, int N, int nq, int32_t* table, int counting, hipStream_t st) {
     k_grid_fallback<KK><<<sg::cdiv(nq, kTile), kTile, 0, st>>>(p.cand, N, p.queue, nq, table, p.misc, counting);
+}
+
+template <int KK>
+void launch_cross(const Plan& p, const QueryPlan& q, const Sorted& qs, const Index& ix, int U, int32_t* knn, int counting, hipStream_t st) {
+    k_cross_search<KK><<<sg::cdiv(U, kWave), kWave, 0, st>>>(p.spts, ix.sidx, p.start, ix.g, q.pts, qs.key, qs.idx, U, knn, q.queue, p.misc, counting);
+}
+
+template <int KK>
+void launch_cross_fallback(const Plan& p, const QueryPlan& q, int N, int U, int nq, int32_t* knn, int counting, hipStream_t st) {
+    k_cross_fallback<KK><<<sg::cdiv(nq, kTile), kTile, 0, st>>>(p.cand, N, q.pts, U, q.queue, nq, knn, p.misc, counting);
 }
 
 }  // namespace
@@ -471,6 +591,110 @@ int sg_nearest_point_grid(const float* d_x, int x_stride, int U, const float* d_
     clock.tick();
     SG_LAUNCH_CHECK();
     leave_stats(t_nearest, g, hm, nq, counting ? hm.evals + (unsigned long long)nq * (unsigned long long)N : 0ull);
+    return SG_OK;
+}
+
+int sg_cloud_knn_cross_grid_set_timing(int on) { t_cross.times.timing = on != 0; return SG_OK; }
+int sg_cloud_knn_cross_grid_stage_times(float* h_us, int cap) { return t_cross.times.copy("sg_cloud_knn_cross_grid_stage_times", h_us, cap); }
+const char* sg_cloud_knn_cross_grid_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
+int sg_cloud_knn_cross_grid_stats(int64_t* h, int cap) { return stats_of(t_cross, "sg_cloud_knn_cross_grid_stats", h, cap); }
+int sg_cloud_knn_cross_grid_set_tuning(int target_occupancy, int ring_limit) {
+    return set_tuning(t_cross, "sg_cloud_knn_cross_grid_set_tuning", target_occupancy, ring_limit);
+}
+
+size_t sg_cloud_knn_cross_grid_ws_bytes(int U, int N, int k) {
+    if ((k != 5 && k != 10 && k != 20) || U < 0 || U > SG_MAX_CLOUD_POINTS || N < k || N > SG_MAX_GRID_POINTS) return 0;
+    if ((long long)U * k > 0x7fffffffll) return 0;
+    return plan_bytes(N) + query_plan_bytes(U);
+}
+
+int sg_cloud_knn_cross_grid(const float* d_x, int x_stride, int U, const float* d_y, int y_stride, int N, int k, float cell, int32_t* d_knn,
+                            float* d_d2, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* who = "sg_cloud_knn_cross_grid";
+    for (int i = 0; i < kNumStats; ++i) t_cross.stats[i] = 0;
+    if (k != 5 && k != 10 && k != 20) return sg::fail(SG_EUNSUP, "%s: k = %d is not built (5, 10, 20)", who, k);
+    SG_REQUIRE(U >= 0, "%s: bad arguments (%d queries, %d candidates)", who, U, N);
+    if (N < k) return sg::fail(SG_EINVAL, "%s: %d candidates for k = %d", who, N, k);
+    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d candidates; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
+    if (U > SG_MAX_CLOUD_POINTS) return sg::fail(SG_EUNSUP, "%s: %d queries; a call takes at most %d", who, U, SG_MAX_CLOUD_POINTS);
+    if ((long long)U * k > 0x7fffffffll)
+        return sg::fail(SG_EUNSUP, "%s: %d queries of %d neighbours; a table holds at most 2^31 - 1 entries", who, U, k);
+    SG_REQUIRE(y_stride >= 3 && x_stride >= 3, "%s: rows of at least 3 floats (x: %d, y: %d)", who, x_stride, y_stride);
+    SG_REQUIRE(std::isfinite(cell) && cell >= 0.0f, "%s: the cell edge must be finite and positive, or 0 for the library's choice (%g)", who, (double)cell);
+    if (U == 0) return SG_OK;
+    SG_REQUIRE(d_x && d_y && d_knn && d_ws, "%s: bad arguments", who);
+    const size_t need = sg_cloud_knn_cross_grid_ws_bytes(U, N, k);
+    SG_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    Plan p{};
+    QueryPlan q{};
+    sg::Carver cv(d_ws, ws_bytes);
+    carve(cv, p, N);
+    carve(cv, q, U);
+    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    hipStream_t st = sg::as_stream(stream);
+    const int counting = t_cross.times.timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, t_cross.times.timing, t_cross.times.us);
+    Index ix{};
+    const int rc = build_index(who, "sg_nearest_point", t_cross, d_y, y_stride, N, d_x, x_stride, U, q.pts, cell, p, clock, st, &ix);
+    if (rc != SG_OK) return rc;
+    const Grid& g = ix.g;
+    // the queries in the order of their cell keys: 64 consecutive ones are a wave's groups
+    k_grid_cells<<<sg::cdiv(U, kBlock), kBlock, 0, st>>>(q.pts, U, g, q.k0, q.v0);
+    const Sorted qs = sort_cells(q.k0, q.k1, q.v0, q.v1, q.hist, U, g.ncells, st);
+    if (k == 5) launch_cross<5>(p, q, qs, ix, U, d_knn, counting, st);
+    else if (k == 10) launch_cross<10>(p, q, qs, ix, U, d_knn, counting, st);
+    else launch_cross<20>(p, q, qs, ix, U, d_knn, counting, st);
+    clock.tick();
+    Misc hm{};
+    SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    const int nq = hm.nq;
+    if (nq < 0 || nq > U) return sg::fail(SG_EHIP, "%s: %d queued queries from %d", who, nq, U);
+    if (nq > 0) {
+        if (k == 5) launch_cross_fallback<5>(p, q, N, U, nq, d_knn, counting, st);
+        else if (k == 10) launch_cross_fallback<10>(p, q, N, U, nq, d_knn, counting, st);
+        else launch_cross_fallback<20>(p, q, N, U, nq, d_knn, counting, st);
+        if (counting) {
+            SG_HIP(hipMemcpyAsync(&hm.evals, &p.misc->evals, 8, hipMemcpyDeviceToHost, st));
+            SG_HIP(hipStreamSynchronize(st));
+        }
+    }
+    if (d_d2) {
+        const int total = U * k;
+        k_cross_d2<<<sg::cdiv(total, kBlock), kBlock, 0, st>>>(d_x, x_stride, d_y, y_stride, N, k, total, d_knn, d_d2);
+    }
+    clock.tick();
+    SG_LAUNCH_CHECK();
+    leave_stats(t_cross, g, hm, nq, hm.evals);
+    return SG_OK;
+}
+
+int sg_knn_vote(const int32_t* d_knn, int U, int k, const int32_t* d_label, int N, int32_t* d_winner, int32_t* d_rep, int32_t* d_count,
+                int32_t* d_tied, void* stream) {
+    const char* who = "sg_knn_vote";
+    SG_REQUIRE(k >= 1 && k <= 32, "%s: 1 <= k <= 32 neighbours a row (%d)", who, k);
+    SG_REQUIRE(U >= 0 && N >= 1, "%s: bad arguments (%d rows, %d labels)", who, U, N);
+    if (U == 0) return SG_OK;
+    SG_REQUIRE(d_knn && d_label && d_winner && d_rep, "%s: bad arguments", who);
+    hipStream_t st = sg::as_stream(stream);
+    int* d_flag = nullptr;                                      // the call has no workspace: its one flag word
+    SG_HIP(hipMalloc((void**)&d_flag, sizeof(int)));
+    int flag = 0;
+    hipError_t e = hipMemsetAsync(d_flag, 0, sizeof(int), st);
+    if (e == hipSuccess) {
+        const int nb = sg::cdiv(U, kBlock);
+        if (k <= 5) k_knn_vote<5><<<nb, kBlock, 0, st>>>(d_knn, U, k, d_label, N, d_winner, d_rep, d_count, d_tied, d_flag);
+        else if (k <= 10) k_knn_vote<10><<<nb, kBlock, 0, st>>>(d_knn, U, k, d_label, N, d_winner, d_rep, d_count, d_tied, d_flag);
+        else if (k <= 20) k_knn_vote<20><<<nb, kBlock, 0, st>>>(d_knn, U, k, d_label, N, d_winner, d_rep, d_count, d_tied, d_flag);
+        else k_knn_vote<32><<<nb, kBlock, 0, st>>>(d_knn, U, k, d_label, N, d_winner, d_rep, d_count, d_tied, d_flag);
+        e = hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipGetLastError();
+    (void)hipFree(d_flag);
+    if (e != hipSuccess) return sg::fail(SG_EHIP, "%s: %s", who, hipGetErrorString(e));
+    if (flag) return sg::fail(SG_EINVAL, "%s: a neighbour index outside 0..%d", who, N - 1);
     return SG_OK;
 }
 

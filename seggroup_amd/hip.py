@@ -169,6 +169,14 @@ SIGNATURES = {
     "sg_nearest_point_grid_stage_name": (C.c_char_p, [_I]),
     "sg_nearest_point_grid_stats": (_I, [vp, _I]),
     "sg_nearest_point_grid_set_tuning": (_I, [_I, _I]),
+    "sg_cloud_knn_cross_grid_ws_bytes": (_Z, [_I, _I, _I]),
+    "sg_cloud_knn_cross_grid": (_I, [vp, _I, _I, vp, _I, _I, _I, C.c_float, vp, vp, vp, _Z, vp]),
+    "sg_cloud_knn_cross_grid_set_timing": (_I, [_I]),
+    "sg_cloud_knn_cross_grid_stage_times": (_I, [vp, _I]),
+    "sg_cloud_knn_cross_grid_stage_name": (C.c_char_p, [_I]),
+    "sg_cloud_knn_cross_grid_stats": (_I, [vp, _I]),
+    "sg_cloud_knn_cross_grid_set_tuning": (_I, [_I, _I]),
+    "sg_knn_vote": (_I, [vp, _I, _I, vp, _I, vp, vp, vp, vp, vp]),
     "sg_components_ws_bytes": (_Z, [_I]),
     "sg_components_edges": (_I, [vp, C.c_longlong, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_components_faces": (_I, [vp, _I, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),

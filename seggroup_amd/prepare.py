@@ -177,6 +177,39 @@ def nearest_point_grid(x, y, cell=None, device=None, stream=None, want_d2=True):
     return idx, d2
 
 
+def knn_cross_stats() -> dict:
+    """nearest_grid_stats for the calling thread's last knn_cross_grid: the same record."""
+    return hip.grid_stats("cloud_knn_cross_grid", ("max_ring", "fallback", "scores"))
+
+
+def knn_cross_grid(x, y, k, cell=None, device=None, stream=None, want_d2=False):
+    """sg_cloud_knn_cross_grid: for every row of x [U, >= 3] its k best-scoring rows of y [N, >= 3], k in {5, 10, 20} --
+    descending score, the lower index first among equal scores, so column 0 is nearest_point_grid's index -- from the exact grid index
+    -> (knn int32 [U, k], d2 float32 [U, k] or None), device tensors.  `cell` forces the cell edge (a performance knob: the result does
+    not depend on it)."""
+    import torch
+    edge = hip.knn_cell(cell)
+    k = int(k)
+    dev = torch_device(device)
+    lib = hip.lib()
+    with torch.cuda.device(dev), on_stream(stream):
+        dx, dy = device_tensor(x, torch.float32, dev), device_tensor(y, torch.float32, dev)
+        if dx.dim() != 2 or dy.dim() != 2 or dx.shape[1] < 3 or dy.shape[1] < 3:
+            raise ValueError("knn_cross_grid: x and y must be [*, >= 3]")
+        u, n = int(dx.shape[0]), int(dy.shape[0])
+        sp = stream_ptr(stream)
+        need = lib.sg_cloud_knn_cross_grid_ws_bytes(u, n, k)
+        if need == 0:                                               # outside the envelope: the library says why, nothing is allocated
+            hip.check(lib.sg_cloud_knn_cross_grid(None, int(dx.shape[1]), u, None, int(dy.shape[1]), n, k, edge, None, None, None, 0, sp))
+        knn = torch.empty((u, k), dtype=torch.int32, device=dev)
+        d2 = torch.empty((u, k), dtype=torch.float32, device=dev) if want_d2 else None
+        ws = workspace(need, dev)
+        hip.check(lib.sg_cloud_knn_cross_grid(dx.data_ptr(), int(dx.shape[1]), u, dy.data_ptr(), int(dy.shape[1]), n, k, edge, knn.data_ptr(),
+                                              d2.data_ptr() if want_d2 else None, ws.data_ptr(), ws.numel(), sp))
+        sync(stream)
+    return knn, d2
+
+
 def get_unmapper(x, y, device=None, index="brute", cell=None):
     """util.py:538-550: for every row of x [U,3] the index of its nearest row of y [N,3] (LongTensor on the device).
     `index="grid"`: the same indices from the exact grid index (`cell` forces its cell edge)."""

@@ -7,15 +7,23 @@ whose `.thin.npz` was not kept -- gets them by nearest vertex: every target vert
 grid index; `index="brute"` is `sg_nearest_point` itself, for at most 2^20 source vertices.  Carrying the values over is `thin.lift` /
 `thin.lift_sgl`: a gather.
 
+Where the source is the denser cloud, its labels are ragged at instance boundaries or the target is offset by a few millimetres, the
+nearest vertex is an arbitrary member of a mixed neighbourhood.  `--vote K` takes the K nearest source vertices
+(`sg_cloud_knn_cross_grid`), lets them vote on one label vector (`sg_knn_vote`: the most frequent value, the one met first among equally
+frequent ones) and carries over ALL values of `rep`, the nearest source vertex that holds the winner -- so a target vertex's labels
+still come from one source vertex, the .sgl stays consistent and every layer stays a function of the segment.
+
     python -m seggroup_amd.transfer --from-scans DIR --to-scans DIR -n EXP --stage S --out ROOT2 [--root .] [--scenes FILE]
-                                    [--workers K] [--index {grid,brute}] [--device D]
+                                    [--workers K] [--index {grid,brute}] [--vote {5,10,20} [--vote-on NAME]] [--device D]
         for every scene present in both trees: results/EXP/<scene>/<S>/ of --root (made on --from-scans) -> the same files at the
         target's V under ROOT2/results/EXP/<scene>/<S>/ (pseudo_labels.sgl and the per-vector .npy files, as `thin --lift` writes
-        them), ROOT2/results/EXP/<scene>/<S>/<scene>.transfer.npz (nearest, d2) and one ROOT2/transfer_report.json
+        them), ROOT2/results/EXP/<scene>/<S>/<scene>.transfer.npz (nearest, d2; with --vote also rep, votes, tied) and one
+        ROOT2/transfer_report.json.  --vote-on: `seg` (the default: the .sgl's seg_of_vertex) or a vector name such as final.ins, taken
+        from the .sgl's expansion or from the .npy file.
 
 Not here: a distance cut-off that un-labels far vertices (a lifted .sgl has no "no segment" for a vertex: the report says how far the
-vertices are, the decision is the user's), interpolation or voting over several neighbours, and segs.json or clicks (rekey.py and thin.py
-own those).
+vertices are, the decision is the user's), interpolation or distance-weighted votes, and segs.json or clicks (rekey.py and thin.py own
+those).
 """
 from __future__ import annotations
 
@@ -25,9 +33,9 @@ import sys
 
 import numpy as np
 
-from . import hip, scans
-from .device import device_tensor, torch_device
-from .prepare import get_unmapper, mesh_arrays, nearest_point_grid, read_ply
+from . import hip, pseudo_labels, scans
+from .device import device_tensor, on_stream, stream_ptr, sync, torch_device
+from .prepare import get_unmapper, knn_cross_grid, mesh_arrays, nearest_point_grid, read_ply
 from .thin import lift_stage
 from .thin import lift as transfer                                  # transfer(values, nearest): values[nearest] on the leading axis
 from .thin import lift_sgl as transfer_sgl                           # transfer_sgl(src, dst, nearest): a .sgl for the target geometry
@@ -35,6 +43,8 @@ from .thin import lift_sgl as transfer_sgl                           # transfer_
 MAP_SUFFIX = ".transfer.npz"
 REPORT_NAME = "transfer_report.json"
 FAR = (0.05, 0.1, 0.5)                                               # the report counts the target vertices farther than these
+VOTE_K = (5, 10, 20)                                                 # the list lengths sg_cloud_knn_cross_grid is built for
+VOTE_ON = ["seg"] + hip.LABEL_NAMES
 
 
 def nearest_vertex(src_xyz, dst_xyz, index: str = "grid", cell=None, device=None, stream=None):
@@ -58,35 +68,115 @@ def nearest_vertex(src_xyz, dst_xyz, index: str = "grid", cell=None, device=None
     return nearest, d2
 
 
+def nearest_vertices(src_xyz, dst_xyz, k, cell=None, device=None, stream=None):
+    """For every target vertex its k nearest source vertices, k in {5, 10, 20} -> (knn int32 [Vdst, k], d2 float32 [Vdst, k]) device
+    tensors: descending pair score, the lower index first among equal scores, so knn[:, 0] is nearest_vertex's answer."""
+    return knn_cross_grid(dst_xyz, src_xyz, k, cell=hip.knn_cell(cell), device=device, stream=stream, want_d2=True)
+
+
+def vote(knn, labels, device=None, stream=None):
+    """sg_knn_vote over the rows of knn [U, k <= 32] (indices into labels [N], any int32 values) -> (winner, rep, count, tied) int32 [U]
+    device tensors: the most frequent label of the row -- the one met first among equally frequent ones --, the nearest neighbour that
+    holds it, how many hold it, and whether another label is as frequent.  An index outside 0..N-1 is a ValueError."""
+    import torch
+    dev = torch_device(device)
+    lib = hip.lib()
+    with torch.cuda.device(dev), on_stream(stream):
+        d_knn, d_lab = device_tensor(knn, torch.int32, dev), device_tensor(labels, torch.int32, dev)
+        if d_knn.dim() != 2 or d_lab.dim() != 1:
+            raise ValueError("vote: knn must be [U, k] and labels [N]")
+        u, k = int(d_knn.shape[0]), int(d_knn.shape[1])
+        out = torch.empty((4, u), dtype=torch.int32, device=dev)
+        hip.check_arg(lib.sg_knn_vote(d_knn.data_ptr(), u, k, d_lab.data_ptr(), int(d_lab.shape[0]), *[out[i].data_ptr() for i in range(4)],
+                                      stream_ptr(stream)))
+        sync(stream)
+    return out[0], out[1], out[2], out[3]
+
+
+def vote_labels(src_dir: str, vote_on: str, n_src: int) -> np.ndarray:
+    """The source labels the neighbours vote on -> int32 [n_src]: `seg` is the .sgl's seg_of_vertex, a vector name its expansion from the
+    .sgl, or the .npy file of that name."""
+    have_sgl = os.path.isfile(os.path.join(src_dir, pseudo_labels.SGL_NAME))
+    if vote_on == "seg":
+        if not have_sgl:
+            raise ValueError(f"{src_dir}: no {pseudo_labels.SGL_NAME}, so there is no segment to vote on -- name a vector with --vote-on "
+                             "(vote_on=), e.g. final.ins")
+        labels = pseudo_labels.load(src_dir).seg_of_vertex
+    elif vote_on not in hip.LABEL_NAMES:
+        raise ValueError("--vote-on (vote_on=) must be 'seg' or one of %s, not %r" % (", ".join(hip.LABEL_NAMES), vote_on))
+    else:
+        lab = pseudo_labels.load(src_dir) if have_sgl else None
+        if lab is not None and vote_on in lab.names:
+            labels = lab.vector(vote_on)
+        elif os.path.isfile(os.path.join(src_dir, vote_on + ".npy")):
+            labels = np.load(os.path.join(src_dir, vote_on + ".npy"))
+        else:
+            raise ValueError(f"{src_dir}: --vote-on (vote_on=) {vote_on}: neither in {pseudo_labels.SGL_NAME} nor {vote_on}.npy")
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or labels.shape[0] != n_src:
+        raise ValueError(f"{src_dir}: --vote-on (vote_on=) {vote_on}: shape {labels.shape} for {n_src} source vertices")
+    return np.ascontiguousarray(labels, dtype=np.int32)
+
+
+def check_vote(vote_k, vote_on, index: str) -> None:
+    """the combinations of vote, vote_on and index that are refused before anything runs (ValueError)"""
+    if vote_k is None:
+        if vote_on is not None:
+            raise ValueError("--vote-on (vote_on=) needs --vote (vote=): without a vote there is nothing to vote on")
+        return
+    if vote_k not in VOTE_K:
+        raise ValueError("--vote (vote=) must be one of %s, not %r" % (VOTE_K, vote_k))
+    if index != "grid":
+        raise ValueError("--vote (vote=) searches through the grid index only -- use --index grid (index='grid')")
+    if vote_on is not None and vote_on not in VOTE_ON:
+        raise ValueError("--vote-on (vote_on=) must be 'seg' or one of %s, not %r" % (", ".join(hip.LABEL_NAMES), vote_on))
+
+
 def _scan_xyz(scans_dir: str, scene: str):
     return mesh_arrays(read_ply(os.path.join(scans_dir, scene, scene + "_vh_clean_2.ply")))[0]
 
 
 def transfer_scene(scene: str, from_scans: str, to_scans: str, exp: str, stage: str, out_root: str, root: str = ".", index: str = "grid",
-                   device=None, stream=None):
+                   device=None, stream=None, vote_k=None, vote_on=None):
     """One scene: results/<exp>/<scene>/<stage>/ under `root`, made on <from_scans>/<scene>, -> the same files for <to_scans>/<scene>
-    under <out_root>/results/...; -> (its entry of transfer_report.json, the files written)."""
+    under <out_root>/results/...; -> (its entry of transfer_report.json, the files written).  With `vote_k` the files are gathered by
+    `rep`, the nearest of the vote_k nearest source vertices that holds their most frequent `vote_on` label."""
+    check_vote(vote_k, vote_on, index)
     src_dir = os.path.join(root, "results", exp, scene, stage)
     if not os.path.isdir(src_dir):
         raise FileNotFoundError(f"{src_dir}: no such export directory")
     src_xyz, dst_xyz = _scan_xyz(from_scans, scene), _scan_xyz(to_scans, scene)
-    d_near, d_d2 = nearest_vertex(src_xyz, dst_xyz, index=index, device=device, stream=stream)
-    nearest, d2 = d_near.cpu().numpy(), d_d2.cpu().numpy()
     dst_dir = os.path.join(out_root, "results", exp, scene, stage)
-    files = lift_stage(src_dir, dst_dir, nearest, int(src_xyz.shape[0]), "transfer", "source vertices")
-    np.savez(os.path.join(dst_dir, scene + MAP_SUFFIX), nearest=nearest, d2=d2)
+    voted = {}
+    if vote_k is None:
+        d_near, d_d2 = nearest_vertex(src_xyz, dst_xyz, index=index, device=device, stream=stream)
+        nearest, d2 = d_near.cpu().numpy(), d_d2.cpu().numpy()
+        gather = nearest
+    else:
+        vote_on = "seg" if vote_on is None else vote_on
+        labels = vote_labels(src_dir, vote_on, int(src_xyz.shape[0]))
+        d_knn, d_d2 = nearest_vertices(src_xyz, dst_xyz, vote_k, device=device, stream=stream)
+        _, d_rep, d_count, d_tied = vote(d_knn, labels, device=device, stream=stream)
+        nearest, d2 = d_knn[:, 0].cpu().numpy().astype(np.int64), np.ascontiguousarray(d_d2[:, 0].cpu().numpy())
+        gather = d_rep.cpu().numpy()
+        voted = {"rep": gather, "votes": d_count.cpu().numpy(), "tied": d_tied.cpu().numpy()}
+    files = lift_stage(src_dir, dst_dir, gather, int(src_xyz.shape[0]), "transfer", "source vertices")
+    np.savez(os.path.join(dst_dir, scene + MAP_SUFFIX), nearest=nearest, d2=d2, **voted)
     dist = np.sqrt(d2.astype(np.float64))
     entry = {"source_V": int(src_xyz.shape[0]), "target_V": int(dst_xyz.shape[0]), "max_distance": float(dist.max()) if dist.size else 0.0,
              "median_distance": float(np.median(dist)) if dist.size else 0.0,
              "farther_than": {"%g" % t: int((dist > t).sum()) for t in FAR}}
+    if voted:
+        entry.update(vote=int(vote_k), vote_on=vote_on, moved=int((gather != nearest).sum()), tied=int(voted["tied"].sum()))
     return entry, files
 
 
 def transfer_results(from_scans: str, to_scans: str, exp: str, stage: str, out_root: str, root: str = ".", scenes=None, workers: int = 4,
-                     index: str = "grid", device=None):
+                     index: str = "grid", device=None, vote_k=None, vote_on=None):
     """Every scene of `from_scans` (or the named ones) that both trees hold -> (report {scene: entry}, missing {scene: why}); writes
-    <out_root>/transfer_report.json.  Workers are threads, each with its own stream."""
+    <out_root>/transfer_report.json.  Workers are threads, each with its own stream.  `vote_k`, `vote_on`: transfer_scene's."""
     hip.knn_index(index)
+    check_vote(vote_k, vote_on, index)
     dev = torch_device(device)
     have_src, have_dst = set(scans.scan_names(from_scans)), set(scans.scan_names(to_scans))
     if scenes is None:
@@ -101,7 +191,8 @@ def transfer_results(from_scans: str, to_scans: str, exp: str, stage: str, out_r
         else:
             todo.append(s)
     report = dict(scans.map_scans(todo, workers, dev, lambda scene, stream: transfer_scene(scene, from_scans, to_scans, exp, stage, out_root, root,
-                                                                                           index, device=dev, stream=stream)[0]))
+                                                                                           index, device=dev, stream=stream, vote_k=vote_k,
+                                                                                           vote_on=vote_on)[0]))
     os.makedirs(out_root, exist_ok=True)
     scans.write_report(os.path.join(out_root, REPORT_NAME), {"experiment": exp, "stage": stage, "index": index, "scenes": report, "missing": missing})
     return report, missing
@@ -118,14 +209,23 @@ def main(argv=None) -> int:
     ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
     scans.add_workers_argument(ap)
     ap.add_argument("--index", choices=sorted(hip.KNN_INDEX), default="grid", help="grid: the exact grid index; brute: every pair (at most 2^20 source vertices)")
+    ap.add_argument("--vote", type=int, choices=VOTE_K, default=None, metavar="K",
+                    help="majority vote over the K nearest source vertices (5, 10 or 20; needs --index grid): every value comes from the nearest "
+                         "of them that holds the winning label")
+    ap.add_argument("--vote-on", choices=VOTE_ON, default=None, metavar="NAME",
+                    help="what the neighbours vote on: seg (the default: the .sgl's seg_of_vertex) or a vector name such as final.ins")
     ap.add_argument("--device", default=None)
     a = ap.parse_args(argv)
     scans.check_workers(ap, a.workers)
     try:
-        report, missing = transfer_results(a.from_scans, a.to_scans, a.exp_name, a.stage, a.out, a.root, scans.scene_list(a.scenes), a.workers,
-                                           a.index, a.device)
+        check_vote(a.vote, a.vote_on, a.index)
     except ValueError as e:
-        if "--index grid" not in str(e):
+        ap.error(str(e))
+    try:
+        report, missing = transfer_results(a.from_scans, a.to_scans, a.exp_name, a.stage, a.out, a.root, scans.scene_list(a.scenes), a.workers,
+                                           a.index, a.device, vote_k=a.vote, vote_on=a.vote_on)
+    except ValueError as e:
+        if "--index grid" not in str(e) and "--vote-on" not in str(e):
             raise
         ap.error(str(e))
     for scene, e in report.items():
