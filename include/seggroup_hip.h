@@ -958,6 +958,40 @@ int sg_cloud_knn_cross_grid_set_tuning(int target_occupancy, int ring_limit);
 int sg_knn_vote(const int32_t* d_knn, int U, int k, const int32_t* d_label, int N, int32_t* d_winner, int32_t* d_rep, int32_t* d_count,
                 int32_t* d_tied, void* stream);
 
+/* Rigid alignment of two clouds: the three pieces around the nearest-point search that a point-to-point ICP needs.
+ *
+ * sg_rigid_apply: h_T is a row-major 3x4 matrix of doubles [R|t] (any finite matrix, not only a rotation).  For every row u of d_x
+ *   [U, x_stride >= 3]:  d_out[u][r] = (float)(((R[r][0]*x + R[r][1]*y) + R[r][2]*z) + t[r]),  the coordinates widened to double, every
+ *   operation rounded once in that order, one final rounding to fp32, no contraction: the bytes of the same statement written element-wise
+ *   in NumPy.  d_out is [U,3], dense.  0 <= U <= SG_MAX_CLOUD_POINTS (above: SG_EUNSUP); U = 0 is SG_OK and touches nothing.  SG_EINVAL:
+ *   null pointers, a stride below 3, U < 0, an entry of h_T that is not finite -- all before the first device call.  The launch is left on
+ *   the stream; the call does not synchronise.
+ *
+ * sg_align_moments: the 17 sums of a closed-form rigid fit over the pairs (x[u], y[idx[u]]) that have d2[u] <= max_d2 (fp32 compare;
+ *   max_d2 may be +inf; a NaN in d2 is never an inlier).  With a = (double)x[u] - h_origin_x and b = (double)y[idx[u]] - h_origin_y, h_out
+ *   receives  n (exact) | sum a [3] | sum b [3] | sum a b^T [9, row-major] | sum (double)d2[u],  accumulated in double.  Deterministic: no
+ *   floating-point atomics; a workgroup of 256 threads folds 1,024 consecutive pairs (thread t takes pairs t, t + 256, t + 512, t + 768 of
+ *   its block in that order, the wave sums run on wave_ops.h's network, the four waves are added in order) into one partial in the
+ *   workspace, and one workgroup adds the partials (thread t takes partials t, t + 256, .. in order, then the same wave network): the
+ *   launch shape and the summation tree depend on U alone, so two calls on the same input write the same 17 x 8 bytes on any device and
+ *   stream.  0 <= U <= SG_MAX_CLOUD_POINTS, 1 <= N <= SG_MAX_CLOUD_POINTS (above: SG_EUNSUP); U = 0 writes 17 zeros and touches no device
+ *   memory.  SG_EINVAL: null pointers, a stride below 3, U < 0, N < 1, max_d2 NaN, an origin that is not finite, a workspace below
+ *   sg_align_moments_ws_bytes(U) (0 outside the envelope) -- all before the first device call --, an entry of d_idx outside 0..N-1, inlier
+ *   or not (checked on the device before anything reads through it; h_out is then not written).  Synchronises the stream.
+ *
+ * sg_align_solve: host only, no device call.  h_m is sg_align_moments' h_out for the same origins.  h_T receives the row-major 3x4 [R|t]
+ *   of the proper rigid transform (det R = +1) that minimises sum |R x + t - y|^2 over the pairs (Kabsch from the moments:
+ *   H = sum a b^T - (sum a)(sum b)^T / n, a one-sided Jacobi SVD of H; R is built from the two leading singular pairs and their cross
+ *   products, which flips the smallest singular direction exactly when the unconstrained optimum is a reflection).  t is expressed for
+ *   un-shifted coordinates (t = ybar - R xbar with the origins added back), so h_T goes straight into sg_rigid_apply.  SG_EINVAL: null
+ *   pointers, a moment or an origin that is not finite, n negative.  SG_EUNSUP with a message that says "degenerate": n < 3, or a second
+ *   singular value at or below 2^-40 of the first (the pairs lie on a line or in a point: the rotation about it is free). */
+int sg_rigid_apply(const float* d_x, int x_stride, int U, const double* h_T, float* d_out, void* stream);
+size_t sg_align_moments_ws_bytes(int U);
+int sg_align_moments(const float* d_x, int x_stride, int U, const float* d_y, int y_stride, int N, const int64_t* d_idx, const float* d_d2,
+                     float max_d2, const double* h_origin_x, const double* h_origin_y, double* h_out, void* d_ws, size_t ws_bytes, void* stream);
+int sg_align_solve(const double* h_m, const double* h_origin_x, const double* h_origin_y, double* h_T);
+
 /* Connected components of a scan's graph.  Vertices 0..V-1, 1 <= V <= SG_MAX_CLOUD_POINTS; the undirected graph comes from
  * one of three sources:
  *   sg_components_edges  d_edges int32 [E,2], 0 <= E < 2^30: a row (a, a) is a no-op, duplicates and both orientations are allowed, no order

@@ -1,0 +1,115 @@
+// Rigid alignment of two clouds, host side: the closed-form fit from sg_align_moments' 17 sums.  No HIP call in this file:
+// it is part of the host-only sanitizer build and runs without a device.
+//
+// Kabsch from the moments: with a = x - origin_x, b = y - origin_y over the n inlier pairs,  H = sum a b^T - (sum a)(sum b)^T / n  is the
+// cross-covariance of the centred pairs, H = U S V^T, and the rotation that minimises sum |R a + t - b|^2 is R = V diag(1, 1, d) U^T with
+// d = det(V) det(U).  The SVD is a one-sided (Hestenes) Jacobi on the columns of H: plane rotations from the right until the columns are
+// orthogonal, H J = U S with J = V accumulated -- the small singular values keep their relative accuracy, which forming H^T H would
+// square away, and the degeneracy threshold below is stated on their ratio.  Only the two leading pairs (u1, v1), (u2, v2) are used:
+//     R = v1 u1^T + v2 u2^T + (v1 x v2)(u1 x u2)^T
+// is V diag(1, 1, d) U^T whatever the signs of u3 and v3 (u3 = det(U) u1 x u2, v3 = det(V) v1 x v2), so a reflection is corrected by
+// flipping the smallest singular direction without ever normalising a third column that may be zero (a planar set).  Both pairs are
+// re-orthonormalised (Gram-Schmidt) first, so R^T R - I stays at a few units of the last place.
+#include "sg_common.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr double kLineRatio = 0x1p-40;         // second singular value at or below this share of the first: the pairs lie on a line
+constexpr int kMaxSweeps = 64;
+
+struct Vec3 { double v[3]; };
+
+double dot(const Vec3& a, const Vec3& b) { return (a.v[0] * b.v[0] + a.v[1] * b.v[1]) + a.v[2] * b.v[2]; }
+Vec3 cross(const Vec3& a, const Vec3& b) {
+    return {{a.v[1] * b.v[2] - a.v[2] * b.v[1], a.v[2] * b.v[0] - a.v[0] * b.v[2], a.v[0] * b.v[1] - a.v[1] * b.v[0]}};
+}
+void normalise(Vec3& a) {
+    const double n = std::sqrt(dot(a, a));
+    for (double& c : a.v) c /= n;
+}
+// a and b orthonormal, a's direction kept
+void orthonormalise(Vec3& a, Vec3& b) {
+    normalise(a);
+    const double p = dot(a, b);
+    for (int i = 0; i < 3; ++i) b.v[i] -= p * a.v[i];
+    normalise(b);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sg_align_solve(const double* h_m, const double* h_origin_x, const double* h_origin_y, double* h_T) {
+    const char* who = "sg_align_solve";
+    SG_REQUIRE(h_m && h_origin_x && h_origin_y && h_T, "%s: bad arguments", who);
+    for (int i = 0; i < 17; ++i) SG_REQUIRE(std::isfinite(h_m[i]), "%s: moment %d is not finite", who, i);
+    for (int i = 0; i < 3; ++i)
+        SG_REQUIRE(std::isfinite(h_origin_x[i]) && std::isfinite(h_origin_y[i]), "%s: an origin that is not finite", who);
+    const double n = h_m[0];
+    SG_REQUIRE(n >= 0.0, "%s: a negative pair count (%g)", who, n);
+    if (n < 3.0) return sg::fail(SG_EUNSUP, "%s: degenerate: %g pairs; a rigid fit needs at least 3", who, n);
+    const double *sa = h_m + 1, *sb = h_m + 4, *sab = h_m + 7;
+    // the columns of H, rotated in place; J accumulates the rotations
+    Vec3 col[3], jc[3];
+    for (int c = 0; c < 3; ++c) {
+        for (int r = 0; r < 3; ++r) {
+            col[c].v[r] = sab[3 * r + c] - sa[r] * sb[c] / n;
+            jc[c].v[r] = r == c ? 1.0 : 0.0;
+        }
+    }
+    for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < 2; ++p) {
+            for (int q = p + 1; q < 3; ++q) {
+                const double alpha = dot(col[p], col[p]), beta = dot(col[q], col[q]), gamma = dot(col[p], col[q]);
+                if (gamma == 0.0 || std::fabs(gamma) <= 0x1p-53 * (std::sqrt(alpha) * std::sqrt(beta))) continue;
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
+                for (int i = 0; i < 3; ++i) {
+                    const double hp = col[p].v[i], hq = col[q].v[i];
+                    col[p].v[i] = c * hp - s * hq;
+                    col[q].v[i] = s * hp + c * hq;
+                    const double jp = jc[p].v[i], jq = jc[q].v[i];
+                    jc[p].v[i] = c * jp - s * jq;
+                    jc[q].v[i] = s * jp + c * jq;
+                }
+            }
+        }
+        if (!rotated) break;
+    }
+    double sv[3];
+    for (int c = 0; c < 3; ++c) sv[c] = std::sqrt(dot(col[c], col[c]));
+    if (!(std::isfinite(sv[0]) && std::isfinite(sv[1]) && std::isfinite(sv[2])))
+        return sg::fail(SG_EINVAL, "%s: the moments overflow the fit", who);
+    int first = 0;
+    for (int c = 1; c < 3; ++c)
+        if (sv[c] > sv[first]) first = c;
+    int second = first == 0 ? 1 : 0;
+    for (int c = 0; c < 3; ++c)
+        if (c != first && sv[c] > sv[second]) second = c;
+    if (!(sv[second] > kLineRatio * sv[first]))
+        return sg::fail(SG_EUNSUP, "%s: degenerate: singular values %g, %g of the pairs' cross-covariance -- they lie on a line or in a point, "
+                                   "the rotation about it is free", who, sv[first], sv[second]);
+    Vec3 u1 = col[first], u2 = col[second], v1 = jc[first], v2 = jc[second];
+    orthonormalise(u1, u2);
+    orthonormalise(v1, v2);
+    const Vec3 u3 = cross(u1, u2), v3 = cross(v1, v2);
+    double R[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) R[r][c] = (v1.v[r] * u1.v[c] + v2.v[r] * u2.v[c]) + v3.v[r] * u3.v[c];
+    for (int r = 0; r < 3; ++r) {
+        double rx = 0.0;                                        // (R xbar)[r] with xbar = sum a / n + origin_x
+        for (int c = 0; c < 3; ++c) {
+            h_T[4 * r + c] = R[r][c];
+            rx += R[r][c] * (sa[c] / n + h_origin_x[c]);
+        }
+        h_T[4 * r + 3] = (sb[r] / n + h_origin_y[r]) - rx;
+    }
+    return SG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,173 @@
+// Rigid alignment of two clouds, device side: what a point-to-point ICP needs around sg_nearest_point_grid.
+//
+//   k_rigid_apply     out[u] = (float)(R x[u] + t) in double, one thread a point, every operation rounded once in the order the header
+//                     states (-ffp-contract=off: no fma), so the bytes are those of the element-wise NumPy statement.
+//   k_align_moments   the 17 sums of the closed-form fit (n | sum a | sum b | sum a b^T | sum d2) over the inlier pairs, in double.  A
+//                     workgroup folds kPairs consecutive pairs into ONE partial row of the workspace: thread t accumulates pairs t, t + 256,
+//                     .. of its block in order, a wave sums on the DPP network of wave_ops.h, the waves' rows are added in order.  An index
+//                     outside 0..N-1 raises the flag word before anything is read through it.
+//   k_align_fold      one workgroup: thread t adds partial rows t, t + 256, .. in order, then the same network.
+// No floating-point atomics; grid, block and both trees are functions of U alone, so the 17 doubles do not depend on the device or the stream.
+// The kernel is a gather: 12 B of x, 8 B of idx and 4 B of d2 streamed per pair, 12 B of y read at random; the ~30 double operations per
+// pair hide under it.
+#include <cmath>
+
+#include "sg_common.h"
+#include "wave_ops.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWave = 64;
+constexpr int kWaves = kBlock / kWave;
+constexpr int kPer = 4;                       // pairs per thread: four independent gathers in flight
+constexpr int kPairs = kBlock * kPer;         // pairs per workgroup = per partial row
+constexpr int kMom = 17;
+
+struct Rigid { double m[12]; };               // row-major 3x4 [R|t]
+struct Origins { double x[3], y[3]; };
+
+__global__ __launch_bounds__(kBlock) void k_rigid_apply(const float* __restrict__ x, int xs, int U, Rigid T, float* __restrict__ out) {
+    const int u = blockIdx.x * kBlock + threadIdx.x;
+    if (u >= U) return;
+    const float* p = x + (size_t)u * xs;
+    const double px = (double)p[0], py = (double)p[1], pz = (double)p[2];
+    float* o = out + (size_t)u * 3;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) o[r] = (float)(((T.m[4 * r] * px + T.m[4 * r + 1] * py) + T.m[4 * r + 2] * pz) + T.m[4 * r + 3]);
+}
+
+// every lane of every wave reaches the reductions (wave_sum needs all 64 lanes): a pair past U, outside the radius or with a bad index adds 0
+__global__ __launch_bounds__(kBlock) void k_align_moments(const float* __restrict__ x, int xs, int U, const float* __restrict__ y, int ys, int N,
+                                                          const int64_t* __restrict__ idx, const float* __restrict__ d2, float max_d2, Origins o,
+                                                          double* __restrict__ partial, int* __restrict__ flag) {
+    __shared__ double s_rows[kWaves][kMom];
+    double acc[kMom];
+#pragma unroll
+    for (int m = 0; m < kMom; ++m) acc[m] = 0.0;
+    const long long base = (long long)blockIdx.x * kPairs + threadIdx.x;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+        const long long u = base + (long long)j * kBlock;
+        if (u >= (long long)U) continue;
+        const int64_t i = idx[u];
+        if (i < 0 || i >= (int64_t)N) { bad = true; continue; }
+        const float dd = d2[u];
+        if (!(dd <= max_d2)) continue;                         // a NaN compares false: never an inlier
+        const float* px = x + (size_t)u * xs;
+        const float* py = y + (size_t)i * ys;
+        const double a[3] = {(double)px[0] - o.x[0], (double)px[1] - o.x[1], (double)px[2] - o.x[2]};
+        const double b[3] = {(double)py[0] - o.y[0], (double)py[1] - o.y[1], (double)py[2] - o.y[2]};
+        acc[0] += 1.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            acc[1 + r] += a[r];
+            acc[4 + r] += b[r];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[7 + 3 * r + c] += a[r] * b[c];
+        }
+        acc[16] += (double)dd;
+    }
+    if (bad) *flag = 1;
+    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+#pragma unroll
+    for (int m = 0; m < kMom; ++m) {
+        const double s = sgw::wave_sum(acc[m]);
+        if (lane == 0) s_rows[wave][m] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < kMom) {
+        double s = s_rows[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) s += s_rows[w][threadIdx.x];
+        partial[(size_t)blockIdx.x * kMom + threadIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_align_fold(const double* __restrict__ partial, int rows, double* __restrict__ out) {
+    __shared__ double s_rows[kWaves][kMom];
+    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+#pragma unroll 1
+    for (int m = 0; m < kMom; ++m) {
+        double acc = 0.0;
+        for (int r = threadIdx.x; r < rows; r += kBlock) acc += partial[(size_t)r * kMom + m];
+        const double s = sgw::wave_sum(acc);
+        if (lane == 0) s_rows[wave][m] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < kMom) {
+        double s = s_rows[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) s += s_rows[w][threadIdx.x];
+        out[threadIdx.x] = s;
+    }
+}
+
+struct Landing { double m[kMom]; int flag; int pad; };   // what one copy brings back: the sums and the flag word
+
+bool finite3(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+}  // namespace
+
+extern "C" {
+
+int sg_rigid_apply(const float* d_x, int x_stride, int U, const double* h_T, float* d_out, void* stream) {
+    const char* who = "sg_rigid_apply";
+    SG_REQUIRE(U >= 0 && x_stride >= 3 && h_T, "%s: bad arguments (%d points, rows of %d floats)", who, U, x_stride);
+    if (U > SG_MAX_CLOUD_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; a call takes at most %d", who, U, SG_MAX_CLOUD_POINTS);
+    Rigid T;
+    for (int i = 0; i < 12; ++i) {
+        SG_REQUIRE(std::isfinite(h_T[i]), "%s: entry %d of the transform is not finite", who, i);
+        T.m[i] = h_T[i];
+    }
+    if (U == 0) return SG_OK;
+    SG_REQUIRE(d_x && d_out, "%s: bad arguments", who);
+    k_rigid_apply<<<sg::cdiv(U, kBlock), kBlock, 0, sg::as_stream(stream)>>>(d_x, x_stride, U, T, d_out);
+    SG_LAUNCH_CHECK();
+    return SG_OK;
+}
+
+size_t sg_align_moments_ws_bytes(int U) {
+    if (U < 0 || U > SG_MAX_CLOUD_POINTS) return 0;
+    return sg::align_up(sizeof(Landing)) + sg::align_up((size_t)std::max(sg::cdiv(U, kPairs), 1) * kMom * sizeof(double));
+}
+
+int sg_align_moments(const float* d_x, int x_stride, int U, const float* d_y, int y_stride, int N, const int64_t* d_idx, const float* d_d2,
+                     float max_d2, const double* h_origin_x, const double* h_origin_y, double* h_out, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* who = "sg_align_moments";
+    SG_REQUIRE(U >= 0 && N >= 1, "%s: bad arguments (%d pairs, %d candidates)", who, U, N);
+    if (U > SG_MAX_CLOUD_POINTS || N > SG_MAX_CLOUD_POINTS)
+        return sg::fail(SG_EUNSUP, "%s: %d pairs into %d candidates; a call takes at most %d of either", who, U, N, SG_MAX_CLOUD_POINTS);
+    SG_REQUIRE(x_stride >= 3 && y_stride >= 3, "%s: rows of at least 3 floats (x: %d, y: %d)", who, x_stride, y_stride);
+    SG_REQUIRE(h_origin_x && h_origin_y && h_out, "%s: bad arguments", who);
+    SG_REQUIRE(!std::isnan(max_d2), "%s: max_d2 is not a number", who);
+    SG_REQUIRE(finite3(h_origin_x) && finite3(h_origin_y), "%s: an origin that is not finite", who);
+    if (U == 0) {
+        for (int m = 0; m < kMom; ++m) h_out[m] = 0.0;
+        return SG_OK;
+    }
+    SG_REQUIRE(d_x && d_y && d_idx && d_d2 && d_ws, "%s: bad arguments", who);
+    const size_t need = sg_align_moments_ws_bytes(U);
+    SG_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    const int rows = sg::cdiv(U, kPairs);
+    sg::Carver cv(d_ws, ws_bytes);
+    Landing* d_land = cv.take<Landing>(1);
+    double* d_partial = cv.take<double>((size_t)rows * kMom);
+    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    Origins o;
+    for (int i = 0; i < 3; ++i) { o.x[i] = h_origin_x[i]; o.y[i] = h_origin_y[i]; }
+    hipStream_t st = sg::as_stream(stream);
+    SG_HIP(hipMemsetAsync(d_land, 0, sizeof(Landing), st));
+    k_align_moments<<<rows, kBlock, 0, st>>>(d_x, x_stride, U, d_y, y_stride, N, d_idx, d_d2, max_d2, o, d_partial, &d_land->flag);
+    k_align_fold<<<1, kBlock, 0, st>>>(d_partial, rows, d_land->m);
+    Landing land{};
+    SG_HIP(hipMemcpyAsync(&land, d_land, sizeof(Landing), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (land.flag) return sg::fail(SG_EINVAL, "%s: an index outside 0..%d", who, N - 1);
+    for (int m = 0; m < kMom; ++m) h_out[m] = land.m[m];
+    return SG_OK;
+}
+
+}  // extern "C"

@@ -177,6 +177,10 @@ SIGNATURES = {
     "sg_cloud_knn_cross_grid_stats": (_I, [vp, _I]),
     "sg_cloud_knn_cross_grid_set_tuning": (_I, [_I, _I]),
     "sg_knn_vote": (_I, [vp, _I, _I, vp, _I, vp, vp, vp, vp, vp]),
+    "sg_rigid_apply": (_I, [vp, _I, _I, vp, vp, vp]),
+    "sg_align_moments_ws_bytes": (_Z, [_I]),
+    "sg_align_moments": (_I, [vp, _I, _I, vp, _I, _I, vp, vp, C.c_float, vp, vp, vp, vp, _Z, vp]),
+    "sg_align_solve": (_I, [vp, vp, vp, vp]),
     "sg_components_ws_bytes": (_Z, [_I]),
     "sg_components_edges": (_I, [vp, C.c_longlong, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_components_faces": (_I, [vp, _I, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),

@@ -13,17 +13,27 @@ nearest vertex is an arbitrary member of a mixed neighbourhood.  `--vote K` (DES
 frequent ones) and carries over ALL values of `rep`, the nearest source vertex that holds the winner -- so a target vertex's labels
 still come from one source vertex, the .sgl stays consistent and every layer stays a function of the segment.
 
+All of this assumes one frame.  Where the target is centimetres to decimetres off -- a photogrammetry cloud beside a laser scan, a
+re-export in another pose, a rescan after a coarse manual registration -- `--align` first finds the rigid transform T that
+maps the TARGET into the source's frame (`align.icp` with `--align-max-dist`, or a `<scene>.align.json` that `python -m seggroup_amd.align`
+wrote), and the search runs on the moved target.  Everything after the search is unchanged: the files are written at the target's own
+geometry, the distances in the report are those after alignment.
+
     python -m seggroup_amd.transfer --from-scans DIR --to-scans DIR -n EXP --stage S --out ROOT2 [--root .] [--scenes FILE]
-                                    [--workers K] [--index {grid,brute}] [--vote {5,10,20} [--vote-on NAME]] [--device D]
+                                    [--workers K] [--index {grid,brute}] [--vote {5,10,20} [--vote-on NAME]]
+                                    [--align {icp,DIR} [--align-max-dist D]] [--device D]
         for every scene present in both trees: results/EXP/<scene>/<S>/ of --root (made on --from-scans) -> the same files at the
         target's V under ROOT2/results/EXP/<scene>/<S>/ (pseudo_labels.sgl and the per-vector .npy files, as `thin --lift` writes
         them), ROOT2/results/EXP/<scene>/<S>/<scene>.transfer.npz (nearest, d2; with --vote also rep, votes, tied) and one
         ROOT2/transfer_report.json.  --vote-on: `seg` (the default: the .sgl's seg_of_vertex) or a vector name such as final.ins, taken
-        from the .sgl's expansion or from the .npy file.
+        from the .sgl's expansion or from the .npy file.  --align icp --align-max-dist D: point-to-point ICP of the target onto the source
+        with the inlier radius D; --align DIR: T from DIR/<scene>.align.json.  With either the .transfer.npz also holds T (float64 [4,4],
+        target -> source frame) and the scene's report entry an `align` record.
 
 Not here: a distance cut-off that un-labels far vertices (a lifted .sgl has no "no segment" for a vertex: the report says how far the
-vertices are, the decision is the user's), interpolation or distance-weighted votes, and segs.json or clicks (rekey.py and thin.py own
-those).
+vertices are -- after the alignment, when there is one -- and the decision is the user's), interpolation or distance-weighted votes,
+anything but a rigid transform between the two geometries (no scale, no deformation, no registration without a starting pose: align.py
+says what its ICP is and is not), and segs.json or clicks (rekey.py and thin.py own those).
 """
 from __future__ import annotations
 
@@ -33,6 +43,7 @@ import sys
 
 import numpy as np
 
+from . import align as rigid
 from . import hip, pseudo_labels, scans
 from .device import device_tensor, on_stream, stream_ptr, sync, torch_device
 from .prepare import get_unmapper, knn_cross_grid, mesh_arrays, nearest_point_grid, read_ply
@@ -132,51 +143,91 @@ def check_vote(vote_k, vote_on, index: str) -> None:
         raise ValueError("--vote-on (vote_on=) must be 'seg' or one of %s, not %r" % (", ".join(hip.LABEL_NAMES), vote_on))
 
 
+def check_align(align, align_max_dist, index: str) -> None:
+    """the combinations of align, align_max_dist and index that are refused before anything runs (ValueError)"""
+    if align is None:
+        if align_max_dist is not None:
+            raise ValueError("--align-max-dist (align_max_dist=) needs --align icp (align='icp'): without an ICP there is no inlier radius")
+        return
+    if index != "grid":
+        raise ValueError("--align (align=) searches through the grid index only -- use --index grid (index='grid')")
+    if align == "icp":
+        if align_max_dist is None or not float(align_max_dist) > 0.0:
+            raise ValueError("--align icp (align='icp') needs --align-max-dist (align_max_dist=) > 0: the inlier radius has no default")
+    else:
+        if align_max_dist is not None:
+            raise ValueError("--align-max-dist (align_max_dist=) goes with --align icp only: --align %s reads its transforms" % (align,))
+        if not os.path.isdir(align):
+            raise ValueError("--align (align=) must be 'icp' or a directory of <scene>%s files, not %r" % (rigid.ALIGN_SUFFIX, align))
+
+
+def scene_alignment(scene: str, src_xyz, dst_xyz, align, align_max_dist, device=None, stream=None):
+    """-> (T float64 [4,4] mapping the target into the source's frame, the scene's `align` record of the report)"""
+    if align == "icp":
+        al = rigid.icp(dst_xyz, src_xyz, align_max_dist, device=device, stream=stream)
+        return al.T, dict(al.scalars(), source="icp")
+    path = rigid.align_path(align, scene)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path}: no alignment for this scene under --align (align=)")
+    doc = rigid.read_align(path)
+    return doc["T"], dict({k: doc.get(k) for k in rigid.SCALARS}, source=path)
+
+
 def _scan_xyz(scans_dir: str, scene: str):
     return mesh_arrays(read_ply(os.path.join(scans_dir, scene, scene + "_vh_clean_2.ply")))[0]
 
 
 def transfer_scene(scene: str, from_scans: str, to_scans: str, exp: str, stage: str, out_root: str, root: str = ".", index: str = "grid",
-                   device=None, stream=None, vote_k=None, vote_on=None):
+                   device=None, stream=None, vote_k=None, vote_on=None, align=None, align_max_dist=None):
     """One scene: results/<exp>/<scene>/<stage>/ under `root`, made on <from_scans>/<scene>, -> the same files for <to_scans>/<scene>
     under <out_root>/results/...; -> (its entry of transfer_report.json, the files written).  With `vote_k` the files are gathered by
-    `rep`, the nearest of the vote_k nearest source vertices that holds their most frequent `vote_on` label."""
+    `rep`, the nearest of the vote_k nearest source vertices that holds their most frequent `vote_on` label.  With `align`
+    ("icp" with `align_max_dist`, or a directory of <scene>.align.json) the search runs on the target moved into the source's frame
+    (DESIGN.md 8p); the files are still the target's."""
     check_vote(vote_k, vote_on, index)
+    check_align(align, align_max_dist, index)
     src_dir = os.path.join(root, "results", exp, scene, stage)
     if not os.path.isdir(src_dir):
         raise FileNotFoundError(f"{src_dir}: no such export directory")
     src_xyz, dst_xyz = _scan_xyz(from_scans, scene), _scan_xyz(to_scans, scene)
     dst_dir = os.path.join(out_root, "results", exp, scene, stage)
-    voted = {}
+    voted, aligned, query = {}, {}, dst_xyz
+    if align is not None:
+        T, record = scene_alignment(scene, src_xyz, dst_xyz, align, align_max_dist, device=device, stream=stream)
+        aligned, query = {"T": T}, rigid.apply(dst_xyz, T, device=device, stream=stream)
     if vote_k is None:
-        d_near, d_d2 = nearest_vertex(src_xyz, dst_xyz, index=index, device=device, stream=stream)
+        d_near, d_d2 = nearest_vertex(src_xyz, query, index=index, device=device, stream=stream)
         nearest, d2 = d_near.cpu().numpy(), d_d2.cpu().numpy()
         gather = nearest
     else:
         vote_on = "seg" if vote_on is None else vote_on
         labels = vote_labels(src_dir, vote_on, int(src_xyz.shape[0]))
-        d_knn, d_d2 = nearest_vertices(src_xyz, dst_xyz, vote_k, device=device, stream=stream)
+        d_knn, d_d2 = nearest_vertices(src_xyz, query, vote_k, device=device, stream=stream)
         _, d_rep, d_count, d_tied = vote(d_knn, labels, device=device, stream=stream)
         nearest, d2 = d_knn[:, 0].cpu().numpy().astype(np.int64), np.ascontiguousarray(d_d2[:, 0].cpu().numpy())
         gather = d_rep.cpu().numpy()
         voted = {"rep": gather, "votes": d_count.cpu().numpy(), "tied": d_tied.cpu().numpy()}
     files = lift_stage(src_dir, dst_dir, gather, int(src_xyz.shape[0]), "transfer", "source vertices")
-    np.savez(os.path.join(dst_dir, scene + MAP_SUFFIX), nearest=nearest, d2=d2, **voted)
+    np.savez(os.path.join(dst_dir, scene + MAP_SUFFIX), nearest=nearest, d2=d2, **voted, **aligned)
     dist = np.sqrt(d2.astype(np.float64))
     entry = {"source_V": int(src_xyz.shape[0]), "target_V": int(dst_xyz.shape[0]), "max_distance": float(dist.max()) if dist.size else 0.0,
              "median_distance": float(np.median(dist)) if dist.size else 0.0,
              "farther_than": {"%g" % t: int((dist > t).sum()) for t in FAR}}
     if voted:
         entry.update(vote=int(vote_k), vote_on=vote_on, moved=int((gather != nearest).sum()), tied=int(voted["tied"].sum()))
+    if aligned:
+        entry["align"] = record
     return entry, files
 
 
 def transfer_results(from_scans: str, to_scans: str, exp: str, stage: str, out_root: str, root: str = ".", scenes=None, workers: int = 4,
-                     index: str = "grid", device=None, vote_k=None, vote_on=None):
+                     index: str = "grid", device=None, vote_k=None, vote_on=None, align=None, align_max_dist=None):
     """Every scene of `from_scans` (or the named ones) that both trees hold -> (report {scene: entry}, missing {scene: why}); writes
-    <out_root>/transfer_report.json.  Workers are threads, each with its own stream.  `vote_k`, `vote_on`: transfer_scene's."""
+    <out_root>/transfer_report.json.  Workers are threads, each with its own stream.  `vote_k`, `vote_on`, `align`, `align_max_dist`:
+    transfer_scene's."""
     hip.knn_index(index)
     check_vote(vote_k, vote_on, index)
+    check_align(align, align_max_dist, index)
     dev = torch_device(device)
     have_src, have_dst = set(scans.scan_names(from_scans)), set(scans.scan_names(to_scans))
     if scenes is None:
@@ -192,7 +243,8 @@ def transfer_results(from_scans: str, to_scans: str, exp: str, stage: str, out_r
             todo.append(s)
     report = dict(scans.map_scans(todo, workers, dev, lambda scene, stream: transfer_scene(scene, from_scans, to_scans, exp, stage, out_root, root,
                                                                                            index, device=dev, stream=stream, vote_k=vote_k,
-                                                                                           vote_on=vote_on)[0]))
+                                                                                           vote_on=vote_on, align=align,
+                                                                                           align_max_dist=align_max_dist)[0]))
     os.makedirs(out_root, exist_ok=True)
     scans.write_report(os.path.join(out_root, REPORT_NAME), {"experiment": exp, "stage": stage, "index": index, "scenes": report, "missing": missing})
     return report, missing
@@ -214,18 +266,24 @@ def main(argv=None) -> int:
                          "of them that holds the winning label")
     ap.add_argument("--vote-on", choices=VOTE_ON, default=None, metavar="NAME",
                     help="what the neighbours vote on: seg (the default: the .sgl's seg_of_vertex) or a vector name such as final.ins")
+    ap.add_argument("--align", default=None, metavar="icp|DIR",
+                    help="move the target into the source's frame before the search (needs --index grid): icp fits the transform here "
+                         "(with --align-max-dist), DIR reads <scene>.align.json as python -m seggroup_amd.align writes it")
+    ap.add_argument("--align-max-dist", type=float, default=None, metavar="D", help="the ICP's inlier radius in the scans' unit (--align icp only)")
     ap.add_argument("--device", default=None)
     a = ap.parse_args(argv)
     scans.check_workers(ap, a.workers)
     try:
         check_vote(a.vote, a.vote_on, a.index)
+        check_align(a.align, a.align_max_dist, a.index)
     except ValueError as e:
         ap.error(str(e))
     try:
         report, missing = transfer_results(a.from_scans, a.to_scans, a.exp_name, a.stage, a.out, a.root, scans.scene_list(a.scenes), a.workers,
-                                           a.index, a.device, vote_k=a.vote, vote_on=a.vote_on)
+                                           a.index, a.device, vote_k=a.vote, vote_on=a.vote_on, align=a.align,
+                                           align_max_dist=a.align_max_dist)
     except ValueError as e:
-        if "--index grid" not in str(e) and "--vote-on" not in str(e):
+        if "--index grid" not in str(e) and "--vote-on" not in str(e) and "max_dist" not in str(e):
             raise
         ap.error(str(e))
     for scene, e in report.items():
