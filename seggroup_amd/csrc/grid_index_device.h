@@ -155,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void k_grid_cellstats(const int* __restrict
 
 // The wave's next group: the lanes of the first pending lane's cell, and that cell's coordinates (wave-uniform).  A search loops
 //     while (const unsigned long long pending = pending_lanes(done)) { const Group grp = pick_group(g, pending, done, mycell); ... }
-// The group is returned by value and picked in one place of the loop: outputs through references cost k_grid_search<21> its occupancy, a
+// The group is returned by value and picked in one place of the loop: outputs through references cost the self-kNN's search at 21 entries its occupancy, a
 // second inlined copy a hundred instructions (profiles/grid_builder_resources.md).
 struct Group {
     bool in;                        // this lane belongs to the group

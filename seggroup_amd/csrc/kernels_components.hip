@@ -150,9 +150,7 @@ int run(const char* who, const Graph& g, int V, int32_t* d_comp, int32_t* d_size
 
 extern "C" {
 
-int sg_components_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
-int sg_components_stage_times(float* h_us, int cap) { return t_times.copy("sg_components_stage_times", h_us, cap); }
-const char* sg_components_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
+SG_STAGE_TIMER_API(components, t_times, kStageNames)
 
 size_t sg_components_ws_bytes(int V) {
     if (V < 1 || V > SG_MAX_CLOUD_POINTS) return 0;

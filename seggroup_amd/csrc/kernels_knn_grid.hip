@@ -11,21 +11,26 @@
 //                       the cells (cx - r .. cx + r, y, z) of one row are ONE contiguous range of the sorted points
 //   sort                stable radix sort of (key, index) over the key's bits in use (sort_device.h); k_grid_gather: the points in sorted order
 //   k_grid_table        dense: start[c] = the first sorted point whose key is >= c, c = 0 .. cells; k_grid_cellstats: occupied, the largest
-//   k_grid_search       one wave per 64 sorted points.  The lanes of one cell form a group and share their candidates: the rows of the
+//   k_ring_search       one wave per 64 sorted points.  The lanes of one cell form a group and share their candidates: the rows of the
 //                       block are staged through LDS in tiles of 256 (float4 + original index), every lane of the group scores its own
 //                       query and inserts by (score, original index) into a register list.  Ring 1 is the 3 x 3 x 3 block, ring r adds
 //                       the shell at Chebyshev distance r; a group stops when all its lanes are settled or its block covers the grid.
-//   k_grid_fallback     the queued queries against the whole cloud in original order (cloud_knn_device.h)
+//   k_queue_search      the queued queries against the whole cloud in original order (cloud_knn_device.h)
 //
 // The lists are written at the ORIGINAL row with ORIGINAL indices.  Plain launches, vector stores.
 //
 // sg_nearest_point_grid is the two-cloud, one-entry form: the same stages index the candidates y (box, E and M2 over the union
-// of both clouds), the queries x are binned by the same formula and sorted by cell key, k_nearest_search walks the rings, and the queue is
-// finished by sg_nearest_point's own kernel.  Both entry points build their index through build_index.
+// of both clouds), the queries x are binned by the same formula and sorted by cell key, the same search walks the rings with a list of one
+// entry, and the queue is finished by sg_nearest_point's own kernel (sgcloud::launch_nearest).
 //
-// sg_cloud_knn_cross_grid is the two-cloud form with a list of k entries: the index and the sorted queries of 8i, the walk
-// and the `full` condition of 8h (k_cross_search), the queue finished by sgcloud::top_scores over every candidate (k_cross_fallback), the
-// squared distances per list entry (k_cross_d2).  sg_knn_vote is the majority vote over such rows (k_knn_vote): integers only.
+// sg_cloud_knn_cross_grid is the two-cloud form with a list of k entries: the index and the sorted queries of 8i, the walk,
+// the `full` condition and the queue kernel of 8h.  Both two-cloud forms leave the squared distances per entry where they are asked for
+// (k_list_d2).  sg_knn_vote is the majority vote over such rows (k_knn_vote): integers only.
+//
+// One of each for the three: k_ring_search<KK, Queries, Out> takes where its queries come from as a type (the sorted candidates
+// themselves, or the sorted queries' original rows) and instantiates at KK = 6, 11, 21 (8h), 1 with int64 rows (8i) and 5, 10, 20 (8o);
+// k_queue_search<KK> takes (queries, candidates), the self-kNN passing its candidates twice; k_list_d2<I> takes the index type.  On the
+// host with_list maps k to the list length and grid_search drives everything behind an entry point's argument checks.
 //
 // The index's own pieces (k_grid_box .. k_grid_cellstats, the Grid, the workspace plan), the steps of its build and the search skeleton
 // (group pick, tile staging, the kernels' leave) live in grid_index_device.h, which the radius graph (kernels_radius.hip)
@@ -33,6 +38,7 @@
 // points are here.
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "sg_common.h"
 #include "sort_device.h"
@@ -143,126 +149,62 @@ __device__ __forceinline__ Walk ring_walk(const Grid& g, bool live, int mycell, 
     return Walk{queued, myr, evals};
 }
 
-template <int KK>
-__global__ __launch_bounds__(kWave) void k_grid_search(const float4* __restrict__ spts, const int* __restrict__ sidx,
-                                                       const unsigned long long* __restrict__ skey, const int* __restrict__ start, Grid g, int N,
-                                                       int32_t* __restrict__ table, int* __restrict__ queue, Misc* __restrict__ m, int counting) {
+// Where a wave's 64 queries come from, as a type (no run-time branch): slot sl of the sorted order -> the query, returned by value as
+// pick_group's Group is.  Both read (points, sorted keys, sorted indices), plain kernel arguments.
+struct Query {
+    float4 me;                          // (x, y, z, |q|^2)
+    int cell, orig;                     // its cell key; the row its list goes to
+};
+struct SortedCandidates {               // the self-kNN (8h): the sorted candidates are the queries, pts is in sorted order
+    static __device__ __forceinline__ Query load(const float4* __restrict__ pts, const unsigned long long* __restrict__ key,
+                                                 const int* __restrict__ idx, int sl) {
+        return Query{pts[sl], (int)key[sl], idx[sl]};
+    }
+};
+struct SortedQueries {                  // two clouds (8i, 8o): the queries' sorted keys name their ORIGINAL rows, pts is in original order
+    static __device__ __forceinline__ Query load(const float4* __restrict__ pts, const unsigned long long* __restrict__ key,
+                                                 const int* __restrict__ idx, int sl) {
+        const int orig = idx[sl];
+        return Query{pts[orig], (int)key[sl], orig};
+    }
+};
+
+// The search: one wave per 64 of the Q queries in the order of their cell keys; the lanes of one cell form a group
+// and share the staged candidate tiles through ring_walk, each with a list of KK entries.  A list that is not full is unsettled
+// (ring_settles takes `full`): with KK = 1 a query whose block holds no candidate keeps -inf and walks on.  Row orig of `out` [Q, KK]
+// receives the list, original candidate indices; queries unsettled at the ring limit are queued with their original row.
+template <int KK, class Queries, class Out>
+__global__ __launch_bounds__(kWave) void k_ring_search(const float4* __restrict__ spts, const int* __restrict__ sidx, const int* __restrict__ start,
+                                                       Grid g, const float4* __restrict__ qpts, const unsigned long long* __restrict__ qskey,
+                                                       const int* __restrict__ qsidx, int Q, Out* __restrict__ out, int* __restrict__ queue,
+                                                       Misc* __restrict__ m, int counting) {
     __shared__ float4 tile[kGTile];
     __shared__ int tidx[kGTile];
     const int s = blockIdx.x * kWave + threadIdx.x;
-    const bool live = s < N;
-    const int sl = live ? s : N - 1;
-    const float4 me = spts[sl];
-    const int mycell = (int)skey[sl];
-    const int orig = sidx[sl];
+    const bool live = s < Q;
+    const Query q = Queries::load(qpts, qskey, qsidx, live ? s : Q - 1);
+    const int orig = q.orig;
     float bs[KK];
     int bi[KK];
-    const Walk w = ring_walk<KK>(g, live, mycell, me, start, spts, sidx, tile, tidx, bs, bi);
+    const Walk w = ring_walk<KK>(g, live, q.cell, q.me, start, spts, sidx, tile, tidx, bs, bi);
     if (live) {
         if (w.queued) {
             queue[atomicAdd(&m->nq, 1)] = orig;
         } else {
 #pragma unroll
-            for (int t = 0; t < KK; ++t) table[(size_t)orig * KK + t] = bi[t];
+            for (int t = 0; t < KK; ++t) out[(size_t)orig * KK + t] = (Out)bi[t];
         }
     }
     search_epilogue(w.ring, w.evals, counting, m);
 }
 
-// the queued queries (original indices) against the whole cloud in original order: k_pc_knn for a compacted list
+// The queued queries (rows of qpts [U]) against all N candidates in original order, by sgcloud::top_scores: k_pc_knn for a compacted
+// list.  The self-kNN passes its candidates as the queries.  Every caller has N >= KK, so top_scores leaves a full list of real indices
+// and the clamp never acts; it only keeps a stored index inside the cloud whatever happens.
 template <int KK>
-__global__ __launch_bounds__(kTile) void k_grid_fallback(const float4* __restrict__ cand, int N, const int* __restrict__ queue, int nq,
-                                                         int32_t* __restrict__ table, Misc* __restrict__ m, int counting) {
-    __shared__ float4 tile[kTile];
-    const int u = blockIdx.x * kTile + threadIdx.x;
-    const bool live = u < nq;
-    const int q = live ? queue[u] : 0;
-    const bool sane = (unsigned)q < (unsigned)N;
-    const float4 me = cand[sane ? q : 0];
-    float bs[KK];
-    int bi[KK];
-    sgcloud::top_scores<KK>(cand, N, me, tile, bs, bi);
-    if (live && sane) {
-#pragma unroll
-        for (int t = 0; t < KK; ++t) table[(size_t)q * KK + t] = bi[t] < N ? bi[t] : q;
-    }
-    if (counting && threadIdx.x == 0) atomicAdd(&m->evals, (unsigned long long)min(kTile, nq - blockIdx.x * kTile) * (unsigned long long)N);
-}
-
-// The two-cloud, one-entry form: one wave per 64 queries in the order of their cell keys; the lanes of one cell form a group
-// and share the staged candidate tiles through k_grid_search's ring_walk, the list is (best score, its original index).  A query whose block
-// holds no candidate keeps -inf and is unsettled by construction.  The result goes to the query's ORIGINAL row; queries unsettled at the
-// ring limit are queued with their original index for k_nearest (kernels_prepare.hip).
-__global__ __launch_bounds__(kWave) void k_nearest_search(const float4* __restrict__ spts, const int* __restrict__ sidx, const int* __restrict__ start,
-                                                          Grid g, const float4* __restrict__ qpts, const unsigned long long* __restrict__ qskey,
-                                                          const int* __restrict__ qsidx, int U, int64_t* __restrict__ out, int* __restrict__ queue,
-                                                          Misc* __restrict__ m, int counting) {
-    __shared__ float4 tile[kGTile];
-    __shared__ int tidx[kGTile];
-    const int s = blockIdx.x * kWave + threadIdx.x;
-    const bool live = s < U;
-    const int sl = live ? s : U - 1;
-    const int orig = qsidx[sl];
-    const float4 me = qpts[orig];
-    const int mycell = (int)qskey[sl];
-    float bs[1];
-    int bi[1];
-    const Walk w = ring_walk<1>(g, live, mycell, me, start, spts, sidx, tile, tidx, bs, bi);
-    if (live) {
-        if (w.queued) queue[atomicAdd(&m->nq, 1)] = orig;
-        else out[orig] = (int64_t)bi[0];
-    }
-    search_epilogue(w.ring, w.evals, counting, m);
-}
-
-// d2[u] = (dx*dx + dy*dy) + dz*dz with d = x[u] - y[idx[u]], every operation rounded once (the file is built without contraction)
-__global__ __launch_bounds__(kBlock) void k_nearest_d2(const float* __restrict__ x, int xs, int U, const float* __restrict__ y, int ys, int N,
-                                                       const int64_t* __restrict__ idx, float* __restrict__ d2) {
-    const int u = blockIdx.x * kBlock + threadIdx.x;
-    if (u >= U) return;
-    const int64_t j = idx[u];
-    if (j < 0 || j >= (int64_t)N) { d2[u] = INFINITY; return; }
-    const float dx = x[(size_t)u * xs] - y[(size_t)j * ys], dy = x[(size_t)u * xs + 1] - y[(size_t)j * ys + 1];
-    const float dz = x[(size_t)u * xs + 2] - y[(size_t)j * ys + 2];
-    d2[u] = (dx * dx + dy * dy) + dz * dz;
-}
-
-// The two-cloud form with a list of KK = k entries: k_nearest_search's wave -- 64 queries in the order of their cell keys,
-// the groups sharing the staged candidate tiles -- with k_grid_search's list.  A list that is not full is unsettled (ring_settles takes
-// `full`), so a query whose block holds fewer than k candidates walks on; row orig of knn receives the list, original candidate indices.
-template <int KK>
-__global__ __launch_bounds__(kWave) void k_cross_search(const float4* __restrict__ spts, const int* __restrict__ sidx, const int* __restrict__ start,
-                                                        Grid g, const float4* __restrict__ qpts, const unsigned long long* __restrict__ qskey,
-                                                        const int* __restrict__ qsidx, int U, int32_t* __restrict__ knn, int* __restrict__ queue,
-                                                        Misc* __restrict__ m, int counting) {
-    __shared__ float4 tile[kGTile];
-    __shared__ int tidx[kGTile];
-    const int s = blockIdx.x * kWave + threadIdx.x;
-    const bool live = s < U;
-    const int sl = live ? s : U - 1;
-    const int orig = qsidx[sl];
-    const float4 me = qpts[orig];
-    const int mycell = (int)qskey[sl];
-    float bs[KK];
-    int bi[KK];
-    const Walk w = ring_walk<KK>(g, live, mycell, me, start, spts, sidx, tile, tidx, bs, bi);
-    if (live) {
-        if (w.queued) {
-            queue[atomicAdd(&m->nq, 1)] = orig;
-        } else {
-#pragma unroll
-            for (int t = 0; t < KK; ++t) knn[(size_t)orig * KK + t] = bi[t];
-        }
-    }
-    search_epilogue(w.ring, w.evals, counting, m);
-}
-
-// the queued queries (original rows of qpts) against every candidate in original order: k_grid_fallback for two clouds.  N >= KK, so the
-// list is full; the clamp only keeps a row inside the cloud whatever happens.
-template <int KK>
-__global__ __launch_bounds__(kTile) void k_cross_fallback(const float4* __restrict__ cand, int N, const float4* __restrict__ qpts, int U,
-                                                          const int* __restrict__ queue, int nq, int32_t* __restrict__ knn, Misc* __restrict__ m,
-                                                          int counting) {
+__global__ __launch_bounds__(kTile) void k_queue_search(const float4* __restrict__ cand, int N, const float4* __restrict__ qpts, int U,
+                                                        const int* __restrict__ queue, int nq, int32_t* __restrict__ out, Misc* __restrict__ m,
+                                                        int counting) {
     __shared__ float4 tile[kTile];
     const int u = blockIdx.x * kTile + threadIdx.x;
     const bool live = u < nq;
@@ -274,19 +216,22 @@ __global__ __launch_bounds__(kTile) void k_cross_fallback(const float4* __restri
     sgcloud::top_scores<KK>(cand, N, me, tile, bs, bi);
     if (live && sane) {
 #pragma unroll
-        for (int t = 0; t < KK; ++t) knn[(size_t)q * KK + t] = bi[t] < N ? bi[t] : N - 1;
+        for (int t = 0; t < KK; ++t) out[(size_t)q * KK + t] = bi[t] < N ? bi[t] : N - 1;
     }
     if (counting && threadIdx.x == 0) atomicAdd(&m->evals, (unsigned long long)min(kTile, nq - blockIdx.x * kTile) * (unsigned long long)N);
 }
 
-// d2[u][t] = (dx*dx + dy*dy) + dz*dz with d = x[u] - y[knn[u][t]]: k_nearest_d2 per list entry, one thread each (total = U k < 2^31)
-__global__ __launch_bounds__(kBlock) void k_cross_d2(const float* __restrict__ x, int xs, const float* __restrict__ y, int ys, int N, int k,
-                                                     int total, const int32_t* __restrict__ knn, float* __restrict__ d2) {
+// d2[u][t] = (dx*dx + dy*dy) + dz*dz with d = x[u] - y[idx[u][t]], every operation rounded once (the file is built without contraction);
+// INFINITY for an index outside the candidates.  One thread per entry (total = U k < 2^31).  K: the entries a row when the caller knows
+// them at compile time (the nearest point: 1, which spares the division), 0: k.
+template <class I, int K>
+__global__ __launch_bounds__(kBlock) void k_list_d2(const float* __restrict__ x, int xs, const float* __restrict__ y, int ys, int N, int k,
+                                                    int total, const I* __restrict__ idx, float* __restrict__ d2) {
     const long long e = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (e >= (long long)total) return;
-    const int u = (int)(e / k);
-    const int j = knn[e];
-    if ((unsigned)j >= (unsigned)N) { d2[e] = INFINITY; return; }
+    const int u = (int)(e / (K ? K : k));
+    const I j = idx[e];
+    if ((std::make_unsigned_t<I>)j >= (std::make_unsigned_t<I>)N) { d2[e] = INFINITY; return; }
     const float dx = x[(size_t)u * xs] - y[(size_t)j * ys], dy = x[(size_t)u * xs + 1] - y[(size_t)j * ys + 1];
     const float dz = x[(size_t)u * xs + 2] - y[(size_t)j * ys + 2];
     d2[e] = (dx * dx + dy * dy) + dz * dz;
@@ -385,11 +330,6 @@ int set_tuning(Session& s, const char* who, int target_occupancy, int ring_limit
     return SG_OK;
 }
 
-void leave_stats(Session& s, const Grid& g, const Misc& hm, int nq, unsigned long long evals) {
-    index_stats(s.stats, g, hm);
-    s.stats[6] = hm.maxring; s.stats[7] = nq; s.stats[8] = (int64_t)evals;
-}
-
 // The stages box, probe, cells, sort and table over the N candidates of `d_points`, through grid_index_device.h's
 // steps: measure, the cell edge (the caller's, or the probe's below), bin, sort_cells, finish_index.  With queries (d_q, U > 0) the box
 // covers both clouds and q_pts receives the queries; the index itself holds the candidates only.  `brute`: the entry point that decides a
@@ -454,38 +394,118 @@ int build_index(const char* who, const char* brute, const Session& ses, const fl
     return SG_OK;
 }
 
-template <int KK>
-void launch_search(const Plan& p, const unsigned long long* skey, const int* sidx, const Grid& g, int N, int32_t* table, int counting,
-                   hipStream_t st) {
-    k_grid_search<KK><<<sg::cdiv(N, kWave), kWave, 0, st>>>(p.spts, sidx, skey, p.start, g, N, table, p.queue, p.misc, counting);
+// k in {5, 10, 20} (the entry points refuse every other) -> f(the list length k + kExtra as a constant)
+template <int kExtra, class F>
+void with_list(int k, F&& f) {
+    if (k == 5) f(std::integral_constant<int, 5 + kExtra>{});
+    else if (k == 10) f(std::integral_constant<int, 10 + kExtra>{});
+    else f(std::integral_constant<int, 20 + kExtra>{});
 }
 
-template <int KK>
-void launch_fallback(const Plan& p, int N, int nq, int32_t* table, int counting, hipStream_t st) {
-    k_grid_fallback<KK><<<sg::cdiv(nq, kTile), kTile, 0, st>>>(p.cand, N, p.queue, nq, table, p.misc, counting);
+enum class Form { kSelf, kNearest, kCross };     // 8h: lists of k + 1 over the cloud itself; 8i: one entry, int64; 8o: lists of k
+
+// Everything behind an entry point's argument checks: the workspace, the index (build_index: the stages box .. table), for two clouds
+// the queries binned by the index's formula and sorted by cell key, then the stage "search" -- the ring search and the read-back of what
+// it left -- and the stage "fallback": the queue against every candidate (8i: by sg_nearest_point's own kernel, its nq * N scores counted
+// here) and the squared distances where they are asked for.  kSelf takes no queries (d_x = nullptr, U = 0): the N candidates are the queries.
+template <Form F, class Out>
+int grid_search(const char* who, const char* brute, Session& ses, const float* d_x, int x_stride, int U, const float* d_y, int y_stride, int N,
+                int k, float cell, Out* d_out, float* d_d2, void* d_ws, size_t ws_bytes, void* stream) {
+    constexpr bool kSelf = F == Form::kSelf;
+    using Queries = std::conditional_t<kSelf, SortedCandidates, SortedQueries>;
+    auto for_list = [&](auto&& f) {
+        if constexpr (F == Form::kNearest) f(std::integral_constant<int, 1>{});
+        else with_list<kSelf ? 1 : 0>(k, f);
+    };
+    Plan p{};
+    QueryPlan q{};
+    sg::Carver cv(d_ws, ws_bytes);
+    carve(cv, p, N);
+    if (!kSelf) carve(cv, q, U);
+    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu bytes)", who, ws_bytes);
+    hipStream_t st = sg::as_stream(stream);
+    const int counting = ses.times.timing ? 1 : 0;
+    sgos::StageClock<kStages> clock(st, ses.times.timing, ses.times.us);
+    Index ix{};
+    const int rc = build_index(who, brute, ses, d_y, y_stride, N, d_x, x_stride, U, q.pts, cell, p, clock, st, &ix);
+    if (rc != SG_OK) return rc;
+    const Grid& g = ix.g;
+    const int Q = kSelf ? N : U;
+    const float4* qpts = kSelf ? p.cand : q.pts;
+    int* queue = kSelf ? p.queue : q.queue;
+    Sorted s{ix.skey, ix.sidx};
+    if (!kSelf) {
+        // the queries in the order of their cell keys: 64 consecutive ones are a wave's groups
+        k_grid_cells<<<sg::cdiv(U, kBlock), kBlock, 0, st>>>(q.pts, U, g, q.k0, q.v0);
+        s = sort_cells(q.k0, q.k1, q.v0, q.v1, q.hist, U, g.ncells, st);
+    }
+    const float4* from = kSelf ? p.spts : q.pts;                  // what Queries::load reads: SortedCandidates the sorted points themselves
+    for_list([&](auto kk) {
+        k_ring_search<decltype(kk)::value, Queries, Out><<<sg::cdiv(Q, kWave), kWave, 0, st>>>(p.spts, ix.sidx, p.start, g, from, s.key, s.idx, Q,
+                                                                                              d_out, queue, p.misc, counting);
+    });
+    clock.tick();
+    Misc hm{};
+    SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    const int nq = hm.nq;
+    if (nq < 0 || nq > Q) return sg::fail(SG_EHIP, "%s: %d queued queries from %d%s", who, nq, Q, kSelf ? " points" : "");
+    if (nq > 0) {
+        if constexpr (F == Form::kNearest) {
+            // sg_nearest_point's kernel, scattered to the queries' rows
+            sgcloud::launch_nearest(d_x, x_stride, queue, nq, p.cand, N, d_out, 1, st);
+            if (counting) hm.evals += (unsigned long long)nq * (unsigned long long)N;
+        } else {
+            for_list([&](auto kk) {
+                k_queue_search<decltype(kk)::value><<<sg::cdiv(nq, kTile), kTile, 0, st>>>(p.cand, N, qpts, Q, queue, nq, d_out, p.misc, counting);
+            });
+            if (counting) SG_HIP(hipMemcpyAsync(&hm.evals, &p.misc->evals, 8, hipMemcpyDeviceToHost, st));
+            if (counting || kSelf) SG_HIP(hipStreamSynchronize(st));      // 8h has always returned with its queue finished
+        }
+    }
+    if (d_d2) {
+        constexpr int kOne = F == Form::kNearest ? 1 : 0;
+        const int per = kOne ? 1 : k, total = U * per;
+        k_list_d2<Out, kOne><<<sg::cdiv(total, kBlock), kBlock, 0, st>>>(d_x, x_stride, d_y, y_stride, N, per, total, d_out, d_d2);
+    }
+    clock.tick();
+    SG_LAUNCH_CHECK();
+    index_stats(ses.stats, g, hm);
+    ses.stats[6] = hm.maxring; ses.stats[7] = nq; ses.stats[8] = (int64_t)hm.evals;
+    return SG_OK;
 }
 
-template <int KK>
-void launch_cross(const Plan& p, const QueryPlan& q, const Sorted& qs, const Index& ix, int U, int32_t* knn, int counting, hipStream_t st) {
-    k_cross_search<KK><<<sg::cdiv(U, kWave), kWave, 0, st>>>(p.spts, ix.sidx, p.start, ix.g, q.pts, qs.key, qs.idx, U, knn, q.queue, p.misc, counting);
+// What the two two-cloud entry points refuse alike, in their order, behind the checks that are their own; `entries` a row (8i: 1)
+template <Form F, class Out>
+int two_cloud_search(const char* who, Session& ses, const float* d_x, int x_stride, int U, const float* d_y, int y_stride, int N, int entries,
+                     float cell, Out* d_out, float* d_d2, void* d_ws, size_t ws_bytes, void* stream) {
+    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d candidates; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
+    if (U > SG_MAX_CLOUD_POINTS) return sg::fail(SG_EUNSUP, "%s: %d queries; a call takes at most %d", who, U, SG_MAX_CLOUD_POINTS);
+    if ((long long)U * entries > 0x7fffffffll)
+        return sg::fail(SG_EUNSUP, "%s: %d queries of %d neighbours; a table holds at most 2^31 - 1 entries", who, U, entries);
+    SG_REQUIRE(y_stride >= 3 && x_stride >= 3, "%s: rows of at least 3 floats (x: %d, y: %d)", who, x_stride, y_stride);
+    SG_REQUIRE(std::isfinite(cell) && cell >= 0.0f, "%s: the cell edge must be finite and positive, or 0 for the library's choice (%g)", who, (double)cell);
+    if (U == 0) return SG_OK;
+    SG_REQUIRE(d_x && d_y && d_out && d_ws, "%s: bad arguments", who);
+    const size_t need = plan_bytes(N) + query_plan_bytes(U);
+    SG_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    return grid_search<F>(who, "sg_nearest_point", ses, d_x, x_stride, U, d_y, y_stride, N, entries, cell, d_out, d_d2, d_ws, ws_bytes, stream);
 }
 
-template <int KK>
-void launch_cross_fallback(const Plan& p, const QueryPlan& q, int N, int U, int nq, int32_t* knn, int counting, hipStream_t st) {
-    k_cross_fallback<KK><<<sg::cdiv(nq, kTile), kTile, 0, st>>>(p.cand, N, q.pts, U, q.queue, nq, knn, p.misc, counting);
-}
+// sg_<family>_stats and sg_<family>_set_tuning over the family's Session
+#define SG_GRID_SESSION_API(family, ses)                                                                                      \
+    int sg_##family##_stats(int64_t* h, int cap) { return stats_of(ses, "sg_" #family "_stats", h, cap); }                   \
+    int sg_##family##_set_tuning(int target_occupancy, int ring_limit) {                                                      \
+        return set_tuning(ses, "sg_" #family "_set_tuning", target_occupancy, ring_limit);                                   \
+    }
 
 }  // namespace
 
 extern "C" {
 
-int sg_pointcloud_knn_grid_set_timing(int on) { t_knn.times.timing = on != 0; return SG_OK; }
-int sg_pointcloud_knn_grid_stage_times(float* h_us, int cap) { return t_knn.times.copy("sg_pointcloud_knn_grid_stage_times", h_us, cap); }
-const char* sg_pointcloud_knn_grid_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
-int sg_pointcloud_knn_grid_stats(int64_t* h, int cap) { return stats_of(t_knn, "sg_pointcloud_knn_grid_stats", h, cap); }
-int sg_pointcloud_knn_grid_set_tuning(int target_occupancy, int ring_limit) {
-    return set_tuning(t_knn, "sg_pointcloud_knn_grid_set_tuning", target_occupancy, ring_limit);
-}
+SG_STAGE_TIMER_API(pointcloud_knn_grid, t_knn.times, kStageNames)
+SG_GRID_SESSION_API(pointcloud_knn_grid, t_knn)
 
 size_t sg_pointcloud_knn_grid_ws_bytes(int N, int k) {
     if (N < 1 || N > SG_MAX_GRID_POINTS || (k != 5 && k != 10 && k != 20)) return 0;
@@ -502,45 +522,13 @@ int sg_pointcloud_knn_grid(const float* d_points, int stride, int N, int k, floa
     if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
     SG_REQUIRE(d_points && stride >= 3 && d_knn && d_ws, "%s: bad arguments", who);
     SG_REQUIRE(std::isfinite(cell) && cell >= 0.0f, "%s: the cell edge must be finite and positive, or 0 for the library's choice (%g)", who, (double)cell);
-    const Plan p = carve(d_ws, ws_bytes, N);
-    if (!p.ok) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_pointcloud_knn_grid_ws_bytes(N, k));
-    hipStream_t st = sg::as_stream(stream);
-    const int counting = t_knn.times.timing ? 1 : 0;
-    sgos::StageClock<kStages> clock(st, t_knn.times.timing, t_knn.times.us);
-    Index ix{};
-    const int rc = build_index(who, "sg_pointcloud_knn", t_knn, d_points, stride, N, nullptr, 0, 0, nullptr, cell, p, clock, st, &ix);
-    if (rc != SG_OK) return rc;
-    const Grid& g = ix.g;
-    if (k == 5) launch_search<6>(p, ix.skey, ix.sidx, g, N, d_knn, counting, st);
-    else if (k == 10) launch_search<11>(p, ix.skey, ix.sidx, g, N, d_knn, counting, st);
-    else launch_search<21>(p, ix.skey, ix.sidx, g, N, d_knn, counting, st);
-    clock.tick();
-    Misc hm{};
-    SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
-    SG_HIP(hipStreamSynchronize(st));
-    SG_LAUNCH_CHECK();
-    const int nq = hm.nq;
-    if (nq < 0 || nq > N) return sg::fail(SG_EHIP, "%s: %d queued queries from %d points", who, nq, N);
-    if (nq > 0) {
-        if (k == 5) launch_fallback<6>(p, N, nq, d_knn, counting, st);
-        else if (k == 10) launch_fallback<11>(p, N, nq, d_knn, counting, st);
-        else launch_fallback<21>(p, N, nq, d_knn, counting, st);
-        if (counting) SG_HIP(hipMemcpyAsync(&hm.evals, &p.misc->evals, 8, hipMemcpyDeviceToHost, st));
-        SG_HIP(hipStreamSynchronize(st));
-    }
-    clock.tick();
-    SG_LAUNCH_CHECK();
-    leave_stats(t_knn, g, hm, nq, hm.evals);
-    return SG_OK;
+    if (ws_bytes < plan_bytes(N)) return sg::fail(SG_ENOMEM, "%s: workspace too small (%zu < %zu)", who, ws_bytes, plan_bytes(N));
+    return grid_search<Form::kSelf>(who, "sg_pointcloud_knn", t_knn, nullptr, 0, 0, d_points, stride, N, k, cell, d_knn, nullptr, d_ws, ws_bytes,
+                                    stream);
 }
 
-int sg_nearest_point_grid_set_timing(int on) { t_nearest.times.timing = on != 0; return SG_OK; }
-int sg_nearest_point_grid_stage_times(float* h_us, int cap) { return t_nearest.times.copy("sg_nearest_point_grid_stage_times", h_us, cap); }
-const char* sg_nearest_point_grid_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
-int sg_nearest_point_grid_stats(int64_t* h, int cap) { return stats_of(t_nearest, "sg_nearest_point_grid_stats", h, cap); }
-int sg_nearest_point_grid_set_tuning(int target_occupancy, int ring_limit) {
-    return set_tuning(t_nearest, "sg_nearest_point_grid_set_tuning", target_occupancy, ring_limit);
-}
+SG_STAGE_TIMER_API(nearest_point_grid, t_nearest.times, kStageNames)
+SG_GRID_SESSION_API(nearest_point_grid, t_nearest)
 
 size_t sg_nearest_point_grid_ws_bytes(int U, int N) {
     if (U < 0 || U > SG_MAX_CLOUD_POINTS || N < 1 || N > SG_MAX_GRID_POINTS) return 0;
@@ -552,55 +540,11 @@ int sg_nearest_point_grid(const float* d_x, int x_stride, int U, const float* d_
     const char* who = "sg_nearest_point_grid";
     for (int i = 0; i < kNumStats; ++i) t_nearest.stats[i] = 0;
     SG_REQUIRE(N >= 1 && U >= 0, "%s: bad arguments (%d queries, %d candidates)", who, U, N);
-    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d candidates; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
-    if (U > SG_MAX_CLOUD_POINTS) return sg::fail(SG_EUNSUP, "%s: %d queries; a call takes at most %d", who, U, SG_MAX_CLOUD_POINTS);
-    SG_REQUIRE(y_stride >= 3 && x_stride >= 3, "%s: rows of at least 3 floats (x: %d, y: %d)", who, x_stride, y_stride);
-    SG_REQUIRE(std::isfinite(cell) && cell >= 0.0f, "%s: the cell edge must be finite and positive, or 0 for the library's choice (%g)", who, (double)cell);
-    if (U == 0) return SG_OK;
-    SG_REQUIRE(d_x && d_y && d_idx && d_ws, "%s: bad arguments", who);
-    SG_REQUIRE(ws_bytes >= sg_nearest_point_grid_ws_bytes(U, N), "%s: workspace too small (%zu < %zu)", who, ws_bytes,
-               sg_nearest_point_grid_ws_bytes(U, N));
-    Plan p{};
-    QueryPlan q{};
-    sg::Carver cv(d_ws, ws_bytes);
-    carve(cv, p, N);
-    carve(cv, q, U);
-    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, sg_nearest_point_grid_ws_bytes(U, N));
-    hipStream_t st = sg::as_stream(stream);
-    const int counting = t_nearest.times.timing ? 1 : 0;
-    sgos::StageClock<kStages> clock(st, t_nearest.times.timing, t_nearest.times.us);
-    Index ix{};
-    const int rc = build_index(who, "sg_nearest_point", t_nearest, d_y, y_stride, N, d_x, x_stride, U, q.pts, cell, p, clock, st, &ix);
-    if (rc != SG_OK) return rc;
-    const Grid& g = ix.g;
-    // the queries in the order of their cell keys: 64 consecutive ones are a wave's groups
-    const int ub = sg::cdiv(U, kBlock);
-    k_grid_cells<<<ub, kBlock, 0, st>>>(q.pts, U, g, q.k0, q.v0);
-    const Sorted qs = sort_cells(q.k0, q.k1, q.v0, q.v1, q.hist, U, g.ncells, st);
-    k_nearest_search<<<sg::cdiv(U, kWave), kWave, 0, st>>>(p.spts, ix.sidx, p.start, g, q.pts, qs.key, qs.idx, U, d_idx, q.queue, p.misc, counting);
-    clock.tick();
-    Misc hm{};
-    SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
-    SG_HIP(hipStreamSynchronize(st));
-    SG_LAUNCH_CHECK();
-    const int nq = hm.nq;
-    if (nq < 0 || nq > U) return sg::fail(SG_EHIP, "%s: %d queued queries from %d", who, nq, U);
-    // the queue against every candidate in original order: sg_nearest_point's kernel, scattered to the queries' rows
-    if (nq > 0) sgcloud::launch_nearest(d_x, x_stride, q.queue, nq, p.cand, N, d_idx, 1, st);
-    if (d_d2) k_nearest_d2<<<ub, kBlock, 0, st>>>(d_x, x_stride, U, d_y, y_stride, N, d_idx, d_d2);
-    clock.tick();
-    SG_LAUNCH_CHECK();
-    leave_stats(t_nearest, g, hm, nq, counting ? hm.evals + (unsigned long long)nq * (unsigned long long)N : 0ull);
-    return SG_OK;
+    return two_cloud_search<Form::kNearest>(who, t_nearest, d_x, x_stride, U, d_y, y_stride, N, 1, cell, d_idx, d_d2, d_ws, ws_bytes, stream);
 }
 
-int sg_cloud_knn_cross_grid_set_timing(int on) { t_cross.times.timing = on != 0; return SG_OK; }
-int sg_cloud_knn_cross_grid_stage_times(float* h_us, int cap) { return t_cross.times.copy("sg_cloud_knn_cross_grid_stage_times", h_us, cap); }
-const char* sg_cloud_knn_cross_grid_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
-int sg_cloud_knn_cross_grid_stats(int64_t* h, int cap) { return stats_of(t_cross, "sg_cloud_knn_cross_grid_stats", h, cap); }
-int sg_cloud_knn_cross_grid_set_tuning(int target_occupancy, int ring_limit) {
-    return set_tuning(t_cross, "sg_cloud_knn_cross_grid_set_tuning", target_occupancy, ring_limit);
-}
+SG_STAGE_TIMER_API(cloud_knn_cross_grid, t_cross.times, kStageNames)
+SG_GRID_SESSION_API(cloud_knn_cross_grid, t_cross)
 
 size_t sg_cloud_knn_cross_grid_ws_bytes(int U, int N, int k) {
     if ((k != 5 && k != 10 && k != 20) || U < 0 || U > SG_MAX_CLOUD_POINTS || N < k || N > SG_MAX_GRID_POINTS) return 0;
@@ -615,59 +559,7 @@ int sg_cloud_knn_cross_grid(const float* d_x, int x_stride, int U, const float* 
     if (k != 5 && k != 10 && k != 20) return sg::fail(SG_EUNSUP, "%s: k = %d is not built (5, 10, 20)", who, k);
     SG_REQUIRE(U >= 0, "%s: bad arguments (%d queries, %d candidates)", who, U, N);
     if (N < k) return sg::fail(SG_EINVAL, "%s: %d candidates for k = %d", who, N, k);
-    if (N > SG_MAX_GRID_POINTS) return sg::fail(SG_EUNSUP, "%s: %d candidates; the grid path holds at most %d", who, N, SG_MAX_GRID_POINTS);
-    if (U > SG_MAX_CLOUD_POINTS) return sg::fail(SG_EUNSUP, "%s: %d queries; a call takes at most %d", who, U, SG_MAX_CLOUD_POINTS);
-    if ((long long)U * k > 0x7fffffffll)
-        return sg::fail(SG_EUNSUP, "%s: %d queries of %d neighbours; a table holds at most 2^31 - 1 entries", who, U, k);
-    SG_REQUIRE(y_stride >= 3 && x_stride >= 3, "%s: rows of at least 3 floats (x: %d, y: %d)", who, x_stride, y_stride);
-    SG_REQUIRE(std::isfinite(cell) && cell >= 0.0f, "%s: the cell edge must be finite and positive, or 0 for the library's choice (%g)", who, (double)cell);
-    if (U == 0) return SG_OK;
-    SG_REQUIRE(d_x && d_y && d_knn && d_ws, "%s: bad arguments", who);
-    const size_t need = sg_cloud_knn_cross_grid_ws_bytes(U, N, k);
-    SG_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    Plan p{};
-    QueryPlan q{};
-    sg::Carver cv(d_ws, ws_bytes);
-    carve(cv, p, N);
-    carve(cv, q, U);
-    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    hipStream_t st = sg::as_stream(stream);
-    const int counting = t_cross.times.timing ? 1 : 0;
-    sgos::StageClock<kStages> clock(st, t_cross.times.timing, t_cross.times.us);
-    Index ix{};
-    const int rc = build_index(who, "sg_nearest_point", t_cross, d_y, y_stride, N, d_x, x_stride, U, q.pts, cell, p, clock, st, &ix);
-    if (rc != SG_OK) return rc;
-    const Grid& g = ix.g;
-    // the queries in the order of their cell keys: 64 consecutive ones are a wave's groups
-    k_grid_cells<<<sg::cdiv(U, kBlock), kBlock, 0, st>>>(q.pts, U, g, q.k0, q.v0);
-    const Sorted qs = sort_cells(q.k0, q.k1, q.v0, q.v1, q.hist, U, g.ncells, st);
-    if (k == 5) launch_cross<5>(p, q, qs, ix, U, d_knn, counting, st);
-    else if (k == 10) launch_cross<10>(p, q, qs, ix, U, d_knn, counting, st);
-    else launch_cross<20>(p, q, qs, ix, U, d_knn, counting, st);
-    clock.tick();
-    Misc hm{};
-    SG_HIP(hipMemcpyAsync(&hm, p.misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
-    SG_HIP(hipStreamSynchronize(st));
-    SG_LAUNCH_CHECK();
-    const int nq = hm.nq;
-    if (nq < 0 || nq > U) return sg::fail(SG_EHIP, "%s: %d queued queries from %d", who, nq, U);
-    if (nq > 0) {
-        if (k == 5) launch_cross_fallback<5>(p, q, N, U, nq, d_knn, counting, st);
-        else if (k == 10) launch_cross_fallback<10>(p, q, N, U, nq, d_knn, counting, st);
-        else launch_cross_fallback<20>(p, q, N, U, nq, d_knn, counting, st);
-        if (counting) {
-            SG_HIP(hipMemcpyAsync(&hm.evals, &p.misc->evals, 8, hipMemcpyDeviceToHost, st));
-            SG_HIP(hipStreamSynchronize(st));
-        }
-    }
-    if (d_d2) {
-        const int total = U * k;
-        k_cross_d2<<<sg::cdiv(total, kBlock), kBlock, 0, st>>>(d_x, x_stride, d_y, y_stride, N, k, total, d_knn, d_d2);
-    }
-    clock.tick();
-    SG_LAUNCH_CHECK();
-    leave_stats(t_cross, g, hm, nq, hm.evals);
-    return SG_OK;
+    return two_cloud_search<Form::kCross>(who, t_cross, d_x, x_stride, U, d_y, y_stride, N, k, cell, d_knn, d_d2, d_ws, ws_bytes, stream);
 }
 
 int sg_knn_vote(const int32_t* d_knn, int U, int k, const int32_t* d_label, int N, int32_t* d_winner, int32_t* d_rep, int32_t* d_count,

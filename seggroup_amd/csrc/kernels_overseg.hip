@@ -184,10 +184,8 @@ void sgos::gather_edges(const int* idx, int E, const int64_t* adj, const float* 
 
 extern "C" {
 
-int sg_overseg_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
 // the stage times in microseconds of this thread's last timed sg_overseg_edges -> number of stages; names through sg_overseg_stage_name
-int sg_overseg_stage_times(float* h_us, int cap) { return t_times.copy("sg_overseg_stage_times", h_us, cap); }
-const char* sg_overseg_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
+SG_STAGE_TIMER_API(overseg, t_times, kStageNames)
 
 size_t sg_overseg_ws_bytes(int V, int F) {
     const size_t n = (size_t)std::max(F, 1) * 3;

@@ -604,9 +604,7 @@ int pcseg_scan_radius(const char* who, const float* d_xyz, int N, float radius, 
 
 extern "C" {
 
-int sg_pcseg_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
-int sg_pcseg_stage_times(float* h_us, int cap) { return t_times.copy("sg_pcseg_stage_times", h_us, cap); }
-const char* sg_pcseg_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
+SG_STAGE_TIMER_API(pcseg, t_times, kStageNames)
 
 size_t sg_pointcloud_knn_ws_bytes(int N) { return sg::align_up((size_t)std::max(N, 1) * 16) + sg::align_up(sizeof(Misc)); }
 

@@ -10,7 +10,7 @@
 //             gap = fl(fl(R h) - slack) > 0  and  fl(fl(gap * gap) * (1 - 2^-9)) > r2  (8h item 3 bounds the axis gap of a point outside the
 //             block from below; 8k shows that the 2^-9 also pays for the roundings of d2).  Computed on the host, the same for every
 //             query; no queue and no fallback.  cell = 0: h just large enough for R = 1, enlarged only until the grid fits the table.
-//   search    k_radius_search<Visitor>: k_grid_search's shape on the same pieces (pick_group, stage_tile, wave_sum).  One wave per 64
+//   search    k_radius_search<Visitor>: the grid kNN's search (k_ring_search) in shape, on the same pieces (pick_group, stage_tile, wave_sum).  One wave per 64
 //             consecutive sorted points; the lanes of one cell form a group, taken in turn by ballot; the (2R+1)^2 row ranges of the
 //             block come from the table; candidates are staged through LDS in tiles of 256 (float4 + original index); each lane of the
 //             group tests its own query.  Nothing is indexed at run time.
@@ -341,9 +341,7 @@ int sg_radius_neighbours_grid(const float* d_points, int stride, int N, float ra
     return sg::radius_lists("sg_radius_neighbours_grid", d_points, stride, N, radius, cell, capacity, d_off, d_idx, h_T, d_ws, ws_bytes, stream);
 }
 
-int sg_radius_grid_set_timing(int on) { t_ses.times.timing = on != 0; return SG_OK; }
-int sg_radius_grid_stage_times(float* h_us, int cap) { return t_ses.times.copy("sg_radius_grid_stage_times", h_us, cap); }
-const char* sg_radius_grid_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
+SG_STAGE_TIMER_API(radius_grid, t_ses.times, kStageNames)
 
 int sg_radius_grid_stats(int64_t* h, int cap) {
     SG_REQUIRE(h && cap >= kNumStats, "sg_radius_grid_stats: room for %d words is needed", kNumStats);

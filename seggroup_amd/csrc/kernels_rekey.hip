@@ -242,9 +242,7 @@ constexpr int kMaxVertices = 1 << 30;
 
 extern "C" {
 
-int sg_segment_vote_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
-int sg_segment_vote_stage_times(float* h_us, int cap) { return t_times.copy("sg_segment_vote_stage_times", h_us, cap); }
-const char* sg_segment_vote_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
+SG_STAGE_TIMER_API(segment_vote, t_times, kStageNames)
 
 size_t sg_segment_vote_ws_bytes(int V) {
     const size_t n = (size_t)std::max(V, 1);

@@ -161,9 +161,7 @@ int run(const Plan& p, const int64_t* d_adj, long long E, const int32_t* d_seg, 
 
 extern "C" {
 
-int sg_segment_graph_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
-int sg_segment_graph_stage_times(float* h_us, int cap) { return t_times.copy("sg_segment_graph_stage_times", h_us, cap); }
-const char* sg_segment_graph_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
+SG_STAGE_TIMER_API(segment_graph, t_times, kStageNames)
 
 size_t sg_segment_graph_ws_bytes(long long E, int S) {
     if (E < 0 || E >= kMaxRows || S < 1 || S > kMaxSegments) return 0;

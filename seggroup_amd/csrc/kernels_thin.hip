@@ -175,9 +175,7 @@ thread_local sgos::StageTimes<kStages> t_times;
 
 extern "C" {
 
-int sg_cloud_thin_set_timing(int on) { t_times.timing = on != 0; return SG_OK; }
-int sg_cloud_thin_stage_times(float* h_us, int cap) { return t_times.copy("sg_cloud_thin_stage_times", h_us, cap); }
-const char* sg_cloud_thin_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
+SG_STAGE_TIMER_API(cloud_thin, t_times, kStageNames)
 
 size_t sg_cloud_thin_ws_bytes(int N) {
     if (N < 1 || N > SG_MAX_CLOUD_POINTS) return 0;

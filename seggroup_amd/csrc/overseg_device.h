@@ -141,4 +141,11 @@ struct StageTimes {
 template <int kStages>
 const char* stage_name(const char* const (&names)[kStages], int i) { return i >= 0 && i < kStages ? names[i] : nullptr; }
 
+// sg_<family>_set_timing / _stage_times / _stage_name over the family's StageTimes object and its names, inside an extern "C" block; a
+// refusal names the symbol it came from by construction
+#define SG_STAGE_TIMER_API(family, times, names)                                                                              \
+    int sg_##family##_set_timing(int on) { (times).timing = on != 0; return SG_OK; }                                         \
+    int sg_##family##_stage_times(float* h_us, int cap) { return (times).copy("sg_" #family "_stage_times", h_us, cap); }    \
+    const char* sg_##family##_stage_name(int i) { return sgos::stage_name(names, i); }
+
 }  // namespace sgos

@@ -450,8 +450,8 @@ def grid_stats(family: str, tail, slots: int = 16) -> dict:
     return out
 
 
-STAGE_FAMILIES = ("overseg", "pcseg", "cloud_thin", "pointcloud_knn_grid", "nearest_point_grid", "components", "radius_grid", "pcseg_radius",
-                  "segment_vote")
+# every family with a per-thread stage timer: the sg_<family>_set_timing(int) of SIGNATURES (the pipeline's and the engine's take a handle)
+STAGE_FAMILIES = tuple(n[3:-len("_set_timing")] for n, sig in SIGNATURES.items() if n.endswith("_set_timing") and sig == (_I, [_I]))
 
 
 @contextlib.contextmanager

@@ -144,6 +144,32 @@ def mesh_arrays(plydata):
 
 
 # ---- device calls -----------------------------------------------------------------------------------------------
+def _two_cloud_grid(name, entry, x, y, ks, dtype, cell, device, stream, want_d2):
+    """One call of a two-cloud grid search `entry(x, xs, U, y, ys, N, *ks, cell, out, d2, ws, bytes, stream)`: the shape check, the
+    workspace, the tensors (rows of `ks` entries, or one value a row) and the sync -> (out, d2 or None)."""
+    import torch
+    edge = hip.knn_cell(cell)
+    dev = torch_device(device)
+    lib = hip.lib()
+    call = getattr(lib, entry)
+    with torch.cuda.device(dev), on_stream(stream):
+        dx, dy = device_tensor(x, torch.float32, dev), device_tensor(y, torch.float32, dev)
+        if dx.dim() != 2 or dy.dim() != 2 or dx.shape[1] < 3 or dy.shape[1] < 3:
+            raise ValueError(f"{name}: x and y must be [*, >= 3]")
+        u, n = int(dx.shape[0]), int(dy.shape[0])
+        sp = stream_ptr(stream)
+        need = getattr(lib, entry + "_ws_bytes")(u, n, *ks)
+        if need == 0:                                               # outside the envelope: the library says why, nothing is allocated
+            hip.check(call(None, int(dx.shape[1]), u, None, int(dy.shape[1]), n, *ks, edge, None, None, None, 0, sp))
+        out = torch.empty((u,) + ks, dtype=getattr(torch, dtype), device=dev)
+        d2 = torch.empty((u,) + ks, dtype=torch.float32, device=dev) if want_d2 else None
+        ws = workspace(need, dev)
+        hip.check(call(dx.data_ptr(), int(dx.shape[1]), u, dy.data_ptr(), int(dy.shape[1]), n, *ks, edge, out.data_ptr(),
+                       d2.data_ptr() if want_d2 else None, ws.data_ptr(), ws.numel(), sp))
+        sync(stream)
+    return out, d2
+
+
 def nearest_grid_stats() -> dict:
     """What the calling thread's last grid-indexed nearest-point search did: cells per axis, occupied cells and the largest
     cell of the candidates' index, the cell edge used, the largest ring count of a query the rings settled, the queries finished against
@@ -155,26 +181,7 @@ def nearest_point_grid(x, y, cell=None, device=None, stream=None, want_d2=True):
     """sg_nearest_point_grid: for every row of x [U, >= 3] the index of its best-scoring row of y [N, >= 3], exactly
     get_unmapper's, from the exact grid index -> (idx int64 [U], d2 float32 [U] or None), device tensors.  `cell` forces the cell edge
     (a performance knob: the result does not depend on it)."""
-    import torch
-    edge = hip.knn_cell(cell)
-    dev = torch_device(device)
-    lib = hip.lib()
-    with torch.cuda.device(dev), on_stream(stream):
-        dx, dy = device_tensor(x, torch.float32, dev), device_tensor(y, torch.float32, dev)
-        if dx.dim() != 2 or dy.dim() != 2 or dx.shape[1] < 3 or dy.shape[1] < 3:
-            raise ValueError("nearest_point_grid: x and y must be [*, >= 3]")
-        u, n = int(dx.shape[0]), int(dy.shape[0])
-        sp = stream_ptr(stream)
-        need = lib.sg_nearest_point_grid_ws_bytes(u, n)
-        if need == 0:                                               # outside the envelope: the library says why, nothing is allocated
-            hip.check(lib.sg_nearest_point_grid(None, int(dx.shape[1]), u, None, int(dy.shape[1]), n, edge, None, None, None, 0, sp))
-        idx = torch.empty(u, dtype=torch.int64, device=dev)
-        d2 = torch.empty(u, dtype=torch.float32, device=dev) if want_d2 else None
-        ws = workspace(need, dev)
-        hip.check(lib.sg_nearest_point_grid(dx.data_ptr(), int(dx.shape[1]), u, dy.data_ptr(), int(dy.shape[1]), n, edge, idx.data_ptr(),
-                                            d2.data_ptr() if want_d2 else None, ws.data_ptr(), ws.numel(), sp))
-        sync(stream)
-    return idx, d2
+    return _two_cloud_grid("nearest_point_grid", "sg_nearest_point_grid", x, y, (), "int64", cell, device, stream, want_d2)
 
 
 def knn_cross_stats() -> dict:
@@ -187,27 +194,7 @@ def knn_cross_grid(x, y, k, cell=None, device=None, stream=None, want_d2=False):
     descending score, the lower index first among equal scores, so column 0 is nearest_point_grid's index -- from the exact grid index
     -> (knn int32 [U, k], d2 float32 [U, k] or None), device tensors.  `cell` forces the cell edge (a performance knob: the result does
     not depend on it)."""
-    import torch
-    edge = hip.knn_cell(cell)
-    k = int(k)
-    dev = torch_device(device)
-    lib = hip.lib()
-    with torch.cuda.device(dev), on_stream(stream):
-        dx, dy = device_tensor(x, torch.float32, dev), device_tensor(y, torch.float32, dev)
-        if dx.dim() != 2 or dy.dim() != 2 or dx.shape[1] < 3 or dy.shape[1] < 3:
-            raise ValueError("knn_cross_grid: x and y must be [*, >= 3]")
-        u, n = int(dx.shape[0]), int(dy.shape[0])
-        sp = stream_ptr(stream)
-        need = lib.sg_cloud_knn_cross_grid_ws_bytes(u, n, k)
-        if need == 0:                                               # outside the envelope: the library says why, nothing is allocated
-            hip.check(lib.sg_cloud_knn_cross_grid(None, int(dx.shape[1]), u, None, int(dy.shape[1]), n, k, edge, None, None, None, 0, sp))
-        knn = torch.empty((u, k), dtype=torch.int32, device=dev)
-        d2 = torch.empty((u, k), dtype=torch.float32, device=dev) if want_d2 else None
-        ws = workspace(need, dev)
-        hip.check(lib.sg_cloud_knn_cross_grid(dx.data_ptr(), int(dx.shape[1]), u, dy.data_ptr(), int(dy.shape[1]), n, k, edge, knn.data_ptr(),
-                                              d2.data_ptr() if want_d2 else None, ws.data_ptr(), ws.numel(), sp))
-        sync(stream)
-    return knn, d2
+    return _two_cloud_grid("knn_cross_grid", "sg_cloud_knn_cross_grid", x, y, (int(k),), "int32", cell, device, stream, want_d2)
 
 
 def get_unmapper(x, y, device=None, index="brute", cell=None):

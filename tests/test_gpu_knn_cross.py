@@ -1,8 +1,9 @@
 """The exact k nearest candidates between two clouds and the vote over them on the GPU: sg_cloud_knn_cross_grid's rows
 EQUAL to the plain statement (tests/knn_cross_ref.brute: the first k columns of a stable descending sort of the score row) on the pairs
 that each catch one mistake, at two forced cells and at the library's; column 0 and its d2 equal to sg_nearest_point_grid's; the wave
-and tile edges, N = k, a cell larger than a staged tile, strides, d2 = NULL; two streams and two cells; every refusal; sg_knn_vote
-against the NumPy rule; and `transfer --vote` on a two-scene tree."""
+and tile edges, N = k, a cell larger than a staged tile, strides, d2 = NULL; two streams and two cells; every refusal; the two query
+policies of the one search kernel against each other (knn_cross_grid(x, x) and the self-kNN); every query of all three entry points
+through the queue at its block edges; sg_knn_vote against the NumPy rule; and `transfer --vote` on a two-scene tree."""
 import json
 import os
 
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 import knn_cross_ref as KC
+import knn_grid_ref as G
 import nearest_grid_ref as NG
 import pcseg_ref as R
 import test_knn_cross_ref as T
@@ -198,6 +200,110 @@ def test_stage_times_and_counted_scores():
     assert t.names == ["box", "probe", "cells", "sort", "table", "search", "fallback"] and all(v >= 0 for v in us) and us[5] > 0
     _equal(got[T._rows(x.shape[0])], T._brute("plain")[:, :10], "a timed call")
     assert 0 < st["scores"] < x.shape[0] * y.shape[0], "fewer pair scores than brute force"
+
+
+# ---- one search kernel under two query policies, one queue kernel ----------------------------------------------------------------
+def _tiny_cloud(n, k, dup=False):
+    rng = np.random.default_rng(1000 * k + n)
+    if dup:                                                     # every point twice: equal scores, the lower index first
+        half = rng.random((n // 2, 3)).astype(np.float32)
+        return np.ascontiguousarray(np.concatenate([half, half], 0))
+    return np.ascontiguousarray(rng.random((n, 3)).astype(np.float32))
+
+
+@pytest.mark.parametrize("k", KC.KS)
+def test_the_two_query_policies_agree(k):
+    """knn_cross_grid(x, x, k) and the self-kNN's first k columns are the first columns of the same stable sort of the same score row:
+    equal as integers at every size, with every point duplicated, at a cell of several rings and at one cell over the cloud"""
+    from seggroup_amd import oversegment, prepare
+    clouds = [(f"N = {n}", _tiny_cloud(n, k)) for n in (k + 1, 63, 64, 65, 257)] + [("dup, N = 130", _tiny_cloud(130, k, dup=True))]
+    for what, x in clouds:
+        want = KC.brute(x, x, k)
+        for cell in (0.1, 1000.0):
+            own = prepare.pointcloud_knn(x, k, device=DEV, index="grid", cell=cell).cpu().numpy()
+            st_own = oversegment.knn_grid_stats()
+            cross, _, st = _cross(x, x, k, cell=cell)
+            assert own.dtype == np.int32 and own.shape == (x.shape[0], k + 1)
+            _equal(cross, np.ascontiguousarray(own[:, :k]), f"{what}, k = {k}, cell = {cell}: the two-cloud rows against the self-kNN's")
+            _equal(cross, want, f"{what}, k = {k}, cell = {cell}: against the plain statement")
+            assert st["cells"] == st_own["cells"] and st["cell"] == st_own["cell"] == np.float32(cell)
+            if cell == 0.1 and x.shape[0] == 257:
+                assert st["max_ring"] > 1 and st_own["max_ring"] > 1, "several rings"
+        assert st["cells"] == (1, 1, 1) and st["fallback"] == 0
+
+
+LATTICE_CELL = 0.01
+
+
+def _lattice():
+    """7 x 7 x 7 candidates of spacing 0.1, and the queries half a spacing off on every axis: at a cell of 0.01 a ring-1 block (0.03 wide)
+    holds one candidate at most round a candidate and none round a query"""
+    if "lattice" not in _rooms:
+        a = (np.arange(7) * 0.1).astype(np.float32)
+        y = np.ascontiguousarray(np.stack(np.meshgrid(a, a, a, indexing="ij"), -1).reshape(-1, 3))
+        _rooms["lattice"] = (np.ascontiguousarray(y + np.float32(0.05)), y)
+    return _rooms["lattice"]
+
+
+class _ring_limit_one:
+    """set_tuning(0, 1) for the three entry points, the defaults again afterwards whatever happens"""
+
+    FAMILIES = ("pointcloud_knn_grid", "nearest_point_grid", "cloud_knn_cross_grid")
+
+    def _set(self, limit):
+        from seggroup_amd import hip
+        for f in self.FAMILIES:
+            assert getattr(hip.lib(), f"sg_{f}_set_tuning")(0, limit) == hip.SG_OK
+
+    def __enter__(self):
+        self._set(1)
+
+    def __exit__(self, *exc):
+        self._set(0)
+
+
+QUEUE_EDGES = [1, 255, 256, 257]
+
+
+@pytest.mark.parametrize("u", QUEUE_EDGES)
+def test_every_query_through_the_queue_two_clouds(u):
+    """ring limit 1: no list fills and the one-entry search sees no candidate, so every row is the queue kernel's (the nearest point:
+    sg_nearest_point's kernel) -- at one query, and one block of 256 less one, full, and one more"""
+    from seggroup_amd import prepare
+    shifted, y = _lattice()
+    x = np.ascontiguousarray(shifted[:u])
+    want1, rings, _ = NG.nearest_grid(x, y, LATTICE_CELL, ring_limit=1)
+    assert (rings == 0).all() and np.array_equal(want1, NG.brute(x, y)), "the statement queues every query"
+    with _ring_limit_one():
+        idx, d2 = prepare.nearest_point_grid(x, y, cell=LATTICE_CELL, device=DEV)
+        st = prepare.nearest_grid_stats()
+        assert st["fallback"] == u and st["max_ring"] == 0, st
+        idx, d2 = idx.cpu().numpy(), d2.cpu().numpy()
+        assert idx.dtype == np.int64 and np.array_equal(idx, want1)
+        assert d2.dtype == np.float32 and d2.tobytes() == NG.d2_of(x, y, want1).tobytes(), "d2 bit for bit"
+        for k in KC.KS:
+            want, rings, grid = KC.knn_cross_grid(x, y, k, LATTICE_CELL, ring_limit=1)
+            assert (rings == 0).all() and np.array_equal(want, grid.whole) and np.array_equal(want, KC.brute(x, y, k))
+            got, d2, st = _cross(x, y, k, cell=LATTICE_CELL, want_d2=True)
+            assert st["fallback"] == u and st["max_ring"] == 0, (k, st)
+            _equal(got, want, f"U = {u}, k = {k}: the queue's rows")
+            assert d2.dtype == np.float32 and d2.tobytes() == KC.d2_of(x, y, want).tobytes(), "d2 bit for bit"
+            assert np.array_equal(got[:, 0].astype(np.int64), want1)
+
+
+@pytest.mark.parametrize("n", [255, 256, 257, 343])
+def test_every_query_through_the_queue_self(n):
+    """the self-kNN on the first n lattice points: a ring-1 block holds the point alone, a list of k + 1 never fills"""
+    from seggroup_amd import oversegment, prepare
+    x = np.ascontiguousarray(_lattice()[1][:n])
+    with _ring_limit_one():
+        for k in KC.KS:
+            want, rings, _ = G.knn_table_grid(x, k, LATTICE_CELL, ring_limit=1)
+            assert (rings == 0).all() and np.array_equal(want, G.brute_rows(x, np.arange(n), k)), "the statement queues every point"
+            got = prepare.pointcloud_knn(x, k, device=DEV, index="grid", cell=LATTICE_CELL).cpu().numpy()
+            st = oversegment.knn_grid_stats()
+            assert st["fallback"] == n and st["max_ring"] == 0, (k, st)
+            _equal(got, want, f"N = {n}, k = {k}: the queue's rows")
 
 
 # ---- the vote ---------------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The stage timers of the cloud tools without a GPU: nine families export sg_*_set_timing, sg_*_stage_times and sg_*_stage_name over one
+"""The stage timers of the cloud tools without a GPU: every family exports sg_*_set_timing, sg_*_stage_times and sg_*_stage_name over one
 piece of plumbing (overseg_device.h's StageTimes), and each keeps the same contract -- the refusals name the family's own function, the
 names are the ones the tools and profiles print, in order, and nothing outside 0 .. stages - 1 has a name.  No device call is made."""
 import ctypes as C
@@ -15,9 +15,11 @@ FAMILIES = {
     "cloud_thin": ("check_box", "keys", "sort", "representatives", "compact", "map"),
     "pointcloud_knn_grid": ("box", "probe", "cells", "sort", "table", "search", "fallback"),
     "nearest_point_grid": ("box", "probe", "cells", "sort", "table", "search", "fallback"),
+    "cloud_knn_cross_grid": ("box", "probe", "cells", "sort", "table", "search", "fallback"),
     "components": ("init", "hook", "flatten", "sizes"),
     "radius_grid": ("box", "cells", "sort", "table", "init", "search", "finish"),
     "segment_vote": ("check", "rank_sort", "rank_unique", "pair_sort", "pair_unique", "arg_max", "vertex_gather"),
+    "segment_graph": ("keys", "sort", "unique", "emit"),
 }
 
 
@@ -53,8 +55,14 @@ class _Recorded:
         return lambda on: (self.switched.append((name, on)), fn(on))[1]
 
 
-def test_the_reader_covers_the_nine_families():
-    assert sorted(hip.STAGE_FAMILIES) == sorted(FAMILIES)
+def test_the_reader_covers_every_family():
+    """the library's set is read off hip.SIGNATURES (the timers a thread switches with one int), so a family without an entry here fails"""
+    exported = sorted(n[len("sg_"):-len("_set_timing")] for n, (_, args) in hip.SIGNATURES.items()
+                      if n.endswith("_set_timing") and args == [C.c_int])
+    assert exported == sorted(FAMILIES)
+    assert sorted(hip.STAGE_FAMILIES) == exported
+    for family in exported:
+        assert all(f"sg_{family}_{f}" in hip.SIGNATURES for f in ("stage_times", "stage_name"))
 
 
 @pytest.mark.parametrize("family", sorted(FAMILIES))
