@@ -992,6 +992,44 @@ int sg_align_moments(const float* d_x, int x_stride, int U, const float* d_y, in
                      float max_d2, const double* h_origin_x, const double* h_origin_y, double* h_out, void* d_ws, size_t ws_bytes, void* stream);
 int sg_align_solve(const double* h_m, const double* h_origin_x, const double* h_origin_y, double* h_T);
 
+/* Point-to-plane ICP: the two pieces that replace sg_align_moments / sg_align_solve when the fixed cloud has normals.
+ *
+ * sg_align_plane_moments: the 31 sums of one Gauss-Newton step on the point-to-plane residual.  d_x [U, x_stride >= 3] is the ORIGINAL
+ *   moving cloud, h_T the row-major 3x4 [R|t] of the current pose, d_y [N, y_stride >= 3] the fixed cloud, d_n [N, n_stride >= 3] its fp32
+ *   normals, d_idx / d_d2 the search's answer for the moved cloud.  A pair u is a candidate when d2[u] <= max_d2 (fp32 compare; max_d2 may
+ *   be +inf; a NaN in d2 is never a candidate).  For a candidate, in double, every operation rounded once in the order written, no
+ *   contraction:
+ *     p[r] = ((R[r][0]*x + R[r][1]*y) + R[r][2]*z) + t[r]        (sg_rigid_apply's statement without its final rounding to fp32)
+ *     a = p - h_origin;  b = (double)y[idx[u]] - h_origin;  n = (double)d_n[idx[u]]
+ *     usable: 0.25 <= (n0*n0 + n1*n1) + n2*n2 <= 4, which a NaN or an infinite component fails; a normal is not re-normalised
+ *     e = a - b;  r = (e0*n0 + e1*n1) + e2*n2
+ *     J = [ a1*n2 - a2*n1,  a2*n0 - a0*n2,  a0*n1 - a1*n0,  n0, n1, n2 ]
+ *   h_out:  [0] usable candidates (exact) | [1] candidates whose normal is not usable (exact) | [2..22] upper triangle of sum J J^T,
+ *   row-major | [23..28] sum J r | [29] sum r r | [30] sum (double)d2 over the usable candidates.  Deterministic exactly as sg_align_moments
+ *   is: no floating-point atomics, cdiv(U, 1024) workgroups of 256 threads, thread t takes pairs t, t + 256, t + 512, t + 768 of its block
+ *   in that order, wave_ops.h's network, the four waves added in order into one partial row, one folding workgroup over the rows (thread t
+ *   takes rows t, t + 256, .. in order): launch shape and both trees depend on U alone, so two calls on the same input write the same
+ *   31 x 8 bytes on any device and stream.  0 <= U <= SG_MAX_CLOUD_POINTS, 1 <= N <= SG_MAX_CLOUD_POINTS (above: SG_EUNSUP); U = 0 writes 31
+ *   zeros and touches no device memory.  SG_EINVAL: null pointers, a stride below 3, U < 0, N < 1, max_d2 NaN, an entry of h_T or of
+ *   h_origin that is not finite, a workspace below sg_align_plane_moments_ws_bytes(U) (0 outside the envelope) -- all before the first
+ *   device call --, an entry of d_idx outside 0..N-1, candidate or not, usable or not (checked on the device before anything reads through
+ *   it; h_out is then not written).  Synchronises the stream once; the sums and the flag come back in one copy.
+ *
+ * sg_align_plane_solve: host only, no device call.  h_m is sg_align_plane_moments' h_out for the same h_origin and the same h_T (row-major
+ *   3x4; the first three rows of a 4x4 serve).  With M = sum J J^T, g = sum J r and D = diag(1/length, 1/length, 1/length, 1, 1, 1) --
+ *   `length` > 0 puts the rotational columns into length units -- D M D = V diag(lambda) V^T by cyclic Jacobi, and the step is
+ *   s = -D V diag(1/lambda) V^T D g = (w, v).  Rw is Rodrigues' rotation of angle |w| about w (sin and cos from their series below 1e-8
+ *   rad); the step acts about the origin: R_new = Rw R, t_new = Rw (t - origin) + origin + v; R_new is re-orthonormalised (Gram-Schmidt
+ *   on rows 0 and 1, row 2 their cross product).  h_T_new receives the row-major 4x4 (last row 0 0 0 1), h_step -- may be null -- the six
+ *   values (w, v).  SG_EINVAL: null pointers, a moment, origin, `length` or entry of h_T that is not finite, length <= 0, n negative.
+ *   SG_EUNSUP with a message that says "degenerate": n < 6, lambda_max <= 0, or lambda_min <= 2^-40 lambda_max (one plane, parallel
+ *   planes, two plane directions: some motion leaves every residual unchanged). */
+size_t sg_align_plane_moments_ws_bytes(int U);
+int sg_align_plane_moments(const float* d_x, int x_stride, int U, const double* h_T, const float* d_y, int y_stride, int N, const float* d_n,
+                           int n_stride, const int64_t* d_idx, const float* d_d2, float max_d2, const double* h_origin, double* h_out, void* d_ws,
+                           size_t ws_bytes, void* stream);
+int sg_align_plane_solve(const double* h_m, const double* h_origin, double length, const double* h_T, double* h_T_new, double* h_step);
+
 /* Connected components of a scan's graph.  Vertices 0..V-1, 1 <= V <= SG_MAX_CLOUD_POINTS; the undirected graph comes from
  * one of three sources:
  *   sg_components_edges  d_edges int32 [E,2], 0 <= E < 2^30: a row (a, a) is a no-op, duplicates and both orientations are allowed, no order

@@ -1,4 +1,4 @@
-"""Rigid alignment of two clouds of one scene: point-to-point ICP on the exact grid index.
+"""Rigid alignment of two clouds of one scene: point-to-point and point-to-plane ICP on the exact grid index.
 
 `transfer`, `transfer --vote` and `thin --lift` assume that both geometries are in one frame.  A photogrammetry cloud beside a laser scan,
 a re-export in a slightly different pose or a rescan after a coarse manual registration are centimetres to decimetres off; this module
@@ -9,15 +9,24 @@ alone) and `sg_align_solve` is Kabsch on the host.  Every iteration fits the ORI
 composed and nothing drifts; the loop ends when the correspondences and the inlier set repeat (a fixed point of the data, not a
 tolerance) or when the fit no longer moves the cloud's box by `min_delta`.
 
+Rooms are floors, walls and furniture faces, and on those point-to-point pairs slide along the planes.  `metric="plane"`
+minimises the distance to the FIXED cloud's tangent planes instead: the search is the same, `sg_align_plane_moments` folds the candidate
+pairs into the 31 sums of one Gauss-Newton step (the same deterministic trees), `sg_align_plane_solve` solves the 6x6 system on the host
+and composes the step onto T.  The fixed cloud's normals are the caller's, or `oversegment.pointcloud_normals` over the grid kNN.
+
     python -m seggroup_amd.align --moving-scans A --fixed-scans B --max-dist D --out DIR
-                                 [--init DIR] [--max-iter 50] [--scenes FILE] [--workers W] [--device D]
+                                 [--init DIR] [--max-iter 50] [--metric {point,plane}] [--normals-k K] [--scenes FILE] [--workers W]
+                                 [--device D]
         for every scene present in both trees: DIR/<scene>.align.json (T as 4 rows of 4, mapping A's coordinates into B's frame, the
         Alignment's scalars, both vertex counts and max_dist) and one DIR/align_report.json.  --init DIR: start from the T of
-        DIR/<scene>.align.json (a file of the same form; only T is read).  `transfer --align DIR` reads these files.
+        DIR/<scene>.align.json (a file of the same form; only T is read).  `transfer --align DIR` reads these files.  --metric plane:
+        the fixed scan's normals come from its faces (`oversegment.vertex_normals`) when its PLY has any, else from the covariance of
+        its --normals-k (default 10) nearest points; the files then also hold metric, normals ("faces" | "knn-K"), skipped,
+        plane_rms_before and plane_rms_after.
 
-Not here, on purpose: point-to-plane, trimmed fractions, robust weights, scale, and any global (init-free) registration.  This is
-point-to-point ICP with a fixed inlier radius: it refines a pose that is already inside its basin, and takes an initial transform for
-everything else.  `max_dist` has no default: like `--max-edge` it depends on the scan's unit and on how wrong the pose may be.
+Not here, on purpose: trimmed fractions, robust weights, scale, and any global (init-free) registration.  This is ICP with a fixed
+inlier radius: it refines a pose that is already inside its basin, and takes an initial transform for everything else.  `max_dist` has
+no default: like `--max-edge` it depends on the scan's unit and on how wrong the pose may be.
 """
 from __future__ import annotations
 
@@ -37,6 +46,8 @@ from .prepare import mesh_arrays, nearest_point_grid, read_ply
 ALIGN_SUFFIX = ".align.json"
 REPORT_NAME = "align_report.json"
 SCALARS = ("iterations", "converged", "inliers", "rms_before", "rms_after", "rotation_deg", "translation")
+PLANE_SCALARS = ("metric", "skipped", "plane_rms_before", "plane_rms_after")     # what metric="plane" adds to them
+METRICS = ("point", "plane")
 
 
 @dataclass
@@ -44,7 +55,10 @@ class Alignment:
     """What icp returns.  `T` [4,4] float64 maps MOVING coordinates into the FIXED cloud's frame; `converged` is "fixed point" (the
     correspondences and the inlier set repeated), "min_delta" (the last fit moved the box by no more than min_delta) or False (max_iter
     searches); `rms_before` / `rms_after` are sqrt(sum d2 / n) over the inliers of the first / the last search (the last search ran at
-    the pose before a final sub-min_delta update); `idx`, `d2`, `inlier` are the last search's device tensors."""
+    the pose before a final sub-min_delta update); `idx`, `d2`, `inlier` are the last search's device tensors.  With metric="plane"
+    (never "fixed point" there) `inliers` counts the candidates with a usable normal, `skipped` those without at the last search, and
+    `plane_rms_before` / `plane_rms_after` are sqrt(sum r^2 / n) of the point-to-plane residual at the first / the last search; a
+    point-to-point Alignment and its scalars() carry none of these."""
     T: np.ndarray
     iterations: int
     converged: object
@@ -56,9 +70,13 @@ class Alignment:
     idx: object = None
     d2: object = None
     inlier: object = None
+    metric: str = "point"
+    skipped: object = None
+    plane_rms_before: object = None
+    plane_rms_after: object = None
 
     def scalars(self) -> dict:
-        return {k: getattr(self, k) for k in SCALARS}
+        return {k: getattr(self, k) for k in SCALARS + (PLANE_SCALARS if self.metric == "plane" else ())}
 
 
 def as_transform(T, who: str = "align") -> np.ndarray:
@@ -139,6 +157,53 @@ def solve(m, origin_x=None, origin_y=None) -> np.ndarray:
     return T
 
 
+def plane_moments(x, T, y, normals, idx, d2, max_dist, origin=None, device=None, stream=None) -> np.ndarray:
+    """sg_align_plane_moments over the pairs (T x[u], y[idx[u]]) with d2[u] <= (float32)(max_dist * max_dist) -> float64 [31]:
+    usable | skipped | upper triangle of sum J J^T [21] | sum J r [6] | sum r r | sum d2, with a = T x - origin, b = y - origin,
+    n = normals[idx[u]], r = (a - b) . n and J = [a x n, n] in double (origin defaults to 0).  x is the ORIGINAL moving cloud; `normals`
+    [N, >= 3] belong to y.  A candidate whose normal is not finite or has a squared length outside 0.25..4 is counted in [1] and adds
+    nothing else.  Deterministic: the same input gives the same bytes.  An index outside 0..N-1 is a ValueError."""
+    import torch
+    T = np.ascontiguousarray(as_transform(T, "plane_moments")[:3])
+    o = _vec3(origin, "plane_moments")
+    max_d2 = float(np.float32(float(max_dist) * float(max_dist)))
+    dev = torch_device(device)
+    lib = hip.lib()
+    out = np.zeros(31, np.float64)
+    with torch.cuda.device(dev), on_stream(stream):
+        d_x, d_y, d_n = _rows(x, dev, "plane_moments"), _rows(y, dev, "plane_moments"), _rows(normals, dev, "plane_moments")
+        d_idx, d_d2 = device_tensor(idx, torch.int64, dev), device_tensor(d2, torch.float32, dev)
+        u = int(d_x.shape[0])
+        if d_idx.shape != (u,) or d_d2.shape != (u,):
+            raise ValueError("plane_moments: idx and d2 hold one entry per row of x")
+        if d_n.shape[0] != d_y.shape[0]:
+            raise ValueError("plane_moments: one normal per row of y (%d normals, %d points)" % (d_n.shape[0], d_y.shape[0]))
+        ws = workspace(lib.sg_align_plane_moments_ws_bytes(u), dev)
+        hip.check_arg(lib.sg_align_plane_moments(d_x.data_ptr(), int(d_x.shape[1]), u, T.ctypes.data, d_y.data_ptr(), int(d_y.shape[1]),
+                                                 int(d_y.shape[0]), d_n.data_ptr(), int(d_n.shape[1]), d_idx.data_ptr(), d_d2.data_ptr(), max_d2,
+                                                 o.ctypes.data, out.ctypes.data, ws.data_ptr(), ws.numel(), stream_ptr(stream)))
+        sync(stream)
+    return out
+
+
+def plane_solve(m, T, origin, length) -> np.ndarray:
+    """sg_align_plane_solve (host only, runs without a GPU): the 31 moments taken at the pose T about `origin` -> T_new float64 [4,4], T
+    with one Gauss-Newton step of the point-to-plane fit composed onto it (rotation re-orthonormalised).  `length` > 0 scales the
+    rotational unknowns into length units for the degeneracy rule.  Fewer than 6 usable pairs, or planes that leave a motion free, raise
+    hip.SgError (SG_EUNSUP, "degenerate"); a non-finite moment, origin, length or T is a ValueError."""
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    if m.shape != (31,):
+        raise ValueError("plane_solve: 31 moments")
+    T34 = np.asarray(T, dtype=np.float64)
+    if T34.shape not in ((4, 4), (3, 4)):
+        raise ValueError("plane_solve: a transform is a [4,4] (or [3,4]) matrix")
+    T34 = np.ascontiguousarray(T34[:3])
+    o = _vec3(origin, "plane_solve")
+    out = np.zeros((4, 4))
+    hip.check_arg(hip.lib().sg_align_plane_solve(m.ctypes.data, o.ctypes.data, float(length), T34.ctypes.data, out.ctypes.data, None))
+    return out
+
+
 def box_corners(lo, hi) -> np.ndarray:
     """the 8 corners of the box lo..hi -> float64 [8,3]"""
     lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
@@ -156,8 +221,8 @@ def rotation_deg(T) -> float:
 
 
 def icp(moving_xyz, fixed_xyz, max_dist, init=None, max_iter: int = 50, min_delta=None, index: str = "grid", device=None,
-        stream=None) -> Alignment:
-    """Point-to-point ICP with a fixed inlier radius -> Alignment; T maps MOVING coordinates into the FIXED cloud's frame.
+        stream=None, metric: str = "point", normals=None, normals_k: int = 10) -> Alignment:
+    """ICP with a fixed inlier radius -> Alignment; T maps MOVING coordinates into the FIXED cloud's frame.  metric="point":
 
         T = init or identity
         repeat up to max_iter times:
@@ -171,8 +236,24 @@ def icp(moving_xyz, fixed_xyz, max_dist, init=None, max_iter: int = 50, min_delt
 
     `min_delta` defaults to one fp32 ulp of the largest absolute coordinate of either cloud (2^-23 max|c|): below it the moved fp32 points
     cannot change by more than their own rounding.  No inliers, or a degenerate fit (fewer than 3 pairs, pairs on a line), is a
-    ValueError that names max_dist."""
+    ValueError that names max_dist.
+
+    metric="plane" (DESIGN.md 8q): `normals` is the FIXED cloud's [N, >= 3] array, or None for pointcloud_normals(fixed, normals_k) over
+    the grid kNN, computed once before the loop; c is the fixed box's centre and L half its diagonal:
+
+        repeat up to max_iter times:
+            p       = apply(moving, T);  idx, d2 = nearest_point_grid(p, fixed);  inlier = d2 <= (float32)(max_dist * max_dist)
+            T_new   = plane_solve(plane_moments(moving, T, fixed, normals, idx, d2, max_dist, c), T, c, L)
+            the moving box's 8 corners move by <= min_delta between T and T_new: T = T_new, converged = "min_delta", stop
+            T = T_new
+
+    There is no "fixed point" rule: a Gauss-Newton step is not closed-form, so repeated pairs do not imply a zero step.  No usable
+    candidate, or planes that leave a motion free, is a ValueError that names max_dist (the latter also "plane")."""
     import torch
+    if metric not in METRICS:
+        raise ValueError("icp: metric must be 'point' or 'plane', not %r" % (metric,))
+    if metric == "point" and normals is not None:
+        raise ValueError("icp: normals belong to metric='plane'; point-to-point ICP does not use them")
     if index != "grid":
         raise ValueError("icp: the search runs through the grid index only (index='grid'), not %r" % (index,))
     max_dist = float(max_dist)
@@ -186,6 +267,10 @@ def icp(moving_xyz, fixed_xyz, max_dist, init=None, max_iter: int = 50, min_delt
         d_mov, d_fix = _rows(moving_xyz, dev, "icp"), _rows(fixed_xyz, dev, "icp")
         if d_mov.shape[0] < 1 or d_fix.shape[0] < 1:
             raise ValueError("icp: a cloud needs at least one point")
+        if normals is not None:
+            normals = _rows(normals, dev, "icp: normals")
+            if normals.shape[0] != d_fix.shape[0]:
+                raise ValueError("icp: one normal per point of the FIXED cloud (%d normals, %d points)" % (normals.shape[0], d_fix.shape[0]))
         box = [(c[:, :3].min(0).values.double().cpu().numpy(), c[:, :3].max(0).values.double().cpu().numpy()) for c in (d_mov, d_fix)]
     if not all(np.isfinite(b).all() for lo_hi in box for b in lo_hi):
         raise ValueError("icp: a coordinate that is not finite")
@@ -195,6 +280,9 @@ def icp(moving_xyz, fixed_xyz, max_dist, init=None, max_iter: int = 50, min_delt
     if min_delta is None:
         min_delta = 2.0 ** -23 * float(max(np.abs(b).max() for lo_hi in box for b in lo_hi))
     max_d2 = float(np.float32(max_dist * max_dist))
+    if metric == "plane":
+        return _icp_plane(d_mov, d_fix, normals, int(normals_k), max_dist, max_d2, T, int(max_iter), min_delta, corners, origin_f,
+                          0.5 * float(np.sqrt(((fhi - flo) ** 2).sum())), dev, stream)
     prev = None
     converged = False
     rms_before = rms_after = None
@@ -233,6 +321,63 @@ def icp(moving_xyz, fixed_xyz, max_dist, init=None, max_iter: int = 50, min_delt
                      rotation_deg=rotation_deg(T), translation=[float(v) for v in T[:3, 3]], idx=idx, d2=d2, inlier=inlier)
 
 
+def fixed_normals(fixed_xyz, k: int = 10, device=None):
+    """the normals metric="plane" uses when the caller has none -> float32 [N,3] device tensor: oversegment.pointcloud_normals over the
+    exact grid kNN-k of the cloud itself"""
+    from .oversegment import pointcloud_normals
+    from .prepare import pointcloud_knn
+    if int(k) < 3:
+        raise ValueError("icp: normals_k must be at least 3 (a plane through fewer neighbours has no normal)")
+    import torch
+    dev = torch_device(device)
+    with torch.cuda.device(dev):
+        xyz = device_tensor(fixed_xyz, torch.float32, dev)[:, :3].contiguous()
+    return pointcloud_normals(xyz, int(k), knn=pointcloud_knn(xyz, int(k), device=dev, index="grid"), device=dev)
+
+
+def _icp_plane(d_mov, d_fix, normals, normals_k, max_dist, max_d2, T, max_iter, min_delta, corners, centre, length, dev, stream) -> Alignment:
+    """icp's metric="plane" loop; the arguments are icp's, checked and on the device"""
+    import torch
+    if normals is None:
+        normals = fixed_normals(d_fix, normals_k, device=dev)
+    if not length > 0.0:
+        raise ValueError("icp: the fixed cloud is a single point; metric='plane' needs planes (max_dist = %g)" % max_dist)
+    converged = False
+    first = None
+    iterations = 0
+    for _ in range(max_iter):
+        moved = apply(d_mov, T, device=dev, stream=stream)
+        idx, d2 = nearest_point_grid(moved, d_fix, device=dev, stream=stream)
+        with torch.cuda.device(dev), on_stream(stream):
+            inlier = d2 <= max_d2
+        iterations += 1
+        m = plane_moments(d_mov, T, d_fix, normals, idx, d2, max_dist, centre, device=dev, stream=stream)
+        n, skipped = int(m[0]), int(m[1])
+        if n == 0:
+            if skipped:
+                raise ValueError("icp: every pair within max_dist = %g was skipped for its normal (%d pairs: the fixed cloud's normals there "
+                                 "are zero, not finite or far from unit length)" % (max_dist, skipped))
+            raise ValueError("icp: no point of the moving cloud has a fixed point within max_dist = %g -- a larger max_dist, or an initial "
+                             "transform (init=, --init) that brings the clouds closer" % max_dist)
+        last = (math.sqrt(m[30] / n), math.sqrt(m[29] / n))
+        if first is None:
+            first = last
+        try:
+            T_new = plane_solve(m, T, centre, length)
+        except hip.SgError as e:
+            if e.code != hip.SG_EUNSUP:
+                raise
+            raise ValueError("icp: the %d pairs within max_dist = %g do not determine a point-to-plane pose (%s)" % (n, max_dist, e)) from None
+        shift = corner_shift(corners, T, T_new)
+        T = T_new
+        if shift <= min_delta:
+            converged = "min_delta"
+            break
+    return Alignment(T=T, iterations=iterations, converged=converged, inliers=n, rms_before=first[0], rms_after=last[0],
+                     rotation_deg=rotation_deg(T), translation=[float(v) for v in T[:3, 3]], idx=idx, d2=d2, inlier=inlier, metric="plane",
+                     skipped=skipped, plane_rms_before=first[1], plane_rms_after=last[1])
+
+
 # ---- files --------------------------------------------------------------------------------------------------------------------------
 def align_path(directory: str, scene: str) -> str:
     return os.path.join(directory, scene + ALIGN_SUFFIX)
@@ -248,8 +393,11 @@ def read_align(path: str) -> dict:
     return doc
 
 
-def write_align(path: str, al: Alignment, moving_v: int, fixed_v: int, max_dist: float) -> dict:
+def write_align(path: str, al: Alignment, moving_v: int, fixed_v: int, max_dist: float, normals=None) -> dict:
+    """`normals`: where a plane Alignment's normals came from ("faces" | "knn-K"); a point-to-point file has no such key"""
     doc = dict(al.scalars(), T=[[float(v) for v in row] for row in al.T], moving_V=int(moving_v), fixed_V=int(fixed_v), max_dist=float(max_dist))
+    if normals is not None:
+        doc["normals"] = normals
     scans.write_report(path, doc)
     return doc
 
@@ -258,22 +406,50 @@ def _scan_xyz(scans_dir: str, scene: str):
     return mesh_arrays(read_ply(os.path.join(scans_dir, scene, scene + scans.PLY_SUFFIX)))[0]
 
 
+def scan_normals(xyz, faces, k: int = 10, device=None):
+    """the normals of a scan as the FIXED cloud of metric="plane" -> (float32 [V,3] device tensor, "faces" | "knn-K"): from its faces
+    (oversegment.vertex_normals; a vertex without a face gets zeros, which the fit skips) when it has any, else from the kNN covariance"""
+    if faces is not None and len(faces):
+        from .oversegment import vertex_normals
+        return vertex_normals(xyz, faces, device=device), "faces"
+    return fixed_normals(xyz, k, device=device), "knn-%d" % int(k)
+
+
+def check_metric(metric, normals_k) -> None:
+    """the combinations of metric and normals_k that are refused before anything runs (ValueError)"""
+    if metric not in METRICS:
+        raise ValueError("--metric (metric=) must be 'point' or 'plane', not %r" % (metric,))
+    if normals_k is not None:
+        if metric != "plane":
+            raise ValueError("--normals-k (normals_k=) needs --metric plane (metric='plane'): point-to-point ICP uses no normals")
+        if int(normals_k) < 3:
+            raise ValueError("--normals-k (normals_k=) must be at least 3")
+
+
 def align_scene(scene: str, moving_scans: str, fixed_scans: str, max_dist: float, out_dir: str, init_dir=None, max_iter: int = 50, device=None,
-                stream=None) -> dict:
+                stream=None, metric: str = "point", normals_k=None) -> dict:
     """One scene: <moving_scans>/<scene> onto <fixed_scans>/<scene> -> its entry of align_report.json; writes <out_dir>/<scene>.align.json"""
+    check_metric(metric, normals_k)
     init = read_align(align_path(init_dir, scene))["T"] if init_dir else None
-    mov, fix = _scan_xyz(moving_scans, scene), _scan_xyz(fixed_scans, scene)
-    al = icp(mov, fix, max_dist, init=init, max_iter=max_iter, device=device, stream=stream)
+    mov = _scan_xyz(moving_scans, scene)
+    fix, _, faces = mesh_arrays(read_ply(os.path.join(fixed_scans, scene, scene + scans.PLY_SUFFIX)))
+    if metric == "plane":
+        nrm, how = scan_normals(fix, faces, 10 if normals_k is None else normals_k, device=device)
+        al = icp(mov, fix, max_dist, init=init, max_iter=max_iter, device=device, stream=stream, metric="plane", normals=nrm)
+    else:
+        how = None
+        al = icp(mov, fix, max_dist, init=init, max_iter=max_iter, device=device, stream=stream)
     os.makedirs(out_dir, exist_ok=True)
-    doc = write_align(align_path(out_dir, scene), al, mov.shape[0], fix.shape[0], max_dist)
+    doc = write_align(align_path(out_dir, scene), al, mov.shape[0], fix.shape[0], max_dist, normals=how)
     del doc["T"]
     return doc
 
 
 def align_scans(moving_scans: str, fixed_scans: str, max_dist: float, out_dir: str, init_dir=None, max_iter: int = 50, scenes=None,
-                workers: int = 4, device=None):
+                workers: int = 4, device=None, metric: str = "point", normals_k=None):
     """Every scene that both trees hold (or the named ones) -> (report {scene: entry}, missing {scene: why}); writes
-    <out_dir>/align_report.json.  Workers are threads, each with its own stream."""
+    <out_dir>/align_report.json.  Workers are threads, each with its own stream.  `metric`, `normals_k`: align_scene's."""
+    check_metric(metric, normals_k)
     dev = torch_device(device)
     have_m, have_f = set(scans.scan_names(moving_scans)), set(scans.scan_names(fixed_scans))
     if scenes is None:
@@ -289,10 +465,13 @@ def align_scans(moving_scans: str, fixed_scans: str, max_dist: float, out_dir: s
         else:
             todo.append(s)
     report = dict(scans.map_scans(todo, workers, dev, lambda scene, stream: align_scene(scene, moving_scans, fixed_scans, max_dist, out_dir,
-                                                                                        init_dir, max_iter, device=dev, stream=stream)))
+                                                                                        init_dir, max_iter, device=dev, stream=stream,
+                                                                                        metric=metric, normals_k=normals_k)))
     os.makedirs(out_dir, exist_ok=True)
-    scans.write_report(os.path.join(out_dir, REPORT_NAME), {"max_dist": float(max_dist), "max_iter": int(max_iter), "scenes": report,
-                                                            "missing": missing})
+    head = {"max_dist": float(max_dist), "max_iter": int(max_iter)}
+    if metric == "plane":
+        head["metric"] = metric
+    scans.write_report(os.path.join(out_dir, REPORT_NAME), dict(head, scenes=report, missing=missing))
     return report, missing
 
 
@@ -304,6 +483,10 @@ def main(argv=None) -> int:
     ap.add_argument("--out", required=True, help="the directory that receives <scene>.align.json and align_report.json")
     ap.add_argument("--init", default=None, help="a directory of <scene>.align.json files whose T the search starts from")
     ap.add_argument("--max-iter", type=int, default=50, help="searches at most (default 50)")
+    ap.add_argument("--metric", choices=METRICS, default="point",
+                    help="point: point-to-point (the default); plane: point-to-plane on the fixed scan's normals (its faces, else its kNN covariance)")
+    ap.add_argument("--normals-k", type=int, default=None, metavar="K",
+                    help="the neighbours of the kNN covariance normals of a face-less fixed scan (--metric plane only; default 10)")
     ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
     scans.add_workers_argument(ap)
     ap.add_argument("--device", default=None)
@@ -312,8 +495,12 @@ def main(argv=None) -> int:
     if not a.max_dist > 0.0 or a.max_iter < 1:
         ap.error("--max-dist must be > 0 and --max-iter at least 1")
     try:
+        check_metric(a.metric, a.normals_k)
+    except ValueError as e:
+        ap.error(str(e))
+    try:
         report, missing = align_scans(a.moving_scans, a.fixed_scans, a.max_dist, a.out, a.init, a.max_iter, scans.scene_list(a.scenes),
-                                      a.workers, a.device)
+                                      a.workers, a.device, metric=a.metric, normals_k=a.normals_k)
     except ValueError as e:
         if "max_dist" not in str(e):
             raise

@@ -10,6 +10,12 @@
 // is V diag(1, 1, d) U^T whatever the signs of u3 and v3 (u3 = det(U) u1 x u2, v3 = det(V) v1 x v2), so a reflection is corrected by
 // flipping the smallest singular direction without ever normalising a third column that may be zero (a planar set).  Both pairs are
 // re-orthonormalised (Gram-Schmidt) first, so R^T R - I stays at a few units of the last place.
+//
+// Point-to-plane: one Gauss-Newton step from sg_align_plane_moments' 31 sums.  The 6x6 normal matrix, with its rotational
+// rows and columns scaled into length units, is diagonalised by cyclic Jacobi (symmetric, so the eigenvalues -- negative rounding residue
+// of a singular matrix included -- come out to a few units of the last place of the LARGEST one, which is what the degeneracy ratio needs),
+// the step is solved in the eigenbasis, applied about the origin by Rodrigues' formula and the rotation re-orthonormalised, so that fifty
+// composed steps are still a rotation.
 #include "sg_common.h"
 
 #include <cmath>
@@ -35,6 +41,56 @@ void orthonormalise(Vec3& a, Vec3& b) {
     const double p = dot(a, b);
     for (int i = 0; i < 3; ++i) b.v[i] -= p * a.v[i];
     normalise(b);
+}
+
+
+constexpr int kPlaneMom = 31;
+constexpr double kPlaneRatio = 0x1p-40;        // smallest eigenvalue at or below this share of the largest: some motion costs nothing
+constexpr double kSeriesBelow = 1e-8;          // radians: below it sin and cos come from their series
+
+// eigenvalues and eigenvectors (the columns of V) of the symmetric A by cyclic Jacobi; A is destroyed.  false: not converged (non-finite input)
+bool jacobi6(double A[6][6], double V[6][6], double lambda[6]) {
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
+        double off = 0.0;
+        for (int p = 0; p < 5; ++p)
+            for (int q = p + 1; q < 6; ++q) off += std::fabs(A[p][q]);
+        if (off == 0.0) {
+            for (int i = 0; i < 6; ++i) lambda[i] = A[i][i];
+            return true;
+        }
+        if (!std::isfinite(off)) return false;
+        for (int p = 0; p < 5; ++p) {
+            for (int q = p + 1; q < 6; ++q) {
+                const double apq = A[p][q];
+                if (apq == 0.0) continue;
+                // an entry that no longer changes either diagonal value is set to zero, not rotated away
+                const double g = 128.0 * std::fabs(apq);
+                if (sweep > 3 && std::fabs(A[p][p]) + g == std::fabs(A[p][p]) && std::fabs(A[q][q]) + g == std::fabs(A[q][q])) {
+                    A[p][q] = A[q][p] = 0.0;
+                    continue;
+                }
+                const double zeta = (A[q][q] - A[p][p]) / (2.0 * apq);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
+                A[p][p] -= t * apq;
+                A[q][q] += t * apq;
+                A[p][q] = A[q][p] = 0.0;
+                for (int k = 0; k < 6; ++k) {
+                    if (k != p && k != q) {
+                        const double akp = A[k][p], akq = A[k][q];
+                        A[k][p] = A[p][k] = c * akp - s * akq;
+                        A[k][q] = A[q][k] = s * akp + c * akq;
+                    }
+                    const double vkp = V[k][p], vkq = V[k][q];
+                    V[k][p] = c * vkp - s * vkq;
+                    V[k][q] = s * vkp + c * vkq;
+                }
+            }
+        }
+    }
+    return false;
 }
 
 }  // namespace
@@ -109,6 +165,79 @@ int sg_align_solve(const double* h_m, const double* h_origin_x, const double* h_
         }
         h_T[4 * r + 3] = (sb[r] / n + h_origin_y[r]) - rx;
     }
+    return SG_OK;
+}
+
+int sg_align_plane_solve(const double* h_m, const double* h_origin, double length, const double* h_T, double* h_T_new, double* h_step) {
+    const char* who = "sg_align_plane_solve";
+    SG_REQUIRE(h_m && h_origin && h_T && h_T_new, "%s: bad arguments", who);
+    for (int i = 0; i < kPlaneMom; ++i) SG_REQUIRE(std::isfinite(h_m[i]), "%s: moment %d is not finite", who, i);
+    for (int i = 0; i < 3; ++i) SG_REQUIRE(std::isfinite(h_origin[i]), "%s: an origin that is not finite", who);
+    for (int i = 0; i < 12; ++i) SG_REQUIRE(std::isfinite(h_T[i]), "%s: entry %d of the transform is not finite", who, i);
+    SG_REQUIRE(std::isfinite(length) && length > 0.0, "%s: the length scale must be finite and > 0 (%g)", who, length);
+    const double n = h_m[0];
+    SG_REQUIRE(n >= 0.0, "%s: a negative pair count (%g)", who, n);
+    if (n < 6.0) return sg::fail(SG_EUNSUP, "%s: degenerate: %g usable pairs; a point-to-plane step needs at least 6", who, n);
+    const double scale[6] = {1.0 / length, 1.0 / length, 1.0 / length, 1.0, 1.0, 1.0};
+    double A[6][6], V[6][6], lambda[6], g[6];
+    int k = 2;
+    for (int r = 0; r < 6; ++r) {
+        for (int c = r; c < 6; ++c) A[r][c] = A[c][r] = (scale[r] * h_m[k++]) * scale[c];
+        g[r] = scale[r] * h_m[23 + r];
+    }
+    if (!jacobi6(A, V, lambda)) return sg::fail(SG_EINVAL, "%s: the moments overflow the fit", who);
+    double lmax = lambda[0], lmin = lambda[0];
+    for (int i = 1; i < 6; ++i) {
+        lmax = std::fmax(lmax, lambda[i]);
+        lmin = std::fmin(lmin, lambda[i]);
+    }
+    if (!(lmax > 0.0) || !(lmin > kPlaneRatio * lmax))
+        return sg::fail(SG_EUNSUP, "%s: degenerate: eigenvalues %g .. %g of the scaled normal matrix -- the planes the pairs lie on leave a "
+                                   "motion free (one plane, parallel planes, two plane directions only)", who, lmin, lmax);
+    double step[6];                                             // s = -D V diag(1 / lambda) V^T D g
+    for (int i = 0; i < 6; ++i) step[i] = 0.0;
+    for (int e = 0; e < 6; ++e) {
+        double proj = 0.0;
+        for (int i = 0; i < 6; ++i) proj += V[i][e] * g[i];
+        proj /= lambda[e];
+        for (int i = 0; i < 6; ++i) step[i] -= V[i][e] * proj;
+    }
+    for (int i = 0; i < 6; ++i) step[i] *= scale[i];
+    for (int i = 0; i < 6; ++i)
+        if (!std::isfinite(step[i])) return sg::fail(SG_EINVAL, "%s: the moments overflow the fit", who);
+    // Rodrigues: Rw = I + (sin th / th) K + ((1 - cos th) / th^2) K K with K the cross-product matrix of w
+    const double* w = step;
+    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2], th = std::sqrt(th2);
+    const double sa = th < kSeriesBelow ? 1.0 - th2 / 6.0 : std::sin(th) / th;
+    const double sb = th < kSeriesBelow ? 0.5 - th2 / 24.0 : (1.0 - std::cos(th)) / th2;
+    const double K[3][3] = {{0.0, -w[2], w[1]}, {w[2], 0.0, -w[0]}, {-w[1], w[0], 0.0}};
+    double Rw[3][3];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) {
+            const double kk = (K[r][0] * K[0][c] + K[r][1] * K[1][c]) + K[r][2] * K[2][c];
+            Rw[r][c] = ((r == c ? 1.0 : 0.0) + sa * K[r][c]) + sb * kk;
+        }
+    }
+    Vec3 row[3];
+    double tn[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) row[r].v[c] = (Rw[r][0] * h_T[c] + Rw[r][1] * h_T[4 + c]) + Rw[r][2] * h_T[8 + c];
+        const double d[3] = {h_T[3] - h_origin[0], h_T[7] - h_origin[1], h_T[11] - h_origin[2]};
+        tn[r] = (((Rw[r][0] * d[0] + Rw[r][1] * d[1]) + Rw[r][2] * d[2]) + h_origin[r]) + step[3 + r];
+    }
+    orthonormalise(row[0], row[1]);                             // rows 0 and 1, then row 2 as their cross product: a proper rotation
+    row[2] = cross(row[0], row[1]);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) {
+            SG_REQUIRE(std::isfinite(row[r].v[c]), "%s: the transform is not a rotation with a translation", who);
+            h_T_new[4 * r + c] = row[r].v[c];
+        }
+        h_T_new[4 * r + 3] = tn[r];
+        h_T_new[12 + r] = 0.0;
+    }
+    h_T_new[15] = 1.0;
+    if (h_step)
+        for (int i = 0; i < 6; ++i) h_step[i] = step[i];
     return SG_OK;
 }
 

@@ -6,10 +6,17 @@
 //                     workgroup folds kPairs consecutive pairs into ONE partial row of the workspace: thread t accumulates pairs t, t + 256,
 //                     .. of its block in order, a wave sums on the DPP network of wave_ops.h, the waves' rows are added in order.  An index
 //                     outside 0..N-1 raises the flag word before anything is read through it.
-//   k_align_fold      one workgroup: thread t adds partial rows t, t + 256, .. in order, then the same network.
+//   k_align_fold      one workgroup: thread t adds partial rows t, t + 256, .. in order, then the same network.  Templated on the row
+//                     width: 17 sums here, 31 for the point-to-plane fit below.
 // No floating-point atomics; grid, block and both trees are functions of U alone, so the 17 doubles do not depend on the device or the stream.
 // The kernel is a gather: 12 B of x, 8 B of idx and 4 B of d2 streamed per pair, 12 B of y read at random; the ~30 double operations per
 // pair hide under it.
+//
+// Point-to-plane:
+//   k_plane_moments   the 31 sums of a Gauss-Newton step on the point-to-plane residual (usable | skipped | upper triangle of sum J J^T |
+//                     sum J r | sum r r | sum d2) over the candidate pairs, with the moving point taken through the current pose in double
+//                     (sg_rigid_apply's statement without its final rounding).  Launch shape, pair order, both trees and the index flag are
+//                     k_align_moments'; 24 B of y and its normal are read at random per pair, ~130 double operations hide under them.
 #include <cmath>
 
 #include "sg_common.h"
@@ -23,9 +30,11 @@ constexpr int kWaves = kBlock / kWave;
 constexpr int kPer = 4;                       // pairs per thread: four independent gathers in flight
 constexpr int kPairs = kBlock * kPer;         // pairs per workgroup = per partial row
 constexpr int kMom = 17;
+constexpr int kPlaneMom = 31;                 // usable | skipped | 21 of J J^T | 6 of J r | r r | d2
 
 struct Rigid { double m[12]; };               // row-major 3x4 [R|t]
 struct Origins { double x[3], y[3]; };
+struct Origin { double c[3]; };
 
 __global__ __launch_bounds__(kBlock) void k_rigid_apply(const float* __restrict__ x, int xs, int U, Rigid T, float* __restrict__ out) {
     const int u = blockIdx.x * kBlock + threadIdx.x;
@@ -85,18 +94,19 @@ __global__ __launch_bounds__(kBlock) void k_align_moments(const float* __restric
     }
 }
 
+template <int kM>
 __global__ __launch_bounds__(kBlock) void k_align_fold(const double* __restrict__ partial, int rows, double* __restrict__ out) {
-    __shared__ double s_rows[kWaves][kMom];
+    __shared__ double s_rows[kWaves][kM];
     const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
 #pragma unroll 1
-    for (int m = 0; m < kMom; ++m) {
+    for (int m = 0; m < kM; ++m) {
         double acc = 0.0;
-        for (int r = threadIdx.x; r < rows; r += kBlock) acc += partial[(size_t)r * kMom + m];
+        for (int r = threadIdx.x; r < rows; r += kBlock) acc += partial[(size_t)r * kM + m];
         const double s = sgw::wave_sum(acc);
         if (lane == 0) s_rows[wave][m] = s;
     }
     __syncthreads();
-    if (threadIdx.x < kMom) {
+    if (threadIdx.x < kM) {
         double s = s_rows[0][threadIdx.x];
 #pragma unroll
         for (int w = 1; w < kWaves; ++w) s += s_rows[w][threadIdx.x];
@@ -104,7 +114,76 @@ __global__ __launch_bounds__(kBlock) void k_align_fold(const double* __restrict_
     }
 }
 
-struct Landing { double m[kMom]; int flag; int pad; };   // what one copy brings back: the sums and the flag word
+// the point-to-plane twin of k_align_moments: the same blocks, the same pair order, the same two trees, 31 sums.  R, t and the origin are
+// wave-uniform (kernel arguments: scalar registers); every operation is written once, in the order the header states, and nothing contracts.
+__global__ __launch_bounds__(kBlock) void k_plane_moments(const float* __restrict__ x, int xs, int U, Rigid T, const float* __restrict__ y, int ys,
+                                                          int N, const float* __restrict__ nrm, int ns, const int64_t* __restrict__ idx,
+                                                          const float* __restrict__ d2, float max_d2, Origin o, double* __restrict__ partial,
+                                                          int* __restrict__ flag) {
+    __shared__ double s_rows[kWaves][kPlaneMom];
+    double acc[kPlaneMom];
+#pragma unroll
+    for (int m = 0; m < kPlaneMom; ++m) acc[m] = 0.0;
+    const long long base = (long long)blockIdx.x * kPairs + threadIdx.x;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+        const long long u = base + (long long)j * kBlock;
+        if (u >= (long long)U) continue;
+        const int64_t i = idx[u];
+        if (i < 0 || i >= (int64_t)N) { bad = true; continue; }
+        const float dd = d2[u];
+        if (!(dd <= max_d2)) continue;                         // a NaN compares false: never a candidate
+        const float* pn = nrm + (size_t)i * ns;
+        const double n[3] = {(double)pn[0], (double)pn[1], (double)pn[2]};
+        const double nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+        if (!(nn >= 0.25 && nn <= 4.0)) {                       // a NaN or an infinite component fails one of the two compares
+            acc[1] += 1.0;
+            continue;
+        }
+        const float* px = x + (size_t)u * xs;
+        const float* py = y + (size_t)i * ys;
+        const double qx = (double)px[0], qy = (double)px[1], qz = (double)px[2];
+        double a[3], e[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double p = ((T.m[4 * r] * qx + T.m[4 * r + 1] * qy) + T.m[4 * r + 2] * qz) + T.m[4 * r + 3];
+            a[r] = p - o.c[r];
+            e[r] = a[r] - ((double)py[r] - o.c[r]);
+        }
+        const double res = (e[0] * n[0] + e[1] * n[1]) + e[2] * n[2];
+        const double J[6] = {a[1] * n[2] - a[2] * n[1], a[2] * n[0] - a[0] * n[2], a[0] * n[1] - a[1] * n[0], n[0], n[1], n[2]};
+        acc[0] += 1.0;
+        int k = 2;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+#pragma unroll
+            for (int c = r; c < 6; ++c) acc[k++] += J[r] * J[c];
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) acc[23 + r] += J[r] * res;
+        acc[29] += res * res;
+        acc[30] += (double)dd;
+    }
+    if (bad) *flag = 1;
+    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+#pragma unroll
+    for (int m = 0; m < kPlaneMom; ++m) {
+        const double s = sgw::wave_sum(acc[m]);
+        if (lane == 0) s_rows[wave][m] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < kPlaneMom) {
+        double s = s_rows[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) s += s_rows[w][threadIdx.x];
+        partial[(size_t)blockIdx.x * kPlaneMom + threadIdx.x] = s;
+    }
+}
+
+template <int kM> struct LandingOf { double m[kM]; int flag; int pad; };   // what one copy brings back: the sums and the flag word
+using Landing = LandingOf<kMom>;
+using PlaneLanding = LandingOf<kPlaneMom>;
 
 bool finite3(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
@@ -160,13 +239,62 @@ int sg_align_moments(const float* d_x, int x_stride, int U, const float* d_y, in
     hipStream_t st = sg::as_stream(stream);
     SG_HIP(hipMemsetAsync(d_land, 0, sizeof(Landing), st));
     k_align_moments<<<rows, kBlock, 0, st>>>(d_x, x_stride, U, d_y, y_stride, N, d_idx, d_d2, max_d2, o, d_partial, &d_land->flag);
-    k_align_fold<<<1, kBlock, 0, st>>>(d_partial, rows, d_land->m);
+    k_align_fold<kMom><<<1, kBlock, 0, st>>>(d_partial, rows, d_land->m);
     Landing land{};
     SG_HIP(hipMemcpyAsync(&land, d_land, sizeof(Landing), hipMemcpyDeviceToHost, st));
     SG_HIP(hipStreamSynchronize(st));
     SG_LAUNCH_CHECK();
     if (land.flag) return sg::fail(SG_EINVAL, "%s: an index outside 0..%d", who, N - 1);
     for (int m = 0; m < kMom; ++m) h_out[m] = land.m[m];
+    return SG_OK;
+}
+
+size_t sg_align_plane_moments_ws_bytes(int U) {
+    if (U < 0 || U > SG_MAX_CLOUD_POINTS) return 0;
+    return sg::align_up(sizeof(PlaneLanding)) + sg::align_up((size_t)std::max(sg::cdiv(U, kPairs), 1) * kPlaneMom * sizeof(double));
+}
+
+int sg_align_plane_moments(const float* d_x, int x_stride, int U, const double* h_T, const float* d_y, int y_stride, int N, const float* d_n,
+                           int n_stride, const int64_t* d_idx, const float* d_d2, float max_d2, const double* h_origin, double* h_out, void* d_ws,
+                           size_t ws_bytes, void* stream) {
+    const char* who = "sg_align_plane_moments";
+    SG_REQUIRE(U >= 0 && N >= 1, "%s: bad arguments (%d pairs, %d candidates)", who, U, N);
+    if (U > SG_MAX_CLOUD_POINTS || N > SG_MAX_CLOUD_POINTS)
+        return sg::fail(SG_EUNSUP, "%s: %d pairs into %d candidates; a call takes at most %d of either", who, U, N, SG_MAX_CLOUD_POINTS);
+    SG_REQUIRE(x_stride >= 3 && y_stride >= 3 && n_stride >= 3, "%s: rows of at least 3 floats (x: %d, y: %d, normals: %d)", who, x_stride, y_stride,
+               n_stride);
+    SG_REQUIRE(h_T && h_origin && h_out, "%s: bad arguments", who);
+    SG_REQUIRE(!std::isnan(max_d2), "%s: max_d2 is not a number", who);
+    SG_REQUIRE(finite3(h_origin), "%s: an origin that is not finite", who);
+    Rigid T;
+    for (int i = 0; i < 12; ++i) {
+        SG_REQUIRE(std::isfinite(h_T[i]), "%s: entry %d of the transform is not finite", who, i);
+        T.m[i] = h_T[i];
+    }
+    if (U == 0) {
+        for (int m = 0; m < kPlaneMom; ++m) h_out[m] = 0.0;
+        return SG_OK;
+    }
+    SG_REQUIRE(d_x && d_y && d_n && d_idx && d_d2 && d_ws, "%s: bad arguments", who);
+    const size_t need = sg_align_plane_moments_ws_bytes(U);
+    SG_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    const int rows = sg::cdiv(U, kPairs);
+    sg::Carver cv(d_ws, ws_bytes);
+    PlaneLanding* d_land = cv.take<PlaneLanding>(1);
+    double* d_partial = cv.take<double>((size_t)rows * kPlaneMom);
+    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    Origin o;
+    for (int i = 0; i < 3; ++i) o.c[i] = h_origin[i];
+    hipStream_t st = sg::as_stream(stream);
+    SG_HIP(hipMemsetAsync(d_land, 0, sizeof(PlaneLanding), st));
+    k_plane_moments<<<rows, kBlock, 0, st>>>(d_x, x_stride, U, T, d_y, y_stride, N, d_n, n_stride, d_idx, d_d2, max_d2, o, d_partial, &d_land->flag);
+    k_align_fold<kPlaneMom><<<1, kBlock, 0, st>>>(d_partial, rows, d_land->m);
+    PlaneLanding land{};
+    SG_HIP(hipMemcpyAsync(&land, d_land, sizeof(PlaneLanding), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    if (land.flag) return sg::fail(SG_EINVAL, "%s: an index outside 0..%d", who, N - 1);
+    for (int m = 0; m < kPlaneMom; ++m) h_out[m] = land.m[m];
     return SG_OK;
 }
 

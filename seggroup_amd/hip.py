@@ -181,6 +181,9 @@ SIGNATURES = {
     "sg_align_moments_ws_bytes": (_Z, [_I]),
     "sg_align_moments": (_I, [vp, _I, _I, vp, _I, _I, vp, vp, C.c_float, vp, vp, vp, vp, _Z, vp]),
     "sg_align_solve": (_I, [vp, vp, vp, vp]),
+    "sg_align_plane_moments_ws_bytes": (_Z, [_I]),
+    "sg_align_plane_moments": (_I, [vp, _I, _I, vp, vp, _I, _I, vp, _I, vp, vp, C.c_float, vp, vp, vp, _Z, vp]),
+    "sg_align_plane_solve": (_I, [vp, vp, C.c_double, vp, vp, vp]),
     "sg_components_ws_bytes": (_Z, [_I]),
     "sg_components_edges": (_I, [vp, C.c_longlong, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_components_faces": (_I, [vp, _I, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),

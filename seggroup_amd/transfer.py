@@ -21,19 +21,21 @@ geometry, the distances in the report are those after alignment.
 
     python -m seggroup_amd.transfer --from-scans DIR --to-scans DIR -n EXP --stage S --out ROOT2 [--root .] [--scenes FILE]
                                     [--workers K] [--index {grid,brute}] [--vote {5,10,20} [--vote-on NAME]]
-                                    [--align {icp,DIR} [--align-max-dist D]] [--device D]
+                                    [--align {icp,DIR} [--align-max-dist D] [--align-metric {point,plane}]] [--device D]
         for every scene present in both trees: results/EXP/<scene>/<S>/ of --root (made on --from-scans) -> the same files at the
         target's V under ROOT2/results/EXP/<scene>/<S>/ (pseudo_labels.sgl and the per-vector .npy files, as `thin --lift` writes
         them), ROOT2/results/EXP/<scene>/<S>/<scene>.transfer.npz (nearest, d2; with --vote also rep, votes, tied) and one
         ROOT2/transfer_report.json.  --vote-on: `seg` (the default: the .sgl's seg_of_vertex) or a vector name such as final.ins, taken
         from the .sgl's expansion or from the .npy file.  --align icp --align-max-dist D: point-to-point ICP of the target onto the source
         with the inlier radius D; --align DIR: T from DIR/<scene>.align.json.  With either the .transfer.npz also holds T (float64 [4,4],
-        target -> source frame) and the scene's report entry an `align` record.
+        target -> source frame) and the scene's report entry an `align` record.  --align-metric plane (with --align icp): point-to-plane
+        ICP on the SOURCE's normals -- its faces when its PLY has any, else its kNN-10 covariance --; the `align` record
+        then also holds metric, normals, skipped, plane_rms_before and plane_rms_after.
 
 Not here: a distance cut-off that un-labels far vertices (a lifted .sgl has no "no segment" for a vertex: the report says how far the
 vertices are -- after the alignment, when there is one -- and the decision is the user's), interpolation or distance-weighted votes,
-anything but a rigid transform between the two geometries (no scale, no deformation, no registration without a starting pose: align.py
-says what its ICP is and is not), and segs.json or clicks (rekey.py and thin.py own those).
+anything but a rigid transform between the two geometries (no scale, no deformation, no trimming or robust weights, no registration
+without a starting pose: align.py says what its ICP is and is not), and segs.json or clicks (rekey.py and thin.py own those).
 """
 from __future__ import annotations
 
@@ -143,8 +145,13 @@ def check_vote(vote_k, vote_on, index: str) -> None:
         raise ValueError("--vote-on (vote_on=) must be 'seg' or one of %s, not %r" % (", ".join(hip.LABEL_NAMES), vote_on))
 
 
-def check_align(align, align_max_dist, index: str) -> None:
-    """the combinations of align, align_max_dist and index that are refused before anything runs (ValueError)"""
+def check_align(align, align_max_dist, index: str, align_metric=None) -> None:
+    """the combinations of align, align_max_dist, align_metric and index that are refused before anything runs (ValueError)"""
+    if align_metric is not None:
+        if align != "icp":
+            raise ValueError("--align-metric (align_metric=) needs --align icp (align='icp'): without an ICP there is no metric to choose")
+        if align_metric not in rigid.METRICS:
+            raise ValueError("--align-metric (align_metric=) must be 'point' or 'plane', not %r" % (align_metric,))
     if align is None:
         if align_max_dist is not None:
             raise ValueError("--align-max-dist (align_max_dist=) needs --align icp (align='icp'): without an ICP there is no inlier radius")
@@ -161,8 +168,13 @@ def check_align(align, align_max_dist, index: str) -> None:
             raise ValueError("--align (align=) must be 'icp' or a directory of <scene>%s files, not %r" % (rigid.ALIGN_SUFFIX, align))
 
 
-def scene_alignment(scene: str, src_xyz, dst_xyz, align, align_max_dist, device=None, stream=None):
-    """-> (T float64 [4,4] mapping the target into the source's frame, the scene's `align` record of the report)"""
+def scene_alignment(scene: str, src_xyz, dst_xyz, align, align_max_dist, device=None, stream=None, align_metric=None, src_faces=None):
+    """-> (T float64 [4,4] mapping the target into the source's frame, the scene's `align` record of the report).  align_metric="plane":
+    the source is the fixed cloud, so the normals are the source's (`src_faces`, else its kNN-10 covariance)."""
+    if align == "icp" and align_metric == "plane":
+        nrm, how = rigid.scan_normals(src_xyz, src_faces, device=device)
+        al = rigid.icp(dst_xyz, src_xyz, align_max_dist, device=device, stream=stream, metric="plane", normals=nrm)
+        return al.T, dict(al.scalars(), normals=how, source="icp")
     if align == "icp":
         al = rigid.icp(dst_xyz, src_xyz, align_max_dist, device=device, stream=stream)
         return al.T, dict(al.scalars(), source="icp")
@@ -173,27 +185,29 @@ def scene_alignment(scene: str, src_xyz, dst_xyz, align, align_max_dist, device=
     return doc["T"], dict({k: doc.get(k) for k in rigid.SCALARS}, source=path)
 
 
-def _scan_xyz(scans_dir: str, scene: str):
-    return mesh_arrays(read_ply(os.path.join(scans_dir, scene, scene + "_vh_clean_2.ply")))[0]
+def _scan_xyz(scans_dir: str, scene: str, faces: bool = False):
+    xyz, _, tri = mesh_arrays(read_ply(os.path.join(scans_dir, scene, scene + "_vh_clean_2.ply")))
+    return (xyz, tri) if faces else xyz
 
 
 def transfer_scene(scene: str, from_scans: str, to_scans: str, exp: str, stage: str, out_root: str, root: str = ".", index: str = "grid",
-                   device=None, stream=None, vote_k=None, vote_on=None, align=None, align_max_dist=None):
+                   device=None, stream=None, vote_k=None, vote_on=None, align=None, align_max_dist=None, align_metric=None):
     """One scene: results/<exp>/<scene>/<stage>/ under `root`, made on <from_scans>/<scene>, -> the same files for <to_scans>/<scene>
     under <out_root>/results/...; -> (its entry of transfer_report.json, the files written).  With `vote_k` the files are gathered by
     `rep`, the nearest of the vote_k nearest source vertices that holds their most frequent `vote_on` label.  With `align`
     ("icp" with `align_max_dist`, or a directory of <scene>.align.json) the search runs on the target moved into the source's frame
-    (DESIGN.md 8p); the files are still the target's."""
+    (DESIGN.md 8p); the files are still the target's.  `align_metric` ("point" | "plane", with align="icp"): the ICP's metric."""
     check_vote(vote_k, vote_on, index)
-    check_align(align, align_max_dist, index)
+    check_align(align, align_max_dist, index, align_metric)
     src_dir = os.path.join(root, "results", exp, scene, stage)
     if not os.path.isdir(src_dir):
         raise FileNotFoundError(f"{src_dir}: no such export directory")
-    src_xyz, dst_xyz = _scan_xyz(from_scans, scene), _scan_xyz(to_scans, scene)
+    (src_xyz, src_faces), dst_xyz = _scan_xyz(from_scans, scene, faces=True), _scan_xyz(to_scans, scene)
     dst_dir = os.path.join(out_root, "results", exp, scene, stage)
     voted, aligned, query = {}, {}, dst_xyz
     if align is not None:
-        T, record = scene_alignment(scene, src_xyz, dst_xyz, align, align_max_dist, device=device, stream=stream)
+        T, record = scene_alignment(scene, src_xyz, dst_xyz, align, align_max_dist, device=device, stream=stream, align_metric=align_metric,
+                                    src_faces=src_faces)
         aligned, query = {"T": T}, rigid.apply(dst_xyz, T, device=device, stream=stream)
     if vote_k is None:
         d_near, d_d2 = nearest_vertex(src_xyz, query, index=index, device=device, stream=stream)
@@ -221,13 +235,13 @@ def transfer_scene(scene: str, from_scans: str, to_scans: str, exp: str, stage: 
 
 
 def transfer_results(from_scans: str, to_scans: str, exp: str, stage: str, out_root: str, root: str = ".", scenes=None, workers: int = 4,
-                     index: str = "grid", device=None, vote_k=None, vote_on=None, align=None, align_max_dist=None):
+                     index: str = "grid", device=None, vote_k=None, vote_on=None, align=None, align_max_dist=None, align_metric=None):
     """Every scene of `from_scans` (or the named ones) that both trees hold -> (report {scene: entry}, missing {scene: why}); writes
-    <out_root>/transfer_report.json.  Workers are threads, each with its own stream.  `vote_k`, `vote_on`, `align`, `align_max_dist`:
-    transfer_scene's."""
+    <out_root>/transfer_report.json.  Workers are threads, each with its own stream.  `vote_k`, `vote_on`, `align`, `align_max_dist`,
+    `align_metric`: transfer_scene's."""
     hip.knn_index(index)
     check_vote(vote_k, vote_on, index)
-    check_align(align, align_max_dist, index)
+    check_align(align, align_max_dist, index, align_metric)
     dev = torch_device(device)
     have_src, have_dst = set(scans.scan_names(from_scans)), set(scans.scan_names(to_scans))
     if scenes is None:
@@ -244,7 +258,8 @@ def transfer_results(from_scans: str, to_scans: str, exp: str, stage: str, out_r
     report = dict(scans.map_scans(todo, workers, dev, lambda scene, stream: transfer_scene(scene, from_scans, to_scans, exp, stage, out_root, root,
                                                                                            index, device=dev, stream=stream, vote_k=vote_k,
                                                                                            vote_on=vote_on, align=align,
-                                                                                           align_max_dist=align_max_dist)[0]))
+                                                                                           align_max_dist=align_max_dist,
+                                                                                           align_metric=align_metric)[0]))
     os.makedirs(out_root, exist_ok=True)
     scans.write_report(os.path.join(out_root, REPORT_NAME), {"experiment": exp, "stage": stage, "index": index, "scenes": report, "missing": missing})
     return report, missing
@@ -270,18 +285,20 @@ def main(argv=None) -> int:
                     help="move the target into the source's frame before the search (needs --index grid): icp fits the transform here "
                          "(with --align-max-dist), DIR reads <scene>.align.json as python -m seggroup_amd.align writes it")
     ap.add_argument("--align-max-dist", type=float, default=None, metavar="D", help="the ICP's inlier radius in the scans' unit (--align icp only)")
+    ap.add_argument("--align-metric", choices=rigid.METRICS, default=None,
+                    help="the ICP's metric (--align icp only): point (the default) or plane, point-to-plane on the source's normals")
     ap.add_argument("--device", default=None)
     a = ap.parse_args(argv)
     scans.check_workers(ap, a.workers)
     try:
         check_vote(a.vote, a.vote_on, a.index)
-        check_align(a.align, a.align_max_dist, a.index)
+        check_align(a.align, a.align_max_dist, a.index, a.align_metric)
     except ValueError as e:
         ap.error(str(e))
     try:
         report, missing = transfer_results(a.from_scans, a.to_scans, a.exp_name, a.stage, a.out, a.root, scans.scene_list(a.scenes), a.workers,
                                            a.index, a.device, vote_k=a.vote, vote_on=a.vote_on, align=a.align,
-                                           align_max_dist=a.align_max_dist)
+                                           align_max_dist=a.align_max_dist, align_metric=a.align_metric)
     except ValueError as e:
         if "--index grid" not in str(e) and "--vote-on" not in str(e) and "max_dist" not in str(e):
             raise
