@@ -1030,6 +1030,62 @@ int sg_align_plane_moments(const float* d_x, int x_stride, int U, const double* 
                            size_t ws_bytes, void* stream);
 int sg_align_plane_solve(const double* h_m, const double* h_origin, double length, const double* h_T, double* h_T_new, double* h_step);
 
+/* Global (init-free) registration: a local descriptor, its nearest neighbour and a hypothesise-and-count RANSAC.  No
+ * floating-point atomics in any of them: two calls on the same input write the same bytes.
+ *
+ * sg_fpfh: d_xyz [N, stride >= 3] fp32, d_normals [N,3] fp32, rows d_off int64 [N+1] / d_idx int32 [off[N]] as sg_radius_neighbours_grid
+ *   writes them (the point itself not in its row; d_idx may be NULL when every row is empty).  d_spfh int32 [N,34]: 3 x 11 bin counts
+ *   (theta | alpha | phi) and the number of counted pairs; d_fpfh float [N,33].  Per pair (i, j in row i), in double on the widened fp32
+ *   inputs, dot(a, b) = (a0*b0 + a1*b1) + a2*b2, nothing contracted:
+ *     d = p_j - p_i; len = sqrt(d.d), the pair is skipped when len == 0; dh = d / len; a1 = n_i.dh; a2 = n_j.dh;
+ *     |a1| < |a2|: u = n_j, t = n_i, dh = -dh; else u = n_i, t = n_j;  phi = u.dh;  v = dh x u, skipped when |v| == 0, v /= |v|;
+ *     w = u x v;  alpha = v.t;  theta = atan2(w.t, u.t);
+ *     bins floor(11 * x) clamped to 0..10 for x = (theta + pi) / (2 pi), (alpha + 1) / 2, (phi + 1) / 2.
+ *   FPFH of i, per sub-histogram: S[b] = sum over the row in stored order, over neighbours with d2_ij = d.d > 0 and pairs_j > 0, of
+ *   ((100 * spfh_j[b]) / pairs_j) / d2_ij in double; fpfh[b] = (float)((100 * S[b]) / sum_b S[b]), the sum over the sub-histogram's 11
+ *   bins in ascending order; an empty row or an all-zero S gives zeros.  0 <= N <= SG_MAX_GRID_POINTS (above: SG_EUNSUP); N = 0 is SG_OK
+ *   and touches nothing.  SG_EINVAL: null pointers, a stride below 3, a workspace below sg_fpfh_ws_bytes(N) -- before the first device call
+ *   --, offsets that do not ascend from 0 to off[N] or a row entry outside 0..N-1 (checked on the device; nothing is read through
+ *   either).  Synchronises the stream.
+ *
+ * sg_feature_nearest: d_a [U,C], d_b [N,C] fp32 dense rows, 1 <= C <= 64.  d2(u, n) = sum over c ascending of (a_c - b_c) * (a_c - b_c),
+ *   every operation rounded once in fp32; d_idx[u] (int64) is the n of the smallest d2, the lowest n among equals, d_d2[u] that d2: the
+ *   bytes of the NumPy float32 statement written channel by channel.  Inputs are finite by contract.  U, N <= 2^18 (above: SG_EUNSUP,
+ *   the message names thinning); N < 1, U < 0 or C outside 1..64: SG_EINVAL; U = 0: SG_OK.  The launch is left on the stream.
+ *
+ * sg_ransac_count: correspondences (d_ci[c], d_cj[c]), c < C, index d_m [U, m_stride >= 3] and d_f [N, f_stride >= 3]; with
+ *   a_c = m[ci[c]] and b_c = f[cj[c]] widened to double.  Triple h = (t0, t1, t2): row h of d_triples int32 [H,3], or, when d_triples is
+ *   NULL, t_e = ((z >> 32) * C) >> 32 with z = splitmix64(seed + (3h + e + 1) * 0x9E3779B97F4A7C15) (z = (z ^ z >> 30) *
+ *   0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31; all modulo 2^64).  d_count[h] = -1 for a rejected
+ *   hypothesis: a repeated t; any edge (0,1), (1,2), (2,0) with la < min_edge or lb < min_edge, la < similarity * lb or
+ *   lb < similarity * la (la, lb its lengths in the two clouds); a height |e1 x (x2 - x0)| below min_edge / 8 in either cloud (e1 the
+ *   UNIT first edge).  Otherwise d_count[h] = the number of c with |R a_c + t - b_c|^2 <= max_dist * max_dist, p[r] = ((R[r][0]*x +
+ *   R[r][1]*y) + R[r][2]*z) + t[r], all in double, [R|t] = sg_triangle_pose of the two triangles.  h_survivors (may be NULL) receives the
+ *   number of hypotheses that were counted.  3 <= C <= 2^18, 0 <= H <= 2^24 (above: SG_EUNSUP); H = 0 is SG_OK.  SG_EINVAL: null
+ *   pointers, strides below 3, U or N < 1, C < 3, max_dist or min_edge not a finite length > 0, similarity outside (0, 1], a workspace
+ *   below sg_ransac_ws_bytes(C, H) -- before the first device call --, a correspondence outside its cloud or an entry of d_triples outside
+ *   0..C-1 (raised on the device before anything is read through it).  Synchronises the stream.  sg_ransac_set_tuning(lanes, timed), per
+ *   calling thread: lanes = 1 | 64 | 0 (the default, 64) share a survivor in the counting kernel, which cannot change a result; timed != 0
+ *   brackets the stages of the thread's next calls with events, and sg_ransac_stage_times / sg_ransac_stage_name then give the
+ *   microseconds of gather, filter and count of the last one, as the other families' readers do.
+ *
+ * sg_triangle_pose: host only, no device call; the function the counting kernel runs (csrc/triangle_pose.h).  h_a, h_b: two triangles,
+ *   x0 | x1 | x2.  Frame of a triangle: e1 = (x1 - x0) / |x1 - x0|, e3 = c / |c| with c = e1 x (x2 - x0), e2 = e3 x e1; R = F_b F_a^T
+ *   with F = [e1 e2 e3] as columns, t = mean(b) - R mean(a), mean[r] = ((x0[r] + x1[r]) + x2[r]) / 3.  h_T receives the row-major 3x4
+ *   [R|t].  SG_EINVAL: null pointers, a coordinate that is not finite.  SG_EUNSUP ("degenerate"): a zero first edge or corners on a line. */
+size_t sg_fpfh_ws_bytes(int N);
+int sg_fpfh(const float* d_xyz, int stride, int N, const float* d_normals, const int64_t* d_off, const int32_t* d_idx, int32_t* d_spfh,
+            float* d_fpfh, void* d_ws, size_t ws_bytes, void* stream);
+int sg_feature_nearest(const float* d_a, int U, const float* d_b, int N, int C, int64_t* d_idx, float* d_d2, void* stream);
+size_t sg_ransac_ws_bytes(int C, int H);
+int sg_ransac_count(const float* d_m, int m_stride, int U, const float* d_f, int f_stride, int N, const int32_t* d_ci, const int32_t* d_cj, int C,
+                    int H, uint64_t seed, const int32_t* d_triples, double max_dist, double similarity, double min_edge, int32_t* d_count,
+                    int* h_survivors, void* d_ws, size_t ws_bytes, void* stream);
+int sg_ransac_set_tuning(int lanes_per_survivor, int timed);
+int sg_ransac_stage_times(float* h_us, int cap);
+const char* sg_ransac_stage_name(int i);
+int sg_triangle_pose(const double* h_a, const double* h_b, double* h_T);
+
 /* Connected components of a scan's graph.  Vertices 0..V-1, 1 <= V <= SG_MAX_CLOUD_POINTS; the undirected graph comes from
  * one of three sources:
  *   sg_components_edges  d_edges int32 [E,2], 0 <= E < 2^30: a row (a, a) is a no-op, duplicates and both orientations are allowed, no order

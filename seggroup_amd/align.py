@@ -16,17 +16,19 @@ and composes the step onto T.  The fixed cloud's normals are the caller's, or `o
 
     python -m seggroup_amd.align --moving-scans A --fixed-scans B --max-dist D --out DIR
                                  [--init DIR] [--max-iter 50] [--metric {point,plane}] [--normals-k K] [--scenes FILE] [--workers W]
-                                 [--device D]
+                                 [--global-init --voxel H [--hypotheses N] [--seed S] [--verify K] [--mutual]] [--device D]
         for every scene present in both trees: DIR/<scene>.align.json (T as 4 rows of 4, mapping A's coordinates into B's frame, the
         Alignment's scalars, both vertex counts and max_dist) and one DIR/align_report.json.  --init DIR: start from the T of
         DIR/<scene>.align.json (a file of the same form; only T is read).  `transfer --align DIR` reads these files.  --metric plane:
         the fixed scan's normals come from its faces (`oversegment.vertex_normals`) when its PLY has any, else from the covariance of
         its --normals-k (default 10) nearest points; the files then also hold metric, normals ("faces" | "knn-K"), skipped,
-        plane_rms_before and plane_rms_after.
+        plane_rms_before and plane_rms_after.  --global-init --voxel H: the search starts from `register.global_registration` of the two
+        scans thinned at H (no starting pose is needed; exclusive with --init), and the files gain a `global` record with
+        the Coarse's scalars.
 
-Not here, on purpose: trimmed fractions, robust weights, scale, and any global (init-free) registration.  This is ICP with a fixed
-inlier radius: it refines a pose that is already inside its basin, and takes an initial transform for everything else.  `max_dist` has
-no default: like `--max-edge` it depends on the scan's unit and on how wrong the pose may be.
+Not here, on purpose: trimmed fractions, robust weights and scale.  This is ICP with a fixed inlier radius: it refines a pose that is
+already inside its basin, and takes an initial transform -- a caller's, or register.py's coarse one -- for everything else.  `max_dist`
+has no default: like `--max-edge` it depends on the scan's unit and on how wrong the pose may be.
 """
 from __future__ import annotations
 
@@ -393,11 +395,14 @@ def read_align(path: str) -> dict:
     return doc
 
 
-def write_align(path: str, al: Alignment, moving_v: int, fixed_v: int, max_dist: float, normals=None) -> dict:
-    """`normals`: where a plane Alignment's normals came from ("faces" | "knn-K"); a point-to-point file has no such key"""
+def write_align(path: str, al: Alignment, moving_v: int, fixed_v: int, max_dist: float, normals=None, coarse=None) -> dict:
+    """`normals`: where a plane Alignment's normals came from ("faces" | "knn-K"); a point-to-point file has no such key.  `coarse`: the
+    register.Coarse the search started from; a file without one has no `global` key"""
     doc = dict(al.scalars(), T=[[float(v) for v in row] for row in al.T], moving_V=int(moving_v), fixed_V=int(fixed_v), max_dist=float(max_dist))
     if normals is not None:
         doc["normals"] = normals
+    if coarse is not None:
+        doc["global"] = dict(coarse.scalars(), T=[[float(v) for v in row] for row in coarse.T])
     scans.write_report(path, doc)
     return doc
 
@@ -426,13 +431,43 @@ def check_metric(metric, normals_k) -> None:
             raise ValueError("--normals-k (normals_k=) must be at least 3")
 
 
+def check_global(global_init, voxel, init_dir, hypotheses=None, seed=None, verify=None, mutual=None) -> None:
+    """the combinations of --global-init and its options that are refused before anything runs (ValueError)"""
+    if not global_init:
+        for name, v in (("--voxel", voxel), ("--hypotheses", hypotheses), ("--seed", seed), ("--verify", verify), ("--mutual", mutual or None)):
+            if v is not None:
+                raise ValueError("%s needs --global-init (global_init=True): without the coarse stage there is nothing it sets" % name)
+        return
+    if init_dir:
+        raise ValueError("--global-init and --init are two starting poses; give one")
+    if voxel is None or not float(voxel) > 0.0:
+        raise ValueError("--global-init needs --voxel (voxel=) > 0: the edge both scans are thinned at, in the scans' unit; it has no default")
+    if hypotheses is not None and not 1 <= int(hypotheses) <= 1 << 24:
+        raise ValueError("--hypotheses (hypotheses=) must be in 1..2^24")
+    if verify is not None and int(verify) < 1:
+        raise ValueError("--verify (verify=) must be at least 1")
+
+
+def global_options(hypotheses=None, seed=None, verify=None, mutual=None) -> dict:
+    """the options of --global-init that were given, as global_registration's keywords"""
+    given = dict(hypotheses=hypotheses, seed=seed, verify=verify, mutual=mutual or None)
+    return {k: v for k, v in given.items() if v is not None}
+
+
 def align_scene(scene: str, moving_scans: str, fixed_scans: str, max_dist: float, out_dir: str, init_dir=None, max_iter: int = 50, device=None,
-                stream=None, metric: str = "point", normals_k=None) -> dict:
-    """One scene: <moving_scans>/<scene> onto <fixed_scans>/<scene> -> its entry of align_report.json; writes <out_dir>/<scene>.align.json"""
+                stream=None, metric: str = "point", normals_k=None, global_init: bool = False, voxel=None, **coarse_options) -> dict:
+    """One scene: <moving_scans>/<scene> onto <fixed_scans>/<scene> -> its entry of align_report.json; writes <out_dir>/<scene>.align.json.
+    `global_init` with `voxel` (and hypotheses=, seed=, verify=, mutual=): the ICP starts from register.global_registration's pose."""
     check_metric(metric, normals_k)
+    check_global(global_init, voxel, init_dir, **coarse_options)
     init = read_align(align_path(init_dir, scene))["T"] if init_dir else None
     mov = _scan_xyz(moving_scans, scene)
     fix, _, faces = mesh_arrays(read_ply(os.path.join(fixed_scans, scene, scene + scans.PLY_SUFFIX)))
+    coarse = None
+    if global_init:
+        from .register import global_registration
+        coarse = global_registration(mov, fix, voxel=float(voxel), device=device, stream=stream, **global_options(**coarse_options))
+        init = coarse.T
     if metric == "plane":
         nrm, how = scan_normals(fix, faces, 10 if normals_k is None else normals_k, device=device)
         al = icp(mov, fix, max_dist, init=init, max_iter=max_iter, device=device, stream=stream, metric="plane", normals=nrm)
@@ -440,16 +475,18 @@ def align_scene(scene: str, moving_scans: str, fixed_scans: str, max_dist: float
         how = None
         al = icp(mov, fix, max_dist, init=init, max_iter=max_iter, device=device, stream=stream)
     os.makedirs(out_dir, exist_ok=True)
-    doc = write_align(align_path(out_dir, scene), al, mov.shape[0], fix.shape[0], max_dist, normals=how)
+    doc = write_align(align_path(out_dir, scene), al, mov.shape[0], fix.shape[0], max_dist, normals=how, coarse=coarse)
     del doc["T"]
     return doc
 
 
 def align_scans(moving_scans: str, fixed_scans: str, max_dist: float, out_dir: str, init_dir=None, max_iter: int = 50, scenes=None,
-                workers: int = 4, device=None, metric: str = "point", normals_k=None):
+                workers: int = 4, device=None, metric: str = "point", normals_k=None, global_init: bool = False, voxel=None, **coarse_options):
     """Every scene that both trees hold (or the named ones) -> (report {scene: entry}, missing {scene: why}); writes
-    <out_dir>/align_report.json.  Workers are threads, each with its own stream.  `metric`, `normals_k`: align_scene's."""
+    <out_dir>/align_report.json.  Workers are threads, each with its own stream.  `metric`, `normals_k`, `global_init`, `voxel` and the
+    coarse stage's options: align_scene's."""
     check_metric(metric, normals_k)
+    check_global(global_init, voxel, init_dir, **coarse_options)
     dev = torch_device(device)
     have_m, have_f = set(scans.scan_names(moving_scans)), set(scans.scan_names(fixed_scans))
     if scenes is None:
@@ -466,11 +503,14 @@ def align_scans(moving_scans: str, fixed_scans: str, max_dist: float, out_dir: s
             todo.append(s)
     report = dict(scans.map_scans(todo, workers, dev, lambda scene, stream: align_scene(scene, moving_scans, fixed_scans, max_dist, out_dir,
                                                                                         init_dir, max_iter, device=dev, stream=stream,
-                                                                                        metric=metric, normals_k=normals_k)))
+                                                                                        metric=metric, normals_k=normals_k,
+                                                                                        global_init=global_init, voxel=voxel, **coarse_options)))
     os.makedirs(out_dir, exist_ok=True)
     head = {"max_dist": float(max_dist), "max_iter": int(max_iter)}
     if metric == "plane":
         head["metric"] = metric
+    if global_init:
+        head["global_init"] = dict(global_options(**coarse_options), voxel=float(voxel))
     scans.write_report(os.path.join(out_dir, REPORT_NAME), dict(head, scenes=report, missing=missing))
     return report, missing
 
@@ -487,6 +527,13 @@ def main(argv=None) -> int:
                     help="point: point-to-point (the default); plane: point-to-plane on the fixed scan's normals (its faces, else its kNN covariance)")
     ap.add_argument("--normals-k", type=int, default=None, metavar="K",
                     help="the neighbours of the kNN covariance normals of a face-less fixed scan (--metric plane only; default 10)")
+    ap.add_argument("--global-init", action="store_true",
+                    help="start from the coarse pose of a global registration (FPFH + RANSAC on the scans thinned at --voxel); no --init needed")
+    ap.add_argument("--voxel", type=float, default=None, metavar="H", help="the edge both scans are thinned at for --global-init (required with it)")
+    ap.add_argument("--hypotheses", type=int, default=None, metavar="N", help="RANSAC triples of --global-init (default 2^20)")
+    ap.add_argument("--seed", type=int, default=None, metavar="S", help="the seed of --global-init's triples (default 0)")
+    ap.add_argument("--verify", type=int, default=None, metavar="K", help="hypotheses --global-init re-scores against the whole scan (default 16)")
+    ap.add_argument("--mutual", action="store_true", help="--global-init keeps only correspondences that are nearest in both directions")
     ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
     scans.add_workers_argument(ap)
     ap.add_argument("--device", default=None)
@@ -494,15 +541,18 @@ def main(argv=None) -> int:
     scans.check_workers(ap, a.workers)
     if not a.max_dist > 0.0 or a.max_iter < 1:
         ap.error("--max-dist must be > 0 and --max-iter at least 1")
+    coarse_options = dict(hypotheses=a.hypotheses, seed=a.seed, verify=a.verify, mutual=a.mutual or None)
     try:
         check_metric(a.metric, a.normals_k)
+        check_global(a.global_init, a.voxel, a.init, **coarse_options)
     except ValueError as e:
         ap.error(str(e))
     try:
         report, missing = align_scans(a.moving_scans, a.fixed_scans, a.max_dist, a.out, a.init, a.max_iter, scans.scene_list(a.scenes),
-                                      a.workers, a.device, metric=a.metric, normals_k=a.normals_k)
+                                      a.workers, a.device, metric=a.metric, normals_k=a.normals_k, global_init=a.global_init, voxel=a.voxel,
+                                      **coarse_options)
     except ValueError as e:
-        if "max_dist" not in str(e):
+        if "max_dist" not in str(e) and "global_registration" not in str(e):
             raise
         ap.error(str(e))
     for scene, e in report.items():

@@ -16,7 +16,10 @@
 // of a singular matrix included -- come out to a few units of the last place of the LARGEST one, which is what the degeneracy ratio needs),
 // the step is solved in the eigenbasis, applied about the origin by Rodrigues' formula and the rotation re-orthonormalised, so that fifty
 // composed steps are still a rotation.
+//
+// Global registration: sg_triangle_pose is triangle_pose.h's function for the host, the one the RANSAC kernels run.
 #include "sg_common.h"
+#include "triangle_pose.h"
 
 #include <cmath>
 
@@ -238,6 +241,22 @@ int sg_align_plane_solve(const double* h_m, const double* h_origin, double lengt
     h_T_new[15] = 1.0;
     if (h_step)
         for (int i = 0; i < 6; ++i) h_step[i] = step[i];
+    return SG_OK;
+}
+
+int sg_triangle_pose(const double* h_a, const double* h_b, double* h_T) {
+    const char* who = "sg_triangle_pose";
+    SG_REQUIRE(h_a && h_b && h_T, "%s: bad arguments", who);
+    for (int i = 0; i < 9; ++i) SG_REQUIRE(std::isfinite(h_a[i]) && std::isfinite(h_b[i]), "%s: a coordinate that is not finite", who);
+    sgtri::Frame fa, fb;
+    sgtri::frame(h_a, fa);
+    sgtri::frame(h_b, fb);
+    if (!(fa.edge > 0.0 && fa.height > 0.0 && fb.edge > 0.0 && fb.height > 0.0))
+        return sg::fail(SG_EUNSUP, "%s: degenerate: a triangle with a zero first edge or with its corners on a line has no frame", who);
+    double T[12];
+    sgtri::pose_of_frames(fa, fb, T);
+    for (int i = 0; i < 12; ++i) SG_REQUIRE(std::isfinite(T[i]), "%s: the coordinates overflow the pose", who);
+    for (int i = 0; i < 12; ++i) h_T[i] = T[i];
     return SG_OK;
 }
 

@@ -184,6 +184,16 @@ SIGNATURES = {
     "sg_align_plane_moments_ws_bytes": (_Z, [_I]),
     "sg_align_plane_moments": (_I, [vp, _I, _I, vp, vp, _I, _I, vp, _I, vp, vp, C.c_float, vp, vp, vp, _Z, vp]),
     "sg_align_plane_solve": (_I, [vp, vp, C.c_double, vp, vp, vp]),
+    "sg_fpfh_ws_bytes": (_Z, [_I]),
+    "sg_fpfh": (_I, [vp, _I, _I, vp, vp, vp, vp, vp, vp, _Z, vp]),
+    "sg_feature_nearest": (_I, [vp, _I, vp, _I, _I, vp, vp, vp]),
+    "sg_ransac_ws_bytes": (_Z, [_I, _I]),
+    "sg_ransac_count": (_I, [vp, _I, _I, vp, _I, _I, vp, vp, _I, _I, C.c_uint64, vp, C.c_double, C.c_double, C.c_double, vp, C.POINTER(C.c_int),
+                             vp, _Z, vp]),
+    "sg_ransac_set_tuning": (_I, [_I, _I]),
+    "sg_ransac_stage_times": (_I, [vp, _I]),
+    "sg_ransac_stage_name": (C.c_char_p, [_I]),
+    "sg_triangle_pose": (_I, [vp, vp, vp]),
     "sg_components_ws_bytes": (_Z, [_I]),
     "sg_components_edges": (_I, [vp, C.c_longlong, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_components_faces": (_I, [vp, _I, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),

@@ -21,7 +21,8 @@ geometry, the distances in the report are those after alignment.
 
     python -m seggroup_amd.transfer --from-scans DIR --to-scans DIR -n EXP --stage S --out ROOT2 [--root .] [--scenes FILE]
                                     [--workers K] [--index {grid,brute}] [--vote {5,10,20} [--vote-on NAME]]
-                                    [--align {icp,DIR} [--align-max-dist D] [--align-metric {point,plane}]] [--device D]
+                                    [--align {icp,DIR} [--align-max-dist D] [--align-metric {point,plane}]
+                                     [--align-init global --align-voxel H]] [--device D]
         for every scene present in both trees: results/EXP/<scene>/<S>/ of --root (made on --from-scans) -> the same files at the
         target's V under ROOT2/results/EXP/<scene>/<S>/ (pseudo_labels.sgl and the per-vector .npy files, as `thin --lift` writes
         them), ROOT2/results/EXP/<scene>/<S>/<scene>.transfer.npz (nearest, d2; with --vote also rep, votes, tied) and one
@@ -145,8 +146,21 @@ def check_vote(vote_k, vote_on, index: str) -> None:
         raise ValueError("--vote-on (vote_on=) must be 'seg' or one of %s, not %r" % (", ".join(hip.LABEL_NAMES), vote_on))
 
 
-def check_align(align, align_max_dist, index: str, align_metric=None) -> None:
-    """the combinations of align, align_max_dist, align_metric and index that are refused before anything runs (ValueError)"""
+ALIGN_INITS = ("global",)
+
+
+def check_align(align, align_max_dist, index: str, align_metric=None, align_init=None, align_voxel=None) -> None:
+    """the combinations of align, align_max_dist, align_metric, align_init, align_voxel and index that are refused before anything runs
+    (ValueError)"""
+    if align_init is not None:
+        if align_init not in ALIGN_INITS:
+            raise ValueError("--align-init (align_init=) must be 'global', not %r" % (align_init,))
+        if align != "icp":
+            raise ValueError("--align-init (align_init=) needs --align icp (align='icp'): a transform that is read needs no starting pose")
+        if align_voxel is None or not float(align_voxel) > 0.0:
+            raise ValueError("--align-init global needs --align-voxel (align_voxel=) > 0: the edge both scans are thinned at has no default")
+    elif align_voxel is not None:
+        raise ValueError("--align-voxel (align_voxel=) needs --align-init global (align_init='global')")
     if align_metric is not None:
         if align != "icp":
             raise ValueError("--align-metric (align_metric=) needs --align icp (align='icp'): without an ICP there is no metric to choose")
@@ -168,16 +182,23 @@ def check_align(align, align_max_dist, index: str, align_metric=None) -> None:
             raise ValueError("--align (align=) must be 'icp' or a directory of <scene>%s files, not %r" % (rigid.ALIGN_SUFFIX, align))
 
 
-def scene_alignment(scene: str, src_xyz, dst_xyz, align, align_max_dist, device=None, stream=None, align_metric=None, src_faces=None):
+def scene_alignment(scene: str, src_xyz, dst_xyz, align, align_max_dist, device=None, stream=None, align_metric=None, src_faces=None,
+                    align_init=None, align_voxel=None):
     """-> (T float64 [4,4] mapping the target into the source's frame, the scene's `align` record of the report).  align_metric="plane":
-    the source is the fixed cloud, so the normals are the source's (`src_faces`, else its kNN-10 covariance)."""
+    the source is the fixed cloud, so the normals are the source's (`src_faces`, else its kNN-10 covariance).  align_init="global": the
+    ICP starts from register.global_registration of the two scans thinned at `align_voxel`; the record gains `global`."""
+    init, coarse = None, {}
+    if align == "icp" and align_init == "global":
+        from .register import global_registration
+        c = global_registration(dst_xyz, src_xyz, voxel=float(align_voxel), device=device, stream=stream)
+        init, coarse = c.T, {"global": c.scalars()}
     if align == "icp" and align_metric == "plane":
         nrm, how = rigid.scan_normals(src_xyz, src_faces, device=device)
-        al = rigid.icp(dst_xyz, src_xyz, align_max_dist, device=device, stream=stream, metric="plane", normals=nrm)
-        return al.T, dict(al.scalars(), normals=how, source="icp")
+        al = rigid.icp(dst_xyz, src_xyz, align_max_dist, init=init, device=device, stream=stream, metric="plane", normals=nrm)
+        return al.T, dict(al.scalars(), normals=how, source="icp", **coarse)
     if align == "icp":
-        al = rigid.icp(dst_xyz, src_xyz, align_max_dist, device=device, stream=stream)
-        return al.T, dict(al.scalars(), source="icp")
+        al = rigid.icp(dst_xyz, src_xyz, align_max_dist, init=init, device=device, stream=stream)
+        return al.T, dict(al.scalars(), source="icp", **coarse)
     path = rigid.align_path(align, scene)
     if not os.path.isfile(path):
         raise FileNotFoundError(f"{path}: no alignment for this scene under --align (align=)")
@@ -191,14 +212,16 @@ def _scan_xyz(scans_dir: str, scene: str, faces: bool = False):
 
 
 def transfer_scene(scene: str, from_scans: str, to_scans: str, exp: str, stage: str, out_root: str, root: str = ".", index: str = "grid",
-                   device=None, stream=None, vote_k=None, vote_on=None, align=None, align_max_dist=None, align_metric=None):
+                   device=None, stream=None, vote_k=None, vote_on=None, align=None, align_max_dist=None, align_metric=None, align_init=None,
+                   align_voxel=None):
     """One scene: results/<exp>/<scene>/<stage>/ under `root`, made on <from_scans>/<scene>, -> the same files for <to_scans>/<scene>
     under <out_root>/results/...; -> (its entry of transfer_report.json, the files written).  With `vote_k` the files are gathered by
     `rep`, the nearest of the vote_k nearest source vertices that holds their most frequent `vote_on` label.  With `align`
     ("icp" with `align_max_dist`, or a directory of <scene>.align.json) the search runs on the target moved into the source's frame
-    (DESIGN.md 8p); the files are still the target's.  `align_metric` ("point" | "plane", with align="icp"): the ICP's metric."""
+    (DESIGN.md 8p); the files are still the target's.  `align_metric` ("point" | "plane", with align="icp"): the ICP's metric.
+    `align_init="global"` with `align_voxel` (align="icp" only): the ICP starts from a global registration."""
     check_vote(vote_k, vote_on, index)
-    check_align(align, align_max_dist, index, align_metric)
+    check_align(align, align_max_dist, index, align_metric, align_init, align_voxel)
     src_dir = os.path.join(root, "results", exp, scene, stage)
     if not os.path.isdir(src_dir):
         raise FileNotFoundError(f"{src_dir}: no such export directory")
@@ -207,7 +230,7 @@ def transfer_scene(scene: str, from_scans: str, to_scans: str, exp: str, stage: 
     voted, aligned, query = {}, {}, dst_xyz
     if align is not None:
         T, record = scene_alignment(scene, src_xyz, dst_xyz, align, align_max_dist, device=device, stream=stream, align_metric=align_metric,
-                                    src_faces=src_faces)
+                                    src_faces=src_faces, align_init=align_init, align_voxel=align_voxel)
         aligned, query = {"T": T}, rigid.apply(dst_xyz, T, device=device, stream=stream)
     if vote_k is None:
         d_near, d_d2 = nearest_vertex(src_xyz, query, index=index, device=device, stream=stream)
@@ -235,13 +258,14 @@ def transfer_scene(scene: str, from_scans: str, to_scans: str, exp: str, stage: 
 
 
 def transfer_results(from_scans: str, to_scans: str, exp: str, stage: str, out_root: str, root: str = ".", scenes=None, workers: int = 4,
-                     index: str = "grid", device=None, vote_k=None, vote_on=None, align=None, align_max_dist=None, align_metric=None):
+                     index: str = "grid", device=None, vote_k=None, vote_on=None, align=None, align_max_dist=None, align_metric=None,
+                     align_init=None, align_voxel=None):
     """Every scene of `from_scans` (or the named ones) that both trees hold -> (report {scene: entry}, missing {scene: why}); writes
     <out_root>/transfer_report.json.  Workers are threads, each with its own stream.  `vote_k`, `vote_on`, `align`, `align_max_dist`,
-    `align_metric`: transfer_scene's."""
+    `align_metric`, `align_init`, `align_voxel`: transfer_scene's."""
     hip.knn_index(index)
     check_vote(vote_k, vote_on, index)
-    check_align(align, align_max_dist, index, align_metric)
+    check_align(align, align_max_dist, index, align_metric, align_init, align_voxel)
     dev = torch_device(device)
     have_src, have_dst = set(scans.scan_names(from_scans)), set(scans.scan_names(to_scans))
     if scenes is None:
@@ -259,7 +283,8 @@ def transfer_results(from_scans: str, to_scans: str, exp: str, stage: str, out_r
                                                                                            index, device=dev, stream=stream, vote_k=vote_k,
                                                                                            vote_on=vote_on, align=align,
                                                                                            align_max_dist=align_max_dist,
-                                                                                           align_metric=align_metric)[0]))
+                                                                                           align_metric=align_metric, align_init=align_init,
+                                                                                           align_voxel=align_voxel)[0]))
     os.makedirs(out_root, exist_ok=True)
     scans.write_report(os.path.join(out_root, REPORT_NAME), {"experiment": exp, "stage": stage, "index": index, "scenes": report, "missing": missing})
     return report, missing
@@ -287,20 +312,24 @@ def main(argv=None) -> int:
     ap.add_argument("--align-max-dist", type=float, default=None, metavar="D", help="the ICP's inlier radius in the scans' unit (--align icp only)")
     ap.add_argument("--align-metric", choices=rigid.METRICS, default=None,
                     help="the ICP's metric (--align icp only): point (the default) or plane, point-to-plane on the source's normals")
+    ap.add_argument("--align-init", choices=ALIGN_INITS, default=None,
+                    help="where the ICP starts (--align icp only): global runs a global registration of the two scans first (with --align-voxel)")
+    ap.add_argument("--align-voxel", type=float, default=None, metavar="H", help="the edge both scans are thinned at for --align-init global")
     ap.add_argument("--device", default=None)
     a = ap.parse_args(argv)
     scans.check_workers(ap, a.workers)
     try:
         check_vote(a.vote, a.vote_on, a.index)
-        check_align(a.align, a.align_max_dist, a.index, a.align_metric)
+        check_align(a.align, a.align_max_dist, a.index, a.align_metric, a.align_init, a.align_voxel)
     except ValueError as e:
         ap.error(str(e))
     try:
         report, missing = transfer_results(a.from_scans, a.to_scans, a.exp_name, a.stage, a.out, a.root, scans.scene_list(a.scenes), a.workers,
                                            a.index, a.device, vote_k=a.vote, vote_on=a.vote_on, align=a.align,
-                                           align_max_dist=a.align_max_dist, align_metric=a.align_metric)
+                                           align_max_dist=a.align_max_dist, align_metric=a.align_metric, align_init=a.align_init,
+                                           align_voxel=a.align_voxel)
     except ValueError as e:
-        if "--index grid" not in str(e) and "--vote-on" not in str(e) and "max_dist" not in str(e):
+        if "--index grid" not in str(e) and "--vote-on" not in str(e) and "max_dist" not in str(e) and "global_registration" not in str(e):
             raise
         ap.error(str(e))
     for scene, e in report.items():
