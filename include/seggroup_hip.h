@@ -1086,6 +1086,61 @@ int sg_ransac_stage_times(float* h_us, int cap);
 const char* sg_ransac_stage_name(int i);
 int sg_triangle_pose(const double* h_a, const double* h_b, double* h_T);
 
+/* Plane extraction: the dominant planes of a cloud by hypothesise-and-count RANSAC, a least-squares refit and the
+ * labelling of a plane's points.  Arithmetic is double on the widened fp32 inputs, dot(a, b) = (a0*b0 + a1*b1) + a2*b2, a x b =
+ * (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0), nothing contracted.  No floating-point atomics: two calls on the same input write
+ * the same bytes.  Points are d_xyz [N, stride >= 3] fp32, 0 <= N <= 2^24 (above: SG_EUNSUP).
+ *
+ * The inlier test of a plane (n, d), one function for all three device entries: |n.p + d| <= dist, and, when d_normals float [N,3] is not
+ * NULL, also min_cos <= |n.nrm_i| < inf -- a normal with a component that is not finite fails it.  A point i is FREE when d_label is NULL
+ * or d_label[i] < 0.
+ *
+ * sg_plane_ransac: the free points, in ASCENDING index, form a dense list of M entries (*h_free = M); triples hold POSITIONS in that
+ *   list.  Triple h = (t0, t1, t2): row h of d_triples int32 [H,3], or, when d_triples is NULL, sg_ransac_count's generator with C := M.
+ *   With p_e the point at position t_e, u = p1 - p0, v = p2 - p0, w = p2 - p1, c = u x v and |x| = sqrt(x.x), hypothesis h is REJECTED
+ *   (d_count[h] = -1, d_plane[h] = 0 0 0 0) unless  t0, t1, t2 are distinct  and  |u| >= min_edge, |v| >= min_edge, |w| >= min_edge  and
+ *   |c| >= (min_sine * |u|) * |v|  -- written so that a NaN rejects.  A kept hypothesis has n = c / |c| (component by component),
+ *   d = -(n.p0), d_plane[h] = (n, d) as double [H,4], and d_count[h] = the number of free points that pass the inlier test.  *h_best = the
+ *   h of the highest count, the lowest h among equals, -1 when every hypothesis was rejected (or H = 0).  M < 3: SG_OK, every hypothesis
+ *   rejected, *h_best = -1, d_triples is not read.  0 <= H <= 2^20 (above: SG_EUNSUP).  SG_EINVAL: null pointers, a stride below 3, dist
+ *   not a finite length >= 0, min_edge not a finite length > 0, min_sine outside (0, 1], min_cos outside 0..1 (read only with d_normals), a
+ *   workspace below sg_plane_ransac_ws_bytes(N, H, d_normals != NULL) -- before the first device call --, an entry of d_triples outside
+ *   0..M-1 (raised on the device before anything is read through it).  Synchronises the stream.
+ *
+ * sg_plane_moments: over the free points that pass the inlier test of h_plane (n, d: four doubles), with q = p - h_origin and
+ *   r = n.p + d, h_out[11] = count | sum q [3] | sum q q^T as xx xy xz yy yz zz | sum r*r.  The reduction trees are sg_align_moments': a
+ *   function of N alone.  N = 0: zeros.  SG_EINVAL: null pointers, a plane or an origin that is not finite, dist, min_cos as above, a
+ *   workspace below sg_plane_moments_ws_bytes(N).  Synchronises the stream.
+ *
+ * sg_plane_fit: host only, no device call.  h_m is sg_plane_moments' h_out for the same h_origin.  C = sum q q^T - (sum q)(sum q)^T / count,
+ *   diagonalised by cyclic Jacobi (no LAPACK, as sg_align_plane_solve); n = the eigenvector of the smallest eigenvalue, unit length, its
+ *   largest-magnitude component positive (the lowest axis among equals); h_plane = (n, -(n.centroid)), h_centroid [3] (may be NULL) =
+ *   h_origin + sum q / count, *h_rms (may be NULL) = sqrt(max(smallest eigenvalue, 0) / count), the inliers' rms distance to the fitted
+ *   plane.  SG_EUNSUP ("degenerate"): count < 3, or a middle eigenvalue that is not above 2^-40 of the largest (points on a line or in one
+ *   place: zero up to the rounding Jacobi leaves).  SG_EINVAL: null pointers, a moment or an origin that is not finite.
+ *
+ * sg_plane_assign: d_label[i] = id at every free point that passes the inlier test of h_plane; *h_labelled = how many.  id >= 0.  SG_EINVAL
+ *   as sg_plane_moments, a negative id, a NULL d_label.  Synchronises the stream.
+ *
+ * sg_plane_set_tuning(compact, timed), per calling thread: compact = 0 lets the counting kernel walk all H hypotheses and skip the
+ *   rejected ones in place instead of walking the compacted kept ones (the default; it cannot change a result); timed != 0 brackets the
+ *   stages of the thread's next calls with events, and sg_plane_stage_times / sg_plane_stage_name then give the microseconds of compact,
+ *   generate, count (the last sg_plane_ransac), moments and assign (the last call of each). */
+size_t sg_plane_ransac_ws_bytes(int N, int H, int with_normals);
+int sg_plane_ransac(const float* d_xyz, int stride, int N, const int32_t* d_label, const float* d_normals, double min_cos, int H, uint64_t seed,
+                    const int32_t* d_triples, double dist, double min_edge, double min_sine, int32_t* d_count, double* d_plane, int* h_free,
+                    int* h_best, void* d_ws, size_t ws_bytes, void* stream);
+size_t sg_plane_moments_ws_bytes(int N);
+int sg_plane_moments(const float* d_xyz, int stride, int N, const int32_t* d_label, const float* d_normals, double min_cos, const double* h_plane,
+                     double dist, const double* h_origin, double* h_out, void* d_ws, size_t ws_bytes, void* stream);
+int sg_plane_fit(const double* h_m, const double* h_origin, double* h_plane, double* h_centroid, double* h_rms);
+size_t sg_plane_assign_ws_bytes(int N);
+int sg_plane_assign(const float* d_xyz, int stride, int N, const float* d_normals, double min_cos, const double* h_plane, double dist, int id,
+                    int32_t* d_label, int* h_labelled, void* d_ws, size_t ws_bytes, void* stream);
+int sg_plane_set_tuning(int compact, int timed);
+int sg_plane_stage_times(float* h_us, int cap);
+const char* sg_plane_stage_name(int i);
+
 /* Connected components of a scan's graph.  Vertices 0..V-1, 1 <= V <= SG_MAX_CLOUD_POINTS; the undirected graph comes from
  * one of three sources:
  *   sg_components_edges  d_edges int32 [E,2], 0 <= E < 2^30: a row (a, a) is a no-op, duplicates and both orientations are allowed, no order

@@ -296,36 +296,51 @@ def clean_scan(scene_path: str, out_dir: str, min_verts: Optional[int] = None, l
         entry.update(radius=float(radius), R=stats["R"], cell=stats["cell"], dropped={"size": by_size})
         if d_count is not None:
             entry["dropped"]["min_neighbours"] = by_count
-    segs = os.path.join(scene_path, scans.segs_json_name(scene))
-    doc = None
-    if os.path.exists(segs):
-        with open(segs) as f:
-            doc = json.load(f)
-        ids = np.asarray(doc["segIndices"], dtype=np.int64)
-        if ids.shape[0] != v:
-            raise ValueError(f"{segs}: {ids.shape[0]} segIndices for {v} vertices")
-        doc["segIndices"] = ids[kept].tolist()
+    doc, ids = kept_segs(scene_path, scene, v, kept)
+    if doc is not None:
         before, after = np.unique(ids), np.unique(ids[kept])
         entry.update(source_segments=int(before.shape[0]), kept_segments=int(after.shape[0]), lost_segments=np.setdiff1d(before, after).tolist())
     if report_only:
         return entry
-    os.makedirs(dst, exist_ok=True)
-    write_ply(ply_out, xyz[kept], rgb[kept], new_faces)
     extra = {}
     if source == "radius":
         extra.update(radius=np.float32(radius), min_neighbours=np.int32(-1 if min_neighbours is None else min_neighbours))
     if d_count is not None:
         extra["count"] = d_count.cpu().numpy()
-    np.savez(os.path.join(dst, scene + MAP_SUFFIX), kept=kept, new_of_old=new_of_old, comp=comp, min_verts=np.int32(-1 if min_verts is None else min_verts),
-             largest=np.bool_(largest), source=np.str_(source), knn=np.int32(knn if source == "knn" else 0),
-             max_edge=np.float32(np.inf if max_edge is None else max_edge), **extra)
+    write_kept_scan(scene_path, dst, scene, xyz, rgb, kept, new_of_old, new_faces, doc, comp=comp,
+                    min_verts=np.int32(-1 if min_verts is None else min_verts), largest=np.bool_(largest), source=np.str_(source),
+                    knn=np.int32(knn if source == "knn" else 0), max_edge=np.float32(np.inf if max_edge is None else max_edge), **extra)
+    return entry
+
+
+def kept_segs(scene_path: str, scene: str, v: int, kept):
+    """the scan's segs.json taken at the kept vertices -> (its document with segIndices cut down, the raw scan's int64 [V] ids), or
+    (None, None) for a scan without one"""
+    segs = os.path.join(scene_path, scans.segs_json_name(scene))
+    if not os.path.exists(segs):
+        return None, None
+    with open(segs) as f:
+        doc = json.load(f)
+    ids = np.asarray(doc["segIndices"], dtype=np.int64)
+    if ids.shape[0] != v:
+        raise ValueError(f"{segs}: {ids.shape[0]} segIndices for {v} vertices")
+    doc["segIndices"] = ids[kept].tolist()
+    return doc, ids
+
+
+def write_kept_scan(scene_path: str, dst: str, scene: str, xyz, rgb, kept, new_of_old, new_faces, doc, **map_fields) -> None:
+    """A scan directory `dst` that holds the kept vertices of <scene_path> only, for `clean_scan` and `planes --remove`: the PLY (kept
+    vertices in ascending raw index with their colours, `new_faces`), <scene>.clean.npz (kept, new_of_old, then `map_fields` in the
+    caller's order), `doc` (kept_segs') as the segs.json when there is one, and the aggregation file copied."""
+    os.makedirs(dst, exist_ok=True)
+    write_ply(os.path.join(dst, scene + scans.PLY_SUFFIX), xyz[kept], rgb[kept], new_faces)
+    np.savez(os.path.join(dst, scene + MAP_SUFFIX), kept=kept, new_of_old=new_of_old, **map_fields)
     if doc is not None:
         with open(os.path.join(dst, scans.segs_json_name(scene)), "w") as f:
             json.dump(doc, f)
     agg = os.path.join(scene_path, scene + ".aggregation.json")
     if os.path.exists(agg):
         shutil.copyfile(agg, os.path.join(dst, scene + ".aggregation.json"))
-    return entry
 
 
 def _check_rules(who, min_verts, largest, radius, min_neighbours):

@@ -18,6 +18,9 @@
 // composed steps are still a rotation.
 //
 // Global registration: sg_triangle_pose is triangle_pose.h's function for the host, the one the RANSAC kernels run.
+//
+// Plane extraction: sg_plane_fit is the least-squares plane through the inliers that sg_plane_moments summed -- the
+// covariance from the 11 sums, the same cyclic Jacobi on 3x3, the eigenvector of the smallest eigenvalue.
 #include "sg_common.h"
 #include "triangle_pose.h"
 
@@ -52,20 +55,21 @@ constexpr double kPlaneRatio = 0x1p-40;        // smallest eigenvalue at or belo
 constexpr double kSeriesBelow = 1e-8;          // radians: below it sin and cos come from their series
 
 // eigenvalues and eigenvectors (the columns of V) of the symmetric A by cyclic Jacobi; A is destroyed.  false: not converged (non-finite input)
-bool jacobi6(double A[6][6], double V[6][6], double lambda[6]) {
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+template <int kN>
+bool jacobi(double A[kN][kN], double V[kN][kN], double lambda[kN]) {
+    for (int i = 0; i < kN; ++i)
+        for (int j = 0; j < kN; ++j) V[i][j] = i == j ? 1.0 : 0.0;
     for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
         double off = 0.0;
-        for (int p = 0; p < 5; ++p)
-            for (int q = p + 1; q < 6; ++q) off += std::fabs(A[p][q]);
+        for (int p = 0; p < kN - 1; ++p)
+            for (int q = p + 1; q < kN; ++q) off += std::fabs(A[p][q]);
         if (off == 0.0) {
-            for (int i = 0; i < 6; ++i) lambda[i] = A[i][i];
+            for (int i = 0; i < kN; ++i) lambda[i] = A[i][i];
             return true;
         }
         if (!std::isfinite(off)) return false;
-        for (int p = 0; p < 5; ++p) {
-            for (int q = p + 1; q < 6; ++q) {
+        for (int p = 0; p < kN - 1; ++p) {
+            for (int q = p + 1; q < kN; ++q) {
                 const double apq = A[p][q];
                 if (apq == 0.0) continue;
                 // an entry that no longer changes either diagonal value is set to zero, not rotated away
@@ -80,7 +84,7 @@ bool jacobi6(double A[6][6], double V[6][6], double lambda[6]) {
                 A[p][p] -= t * apq;
                 A[q][q] += t * apq;
                 A[p][q] = A[q][p] = 0.0;
-                for (int k = 0; k < 6; ++k) {
+                for (int k = 0; k < kN; ++k) {
                     if (k != p && k != q) {
                         const double akp = A[k][p], akq = A[k][q];
                         A[k][p] = A[p][k] = c * akp - s * akq;
@@ -188,7 +192,7 @@ int sg_align_plane_solve(const double* h_m, const double* h_origin, double lengt
         for (int c = r; c < 6; ++c) A[r][c] = A[c][r] = (scale[r] * h_m[k++]) * scale[c];
         g[r] = scale[r] * h_m[23 + r];
     }
-    if (!jacobi6(A, V, lambda)) return sg::fail(SG_EINVAL, "%s: the moments overflow the fit", who);
+    if (!jacobi<6>(A, V, lambda)) return sg::fail(SG_EINVAL, "%s: the moments overflow the fit", who);
     double lmax = lambda[0], lmin = lambda[0];
     for (int i = 1; i < 6; ++i) {
         lmax = std::fmax(lmax, lambda[i]);
@@ -241,6 +245,51 @@ int sg_align_plane_solve(const double* h_m, const double* h_origin, double lengt
     h_T_new[15] = 1.0;
     if (h_step)
         for (int i = 0; i < 6; ++i) h_step[i] = step[i];
+    return SG_OK;
+}
+
+int sg_plane_fit(const double* h_m, const double* h_origin, double* h_plane, double* h_centroid, double* h_rms) {
+    const char* who = "sg_plane_fit";
+    SG_REQUIRE(h_m && h_origin && h_plane, "%s: bad arguments", who);
+    for (int i = 0; i < 11; ++i) SG_REQUIRE(std::isfinite(h_m[i]), "%s: moment %d is not finite", who, i);
+    for (int i = 0; i < 3; ++i) SG_REQUIRE(std::isfinite(h_origin[i]), "%s: an origin that is not finite", who);
+    const double n = h_m[0];
+    SG_REQUIRE(n >= 0.0, "%s: a negative point count (%g)", who, n);
+    if (n < 3.0) return sg::fail(SG_EUNSUP, "%s: degenerate: %g points; a plane needs at least 3", who, n);
+    const double* sq = h_m + 1;
+    const int at[3][3] = {{4, 5, 6}, {5, 7, 8}, {6, 8, 9}};      // xx xy xz yy yz zz
+    double A[3][3], V[3][3], lambda[3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) A[r][c] = h_m[at[r][c]] - sq[r] * sq[c] / n;
+    if (!jacobi<3>(A, V, lambda)) return sg::fail(SG_EINVAL, "%s: the moments overflow the fit", who);
+    int lo = 0, hi = 0;
+    for (int i = 1; i < 3; ++i) {
+        if (lambda[i] < lambda[lo]) lo = i;
+        if (lambda[i] > lambda[hi]) hi = i;
+    }
+    if (lo == hi) hi = (lo + 1) % 3;                              // three equal eigenvalues
+    const int mid = 3 - lo - hi;
+    // the middle eigenvalue is what separates a plane from a line; Jacobi leaves rounding residue of either sign where it is zero
+    if (!(lambda[hi] > 0.0) || !(lambda[mid] > kLineRatio * lambda[hi]))
+        return sg::fail(SG_EUNSUP, "%s: degenerate: eigenvalues %g, %g, %g of the points' covariance -- they lie on a line or in a point, the "
+                                   "plane through them is free", who, lambda[lo], lambda[mid], lambda[hi]);
+    Vec3 nrm = {{V[0][lo], V[1][lo], V[2][lo]}};
+    normalise(nrm);
+    int big = 0;                                                  // the largest-magnitude component is made positive, ties to the lowest axis
+    for (int i = 1; i < 3; ++i)
+        if (std::fabs(nrm.v[i]) > std::fabs(nrm.v[big])) big = i;
+    if (nrm.v[big] < 0.0)
+        for (double& c : nrm.v) c = -c;
+    Vec3 centre;
+    for (int i = 0; i < 3; ++i) centre.v[i] = h_origin[i] + sq[i] / n;
+    const double d = -dot(nrm, centre);
+    SG_REQUIRE(std::isfinite(d) && std::isfinite(nrm.v[0]) && std::isfinite(nrm.v[1]) && std::isfinite(nrm.v[2]), "%s: the moments overflow the fit",
+               who);
+    for (int i = 0; i < 3; ++i) h_plane[i] = nrm.v[i];
+    h_plane[3] = d;
+    if (h_centroid)
+        for (int i = 0; i < 3; ++i) h_centroid[i] = centre.v[i];
+    if (h_rms) *h_rms = std::sqrt(std::fmax(lambda[lo], 0.0) / n);
     return SG_OK;
 }
 

@@ -6,8 +6,8 @@
 //                     workgroup folds kPairs consecutive pairs into ONE partial row of the workspace: thread t accumulates pairs t, t + 256,
 //                     .. of its block in order, a wave sums on the DPP network of wave_ops.h, the waves' rows are added in order.  An index
 //                     outside 0..N-1 raises the flag word before anything is read through it.
-//   k_align_fold      one workgroup: thread t adds partial rows t, t + 256, .. in order, then the same network.  Templated on the row
-//                     width: 17 sums here, 31 for the point-to-plane fit below.
+//   k_align_fold      (moments_fold_device.h) one workgroup: thread t adds partial rows t, t + 256, .. in order, then the same network.
+//                     Templated on the row width: 17 sums here, 31 for the point-to-plane fit below.
 // No floating-point atomics; grid, block and both trees are functions of U alone, so the 17 doubles do not depend on the device or the stream.
 // The kernel is a gather: 12 B of x, 8 B of idx and 4 B of d2 streamed per pair, 12 B of y read at random; the ~30 double operations per
 // pair hide under it.
@@ -19,10 +19,13 @@
 //                     k_align_moments'; 24 B of y and its normal are read at random per pair, ~130 double operations hide under them.
 #include <cmath>
 
+#include "moments_fold_device.h"
 #include "sg_common.h"
 #include "wave_ops.h"
 
 namespace {
+
+using sgmom::k_align_fold;
 
 constexpr int kBlock = 256;
 constexpr int kWave = 64;
@@ -91,26 +94,6 @@ __global__ __launch_bounds__(kBlock) void k_align_moments(const float* __restric
 #pragma unroll
         for (int w = 1; w < kWaves; ++w) s += s_rows[w][threadIdx.x];
         partial[(size_t)blockIdx.x * kMom + threadIdx.x] = s;
-    }
-}
-
-template <int kM>
-__global__ __launch_bounds__(kBlock) void k_align_fold(const double* __restrict__ partial, int rows, double* __restrict__ out) {
-    __shared__ double s_rows[kWaves][kM];
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-#pragma unroll 1
-    for (int m = 0; m < kM; ++m) {
-        double acc = 0.0;
-        for (int r = threadIdx.x; r < rows; r += kBlock) acc += partial[(size_t)r * kM + m];
-        const double s = sgw::wave_sum(acc);
-        if (lane == 0) s_rows[wave][m] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < kM) {
-        double s = s_rows[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) s += s_rows[w][threadIdx.x];
-        out[threadIdx.x] = s;
     }
 }
 

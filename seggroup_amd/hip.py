@@ -194,6 +194,17 @@ SIGNATURES = {
     "sg_ransac_stage_times": (_I, [vp, _I]),
     "sg_ransac_stage_name": (C.c_char_p, [_I]),
     "sg_triangle_pose": (_I, [vp, vp, vp]),
+    "sg_plane_ransac_ws_bytes": (_Z, [_I, _I, _I]),
+    "sg_plane_ransac": (_I, [vp, _I, _I, vp, vp, C.c_double, _I, C.c_uint64, vp, C.c_double, C.c_double, C.c_double, vp, vp, C.POINTER(C.c_int),
+                             C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_plane_moments_ws_bytes": (_Z, [_I]),
+    "sg_plane_moments": (_I, [vp, _I, _I, vp, vp, C.c_double, vp, C.c_double, vp, vp, vp, _Z, vp]),
+    "sg_plane_fit": (_I, [vp, vp, vp, vp, vp]),
+    "sg_plane_assign_ws_bytes": (_Z, [_I]),
+    "sg_plane_assign": (_I, [vp, _I, _I, vp, C.c_double, vp, C.c_double, _I, vp, C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_plane_set_tuning": (_I, [_I, _I]),
+    "sg_plane_stage_times": (_I, [vp, _I]),
+    "sg_plane_stage_name": (C.c_char_p, [_I]),
     "sg_components_ws_bytes": (_Z, [_I]),
     "sg_components_edges": (_I, [vp, C.c_longlong, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_components_faces": (_I, [vp, _I, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
