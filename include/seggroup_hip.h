@@ -1141,6 +1141,61 @@ int sg_plane_set_tuning(int compact, int timed);
 int sg_plane_stage_times(float* h_us, int cap);
 const char* sg_plane_stage_name(int i);
 
+/* Oriented boxes of labelled points: a label index -- a segmented view of a cloud by a per-point int32 vector -- and the
+ * per-label reductions a box needs.  A point is LABELLED when d_label[i] >= 0; negative labels are ignored; every non-negative int32 is a
+ * legal value and values need not be dense.  Points are rows of `stride` >= 3 floats, 0 <= N <= 2^24.  Arithmetic is double on the
+ * widened fp32 inputs, dot(a, b) = (a0*b0 + a1*b1) + a2*b2, every operation rounded once, nothing contracted, no floating-point atomics.
+ * Every device entry synchronises the stream once; a _ws_bytes function returns 0 for a size the entry does not take.
+ *
+ * sg_label_index: d_order[0..M-1] = the labelled points sorted by label, in ascending index within a label (M = N - *h_ignored);
+ *   d_value[0..L-1] = the distinct labels, ascending; d_start[0..L] = their offsets in d_order, d_start[L] = M.  Integers only: it is
+ *   np.argsort(labels[labels >= 0], kind="stable") mapped back to raw indices, with np.unique.  d_order, d_value and d_start hold N, N and
+ *   N + 1 entries (L can equal N; d_order and d_value are scratch behind M and L).  N = 0 or no labelled point: SG_OK with *h_L = 0.
+ *
+ * sg_label_moments: d_m [L,10] = count | sum q [3] | sum q q^T (xx xy xz yy yz zz) with q = p - p_first, p_first the label's lowest-index
+ *   point (d_order[d_start[l]]): every label is conditioned on itself, and the sums are the same wherever the cloud lies.  A label's list
+ *   is cut into chunks of 1,024 consecutive entries; a chunk is summed on the first tree of sg_align_moments (thread t of 256 adds entries
+ *   t, t + 256, .. in order, a wave sums on its fixed network, the four waves in order); the chunks of a label are added in ascending
+ *   order.  A function of the label's count alone: repeated calls give the same bytes.  d_lo / d_hi [L,3] = the float32 minima and maxima
+ *   per axis, exact bits of the inputs.
+ *
+ * sg_label_yaw_boxes: for every angle a < A with (c, s) = h_cs[a] (host doubles; the caller takes cos / sin, no device transcendental
+ *   enters): u = c*x + s*y, v = c*y - s*x, each two rounded products and one rounded sum or difference; the extents umin, umax, vmin,
+ *   vmax over the label.  d_best[l] = the a with the smallest (umax - umin) * (vmax - vmin), the lowest a among equals; d_ext [L,4] its
+ *   extents; d_all (NULL, or [L,A,4]) all of them.  1 <= A <= 1024.  Exact: minima are order-free.
+ *
+ * sg_label_frame_extents: d_frame [L,9] doubles, a row-major 3 x 3 frame per label; d_ext [L,6] = min, max of dot(row_k, p), k = 0, 1, 2.
+ *
+ * sg_box_axes: host only, no device call.  h_m = one row of d_m.  C = (sum q q^T - (sum q)(sum q)^T / count) / count, cyclic Jacobi; the
+ *   rows of h_R [9] are the eigenvectors by descending eigenvalue (the lower axis first among equals), rows 0 and 1 with their
+ *   largest-magnitude component positive (the lowest axis among equals), row 2 = row 0 x row 1; h_eig [3] (may be NULL) the eigenvalues
+ *   in that order.  When the largest eigenvalue is not positive -- one point, or points that coincide -- no direction is singled out and
+ *   h_R is the identity.  Points on a line fix row 0 only; row 1 is then whatever Jacobi leaves, the same on every run.
+ *
+ * SG_EINVAL: a null pointer, stride < 3, L > N, A outside 1..1024, an entry of h_cs that is not finite, a workspace below the _ws_bytes
+ *   function (all before the first device call); count < 1 or a moment that is not finite (sg_box_axes); a labelled point with a
+ *   coordinate that is not finite, or a d_start / d_order that is not an index of this cloud (one flag word on the device, read with the
+ *   call's synchronisation; the outputs are then undefined).  Ignored points may hold anything.  SG_EUNSUP: N above 2^24; d_all with
+ *   L * A > 2^24.  sg_label_set_tuning(timed), per calling thread: timed = 1 times the thread's next calls with events, and
+ *   sg_label_stage_times / sg_label_stage_name then give the microseconds of index, moments, yaw and frame, the last call of each
+ *   (room for 4 floats; tools/time_boxes.py). */
+size_t sg_label_index_ws_bytes(int N);
+int sg_label_index(const int32_t* d_label, int N, int32_t* d_order, int32_t* d_value, int32_t* d_start, int* h_L, int* h_ignored, void* d_ws,
+                   size_t ws_bytes, void* stream);
+size_t sg_label_moments_ws_bytes(int N, int L);
+int sg_label_moments(const float* d_xyz, int stride, int N, const int32_t* d_order, const int32_t* d_start, int L, double* d_m, float* d_lo,
+                     float* d_hi, void* d_ws, size_t ws_bytes, void* stream);
+size_t sg_label_yaw_boxes_ws_bytes(int N, int L, int A);
+int sg_label_yaw_boxes(const float* d_xyz, int stride, int N, const int32_t* d_order, const int32_t* d_start, int L, const double* h_cs, int A,
+                       int32_t* d_best, double* d_ext, double* d_all, void* d_ws, size_t ws_bytes, void* stream);
+size_t sg_label_frame_extents_ws_bytes(int N, int L);
+int sg_label_frame_extents(const float* d_xyz, int stride, int N, const int32_t* d_order, const int32_t* d_start, int L, const double* d_frame,
+                           double* d_ext, void* d_ws, size_t ws_bytes, void* stream);
+int sg_box_axes(const double* h_m, double* h_R, double* h_eig);
+int sg_label_set_tuning(int timed);
+int sg_label_stage_times(float* h_us, int cap);
+const char* sg_label_stage_name(int i);
+
 /* Connected components of a scan's graph.  Vertices 0..V-1, 1 <= V <= SG_MAX_CLOUD_POINTS; the undirected graph comes from
  * one of three sources:
  *   sg_components_edges  d_edges int32 [E,2], 0 <= E < 2^30: a row (a, a) is a no-op, duplicates and both orientations are allowed, no order

@@ -21,6 +21,9 @@
 //
 // Plane extraction: sg_plane_fit is the least-squares plane through the inliers that sg_plane_moments summed -- the
 // covariance from the 11 sums, the same cyclic Jacobi on 3x3, the eigenvector of the smallest eigenvalue.
+//
+// Oriented boxes: sg_box_axes is the frame of one label from sg_label_moments' ten sums -- the covariance, the same Jacobi,
+// the eigenvectors as rows by descending eigenvalue, signs fixed, the third row the cross product of the first two.
 #include "sg_common.h"
 #include "triangle_pose.h"
 
@@ -290,6 +293,46 @@ int sg_plane_fit(const double* h_m, const double* h_origin, double* h_plane, dou
     if (h_centroid)
         for (int i = 0; i < 3; ++i) h_centroid[i] = centre.v[i];
     if (h_rms) *h_rms = std::sqrt(std::fmax(lambda[lo], 0.0) / n);
+    return SG_OK;
+}
+
+int sg_box_axes(const double* h_m, double* h_R, double* h_eig) {
+    const char* who = "sg_box_axes";
+    SG_REQUIRE(h_m && h_R, "%s: bad arguments", who);
+    for (int i = 0; i < 10; ++i) SG_REQUIRE(std::isfinite(h_m[i]), "%s: moment %d is not finite", who, i);
+    const double n = h_m[0];
+    SG_REQUIRE(n >= 1.0, "%s: a box needs at least one point (count %g)", who, n);
+    const double* sq = h_m + 1;
+    const int at[3][3] = {{4, 5, 6}, {5, 7, 8}, {6, 8, 9}};      // xx xy xz yy yz zz
+    double A[3][3], V[3][3], lambda[3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) A[r][c] = (h_m[at[r][c]] - sq[r] * sq[c] / n) / n;
+    if (!jacobi<3>(A, V, lambda)) return sg::fail(SG_EINVAL, "%s: the moments overflow the covariance", who);
+    int ord[3] = {0, 1, 2};                                       // descending eigenvalue, the lower index first among equals
+    for (int i = 1; i < 3; ++i)
+        for (int j = i; j > 0 && lambda[ord[j]] > lambda[ord[j - 1]]; --j) std::swap(ord[j], ord[j - 1]);
+    Vec3 row[3];
+    if (!(lambda[ord[0]] > 0.0)) {
+        // one point, or points that coincide: no direction is singled out, the frame is the identity
+        for (int r = 0; r < 3; ++r) row[r] = {{r == 0 ? 1.0 : 0.0, r == 1 ? 1.0 : 0.0, r == 2 ? 1.0 : 0.0}};
+    } else {
+        for (int r = 0; r < 2; ++r) {
+            row[r] = {{V[0][ord[r]], V[1][ord[r]], V[2][ord[r]]}};
+            int big = 0;                                          // the largest-magnitude component is made positive, ties to the lowest axis
+            for (int i = 1; i < 3; ++i)
+                if (std::fabs(row[r].v[i]) > std::fabs(row[r].v[big])) big = i;
+            if (row[r].v[big] < 0.0)
+                for (double& c : row[r].v) c = -c;
+        }
+        row[2] = cross(row[0], row[1]);
+    }
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            SG_REQUIRE(std::isfinite(row[r].v[c]), "%s: the moments overflow the covariance", who);
+            h_R[3 * r + c] = row[r].v[c];
+        }
+    if (h_eig)
+        for (int r = 0; r < 3; ++r) h_eig[r] = lambda[ord[r]];
     return SG_OK;
 }
 

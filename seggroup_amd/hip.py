@@ -205,6 +205,18 @@ SIGNATURES = {
     "sg_plane_set_tuning": (_I, [_I, _I]),
     "sg_plane_stage_times": (_I, [vp, _I]),
     "sg_plane_stage_name": (C.c_char_p, [_I]),
+    "sg_label_index_ws_bytes": (_Z, [_I]),
+    "sg_label_index": (_I, [vp, _I, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, _Z, vp]),
+    "sg_label_moments_ws_bytes": (_Z, [_I, _I]),
+    "sg_label_moments": (_I, [vp, _I, _I, vp, vp, _I, vp, vp, vp, vp, _Z, vp]),
+    "sg_label_yaw_boxes_ws_bytes": (_Z, [_I, _I, _I]),
+    "sg_label_yaw_boxes": (_I, [vp, _I, _I, vp, vp, _I, vp, _I, vp, vp, vp, vp, _Z, vp]),
+    "sg_label_frame_extents_ws_bytes": (_Z, [_I, _I]),
+    "sg_label_frame_extents": (_I, [vp, _I, _I, vp, vp, _I, vp, vp, vp, _Z, vp]),
+    "sg_box_axes": (_I, [vp, vp, vp]),
+    "sg_label_set_tuning": (_I, [_I]),
+    "sg_label_stage_times": (_I, [vp, _I]),
+    "sg_label_stage_name": (C.c_char_p, [_I]),
     "sg_components_ws_bytes": (_Z, [_I]),
     "sg_components_edges": (_I, [vp, C.c_longlong, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
     "sg_components_faces": (_I, [vp, _I, _I, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
