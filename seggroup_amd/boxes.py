@@ -41,7 +41,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import hip, scans
-from .device import device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
+from .device import device_rows, device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
 
 MAX_POINTS = 1 << 24
 MAX_ANGLES = 1024
@@ -104,16 +104,6 @@ class Boxes:
         return self.center[:, None, :] + np.einsum("lka,lac->lkc", half, self.R)
 
 
-def _cloud(xyz, dev, who: str):
-    import torch
-    d = device_tensor(xyz, torch.float32, dev)
-    if d.dim() != 2 or d.shape[1] < 3:
-        raise ValueError(f"{who}: a cloud is [N, >= 3] rows with xyz first")
-    if d.shape[0] > MAX_POINTS:
-        raise hip.SgError(hip.SG_EUNSUP, "%s: %d points; a call takes at most 2^24" % (who, d.shape[0]))
-    return d
-
-
 def label_index(labels, device=None, stream=None) -> LabelIndex:
     """sg_label_index of an int vector [N] -> LabelIndex.  A point is labelled when its label is >= 0."""
     import torch
@@ -152,7 +142,7 @@ def label_moments(xyz, index: LabelIndex, device=None, stream=None) -> Moments:
     dev = torch_device(device)
     lib = hip.lib()
     with torch.cuda.device(dev), on_stream(stream):
-        d_xyz = _cloud(xyz, dev, "label_moments")
+        d_xyz = device_rows(xyz, dev, "label_moments", MAX_POINTS)
         n, l = _sizes(d_xyz, index, "label_moments")
         m = torch.empty((l, 10), dtype=torch.float64, device=dev)
         lo = torch.empty((l, 3), dtype=torch.float32, device=dev)
@@ -190,7 +180,7 @@ def yaw_boxes(xyz, index: LabelIndex, angles=DEFAULT_ANGLES, cs=None, all_extent
     dev = torch_device(device)
     lib = hip.lib()
     with torch.cuda.device(dev), on_stream(stream):
-        d_xyz = _cloud(xyz, dev, "yaw_boxes")
+        d_xyz = device_rows(xyz, dev, "yaw_boxes", MAX_POINTS)
         n, l = _sizes(d_xyz, index, "yaw_boxes")
         best = torch.empty(l, dtype=torch.int32, device=dev)
         ext = torch.empty((l, 4), dtype=torch.float64, device=dev)
@@ -214,7 +204,7 @@ def frame_extents(xyz, index: LabelIndex, frames, device=None, stream=None):
     dev = torch_device(device)
     lib = hip.lib()
     with torch.cuda.device(dev), on_stream(stream):
-        d_xyz = _cloud(xyz, dev, "frame_extents")
+        d_xyz = device_rows(xyz, dev, "frame_extents", MAX_POINTS)
         n, l = _sizes(d_xyz, index, "frame_extents")
         d_fr = device_tensor(frames, torch.float64, dev)
         if tuple(d_fr.shape) not in ((l, 3, 3), (l, 9)):
@@ -304,7 +294,7 @@ def label_boxes(xyz, labels, kind="yaw", angles=None, min_points=1, device=None,
     _check_pair(xyz, labels)
     dev = torch_device(device)
     with torch.cuda.device(dev), on_stream(stream):
-        d_xyz = _cloud(xyz, dev, "label_boxes")
+        d_xyz = device_rows(xyz, dev, "label_boxes", MAX_POINTS)
     index = label_index(labels, dev, stream)
     mom = label_moments(d_xyz, index, dev, stream)
     best = ext = frames = None

@@ -3,11 +3,11 @@
 //   k_rigid_apply     out[u] = (float)(R x[u] + t) in double, one thread a point, every operation rounded once in the order the header
 //                     states (-ffp-contract=off: no fma), so the bytes are those of the element-wise NumPy statement.
 //   k_align_moments   the 17 sums of the closed-form fit (n | sum a | sum b | sum a b^T | sum d2) over the inlier pairs, in double.  A
-//                     workgroup folds kPairs consecutive pairs into ONE partial row of the workspace: thread t accumulates pairs t, t + 256,
-//                     .. of its block in order, a wave sums on the DPP network of wave_ops.h, the waves' rows are added in order.  An index
-//                     outside 0..N-1 raises the flag word before anything is read through it.
-//   k_align_fold      (moments_fold_device.h) one workgroup: thread t adds partial rows t, t + 256, .. in order, then the same network.
-//                     Templated on the row width: 17 sums here, 31 for the point-to-plane fit below.
+//                     workgroup folds 1,024 consecutive pairs into ONE partial row of the workspace: thread t accumulates pairs t, t + 256,
+//                     .. of its block in order and sgmom::block_row (moments_device.h) is the first tree.  An index outside 0..N-1 raises
+//                     the flag word before anything is read through it.
+//   sgmom::k_fold     (moments_device.h) the second tree over the partial rows, templated on the row width: 17 sums here, 31 for the
+//                     point-to-plane fit below.  sgmom::reduce is the host sequence around both: workspace, launches, one copy back.
 // No floating-point atomics; grid, block and both trees are functions of U alone, so the 17 doubles do not depend on the device or the stream.
 // The kernel is a gather: 12 B of x, 8 B of idx and 4 B of d2 streamed per pair, 12 B of y read at random; the ~30 double operations per
 // pair hide under it.
@@ -19,25 +19,20 @@
 //                     k_align_moments'; 24 B of y and its normal are read at random per pair, ~130 double operations hide under them.
 #include <cmath>
 
-#include "moments_fold_device.h"
+#include "moments_device.h"
 #include "sg_common.h"
-#include "wave_ops.h"
 
 namespace {
 
-using sgmom::k_align_fold;
+using sgmom::kBlock;
+using sgmom::kPer;
+using sgmom::Origin;
+using sgmom::Rigid;
 
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kBlock / kWave;
-constexpr int kPer = 4;                       // pairs per thread: four independent gathers in flight
-constexpr int kPairs = kBlock * kPer;         // pairs per workgroup = per partial row
 constexpr int kMom = 17;
 constexpr int kPlaneMom = 31;                 // usable | skipped | 21 of J J^T | 6 of J r | r r | d2
 
-struct Rigid { double m[12]; };               // row-major 3x4 [R|t]
 struct Origins { double x[3], y[3]; };
-struct Origin { double c[3]; };
 
 __global__ __launch_bounds__(kBlock) void k_rigid_apply(const float* __restrict__ x, int xs, int U, Rigid T, float* __restrict__ out) {
     const int u = blockIdx.x * kBlock + threadIdx.x;
@@ -49,15 +44,14 @@ __global__ __launch_bounds__(kBlock) void k_rigid_apply(const float* __restrict_
     for (int r = 0; r < 3; ++r) o[r] = (float)(((T.m[4 * r] * px + T.m[4 * r + 1] * py) + T.m[4 * r + 2] * pz) + T.m[4 * r + 3]);
 }
 
-// every lane of every wave reaches the reductions (wave_sum needs all 64 lanes): a pair past U, outside the radius or with a bad index adds 0
+// every thread reaches block_row: a pair past U, outside the radius or with a bad index adds 0
 __global__ __launch_bounds__(kBlock) void k_align_moments(const float* __restrict__ x, int xs, int U, const float* __restrict__ y, int ys, int N,
                                                           const int64_t* __restrict__ idx, const float* __restrict__ d2, float max_d2, Origins o,
                                                           double* __restrict__ partial, int* __restrict__ flag) {
-    __shared__ double s_rows[kWaves][kMom];
     double acc[kMom];
 #pragma unroll
     for (int m = 0; m < kMom; ++m) acc[m] = 0.0;
-    const long long base = (long long)blockIdx.x * kPairs + threadIdx.x;
+    const long long base = (long long)blockIdx.x * sgmom::kItems + threadIdx.x;
     bool bad = false;
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
@@ -82,19 +76,7 @@ __global__ __launch_bounds__(kBlock) void k_align_moments(const float* __restric
         acc[16] += (double)dd;
     }
     if (bad) *flag = 1;
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-#pragma unroll
-    for (int m = 0; m < kMom; ++m) {
-        const double s = sgw::wave_sum(acc[m]);
-        if (lane == 0) s_rows[wave][m] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < kMom) {
-        double s = s_rows[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) s += s_rows[w][threadIdx.x];
-        partial[(size_t)blockIdx.x * kMom + threadIdx.x] = s;
-    }
+    sgmom::block_row(acc, partial + (size_t)blockIdx.x * kMom);
 }
 
 // the point-to-plane twin of k_align_moments: the same blocks, the same pair order, the same two trees, 31 sums.  R, t and the origin are
@@ -103,11 +85,10 @@ __global__ __launch_bounds__(kBlock) void k_plane_moments(const float* __restric
                                                           int N, const float* __restrict__ nrm, int ns, const int64_t* __restrict__ idx,
                                                           const float* __restrict__ d2, float max_d2, Origin o, double* __restrict__ partial,
                                                           int* __restrict__ flag) {
-    __shared__ double s_rows[kWaves][kPlaneMom];
     double acc[kPlaneMom];
 #pragma unroll
     for (int m = 0; m < kPlaneMom; ++m) acc[m] = 0.0;
-    const long long base = (long long)blockIdx.x * kPairs + threadIdx.x;
+    const long long base = (long long)blockIdx.x * sgmom::kItems + threadIdx.x;
     bool bad = false;
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
@@ -149,26 +130,8 @@ __global__ __launch_bounds__(kBlock) void k_plane_moments(const float* __restric
         acc[30] += (double)dd;
     }
     if (bad) *flag = 1;
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-#pragma unroll
-    for (int m = 0; m < kPlaneMom; ++m) {
-        const double s = sgw::wave_sum(acc[m]);
-        if (lane == 0) s_rows[wave][m] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < kPlaneMom) {
-        double s = s_rows[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) s += s_rows[w][threadIdx.x];
-        partial[(size_t)blockIdx.x * kPlaneMom + threadIdx.x] = s;
-    }
+    sgmom::block_row(acc, partial + (size_t)blockIdx.x * kPlaneMom);
 }
-
-template <int kM> struct LandingOf { double m[kM]; int flag; int pad; };   // what one copy brings back: the sums and the flag word
-using Landing = LandingOf<kMom>;
-using PlaneLanding = LandingOf<kPlaneMom>;
-
-bool finite3(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 }  // namespace
 
@@ -179,10 +142,7 @@ int sg_rigid_apply(const float* d_x, int x_stride, int U, const double* h_T, flo
     SG_REQUIRE(U >= 0 && x_stride >= 3 && h_T, "%s: bad arguments (%d points, rows of %d floats)", who, U, x_stride);
     if (U > SG_MAX_CLOUD_POINTS) return sg::fail(SG_EUNSUP, "%s: %d points; a call takes at most %d", who, U, SG_MAX_CLOUD_POINTS);
     Rigid T;
-    for (int i = 0; i < 12; ++i) {
-        SG_REQUIRE(std::isfinite(h_T[i]), "%s: entry %d of the transform is not finite", who, i);
-        T.m[i] = h_T[i];
-    }
+    if (int rc = sgmom::read_rigid(who, h_T, &T)) return rc;
     if (U == 0) return SG_OK;
     SG_REQUIRE(d_x && d_out, "%s: bad arguments", who);
     k_rigid_apply<<<sg::cdiv(U, kBlock), kBlock, 0, sg::as_stream(stream)>>>(d_x, x_stride, U, T, d_out);
@@ -190,10 +150,7 @@ int sg_rigid_apply(const float* d_x, int x_stride, int U, const double* h_T, flo
     return SG_OK;
 }
 
-size_t sg_align_moments_ws_bytes(int U) {
-    if (U < 0 || U > SG_MAX_CLOUD_POINTS) return 0;
-    return sg::align_up(sizeof(Landing)) + sg::align_up((size_t)std::max(sg::cdiv(U, kPairs), 1) * kMom * sizeof(double));
-}
+size_t sg_align_moments_ws_bytes(int U) { return (U < 0 || U > SG_MAX_CLOUD_POINTS) ? 0 : sgmom::ws_bytes<kMom>(U); }
 
 int sg_align_moments(const float* d_x, int x_stride, int U, const float* d_y, int y_stride, int N, const int64_t* d_idx, const float* d_d2,
                      float max_d2, const double* h_origin_x, const double* h_origin_y, double* h_out, void* d_ws, size_t ws_bytes, void* stream) {
@@ -204,38 +161,25 @@ int sg_align_moments(const float* d_x, int x_stride, int U, const float* d_y, in
     SG_REQUIRE(x_stride >= 3 && y_stride >= 3, "%s: rows of at least 3 floats (x: %d, y: %d)", who, x_stride, y_stride);
     SG_REQUIRE(h_origin_x && h_origin_y && h_out, "%s: bad arguments", who);
     SG_REQUIRE(!std::isnan(max_d2), "%s: max_d2 is not a number", who);
-    SG_REQUIRE(finite3(h_origin_x) && finite3(h_origin_y), "%s: an origin that is not finite", who);
+    SG_REQUIRE(sgmom::finite_n<3>(h_origin_x) && sgmom::finite_n<3>(h_origin_y), "%s: an origin that is not finite", who);
     if (U == 0) {
         for (int m = 0; m < kMom; ++m) h_out[m] = 0.0;
         return SG_OK;
     }
     SG_REQUIRE(d_x && d_y && d_idx && d_d2 && d_ws, "%s: bad arguments", who);
-    const size_t need = sg_align_moments_ws_bytes(U);
-    SG_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    const int rows = sg::cdiv(U, kPairs);
-    sg::Carver cv(d_ws, ws_bytes);
-    Landing* d_land = cv.take<Landing>(1);
-    double* d_partial = cv.take<double>((size_t)rows * kMom);
-    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
     Origins o;
     for (int i = 0; i < 3; ++i) { o.x[i] = h_origin_x[i]; o.y[i] = h_origin_y[i]; }
     hipStream_t st = sg::as_stream(stream);
-    SG_HIP(hipMemsetAsync(d_land, 0, sizeof(Landing), st));
-    k_align_moments<<<rows, kBlock, 0, st>>>(d_x, x_stride, U, d_y, y_stride, N, d_idx, d_d2, max_d2, o, d_partial, &d_land->flag);
-    k_align_fold<kMom><<<1, kBlock, 0, st>>>(d_partial, rows, d_land->m);
-    Landing land{};
-    SG_HIP(hipMemcpyAsync(&land, d_land, sizeof(Landing), hipMemcpyDeviceToHost, st));
-    SG_HIP(hipStreamSynchronize(st));
-    SG_LAUNCH_CHECK();
-    if (land.flag) return sg::fail(SG_EINVAL, "%s: an index outside 0..%d", who, N - 1);
-    for (int m = 0; m < kMom; ++m) h_out[m] = land.m[m];
+    int flag = 0;
+    auto first = [&](int rows, double* d_partial, int* d_flag) {
+        k_align_moments<<<rows, kBlock, 0, st>>>(d_x, x_stride, U, d_y, y_stride, N, d_idx, d_d2, max_d2, o, d_partial, d_flag);
+    };
+    if (int rc = sgmom::reduce<kMom>(who, U, d_ws, ws_bytes, st, first, h_out, &flag)) return rc;
+    if (flag) return sg::fail(SG_EINVAL, "%s: an index outside 0..%d", who, N - 1);
     return SG_OK;
 }
 
-size_t sg_align_plane_moments_ws_bytes(int U) {
-    if (U < 0 || U > SG_MAX_CLOUD_POINTS) return 0;
-    return sg::align_up(sizeof(PlaneLanding)) + sg::align_up((size_t)std::max(sg::cdiv(U, kPairs), 1) * kPlaneMom * sizeof(double));
-}
+size_t sg_align_plane_moments_ws_bytes(int U) { return (U < 0 || U > SG_MAX_CLOUD_POINTS) ? 0 : sgmom::ws_bytes<kPlaneMom>(U); }
 
 int sg_align_plane_moments(const float* d_x, int x_stride, int U, const double* h_T, const float* d_y, int y_stride, int N, const float* d_n,
                            int n_stride, const int64_t* d_idx, const float* d_d2, float max_d2, const double* h_origin, double* h_out, void* d_ws,
@@ -248,36 +192,22 @@ int sg_align_plane_moments(const float* d_x, int x_stride, int U, const double* 
                n_stride);
     SG_REQUIRE(h_T && h_origin && h_out, "%s: bad arguments", who);
     SG_REQUIRE(!std::isnan(max_d2), "%s: max_d2 is not a number", who);
-    SG_REQUIRE(finite3(h_origin), "%s: an origin that is not finite", who);
+    SG_REQUIRE(sgmom::finite_n<3>(h_origin), "%s: an origin that is not finite", who);
     Rigid T;
-    for (int i = 0; i < 12; ++i) {
-        SG_REQUIRE(std::isfinite(h_T[i]), "%s: entry %d of the transform is not finite", who, i);
-        T.m[i] = h_T[i];
-    }
+    if (int rc = sgmom::read_rigid(who, h_T, &T)) return rc;
     if (U == 0) {
         for (int m = 0; m < kPlaneMom; ++m) h_out[m] = 0.0;
         return SG_OK;
     }
     SG_REQUIRE(d_x && d_y && d_n && d_idx && d_d2 && d_ws, "%s: bad arguments", who);
-    const size_t need = sg_align_plane_moments_ws_bytes(U);
-    SG_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    const int rows = sg::cdiv(U, kPairs);
-    sg::Carver cv(d_ws, ws_bytes);
-    PlaneLanding* d_land = cv.take<PlaneLanding>(1);
-    double* d_partial = cv.take<double>((size_t)rows * kPlaneMom);
-    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    Origin o;
-    for (int i = 0; i < 3; ++i) o.c[i] = h_origin[i];
+    const Origin o = sgmom::origin_of(h_origin);
     hipStream_t st = sg::as_stream(stream);
-    SG_HIP(hipMemsetAsync(d_land, 0, sizeof(PlaneLanding), st));
-    k_plane_moments<<<rows, kBlock, 0, st>>>(d_x, x_stride, U, T, d_y, y_stride, N, d_n, n_stride, d_idx, d_d2, max_d2, o, d_partial, &d_land->flag);
-    k_align_fold<kPlaneMom><<<1, kBlock, 0, st>>>(d_partial, rows, d_land->m);
-    PlaneLanding land{};
-    SG_HIP(hipMemcpyAsync(&land, d_land, sizeof(PlaneLanding), hipMemcpyDeviceToHost, st));
-    SG_HIP(hipStreamSynchronize(st));
-    SG_LAUNCH_CHECK();
-    if (land.flag) return sg::fail(SG_EINVAL, "%s: an index outside 0..%d", who, N - 1);
-    for (int m = 0; m < kPlaneMom; ++m) h_out[m] = land.m[m];
+    int flag = 0;
+    auto first = [&](int rows, double* d_partial, int* d_flag) {
+        k_plane_moments<<<rows, kBlock, 0, st>>>(d_x, x_stride, U, T, d_y, y_stride, N, d_n, n_stride, d_idx, d_d2, max_d2, o, d_partial, d_flag);
+    };
+    if (int rc = sgmom::reduce<kPlaneMom>(who, U, d_ws, ws_bytes, st, first, h_out, &flag)) return rc;
+    if (flag) return sg::fail(SG_EINVAL, "%s: an index outside 0..%d", who, N - 1);
     return SG_OK;
 }
 

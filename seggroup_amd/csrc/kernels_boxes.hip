@@ -10,8 +10,8 @@
 //                      make the chunk table; k_lb_chunk_labels bisects the offsets, one thread a chunk, so that a workgroup finds its
 //                      (label, chunk) with one load.
 //   k_lb_moments       one workgroup per (label, chunk): count | sum q | sum q q^T with q = p - p_first on the first tree of
-//                      k_align_moments (thread t adds entries t, t + 256, .. in order, a wave sums on the DPP network, the waves in order),
-//                      the float minima and maxima beside them.  A label of one chunk is written where it belongs, a longer one leaves a
+//                      moments_device.h (thread t adds entries t, t + 256, .. in order, then sgmom::block_row), the float minima and
+//                      maxima beside them.  A label of one chunk is written where it belongs, a longer one leaves a
 //                      partial row per chunk and k_lb_moments_fold adds them in ascending order.
 //   k_lb_yaw           one workgroup per (label, chunk).  The chunk's x, y go into LDS once, as doubles.  A lane owns an angle: c, s and
 //                      four extremes in registers; every lane reads the same LDS address (a broadcast, conflict-free -- 8s.4).  The four
@@ -22,6 +22,7 @@
 // No floating-point atomics.  The only integer atomic is the OR into the flag word.
 #include <cmath>
 
+#include "moments_device.h"
 #include "overseg_device.h"
 #include "scan64_device.h"
 #include "sg_common.h"
@@ -36,8 +37,9 @@ constexpr int kWaves = kBlock / kWave;
 constexpr int kMaxPoints = 1 << 24;
 constexpr int kMaxAngles = 1024;
 constexpr int kMaxAll = 1 << 24;              // L * A of d_all
-constexpr int kChunk = 1024;                  // entries of a label's list per workgroup: k_align_moments' 256 threads x 4
+constexpr int kChunk = sgmom::kItems;         // entries of a label's list per workgroup: the moment kernels' 256 threads x 4
 constexpr int kPer = kChunk / kBlock;
+static_assert(kBlock == sgmom::kBlock && kPer == sgmom::kPer, "k_lb_moments runs on the launch shape of moments_device.h");
 constexpr int kMom = 10;
 constexpr unsigned kIgnoredKey = 0x80000000u;
 constexpr int kBadPoint = 1, kBadIndex = 2;   // the flag word's bits
@@ -130,13 +132,12 @@ __device__ __forceinline__ const float* point_of(const float* __restrict__ xyz, 
     return p;
 }
 
-// every lane of every wave reaches the reductions (wave_sum needs all 64 lanes): an entry past the chunk adds 0
+// every thread of a workgroup that has a chunk reaches block_row and the wave reductions: an entry past the chunk adds 0
 __global__ __launch_bounds__(kBlock) void k_lb_moments(const float* __restrict__ xyz, int xs, int N, const int32_t* __restrict__ order,
                                                        const int32_t* __restrict__ start, int L, const int32_t* __restrict__ lab_of, const int64_t* __restrict__ coff,
                                                        const int64_t* __restrict__ poff, double* __restrict__ out_m, float* __restrict__ out_lo,
                                                        float* __restrict__ out_hi, double* __restrict__ part_m, float* __restrict__ part_e,
                                                        int* __restrict__ flag) {
-    __shared__ double s_rows[kWaves][kMom];
     __shared__ float s_ext[kWaves][6];
     Chunk ck;
     if (!find_chunk(lab_of, coff, poff, start, L, N, &ck)) return;               // uniform over the workgroup
@@ -170,24 +171,13 @@ __global__ __launch_bounds__(kBlock) void k_lb_moments(const float* __restrict__
     }
     const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
 #pragma unroll
-    for (int m = 0; m < kMom; ++m) {
-        const double s = sgw::wave_sum(acc[m]);
-        if (lane == 0) s_rows[wave][m] = s;
-    }
-#pragma unroll
     for (int r = 0; r < 3; ++r) {
         const float a = sgw::wave_min(lo[r]), b = sgw::wave_max(hi[r]);
         if (lane == 0) { s_ext[wave][r] = a; s_ext[wave][3 + r] = b; }
     }
-    __syncthreads();
     const bool whole = ck.chunks == 1;
-    if (threadIdx.x < kMom) {
-        double s = s_rows[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) s += s_rows[w][threadIdx.x];
-        if (whole) out_m[(size_t)ck.l * kMom + threadIdx.x] = s;
-        else part_m[(size_t)ck.prow * kMom + threadIdx.x] = s;
-    } else if (threadIdx.x >= kWave && threadIdx.x < kWave + 6) {
+    sgmom::block_row(acc, whole ? out_m + (size_t)ck.l * kMom : part_m + (size_t)ck.prow * kMom);   // its barrier covers s_ext too
+    if (threadIdx.x >= kWave && threadIdx.x < kWave + 6) {
         const int r = threadIdx.x - kWave;
         float v = s_ext[0][r];
 #pragma unroll

@@ -3,10 +3,10 @@
 //
 //   k_pl_flag / k_pl_compact  the free points (label < 0, or all of them) in ASCENDING index into dense rows of xyz (and normals): 1 / 0 per
 //                      point, scan64_device.h's exclusive sum, a scatter.  Triples index this list, so its order is part of the contract.
-//   k_pl_generate      one thread per hypothesis: the triple (splitmix64 of the seed with C := M, or the caller's row, checked against
-//                      0..M-1 before anything is read through it), the rejection rules in double, the unit normal and offset into
-//                      d_plane[h], count[h] = 0 / -1, and the kept h compacted through one integer counter (their order may vary; every
-//                      result is stored at [h], so nothing depends on it).
+//   k_pl_generate      one thread per hypothesis: the triple (ransac_draw_device.h with C := M: splitmix64 of the seed, or the caller's
+//                      row, checked against 0..M-1 before anything is read through it), the rejection rules in double, the unit normal
+//                      and offset into d_plane[h], count[h] = 0 / -1, and the kept h compacted through one integer counter (their order
+//                      may vary; every result is stored at [h], so nothing depends on it).
 //   k_pl_count         over the kept hypotheses only.  The shape sg_feature_nearest measured: a thread holds kHyp planes in registers
 //                      (4 x 4 doubles), the free points go through LDS in tiles of kTile, widened to double once when the tile is filled,
 //                      and every lane reads the same address (a broadcast: no bank conflict whatever the layout).  1,024 hypotheses do
@@ -14,36 +14,34 @@
 //                      counts meet in an integer atomicAdd -- the sum does not depend on the order of arrival.
 //   k_pl_best          the highest count, the lowest h among equals: one 64-bit integer maximum over (count, ~h).
 //   k_pl_moments       n | sum q | sum q q^T (xx xy xz yy yz zz) | sum r^2 over the free inliers of ONE plane, q = p - origin; the launch
-//                      shape and both reduction trees of k_align_moments (kernels_align.hip): a workgroup folds 1,024 consecutive points
-//                      into one partial row, k_align_fold adds the rows.
+//                      shape and both reduction trees are moments_device.h's: a workgroup folds 1,024 consecutive points into one partial
+//                      row (sgmom::block_row), sgmom::k_fold adds the rows, sgmom::reduce is the host sequence.
 //   k_pl_assign        label[i] = id at the free inliers of one plane; the number labelled through a ballot and one integer atomicAdd.
 // The inlier test is one function, inlier(), for the count, the moments and the labelling.  No floating-point atomics: two calls on the
 // same input write the same bytes.
 #include <cmath>
 
-#include "moments_fold_device.h"
+#include "moments_device.h"
 #include "overseg_device.h"
+#include "ransac_draw_device.h"
 #include "scan64_device.h"
 #include "sg_common.h"
-#include "wave_ops.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using sgmom::kBlock;
+using sgmom::Origin;
+
 constexpr int kWave = 64;
-constexpr int kWaves = kBlock / kWave;
 constexpr int kMaxPoints = 1 << 24;
 constexpr int kMaxHypotheses = 1 << 20;
 constexpr int kHyp = 4;                       // hypotheses per thread of the counting kernel
 constexpr int kTile = 1024;                   // free points per LDS tile: 1,024 x 3 doubles = 24 KiB (48 KiB with normals)
 constexpr int kCountWaves = 2048;             // the segments are cut so that about this many waves are in flight
-constexpr int kPer = 4;                       // points per thread of the moment kernel, as in k_align_moments
-constexpr int kPoints = kBlock * kPer;        // points per workgroup = per partial row
 constexpr int kMom = 11;
 
 struct Flags { int flag; int kept; unsigned long long best; int labelled; int pad; };
 struct Plane { double n[3], d; };
-struct Origin { double c[3]; };
 struct GenParams { double min_edge, min_sine; };
 struct Test { double dist, min_cos; };
 
@@ -95,22 +93,12 @@ __global__ __launch_bounds__(kBlock) void k_pl_generate(const float* __restrict_
     double out[4] = {0.0, 0.0, 0.0, 0.0};
     bool keep = M >= 3;
     int t[3] = {0, 0, 0};
-    if (keep && triples) {
-        for (int e = 0; e < 3; ++e) {
-            t[e] = triples[(size_t)h * 3 + e];
-            keep = keep && t[e] >= 0 && (long long)t[e] < M;
-        }
+    if (keep) {                                                          // the flag is raised only with three free points or more
+        bool distinct;
+        keep = sgdraw::triple_of(h, triples, seed, (int)M, t, &distinct);  // M <= N <= 2^24: the sum of N flags of 0 / 1
         if (!keep) atomicOr(&fl->flag, 2);
-    } else if (keep) {
-        for (int e = 0; e < 3; ++e) {
-            unsigned long long z = seed + (3ull * (unsigned long long)h + (unsigned long long)e + 1ull) * 0x9E3779B97F4A7C15ull;
-            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-            z ^= z >> 31;
-            t[e] = (int)(((z >> 32) * (unsigned long long)M) >> 32);    // < M <= 2^24
-        }
+        keep = keep && distinct;
     }
-    keep = keep && t[0] != t[1] && t[1] != t[2] && t[0] != t[2];
     if (keep) {
         double p[3][3];
         for (int e = 0; e < 3; ++e)
@@ -196,17 +184,16 @@ __global__ __launch_bounds__(kBlock) void k_pl_best(const int32_t* __restrict__ 
     if (threadIdx.x % kWave == 0 && key) atomicMax(best, key);
 }
 
-// every lane of every wave reaches the reductions (wave_sum needs all 64 lanes): a point past N, not free or outside the plane adds 0
+// every thread reaches block_row: a point past N, not free or outside the plane adds 0
 __global__ __launch_bounds__(kBlock) void k_pl_moments(const float* __restrict__ xyz, int xs, const int32_t* __restrict__ label,
                                                        const float* __restrict__ normals, int N, Plane pl, Test test, Origin o,
                                                        double* __restrict__ partial) {
-    __shared__ double s_rows[kWaves][kMom];
     double acc[kMom];
 #pragma unroll
     for (int m = 0; m < kMom; ++m) acc[m] = 0.0;
-    const long long base = (long long)blockIdx.x * kPoints + threadIdx.x;
+    const long long base = (long long)blockIdx.x * sgmom::kItems + threadIdx.x;
 #pragma unroll
-    for (int j = 0; j < kPer; ++j) {
+    for (int j = 0; j < sgmom::kPer; ++j) {
         const long long i = base + (long long)j * kBlock;
         if (i >= (long long)N) continue;
         if (label && label[i] >= 0) continue;
@@ -228,19 +215,7 @@ __global__ __launch_bounds__(kBlock) void k_pl_moments(const float* __restrict__
         }
         acc[10] += res * res;
     }
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-#pragma unroll
-    for (int m = 0; m < kMom; ++m) {
-        const double s = sgw::wave_sum(acc[m]);
-        if (lane == 0) s_rows[wave][m] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < kMom) {
-        double s = s_rows[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) s += s_rows[w][threadIdx.x];
-        partial[(size_t)blockIdx.x * kMom + threadIdx.x] = s;
-    }
+    sgmom::block_row(acc, partial + (size_t)blockIdx.x * kMom);
 }
 
 __global__ __launch_bounds__(kBlock) void k_pl_assign(const float* __restrict__ xyz, int xs, const float* __restrict__ normals, int N, Plane pl,
@@ -261,18 +236,14 @@ __global__ __launch_bounds__(kBlock) void k_pl_assign(const float* __restrict__ 
     if (threadIdx.x % kWave == 0 && n) atomicAdd(labelled, n);
 }
 
-struct Landing { double m[kMom]; };
-
 constexpr int kStages = 5;
 const char* const kStageNames[kStages] = {"compact", "generate", "count", "moments", "assign"};
 thread_local sgos::StageTimes<kStages> t_plane;
 thread_local bool t_compact = true;
 
-bool finite4(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]) && std::isfinite(v[3]); }
-
 // what the three entry points share: the plane, the distance and the optional normal test, checked
 int read_test(const char* who, const double* h_plane, double dist, const float* d_normals, double min_cos, Plane* pl, Test* test) {
-    SG_REQUIRE(h_plane && finite4(h_plane), "%s: the plane is four finite numbers (n, d)", who);
+    SG_REQUIRE(h_plane && sgmom::finite_n<4>(h_plane), "%s: the plane is four finite numbers (n, d)", who);
     SG_REQUIRE(std::isfinite(dist) && dist >= 0.0, "%s: dist must be a finite length >= 0 (%g)", who, dist);
     SG_REQUIRE(!d_normals || (min_cos >= 0.0 && min_cos <= 1.0), "%s: min_cos must be in 0..1 (%g)", who, min_cos);
     for (int r = 0; r < 3; ++r) pl->n[r] = h_plane[r];
@@ -375,10 +346,7 @@ int sg_plane_ransac(const float* d_xyz, int stride, int N, const int32_t* d_labe
     return SG_OK;
 }
 
-size_t sg_plane_moments_ws_bytes(int N) {
-    if (N < 0 || N > kMaxPoints) return 0;
-    return sg::align_up(sizeof(Landing)) + sg::align_up((size_t)std::max(sg::cdiv(N, kPoints), 1) * kMom * sizeof(double));
-}
+size_t sg_plane_moments_ws_bytes(int N) { return (N < 0 || N > kMaxPoints) ? 0 : sgmom::ws_bytes<kMom>(N); }
 
 int sg_plane_moments(const float* d_xyz, int stride, int N, const int32_t* d_label, const float* d_normals, double min_cos, const double* h_plane,
                      double dist, const double* h_origin, double* h_out, void* d_ws, size_t ws_bytes, void* stream) {
@@ -389,34 +357,19 @@ int sg_plane_moments(const float* d_xyz, int stride, int N, const int32_t* d_lab
     Test test;
     if (int rc = read_test(who, h_plane, dist, d_normals, min_cos, &pl, &test)) return rc;
     SG_REQUIRE(h_origin && h_out, "%s: bad arguments", who);
-    SG_REQUIRE(std::isfinite(h_origin[0]) && std::isfinite(h_origin[1]) && std::isfinite(h_origin[2]), "%s: an origin that is not finite", who);
+    SG_REQUIRE(sgmom::finite_n<3>(h_origin), "%s: an origin that is not finite", who);
     if (N == 0) {
         for (int m = 0; m < kMom; ++m) h_out[m] = 0.0;
         return SG_OK;
     }
     SG_REQUIRE(d_xyz && d_ws, "%s: bad arguments", who);
-    const size_t need = sg_plane_moments_ws_bytes(N);
-    SG_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    const int rows = sg::cdiv(N, kPoints);
-    sg::Carver cv(d_ws, ws_bytes);
-    Landing* d_land = cv.take<Landing>(1);
-    double* d_partial = cv.take<double>((size_t)rows * kMom);
-    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    Origin o;
-    for (int i = 0; i < 3; ++i) o.c[i] = h_origin[i];
+    const Origin o = sgmom::origin_of(h_origin);
     hipStream_t st = sg::as_stream(stream);
-    Landing land{};
-    {
-        sgos::StageClock<1> clock(st, t_plane.timing, t_plane.us + 3);
+    sgos::StageClock<1> clock(st, t_plane.timing, t_plane.us + 3);
+    auto first = [&](int rows, double* d_partial, int*) {
         k_pl_moments<<<rows, kBlock, 0, st>>>(d_xyz, stride, d_label, d_normals, N, pl, test, o, d_partial);
-        sgmom::k_align_fold<kMom><<<1, kBlock, 0, st>>>(d_partial, rows, d_land->m);
-        SG_HIP(hipMemcpyAsync(&land, d_land, sizeof(Landing), hipMemcpyDeviceToHost, st));
-        clock.tick();
-        SG_HIP(hipStreamSynchronize(st));
-    }
-    SG_LAUNCH_CHECK();
-    for (int m = 0; m < kMom; ++m) h_out[m] = land.m[m];
-    return SG_OK;
+    };
+    return sgmom::reduce<kMom>(who, N, d_ws, ws_bytes, st, first, h_out, nullptr, [&] { clock.tick(); });   // no flag: k_pl_moments raises none
 }
 
 size_t sg_plane_assign_ws_bytes(int N) { return (N < 0 || N > kMaxPoints) ? 0 : sg::align_up(sizeof(Flags)); }

@@ -15,14 +15,16 @@
 //                      into segments (blockIdx.y) and a query's answers meet in one 64-bit integer minimum over (d2 bits, index): d2 >= +0
 //                      orders as its bits do, the index in the low word sends ties to the lowest -- whatever the order of arrival.
 //   k_ransac_gather    the C correspondences' points packed into two dense arrays; an index out of range raises the flag first.
-//   k_ransac_filter    one thread per hypothesis: the triple (splitmix64 of the seed, or the caller's), the pre-rejection in double, and the
-//                      surviving h compacted through one integer counter (their order may vary; nothing depends on it).
+//   k_ransac_filter    one thread per hypothesis: the triple (ransac_draw_device.h: splitmix64 of the seed, or the caller's), the
+//                      pre-rejection in double, and the surviving h compacted through one integer counter (their order may vary;
+//                      nothing depends on it).
 //   k_ransac_count     over the survivors only: the pose of triangle_pose.h again from the triple, the correspondences tiled through LDS,
 //                      one wave (or, by sg_ransac_set_tuning, one thread) per survivor.  The result is stored at [h].
 // No floating-point atomics anywhere: two calls on the same input write the same bytes.
 #include <cmath>
 
 #include "overseg_device.h"
+#include "ransac_draw_device.h"
 #include "sg_common.h"
 #include "triangle_pose.h"
 #include "wave_ops.h"
@@ -235,27 +237,6 @@ __global__ __launch_bounds__(kBlock) void k_ransac_gather(const float* __restric
     }
 }
 
-// triple h: the caller's row, or index e = ((z >> 32) * C) >> 32 of splitmix64(seed + (3h + e + 1) * golden).  false: a caller's entry
-// outside 0..C-1 (nothing may be read through it)
-__device__ __forceinline__ bool triple_of(int h, const int32_t* __restrict__ triples, unsigned long long seed, int C, int* t) {
-    if (triples) {
-        bool ok = true;
-        for (int e = 0; e < 3; ++e) {
-            t[e] = triples[(size_t)h * 3 + e];
-            ok = ok && (unsigned)t[e] < (unsigned)C;
-        }
-        return ok;
-    }
-    for (int e = 0; e < 3; ++e) {
-        unsigned long long z = seed + (3ull * (unsigned long long)h + (unsigned long long)e + 1ull) * 0x9E3779B97F4A7C15ull;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
-        t[e] = (int)(((z >> 32) * (unsigned long long)C) >> 32);
-    }
-    return true;
-}
-
 __device__ __forceinline__ void load_triangle(const float* __restrict__ p, const int* t, double* x) {
     for (int e = 0; e < 3; ++e)
         for (int r = 0; r < 3; ++r) x[3 * e + r] = (double)p[(size_t)t[e] * 3 + r];
@@ -269,12 +250,12 @@ __global__ __launch_bounds__(kBlock) void k_ransac_filter(const float* __restric
     const int h = blockIdx.x * kBlock + threadIdx.x;
     if (h >= H) return;
     int t[3];
-    if (!triple_of(h, triples, seed, C, t)) {
+    bool keep;
+    if (!sgdraw::triple_of(h, triples, seed, C, t, &keep)) {
         atomicOr(&fl->flag, 2);
         count[h] = -1;
         return;
     }
-    bool keep = t[0] != t[1] && t[1] != t[2] && t[0] != t[2];
     if (keep) {
         double a[9], b[9];
         load_triangle(pa, t, a);
@@ -313,7 +294,8 @@ __global__ __launch_bounds__(kBlock) void k_ransac_count(const float* __restrict
     if (active) {
         h = surv[s];
         int t[3];
-        triple_of(h, triples, seed, C, t);                           // a survivor's triple passed the filter's checks
+        bool distinct;
+        sgdraw::triple_of(h, triples, seed, C, t, &distinct);        // a survivor's triple passed the filter's checks
         double a[9], b[9];
         load_triangle(pa, t, a);
         load_triangle(pb, t, b);

@@ -66,3 +66,14 @@ def device_cloud(xyz, dev, who: str, exact: bool = False):
     if d_xyz.shape[0] < 1:
         raise ValueError(f"{who}: a cloud needs at least one point")
     return d_xyz, int(d_xyz.shape[0])
+
+
+def device_rows(xyz, dev, who: str, limit: int):
+    """-> float32 device tensor of a cloud that may be empty: [N, >= 3] rows with xyz first, N at most `limit` (a power of two)"""
+    import torch
+    d = device_tensor(xyz, torch.float32, dev)
+    if d.dim() != 2 or d.shape[1] < 3:
+        raise ValueError(f"{who}: a cloud is [N, >= 3] rows with xyz first")
+    if d.shape[0] > limit:
+        raise hip.SgError(hip.SG_EUNSUP, "%s: %d points; a call takes at most 2^%d" % (who, d.shape[0], limit.bit_length() - 1))
+    return d

@@ -45,7 +45,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import hip, scans
-from .device import device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
+from .device import device_rows, device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
 
 MAX_POINTS = 1 << 24
 MAX_HYPOTHESES = 1 << 20
@@ -83,16 +83,6 @@ class Planes:
                    hypotheses=np.int32(self.hypotheses), seed=np.int64(self.seed), min_edge=np.float64(self.min_edge),
                    min_sine=np.float64(self.min_sine), normal_angle=np.float64(np.nan if self.normal_angle is None else self.normal_angle))
         return out
-
-
-def _cloud(xyz, dev, who: str):
-    import torch
-    d = device_tensor(xyz, torch.float32, dev)
-    if d.dim() != 2 or d.shape[1] < 3:
-        raise ValueError(f"{who}: a cloud is [N, >= 3] rows with xyz first")
-    if d.shape[0] > MAX_POINTS:
-        raise hip.SgError(hip.SG_EUNSUP, "%s: %d points; a call takes at most 2^24" % (who, d.shape[0]))
-    return d
 
 
 def _side(labels, normals, n: int, dev, who: str):
@@ -138,7 +128,7 @@ def plane_ransac(xyz, dist, hypotheses, seed=0, labels=None, min_edge=None, min_
     h = int(hypotheses)
     min_edge = 10.0 * float(dist) if min_edge is None else float(min_edge)
     with torch.cuda.device(dev), on_stream(stream):
-        d_xyz = _cloud(xyz, dev, "plane_ransac")
+        d_xyz = device_rows(xyz, dev, "plane_ransac", MAX_POINTS)
         n = int(d_xyz.shape[0])
         d_lab, d_nrm = _side(labels, normals, n, dev, "plane_ransac")
         d_tri = None
@@ -171,7 +161,7 @@ def plane_moments(xyz, plane, dist, origin=None, labels=None, normals=None, min_
     lib = hip.lib()
     out = np.zeros(11, np.float64)
     with torch.cuda.device(dev), on_stream(stream):
-        d_xyz = _cloud(xyz, dev, "plane_moments")
+        d_xyz = device_rows(xyz, dev, "plane_moments", MAX_POINTS)
         n = int(d_xyz.shape[0])
         d_lab, d_nrm = _side(labels, normals, n, dev, "plane_moments")
         ws = workspace(lib.sg_plane_moments_ws_bytes(n), dev)
@@ -203,7 +193,7 @@ def plane_assign(xyz, labels, plane, dist, plane_id, normals=None, min_cos=0.0, 
     dev = torch_device(device)
     lib = hip.lib()
     with torch.cuda.device(dev), on_stream(stream):
-        d_xyz = _cloud(xyz, dev, "plane_assign")
+        d_xyz = device_rows(xyz, dev, "plane_assign", MAX_POINTS)
         n = int(d_xyz.shape[0])
         if labels is None:
             raise ValueError("plane_assign: labels [N] are needed (-1: free)")
@@ -257,7 +247,7 @@ def detect_planes(xyz, dist, max_planes=16, min_points=None, hypotheses=4096, se
     max_planes, hypotheses, seed, min_sine = int(max_planes), int(hypotheses), int(seed), float(min_sine)
     dev = torch_device(device)
     with torch.cuda.device(dev), on_stream(stream):
-        d_xyz = _cloud(xyz, dev, "detect_planes")
+        d_xyz = device_rows(xyz, dev, "detect_planes", MAX_POINTS)
         n = int(d_xyz.shape[0])
         _, d_nrm = _side(None, normals, n, dev, "detect_planes")
         d_lab = torch.full((n,), -1, dtype=torch.int32, device=dev)
