@@ -1064,10 +1064,9 @@ int sg_align_plane_solve(const double* h_m, const double* h_origin, double lengt
  *   number of hypotheses that were counted.  3 <= C <= 2^18, 0 <= H <= 2^24 (above: SG_EUNSUP); H = 0 is SG_OK.  SG_EINVAL: null
  *   pointers, strides below 3, U or N < 1, C < 3, max_dist or min_edge not a finite length > 0, similarity outside (0, 1], a workspace
  *   below sg_ransac_ws_bytes(C, H) -- before the first device call --, a correspondence outside its cloud or an entry of d_triples outside
- *   0..C-1 (raised on the device before anything is read through it).  Synchronises the stream.  sg_ransac_set_tuning(lanes, timed), per
- *   calling thread: lanes = 1 | 64 | 0 (the default, 64) share a survivor in the counting kernel, which cannot change a result; timed != 0
- *   brackets the stages of the thread's next calls with events, and sg_ransac_stage_times / sg_ransac_stage_name then give the
- *   microseconds of gather, filter and count of the last one, as the other families' readers do.
+ *   0..C-1 (raised on the device before anything is read through it).  Synchronises the stream.  sg_ransac_set_tuning(lanes), per calling
+ *   thread: lanes = 1 | 64 | 0 (the default, 64) share a survivor in the counting kernel, which cannot change a result.  Stage times by
+ *   events, as sg_overseg_set_timing: room for 3 floats (gather, filter, count of the last call; tools/time_register.py).
  *
  * sg_triangle_pose: host only, no device call; the function the counting kernel runs (csrc/triangle_pose.h).  h_a, h_b: two triangles,
  *   x0 | x1 | x2.  Frame of a triangle: e1 = (x1 - x0) / |x1 - x0|, e3 = c / |c| with c = e1 x (x2 - x0), e2 = e3 x e1; R = F_b F_a^T
@@ -1081,7 +1080,8 @@ size_t sg_ransac_ws_bytes(int C, int H);
 int sg_ransac_count(const float* d_m, int m_stride, int U, const float* d_f, int f_stride, int N, const int32_t* d_ci, const int32_t* d_cj, int C,
                     int H, uint64_t seed, const int32_t* d_triples, double max_dist, double similarity, double min_edge, int32_t* d_count,
                     int* h_survivors, void* d_ws, size_t ws_bytes, void* stream);
-int sg_ransac_set_tuning(int lanes_per_survivor, int timed);
+int sg_ransac_set_tuning(int lanes_per_survivor);
+int sg_ransac_set_timing(int on);
 int sg_ransac_stage_times(float* h_us, int cap);
 const char* sg_ransac_stage_name(int i);
 int sg_triangle_pose(const double* h_a, const double* h_b, double* h_T);
@@ -1122,10 +1122,10 @@ int sg_triangle_pose(const double* h_a, const double* h_b, double* h_T);
  * sg_plane_assign: d_label[i] = id at every free point that passes the inlier test of h_plane; *h_labelled = how many.  id >= 0.  SG_EINVAL
  *   as sg_plane_moments, a negative id, a NULL d_label.  Synchronises the stream.
  *
- * sg_plane_set_tuning(compact, timed), per calling thread: compact = 0 lets the counting kernel walk all H hypotheses and skip the
- *   rejected ones in place instead of walking the compacted kept ones (the default; it cannot change a result); timed != 0 brackets the
- *   stages of the thread's next calls with events, and sg_plane_stage_times / sg_plane_stage_name then give the microseconds of compact,
- *   generate, count (the last sg_plane_ransac), moments and assign (the last call of each). */
+ * sg_plane_set_tuning(compact), per calling thread: compact = 0 lets the counting kernel walk all H hypotheses and skip the rejected
+ *   ones in place instead of walking the compacted kept ones (the default; it cannot change a result).  Stage times by events, as
+ *   sg_overseg_set_timing: room for 5 floats -- compact, generate, count (the last sg_plane_ransac), moments and assign (the last call of
+ *   each; tools/time_planes.py). */
 size_t sg_plane_ransac_ws_bytes(int N, int H, int with_normals);
 int sg_plane_ransac(const float* d_xyz, int stride, int N, const int32_t* d_label, const float* d_normals, double min_cos, int H, uint64_t seed,
                     const int32_t* d_triples, double dist, double min_edge, double min_sine, int32_t* d_count, double* d_plane, int* h_free,
@@ -1137,7 +1137,8 @@ int sg_plane_fit(const double* h_m, const double* h_origin, double* h_plane, dou
 size_t sg_plane_assign_ws_bytes(int N);
 int sg_plane_assign(const float* d_xyz, int stride, int N, const float* d_normals, double min_cos, const double* h_plane, double dist, int id,
                     int32_t* d_label, int* h_labelled, void* d_ws, size_t ws_bytes, void* stream);
-int sg_plane_set_tuning(int compact, int timed);
+int sg_plane_set_tuning(int compact);
+int sg_plane_set_timing(int on);
 int sg_plane_stage_times(float* h_us, int cap);
 const char* sg_plane_stage_name(int i);
 
@@ -1176,9 +1177,8 @@ const char* sg_plane_stage_name(int i);
  *   function (all before the first device call); count < 1 or a moment that is not finite (sg_box_axes); a labelled point with a
  *   coordinate that is not finite, or a d_start / d_order that is not an index of this cloud (one flag word on the device, read with the
  *   call's synchronisation; the outputs are then undefined).  Ignored points may hold anything.  SG_EUNSUP: N above 2^24; d_all with
- *   L * A > 2^24.  sg_label_set_tuning(timed), per calling thread: timed = 1 times the thread's next calls with events, and
- *   sg_label_stage_times / sg_label_stage_name then give the microseconds of index, moments, yaw and frame, the last call of each
- *   (room for 4 floats; tools/time_boxes.py). */
+ *   L * A > 2^24.  Stage times by events, as sg_overseg_set_timing: room for 4 floats -- index, moments, yaw and frame, the last call
+ *   of each (tools/time_boxes.py). */
 size_t sg_label_index_ws_bytes(int N);
 int sg_label_index(const int32_t* d_label, int N, int32_t* d_order, int32_t* d_value, int32_t* d_start, int* h_L, int* h_ignored, void* d_ws,
                    size_t ws_bytes, void* stream);
@@ -1192,7 +1192,7 @@ size_t sg_label_frame_extents_ws_bytes(int N, int L);
 int sg_label_frame_extents(const float* d_xyz, int stride, int N, const int32_t* d_order, const int32_t* d_start, int L, const double* d_frame,
                            double* d_ext, void* d_ws, size_t ws_bytes, void* stream);
 int sg_box_axes(const double* h_m, double* h_R, double* h_eig);
-int sg_label_set_tuning(int timed);
+int sg_label_set_timing(int on);
 int sg_label_stage_times(float* h_us, int cap);
 const char* sg_label_stage_name(int i);
 

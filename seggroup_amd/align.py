@@ -42,7 +42,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import hip, scans
-from .device import device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
+from .device import cloud_box, device_rows, device_tensor, on_stream, stream_ptr, sync, torch_device, vec3, workspace
 from .prepare import mesh_arrays, nearest_point_grid, read_ply
 
 ALIGN_SUFFIX = ".align.json"
@@ -91,21 +91,6 @@ def as_transform(T, who: str = "align") -> np.ndarray:
     return out
 
 
-def _vec3(v, who: str):
-    v = np.ascontiguousarray(np.zeros(3) if v is None else v, dtype=np.float64)
-    if v.shape != (3,):
-        raise ValueError(f"{who}: an origin is 3 numbers")
-    return v
-
-
-def _rows(a, dev, who: str):
-    import torch
-    d = device_tensor(a, torch.float32, dev)
-    if d.dim() != 2 or d.shape[1] < 3:
-        raise ValueError(f"{who}: a cloud is [N, >= 3] rows with xyz first")
-    return d
-
-
 def apply(xyz, T, device=None, stream=None):
     """sg_rigid_apply: out[u][r] = (float)(((R[r][0]*x + R[r][1]*y) + R[r][2]*z) + t[r]) in double, one rounding to fp32 -> float32 [U,3]
     device tensor.  xyz is [U, >= 3]; T any finite [4,4] / [3,4] matrix."""
@@ -114,7 +99,7 @@ def apply(xyz, T, device=None, stream=None):
     dev = torch_device(device)
     lib = hip.lib()
     with torch.cuda.device(dev), on_stream(stream):
-        d_x = _rows(xyz, dev, "apply")
+        d_x = device_rows(xyz, dev, "apply")
         u = int(d_x.shape[0])
         out = torch.empty((u, 3), dtype=torch.float32, device=dev)
         hip.check_arg(lib.sg_rigid_apply(d_x.data_ptr(), int(d_x.shape[1]), u, T.ctypes.data, out.data_ptr(), stream_ptr(stream)))
@@ -127,13 +112,13 @@ def moments(x, y, idx, d2, max_dist, origin_x=None, origin_y=None, device=None, 
     n | sum a [3] | sum b [3] | sum a b^T [9] | sum d2, with a = x - origin_x and b = y - origin_y in double (origins default to 0).
     Deterministic: the same input gives the same bytes.  An index outside 0..N-1 is a ValueError."""
     import torch
-    ox, oy = _vec3(origin_x, "moments"), _vec3(origin_y, "moments")
+    ox, oy = vec3(origin_x, "moments"), vec3(origin_y, "moments")
     max_d2 = float(np.float32(float(max_dist) * float(max_dist)))
     dev = torch_device(device)
     lib = hip.lib()
     out = np.zeros(17, np.float64)
     with torch.cuda.device(dev), on_stream(stream):
-        d_x, d_y = _rows(x, dev, "moments"), _rows(y, dev, "moments")
+        d_x, d_y = device_rows(x, dev, "moments"), device_rows(y, dev, "moments")
         d_idx, d_d2 = device_tensor(idx, torch.int64, dev), device_tensor(d2, torch.float32, dev)
         u = int(d_x.shape[0])
         if d_idx.shape != (u,) or d_d2.shape != (u,):
@@ -153,7 +138,7 @@ def solve(m, origin_x=None, origin_y=None) -> np.ndarray:
     m = np.ascontiguousarray(m, dtype=np.float64)
     if m.shape != (17,):
         raise ValueError("solve: 17 moments")
-    ox, oy = _vec3(origin_x, "solve"), _vec3(origin_y, "solve")
+    ox, oy = vec3(origin_x, "solve"), vec3(origin_y, "solve")
     T = np.eye(4)
     hip.check_arg(hip.lib().sg_align_solve(m.ctypes.data, ox.ctypes.data, oy.ctypes.data, T.ctypes.data))
     return T
@@ -167,13 +152,13 @@ def plane_moments(x, T, y, normals, idx, d2, max_dist, origin=None, device=None,
     nothing else.  Deterministic: the same input gives the same bytes.  An index outside 0..N-1 is a ValueError."""
     import torch
     T = np.ascontiguousarray(as_transform(T, "plane_moments")[:3])
-    o = _vec3(origin, "plane_moments")
+    o = vec3(origin, "plane_moments")
     max_d2 = float(np.float32(float(max_dist) * float(max_dist)))
     dev = torch_device(device)
     lib = hip.lib()
     out = np.zeros(31, np.float64)
     with torch.cuda.device(dev), on_stream(stream):
-        d_x, d_y, d_n = _rows(x, dev, "plane_moments"), _rows(y, dev, "plane_moments"), _rows(normals, dev, "plane_moments")
+        d_x, d_y, d_n = device_rows(x, dev, "plane_moments"), device_rows(y, dev, "plane_moments"), device_rows(normals, dev, "plane_moments")
         d_idx, d_d2 = device_tensor(idx, torch.int64, dev), device_tensor(d2, torch.float32, dev)
         u = int(d_x.shape[0])
         if d_idx.shape != (u,) or d_d2.shape != (u,):
@@ -200,7 +185,7 @@ def plane_solve(m, T, origin, length) -> np.ndarray:
     if T34.shape not in ((4, 4), (3, 4)):
         raise ValueError("plane_solve: a transform is a [4,4] (or [3,4]) matrix")
     T34 = np.ascontiguousarray(T34[:3])
-    o = _vec3(origin, "plane_solve")
+    o = vec3(origin, "plane_solve")
     out = np.zeros((4, 4))
     hip.check_arg(hip.lib().sg_align_plane_solve(m.ctypes.data, o.ctypes.data, float(length), T34.ctypes.data, out.ctypes.data, None))
     return out
@@ -266,61 +251,73 @@ def icp(moving_xyz, fixed_xyz, max_dist, init=None, max_iter: int = 50, min_delt
     T = np.eye(4) if init is None else as_transform(init, "icp: init")
     dev = torch_device(device)
     with torch.cuda.device(dev), on_stream(stream):
-        d_mov, d_fix = _rows(moving_xyz, dev, "icp"), _rows(fixed_xyz, dev, "icp")
+        d_mov, d_fix = device_rows(moving_xyz, dev, "icp"), device_rows(fixed_xyz, dev, "icp")
         if d_mov.shape[0] < 1 or d_fix.shape[0] < 1:
             raise ValueError("icp: a cloud needs at least one point")
         if normals is not None:
-            normals = _rows(normals, dev, "icp: normals")
+            normals = device_rows(normals, dev, "icp: normals")
             if normals.shape[0] != d_fix.shape[0]:
                 raise ValueError("icp: one normal per point of the FIXED cloud (%d normals, %d points)" % (normals.shape[0], d_fix.shape[0]))
-        box = [(c[:, :3].min(0).values.double().cpu().numpy(), c[:, :3].max(0).values.double().cpu().numpy()) for c in (d_mov, d_fix)]
-    if not all(np.isfinite(b).all() for lo_hi in box for b in lo_hi):
-        raise ValueError("icp: a coordinate that is not finite")
-    (mlo, mhi), (flo, fhi) = box
+        (mlo, mhi), (flo, fhi) = cloud_box(d_mov, "icp"), cloud_box(d_fix, "icp")
     origin_m, origin_f = 0.5 * (mlo + mhi), 0.5 * (flo + fhi)
     corners = box_corners(mlo, mhi)
     if min_delta is None:
-        min_delta = 2.0 ** -23 * float(max(np.abs(b).max() for lo_hi in box for b in lo_hi))
+        min_delta = 2.0 ** -23 * float(max(np.abs(b).max() for b in (mlo, mhi, flo, fhi)))
     max_d2 = float(np.float32(max_dist * max_dist))
-    if metric == "plane":
-        return _icp_plane(d_mov, d_fix, normals, int(normals_k), max_dist, max_d2, T, int(max_iter), min_delta, corners, origin_f,
-                          0.5 * float(np.sqrt(((fhi - flo) ** 2).sum())), dev, stream)
-    prev = None
+    # what a metric supplies: its sums at a pose, its fit, where the skipped count and the rms terms sit in the sums, whether repeated pairs
+    # end the loop, and what its fit finds
+    if metric == "point":
+        sums = lambda T, idx, d2: moments(d_mov, d_fix, idx, d2, max_dist, origin_m, origin_f, device=dev, stream=stream)
+        fit = lambda m, T: solve(m, origin_m, origin_f)
+        at_skipped, at_rms, fixed_point, finds = None, (16,), True, "a pose"
+    else:
+        if normals is None:
+            normals = fixed_normals(d_fix, int(normals_k), device=dev)
+        length = 0.5 * float(np.sqrt(((fhi - flo) ** 2).sum()))
+        if not length > 0.0:
+            raise ValueError("icp: the fixed cloud is a single point; metric='plane' needs planes (max_dist = %g)" % max_dist)
+        sums = lambda T, idx, d2: plane_moments(d_mov, T, d_fix, normals, idx, d2, max_dist, origin_f, device=dev, stream=stream)
+        fit = lambda m, T: plane_solve(m, T, origin_f, length)
+        at_skipped, at_rms, fixed_point, finds = 1, (30, 29), False, "a point-to-plane pose"
+    prev = first = None
     converged = False
-    rms_before = rms_after = None
     iterations = 0
     for _ in range(int(max_iter)):
         moved = apply(d_mov, T, device=dev, stream=stream)
         idx, d2 = nearest_point_grid(moved, d_fix, device=dev, stream=stream)
         with torch.cuda.device(dev), on_stream(stream):
             inlier = d2 <= max_d2
-            same = prev is not None and bool(torch.equal(idx, prev[0])) and bool(torch.equal(inlier, prev[1]))
+            same = fixed_point and prev is not None and bool(torch.equal(idx, prev[0])) and bool(torch.equal(inlier, prev[1]))
         iterations += 1
-        m = moments(d_mov, d_fix, idx, d2, max_dist, origin_m, origin_f, device=dev, stream=stream)
-        n = int(m[0])
+        m = sums(T, idx, d2)
+        n, skipped = int(m[0]), None if at_skipped is None else int(m[at_skipped])
         if n == 0:
+            if skipped:
+                raise ValueError("icp: every pair within max_dist = %g was skipped for its normal (%d pairs: the fixed cloud's normals there "
+                                 "are zero, not finite or far from unit length)" % (max_dist, skipped))
             raise ValueError("icp: no point of the moving cloud has a fixed point within max_dist = %g -- a larger max_dist, or an initial "
                              "transform (init=, --init) that brings the clouds closer" % max_dist)
-        rms_after = math.sqrt(m[16] / n)
-        if rms_before is None:
-            rms_before = rms_after
+        last = [math.sqrt(m[i] / n) for i in at_rms]
+        if first is None:
+            first = last
         prev = (idx, inlier)
         if same:
             converged = "fixed point"
             break
         try:
-            T_new = solve(m, origin_m, origin_f)
+            T_new = fit(m, T)
         except hip.SgError as e:
             if e.code != hip.SG_EUNSUP:
                 raise
-            raise ValueError("icp: the %d pairs within max_dist = %g do not determine a pose (%s)" % (n, max_dist, e)) from None
+            raise ValueError("icp: the %d pairs within max_dist = %g do not determine %s (%s)" % (n, max_dist, finds, e)) from None
         shift = corner_shift(corners, T, T_new)
         T = T_new
         if shift <= min_delta:
             converged = "min_delta"
             break
-    return Alignment(T=T, iterations=iterations, converged=converged, inliers=n, rms_before=rms_before, rms_after=rms_after,
-                     rotation_deg=rotation_deg(T), translation=[float(v) for v in T[:3, 3]], idx=idx, d2=d2, inlier=inlier)
+    plane = {} if metric == "point" else dict(metric="plane", skipped=skipped, plane_rms_before=first[1], plane_rms_after=last[1])
+    return Alignment(T=T, iterations=iterations, converged=converged, inliers=n, rms_before=first[0], rms_after=last[0],
+                     rotation_deg=rotation_deg(T), translation=[float(v) for v in T[:3, 3]], idx=idx, d2=d2, inlier=inlier, **plane)
 
 
 def fixed_normals(fixed_xyz, k: int = 10, device=None):
@@ -335,49 +332,6 @@ def fixed_normals(fixed_xyz, k: int = 10, device=None):
     with torch.cuda.device(dev):
         xyz = device_tensor(fixed_xyz, torch.float32, dev)[:, :3].contiguous()
     return pointcloud_normals(xyz, int(k), knn=pointcloud_knn(xyz, int(k), device=dev, index="grid"), device=dev)
-
-
-def _icp_plane(d_mov, d_fix, normals, normals_k, max_dist, max_d2, T, max_iter, min_delta, corners, centre, length, dev, stream) -> Alignment:
-    """icp's metric="plane" loop; the arguments are icp's, checked and on the device"""
-    import torch
-    if normals is None:
-        normals = fixed_normals(d_fix, normals_k, device=dev)
-    if not length > 0.0:
-        raise ValueError("icp: the fixed cloud is a single point; metric='plane' needs planes (max_dist = %g)" % max_dist)
-    converged = False
-    first = None
-    iterations = 0
-    for _ in range(max_iter):
-        moved = apply(d_mov, T, device=dev, stream=stream)
-        idx, d2 = nearest_point_grid(moved, d_fix, device=dev, stream=stream)
-        with torch.cuda.device(dev), on_stream(stream):
-            inlier = d2 <= max_d2
-        iterations += 1
-        m = plane_moments(d_mov, T, d_fix, normals, idx, d2, max_dist, centre, device=dev, stream=stream)
-        n, skipped = int(m[0]), int(m[1])
-        if n == 0:
-            if skipped:
-                raise ValueError("icp: every pair within max_dist = %g was skipped for its normal (%d pairs: the fixed cloud's normals there "
-                                 "are zero, not finite or far from unit length)" % (max_dist, skipped))
-            raise ValueError("icp: no point of the moving cloud has a fixed point within max_dist = %g -- a larger max_dist, or an initial "
-                             "transform (init=, --init) that brings the clouds closer" % max_dist)
-        last = (math.sqrt(m[30] / n), math.sqrt(m[29] / n))
-        if first is None:
-            first = last
-        try:
-            T_new = plane_solve(m, T, centre, length)
-        except hip.SgError as e:
-            if e.code != hip.SG_EUNSUP:
-                raise
-            raise ValueError("icp: the %d pairs within max_dist = %g do not determine a point-to-plane pose (%s)" % (n, max_dist, e)) from None
-        shift = corner_shift(corners, T, T_new)
-        T = T_new
-        if shift <= min_delta:
-            converged = "min_delta"
-            break
-    return Alignment(T=T, iterations=iterations, converged=converged, inliers=n, rms_before=first[0], rms_after=last[0],
-                     rotation_deg=rotation_deg(T), translation=[float(v) for v in T[:3, 3]], idx=idx, d2=d2, inlier=inlier, metric="plane",
-                     skipped=skipped, plane_rms_before=first[1], plane_rms_after=last[1])
 
 
 # ---- files --------------------------------------------------------------------------------------------------------------------------

@@ -436,20 +436,13 @@ def boxes_scans(scans_dir: str, out_dir: str, scenes=None, workers: int = 4, dev
                                                  options.get("kind", "yaw"), options.get("angles"), options.get("min_points"),
                                                  options.get("classes"), options.get("detector_files", False))
     dev = torch_device(device)
-    if scenes is None:
-        scenes = scans.scan_names(scans_dir)
-        if options.get("exp") is not None:
-            base = os.path.join(options.get("root", "."), "results", options["exp"])
-            scenes = [s for s in scenes if os.path.isdir(os.path.join(base, s, options.get("stage", "epoch_last")))]
-    done = scans.map_scans(scenes, workers, dev, lambda scene, stream: boxes_scan(os.path.join(scans_dir, scene), out_dir, device=dev,
-                                                                                  stream=stream, **options))
-    report = {scene: entry for scene, entry in done if entry is not None}
-    skipped = [scene for scene, entry in done if entry is None]
-    os.makedirs(out_dir, exist_ok=True)
+    if scenes is None and options.get("exp") is not None:
+        base = os.path.join(options.get("root", "."), "results", options["exp"])
+        scenes = [s for s in scans.scan_names(scans_dir) if os.path.isdir(os.path.join(base, s, options.get("stage", "epoch_last")))]
     head = {"kind": kind, "angles": a, "min_points": min_points, "classes": classes}
     head.update({k: options[k] for k in ("exp", "stage", "layer", "labels_from", "suffix", "key") if options.get(k) is not None})
-    scans.write_report(os.path.join(out_dir, REPORT_NAME), dict(head, scenes=report, skipped=skipped))
-    return report, skipped
+    return scans.run_scans(scans_dir, scenes, workers, dev, out_dir, REPORT_NAME, head,
+                           lambda path, stream: boxes_scan(path, out_dir, device=dev, stream=stream, **options))
 
 
 def main(argv=None) -> int:
@@ -470,10 +463,7 @@ def main(argv=None) -> int:
     ap.add_argument("--classes", default=None, help="experiment route: scannet18 (default) keeps the instances of the 18 benchmark classes; all")
     ap.add_argument("--detector-files", action="store_true", help="write <scene>_bbox.npy, float64 [K,7] = centre, full size, class id")
     ap.add_argument("--ply", action="store_true", help="write <scene>.boxes.ply, 8 vertices and 12 triangles per box")
-    ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
-    ap.add_argument("--force", action="store_true", help="overwrite existing results")
-    scans.add_workers_argument(ap)
-    ap.add_argument("--device", default=None)
+    scans.add_batch_arguments(ap, "overwrite existing results")
     a = ap.parse_args(argv)
     scans.check_workers(ap, a.workers)
     if a.exp_name is None and (a.stage is not None or a.layer is not None or a.root is not None):
@@ -487,11 +477,8 @@ def main(argv=None) -> int:
         route = dict(exp=a.exp_name, stage=a.stage or "epoch_last", layer=a.layer or "final", root=a.root or ".")
     report, skipped = boxes_scans(a.scans, a.out, scans.scene_list(a.scenes), a.workers, a.device, kind=a.kind, angles=a.angles,
                                   min_points=a.min_points, classes=a.classes, detector_files=a.detector_files, ply=a.ply, force=a.force, **route)
-    for scene, e in report.items():
-        print("boxes", scene, e["V"], "vertices,", e["instances"], "instances,", e["kept"], "kept,", e["ignored"], "ignored")
-    for s in skipped:
-        print("skipped", s, "(its .boxes.npz exists; --force overwrites)")
-    print(f"{len(report)} written, {len(skipped)} skipped")
+    scans.print_outcome(report, skipped, lambda scene, e: ("boxes", scene, e["V"], "vertices,", e["instances"], "instances,", e["kept"], "kept,",
+                                                           e["ignored"], "ignored"), "(its .boxes.npz exists; --force overwrites)")
     return 0
 
 

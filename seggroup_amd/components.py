@@ -363,22 +363,13 @@ def clean_scans(scans_dir: str, out_dir: str, min_verts: Optional[int] = None, l
     <out_dir>/clean_report.json.  Workers are threads, each with its own stream."""
     _check_rules("clean_scans", min_verts, largest, radius, min_neighbours)
     dev = torch_device(device)
-    if scenes is None:
-        scenes = scans.scan_names(scans_dir)
-    done = scans.map_scans(scenes, workers, dev, lambda scene, stream: clean_scan(os.path.join(scans_dir, scene), out_dir, min_verts, largest,
-                                                                                  pointcloud, knn, max_edge, index, force, device=dev,
-                                                                                  stream=stream, report_only=report_only, radius=radius,
-                                                                                  min_neighbours=min_neighbours))
-    report = {scene: entry for scene, entry in done if entry is not None}
-    skipped = [scene for scene, entry in done if entry is None]
-    os.makedirs(out_dir, exist_ok=True)
-    doc = {"min_verts": min_verts, "largest": bool(largest), "pointcloud": bool(pointcloud), "knn": int(knn),
-           "max_edge": None if max_edge is None else float(max_edge), "index": index, "report_only": bool(report_only),
-           "scenes": report, "skipped": skipped}
+    head = {"min_verts": min_verts, "largest": bool(largest), "pointcloud": bool(pointcloud), "knn": int(knn),
+            "max_edge": None if max_edge is None else float(max_edge), "index": index, "report_only": bool(report_only)}
     if radius is not None:
-        doc.update(radius=float(radius), min_neighbours=None if min_neighbours is None else int(min_neighbours))
-    scans.write_report(os.path.join(out_dir, REPORT_NAME), doc)
-    return report, skipped
+        head.update(radius=float(radius), min_neighbours=None if min_neighbours is None else int(min_neighbours))
+    return scans.run_scans(scans_dir, scenes, workers, dev, out_dir, REPORT_NAME, head,
+                           lambda path, stream: clean_scan(path, out_dir, min_verts, largest, pointcloud, knn, max_edge, index, force, device=dev,
+                                                           stream=stream, report_only=report_only, radius=radius, min_neighbours=min_neighbours))
 
 
 # ---- pseudo instances that fall apart -------------------------------------------------------------------------------------------------
@@ -467,11 +458,8 @@ def main(argv=None) -> int:
     ap.add_argument("--radius", type=_positive, default=None,
                     help="the radius graph in place of the kNN graph: every pair of points at most this far apart, in the scan's unit")
     ap.add_argument("--min-neighbours", type=int, default=None, help="with --radius: keep the vertices with at least this many points within the radius")
-    ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
-    ap.add_argument("--force", action="store_true", help="overwrite existing cleaned scans")
     ap.add_argument("--report-only", action="store_true", help="write clean_report.json and no scan")
-    scans.add_workers_argument(ap)
-    ap.add_argument("--device", default=None)
+    scans.add_batch_arguments(ap, "overwrite existing cleaned scans")
     ap.add_argument("--fragments", action="store_true", help="report the pseudo instances that are in more than one piece")
     ap.add_argument("-n", "--exp_name", default=None, help="--fragments: name of the experiment")
     ap.add_argument("--stage", default="epoch_last", help="--fragments: the export directory's name")
@@ -531,11 +519,9 @@ def main(argv=None) -> int:
     new = dict(radius=a.radius, min_neighbours=a.min_neighbours) if a.radius is not None else {}
     report, skipped = clean_scans(a.scans, a.out, a.min_verts, a.largest, a.pointcloud, a.knn, a.max_edge, a.index, names, a.force, a.workers,
                                   a.device, a.report_only, **new)
-    for scene, e in report.items():
-        print("cleaned", scene, e["V"], "->", e["M"], "vertices,", e["components"], "->", e["kept_components"], "components")
-    for s in skipped:
-        print("skipped", s, "(cleaned scan exists; --force overwrites)")
-    print(f"{len(report)} {'reported' if a.report_only else 'written'}, {len(skipped)} skipped")
+    scans.print_outcome(report, skipped, lambda scene, e: ("cleaned", scene, e["V"], "->", e["M"], "vertices,", e["components"], "->",
+                                                           e["kept_components"], "components"),
+                        "(cleaned scan exists; --force overwrites)", "reported" if a.report_only else "written")
     return 0
 
 

@@ -51,7 +51,22 @@ void orthonormalise(Vec3& a, Vec3& b) {
     for (int i = 0; i < 3; ++i) b.v[i] -= p * a.v[i];
     normalise(b);
 }
-
+// the largest-magnitude component is made positive, ties to the lowest axis
+void fix_sign(Vec3& a) {
+    int big = 0;
+    for (int i = 1; i < 3; ++i)
+        if (std::fabs(a.v[i]) > std::fabs(a.v[big])) big = i;
+    if (a.v[big] < 0.0)
+        for (double& c : a.v) c = -c;
+}
+// count | sum q [3] | sum q q^T (xx xy xz yy yz zz) -> A = sum q q^T - (sum q)(sum q)^T / count
+void scatter(const double* h_m, double A[3][3]) {
+    const double n = h_m[0];
+    const double* sq = h_m + 1;
+    const int at[3][3] = {{4, 5, 6}, {5, 7, 8}, {6, 8, 9}};
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) A[r][c] = h_m[at[r][c]] - sq[r] * sq[c] / n;
+}
 
 constexpr int kPlaneMom = 31;
 constexpr double kPlaneRatio = 0x1p-40;        // smallest eigenvalue at or below this share of the largest: some motion costs nothing
@@ -260,10 +275,8 @@ int sg_plane_fit(const double* h_m, const double* h_origin, double* h_plane, dou
     SG_REQUIRE(n >= 0.0, "%s: a negative point count (%g)", who, n);
     if (n < 3.0) return sg::fail(SG_EUNSUP, "%s: degenerate: %g points; a plane needs at least 3", who, n);
     const double* sq = h_m + 1;
-    const int at[3][3] = {{4, 5, 6}, {5, 7, 8}, {6, 8, 9}};      // xx xy xz yy yz zz
     double A[3][3], V[3][3], lambda[3];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) A[r][c] = h_m[at[r][c]] - sq[r] * sq[c] / n;
+    scatter(h_m, A);
     if (!jacobi<3>(A, V, lambda)) return sg::fail(SG_EINVAL, "%s: the moments overflow the fit", who);
     int lo = 0, hi = 0;
     for (int i = 1; i < 3; ++i) {
@@ -278,11 +291,7 @@ int sg_plane_fit(const double* h_m, const double* h_origin, double* h_plane, dou
                                    "plane through them is free", who, lambda[lo], lambda[mid], lambda[hi]);
     Vec3 nrm = {{V[0][lo], V[1][lo], V[2][lo]}};
     normalise(nrm);
-    int big = 0;                                                  // the largest-magnitude component is made positive, ties to the lowest axis
-    for (int i = 1; i < 3; ++i)
-        if (std::fabs(nrm.v[i]) > std::fabs(nrm.v[big])) big = i;
-    if (nrm.v[big] < 0.0)
-        for (double& c : nrm.v) c = -c;
+    fix_sign(nrm);
     Vec3 centre;
     for (int i = 0; i < 3; ++i) centre.v[i] = h_origin[i] + sq[i] / n;
     const double d = -dot(nrm, centre);
@@ -302,11 +311,10 @@ int sg_box_axes(const double* h_m, double* h_R, double* h_eig) {
     for (int i = 0; i < 10; ++i) SG_REQUIRE(std::isfinite(h_m[i]), "%s: moment %d is not finite", who, i);
     const double n = h_m[0];
     SG_REQUIRE(n >= 1.0, "%s: a box needs at least one point (count %g)", who, n);
-    const double* sq = h_m + 1;
-    const int at[3][3] = {{4, 5, 6}, {5, 7, 8}, {6, 8, 9}};      // xx xy xz yy yz zz
     double A[3][3], V[3][3], lambda[3];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) A[r][c] = (h_m[at[r][c]] - sq[r] * sq[c] / n) / n;
+    scatter(h_m, A);
+    for (auto& row : A)
+        for (double& a : row) a /= n;
     if (!jacobi<3>(A, V, lambda)) return sg::fail(SG_EINVAL, "%s: the moments overflow the covariance", who);
     int ord[3] = {0, 1, 2};                                       // descending eigenvalue, the lower index first among equals
     for (int i = 1; i < 3; ++i)
@@ -318,11 +326,7 @@ int sg_box_axes(const double* h_m, double* h_R, double* h_eig) {
     } else {
         for (int r = 0; r < 2; ++r) {
             row[r] = {{V[0][ord[r]], V[1][ord[r]], V[2][ord[r]]}};
-            int big = 0;                                          // the largest-magnitude component is made positive, ties to the lowest axis
-            for (int i = 1; i < 3; ++i)
-                if (std::fabs(row[r].v[i]) > std::fabs(row[r].v[big])) big = i;
-            if (row[r].v[big] < 0.0)
-                for (double& c : row[r].v) c = -c;
+            fix_sign(row[r]);
         }
         row[2] = cross(row[0], row[1]);
     }

@@ -437,13 +437,7 @@ int land_flag(const char* who, const Table& t, hipStream_t st) {
 
 extern "C" {
 
-// (the name follows sg_plane_set_tuning: the sg_*_set_timing families are the grid tools' and are listed where they are tested)
-int sg_label_set_tuning(int timed) {
-    t_label.timing = timed != 0;
-    return SG_OK;
-}
-int sg_label_stage_times(float* h_us, int cap) { return t_label.copy("sg_label_stage_times", h_us, cap); }
-const char* sg_label_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
+SG_STAGE_TIMER_API(label, t_label, kStageNames)
 
 size_t sg_label_index_ws_bytes(int N) {
     if (N < 0 || N > kMaxPoints) return 0;

@@ -257,13 +257,12 @@ int read_test(const char* who, const double* h_plane, double dist, const float* 
 
 extern "C" {
 
-int sg_plane_set_tuning(int compact, int timed) {
+SG_STAGE_TIMER_API(plane, t_plane, kStageNames)
+
+int sg_plane_set_tuning(int compact) {
     t_compact = compact != 0;
-    t_plane.timing = timed != 0;
     return SG_OK;
 }
-int sg_plane_stage_times(float* h_us, int cap) { return t_plane.copy("sg_plane_stage_times", h_us, cap); }
-const char* sg_plane_stage_name(int i) { return sgos::stage_name(kStageNames, i); }
 
 size_t sg_plane_ransac_ws_bytes(int N, int H, int with_normals) {
     if (N < 0 || N > kMaxPoints || H < 0 || H > kMaxHypotheses) return 0;

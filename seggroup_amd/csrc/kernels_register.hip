@@ -389,14 +389,12 @@ int sg_feature_nearest(const float* d_a, int U, const float* d_b, int N, int C, 
     return SG_OK;
 }
 
-int sg_ransac_stage_times(float* h_us, int cap) { return t_ransac.copy("sg_ransac_stage_times", h_us, cap); }
-const char* sg_ransac_stage_name(int i) { return sgos::stage_name(kRansacStageNames, i); }
+SG_STAGE_TIMER_API(ransac, t_ransac, kRansacStageNames)
 
-int sg_ransac_set_tuning(int lanes_per_survivor, int timed) {
+int sg_ransac_set_tuning(int lanes_per_survivor) {
     SG_REQUIRE(lanes_per_survivor == 0 || lanes_per_survivor == 1 || lanes_per_survivor == kWave,
                "sg_ransac_set_tuning: 1 or 64 lanes per survivor (0: the default), not %d", lanes_per_survivor);
     t_ransac_lanes = lanes_per_survivor ? lanes_per_survivor : kWave;
-    t_ransac.timing = timed != 0;
     return SG_OK;
 }
 

@@ -68,12 +68,28 @@ def device_cloud(xyz, dev, who: str, exact: bool = False):
     return d_xyz, int(d_xyz.shape[0])
 
 
-def device_rows(xyz, dev, who: str, limit: int):
-    """-> float32 device tensor of a cloud that may be empty: [N, >= 3] rows with xyz first, N at most `limit` (a power of two)"""
+def device_rows(xyz, dev, who: str, limit=None):
+    """-> float32 device tensor of a cloud that may be empty: [N, >= 3] rows with xyz first, N at most `limit` (a power of two) if given"""
     import torch
     d = device_tensor(xyz, torch.float32, dev)
     if d.dim() != 2 or d.shape[1] < 3:
         raise ValueError(f"{who}: a cloud is [N, >= 3] rows with xyz first")
-    if d.shape[0] > limit:
+    if limit is not None and d.shape[0] > limit:
         raise hip.SgError(hip.SG_EUNSUP, "%s: %d points; a call takes at most 2^%d" % (who, d.shape[0], limit.bit_length() - 1))
     return d
+
+
+def vec3(v, who: str) -> np.ndarray:
+    """an origin for a library call -> contiguous float64 [3]; None is the zero vector"""
+    v = np.ascontiguousarray(np.zeros(3) if v is None else v, dtype=np.float64)
+    if v.shape != (3,):
+        raise ValueError(f"{who}: an origin is 3 numbers")
+    return v
+
+
+def cloud_box(d_xyz, who: str):
+    """the box of a device cloud of at least one point -> (lo, hi) float64 [3] on the host; a coordinate that is not finite is a ValueError"""
+    lo, hi = (m(0).values.double().cpu().numpy() for m in (d_xyz[:, :3].min, d_xyz[:, :3].max))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError(f"{who}: a coordinate that is not finite")
+    return lo, hi

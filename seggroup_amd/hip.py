@@ -190,7 +190,8 @@ SIGNATURES = {
     "sg_ransac_ws_bytes": (_Z, [_I, _I]),
     "sg_ransac_count": (_I, [vp, _I, _I, vp, _I, _I, vp, vp, _I, _I, C.c_uint64, vp, C.c_double, C.c_double, C.c_double, vp, C.POINTER(C.c_int),
                              vp, _Z, vp]),
-    "sg_ransac_set_tuning": (_I, [_I, _I]),
+    "sg_ransac_set_tuning": (_I, [_I]),
+    "sg_ransac_set_timing": (_I, [_I]),
     "sg_ransac_stage_times": (_I, [vp, _I]),
     "sg_ransac_stage_name": (C.c_char_p, [_I]),
     "sg_triangle_pose": (_I, [vp, vp, vp]),
@@ -202,7 +203,8 @@ SIGNATURES = {
     "sg_plane_fit": (_I, [vp, vp, vp, vp, vp]),
     "sg_plane_assign_ws_bytes": (_Z, [_I]),
     "sg_plane_assign": (_I, [vp, _I, _I, vp, C.c_double, vp, C.c_double, _I, vp, C.POINTER(C.c_int), vp, _Z, vp]),
-    "sg_plane_set_tuning": (_I, [_I, _I]),
+    "sg_plane_set_tuning": (_I, [_I]),
+    "sg_plane_set_timing": (_I, [_I]),
     "sg_plane_stage_times": (_I, [vp, _I]),
     "sg_plane_stage_name": (C.c_char_p, [_I]),
     "sg_label_index_ws_bytes": (_Z, [_I]),
@@ -214,7 +216,7 @@ SIGNATURES = {
     "sg_label_frame_extents_ws_bytes": (_Z, [_I, _I]),
     "sg_label_frame_extents": (_I, [vp, _I, _I, vp, vp, _I, vp, vp, vp, _Z, vp]),
     "sg_box_axes": (_I, [vp, vp, vp]),
-    "sg_label_set_tuning": (_I, [_I]),
+    "sg_label_set_timing": (_I, [_I]),
     "sg_label_stage_times": (_I, [vp, _I]),
     "sg_label_stage_name": (C.c_char_p, [_I]),
     "sg_components_ws_bytes": (_Z, [_I]),

@@ -45,7 +45,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import hip, scans
-from .device import device_rows, device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
+from .device import cloud_box, device_rows, device_tensor, on_stream, stream_ptr, sync, torch_device, vec3, workspace
 
 MAX_POINTS = 1 << 24
 MAX_HYPOTHESES = 1 << 20
@@ -108,13 +108,6 @@ def _plane4(plane, who: str) -> np.ndarray:
     return p
 
 
-def _vec3(v, who: str) -> np.ndarray:
-    v = np.ascontiguousarray(np.zeros(3) if v is None else v, dtype=np.float64)
-    if v.shape != (3,):
-        raise ValueError(f"{who}: an origin is 3 numbers")
-    return v
-
-
 def plane_ransac(xyz, dist, hypotheses, seed=0, labels=None, min_edge=None, min_sine=0.1, triples=None, normals=None, min_cos=0.0, device=None,
                  stream=None):
     """sg_plane_ransac -> (count int32 [H], plane float64 [H,4] device tensors, free, best).  The FREE points are those with labels < 0 (all
@@ -156,7 +149,7 @@ def plane_moments(xyz, plane, dist, origin=None, labels=None, normals=None, min_
     """sg_plane_moments over the free points within `dist` of `plane` (n, d) -> float64 [11]: count | sum q [3] | sum q q^T as xx xy xz yy
     yz zz | sum r^2, with q = p - origin and r = n.p + d in double.  Deterministic: the same input gives the same bytes."""
     import torch
-    pl, o = _plane4(plane, "plane_moments"), _vec3(origin, "plane_moments")
+    pl, o = _plane4(plane, "plane_moments"), vec3(origin, "plane_moments")
     dev = torch_device(device)
     lib = hip.lib()
     out = np.zeros(11, np.float64)
@@ -179,7 +172,7 @@ def plane_fit(m, origin=None):
     m = np.ascontiguousarray(m, dtype=np.float64)
     if m.shape != (11,):
         raise ValueError("plane_fit: 11 moments")
-    o = _vec3(origin, "plane_fit")
+    o = vec3(origin, "plane_fit")
     plane, centroid, rms = np.zeros(4), np.zeros(3), C.c_double(0.0)
     hip.check_arg(hip.lib().sg_plane_fit(m.ctypes.data, o.ctypes.data, plane.ctypes.data, centroid.ctypes.data, C.byref(rms)))
     return plane, centroid, float(rms.value)
@@ -253,9 +246,7 @@ def detect_planes(xyz, dist, max_planes=16, min_points=None, hypotheses=4096, se
         d_lab = torch.full((n,), -1, dtype=torch.int32, device=dev)
         origin = np.zeros(3)
         if n:
-            lo, hi = d_xyz[:, :3].min(0).values.double().cpu().numpy(), d_xyz[:, :3].max(0).values.double().cpu().numpy()
-            if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
-                raise ValueError("detect_planes: a coordinate that is not finite")
+            lo, hi = cloud_box(d_xyz, "detect_planes")
             origin = 0.5 * (lo + hi)
     found = []
     for p in range(max_planes if n >= 3 else 0):
@@ -412,17 +403,10 @@ def planes_scans(scans_dir: str, out_dir: str, dist, min_points, scenes=None, wo
     check_parameters(dist, min_points, options.get("max_planes", 16), options.get("hypotheses", 4096), options.get("min_edge"), 0.1,
                      options.get("normal_angle"))
     dev = torch_device(device)
-    if scenes is None:
-        scenes = scans.scan_names(scans_dir)
-    done = scans.map_scans(scenes, workers, dev, lambda scene, stream: planes_scan(os.path.join(scans_dir, scene), out_dir, dist, min_points,
-                                                                                   device=dev, stream=stream, **options))
-    report = {scene: entry for scene, entry in done if entry is not None}
-    skipped = [scene for scene, entry in done if entry is None]
-    os.makedirs(out_dir, exist_ok=True)
     head = {"dist": float(dist), "min_points": int(min_points)}
     head.update({k: v for k, v in options.items() if v is not None and k != "force"})
-    scans.write_report(os.path.join(out_dir, REPORT_NAME), dict(head, scenes=report, skipped=skipped))
-    return report, skipped
+    return scans.run_scans(scans_dir, scenes, workers, dev, out_dir, REPORT_NAME, head,
+                           lambda path, stream: planes_scan(path, out_dir, dist, min_points, device=dev, stream=stream, **options))
 
 
 def main(argv=None) -> int:
@@ -441,10 +425,7 @@ def main(argv=None) -> int:
     ap.add_argument("--level", nargs="?", const="largest", default=None, type=_level_arg, metavar="largest|INDEX",
                     help="write the scan levelled on its largest plane (or on plane INDEX): that plane at z = 0, the scan above it")
     ap.add_argument("--remove", action="store_true", help="write the scan without the points of any plane")
-    ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
-    ap.add_argument("--force", action="store_true", help="overwrite existing results")
-    scans.add_workers_argument(ap)
-    ap.add_argument("--device", default=None)
+    scans.add_batch_arguments(ap, "overwrite existing results")
     a = ap.parse_args(argv)
     scans.check_workers(ap, a.workers)
     try:
@@ -455,11 +436,8 @@ def main(argv=None) -> int:
     report, skipped = planes_scans(a.scans, a.out, a.dist, a.min_points, scans.scene_list(a.scenes), a.workers, a.device, max_planes=a.max_planes,
                                    hypotheses=a.hypotheses, seed=a.seed, min_edge=a.min_edge, normal_angle=a.normal_angle,
                                    normals_k=a.normals_k, level=a.level, remove=a.remove, force=a.force)
-    for scene, e in report.items():
-        print("planes", scene, e["V"], "vertices,", len(e["planes"]), "planes,", e["unlabelled"], "unlabelled")
-    for s in skipped:
-        print("skipped", s, "(its .planes.npz exists; --force overwrites)")
-    print(f"{len(report)} written, {len(skipped)} skipped")
+    scans.print_outcome(report, skipped, lambda scene, e: ("planes", scene, e["V"], "vertices,", len(e["planes"]), "planes,", e["unlabelled"],
+                                                           "unlabelled"), "(its .planes.npz exists; --force overwrites)")
     return 0
 
 

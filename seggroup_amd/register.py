@@ -24,7 +24,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import align, hip
-from .device import device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
+from .device import device_rows, device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
 
 BINS = 33
 MAX_POINTS = 1 << 18
@@ -63,14 +63,6 @@ class Coarse:
         return {k: getattr(self, k) for k in COARSE_SCALARS}
 
 
-def _xyz(a, dev, who: str):
-    import torch
-    d = device_tensor(a, torch.float32, dev)
-    if d.dim() != 2 or d.shape[1] < 3:
-        raise ValueError(f"{who}: a cloud is [N, >= 3] rows with xyz first")
-    return d
-
-
 def fpfh(xyz, normals, radius, lists=None, want_spfh=False, device=None, stream=None):
     """sg_fpfh -> float32 [N,33] device tensor (with want_spfh: also the int32 [N,34] bin counts and pair count).  xyz [N, >= 3], normals
     [N,3]; the neighbourhoods are `lists` = (indptr int64 [N+1], indices int32 [T]) or components.radius_neighbours(xyz, radius).  Lists
@@ -79,7 +71,7 @@ def fpfh(xyz, normals, radius, lists=None, want_spfh=False, device=None, stream=
     dev = torch_device(device)
     lib = hip.lib()
     with torch.cuda.device(dev), on_stream(stream):
-        d_xyz = _xyz(xyz, dev, "fpfh")
+        d_xyz = device_rows(xyz, dev, "fpfh")
         n = int(d_xyz.shape[0])
         d_nrm = device_tensor(normals, torch.float32, dev)
         if tuple(d_nrm.shape) != (n, 3):
@@ -133,7 +125,7 @@ def ransac_count(moving, fixed, ci, cj, hypotheses, max_dist, seed=0, similarity
     h = int(hypotheses)
     min_edge = 3.0 * float(max_dist) if min_edge is None else float(min_edge)
     with torch.cuda.device(dev), on_stream(stream):
-        d_m, d_f = _xyz(moving, dev, "ransac_count"), _xyz(fixed, dev, "ransac_count")
+        d_m, d_f = device_rows(moving, dev, "ransac_count"), device_rows(fixed, dev, "ransac_count")
         d_ci, d_cj = device_tensor(ci, torch.int32, dev), device_tensor(cj, torch.int32, dev)
         c = int(d_ci.shape[0])
         if d_ci.dim() != 1 or tuple(d_cj.shape) != (c,):
@@ -228,7 +220,7 @@ def global_registration(moving_xyz, fixed_xyz, voxel=None, normal_radius=None, f
     clouds = []
     with torch.cuda.device(dev), on_stream(stream):
         for name, xyz in (("moving", moving_xyz), ("fixed", fixed_xyz)):
-            d = _xyz(xyz, dev, "global_registration")[:, :3].contiguous()
+            d = device_rows(xyz, dev, "global_registration")[:, :3].contiguous()
             if d.shape[0] < 3:
                 raise ValueError("global_registration: the %s cloud has %d points; a pose needs at least 3" % (name, d.shape[0]))
             if voxel is not None:

@@ -348,8 +348,12 @@ def rekey_scan(scene_path: str, out_root: str, new_seg=None, k_thresh: float = 0
         _write_bytes(targets["segs"], _json_bytes({"params": {}, "sceneId": name, "segIndices": [int(s) for s in new_arr]}))
     _write_bytes(targets["agg"], _json_bytes(res.aggregation))
     tsv_out = os.path.join(out_root, "scannetv2-labels.combined.tsv")
-    if not os.path.exists(tsv_out) or open(tsv_out, "rb").read() != tsv:
-        if os.path.exists(tsv_out) and not force:
+    have = None                                                           # looked at once: another worker may write the same file meanwhile
+    if os.path.exists(tsv_out):
+        with open(tsv_out, "rb") as f:
+            have = f.read()
+    if have != tsv:
+        if have is not None and not force:
             raise FileExistsError(f"rekey_scan: {tsv_out} exists and differs from the source's (force=True overwrites)")
         _write_bytes(tsv_out, tsv)
     if manual is not None:

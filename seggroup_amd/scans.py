@@ -55,6 +55,14 @@ def add_workers_argument(ap) -> None:
     ap.add_argument("--workers", type=int, default=4, help=f"threads, each with its own stream (at most {MAX_WORKERS})")
 
 
+def add_batch_arguments(ap, force_help: str) -> None:
+    """the options every batch command that writes per-scan results has: --scenes, --force, --workers, --device"""
+    ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
+    ap.add_argument("--force", action="store_true", help=force_help)
+    add_workers_argument(ap)
+    ap.add_argument("--device", default=None)
+
+
 def check_workers(ap, workers: int) -> None:
     if not 1 <= workers <= MAX_WORKERS:
         ap.error(f"--workers must be in 1..{MAX_WORKERS}")
@@ -87,3 +95,26 @@ def map_scans(scenes, workers, dev, fn):
 
     with concurrent.futures.ThreadPoolExecutor(max_workers=worker_count(workers, len(scenes))) as pool:
         return list(pool.map(one, scenes))
+
+
+def run_scans(scans_dir: str, scenes, workers, dev, out_dir: str, report_name: str, head: dict, one):
+    """A batch command: one(scene_path, stream) -> the scan's entry, or None for a scan whose result was there already, over the named
+    scans (None: every scan directory under `scans_dir`) -> (report {scene: entry}, skipped scene names); writes <out_dir>/<report_name>,
+    `head` with the report and the skipped names."""
+    if scenes is None:
+        scenes = scan_names(scans_dir)
+    done = map_scans(scenes, workers, dev, lambda scene, stream: one(os.path.join(scans_dir, scene), stream))
+    report = {scene: entry for scene, entry in done if entry is not None}
+    skipped = [scene for scene, entry in done if entry is None]
+    os.makedirs(out_dir, exist_ok=True)
+    write_report(os.path.join(out_dir, report_name), dict(head, scenes=report, skipped=skipped))
+    return report, skipped
+
+
+def print_outcome(report, skipped, line, skipped_note: str, verb: str = "written") -> None:
+    """what a batch command prints: line(scene, entry) -> the words of a scene's line, a line per skipped scene, the tail"""
+    for scene, entry in report.items():
+        print(*line(scene, entry))
+    for s in skipped:
+        print("skipped", s, skipped_note)
+    print(f"{len(report)} {verb}, {len(skipped)} skipped")

@@ -130,15 +130,8 @@ def thin_scans(scans_dir: str, out_dir: str, voxel: float, scenes=None, force: b
     """Every scan directory under `scans_dir` (or the named ones) -> (report {scene: entry}, skipped scene names); writes
     <out_dir>/thin_report.json.  Workers are threads, each with its own stream."""
     dev = torch_device(device)
-    if scenes is None:
-        scenes = scans.scan_names(scans_dir)
-    done = scans.map_scans(scenes, workers, dev, lambda scene, stream: thin_scan(os.path.join(scans_dir, scene), out_dir, voxel, force, device=dev,
-                                                                                 stream=stream))
-    report = {scene: entry for scene, entry in done if entry is not None}
-    skipped = [scene for scene, entry in done if entry is None]
-    os.makedirs(out_dir, exist_ok=True)
-    scans.write_report(os.path.join(out_dir, REPORT_NAME), {"voxel": float(np.float32(voxel)), "scenes": report, "skipped": skipped})
-    return report, skipped
+    return scans.run_scans(scans_dir, scenes, workers, dev, out_dir, REPORT_NAME, {"voxel": float(np.float32(voxel))},
+                           lambda path, stream: thin_scan(path, out_dir, voxel, force, device=dev, stream=stream))
 
 
 def lift_stage(src: str, dst: str, index_map, n_src: int, verb: str = "lift", unit: str = "thinned points"):
@@ -183,10 +176,7 @@ def main(argv=None) -> int:
     ap.add_argument("--scans", default=None, help="directory of scan directories (<scene>/<scene>_vh_clean_2.ply)")
     ap.add_argument("--out", required=True, help="where the thinned scan directories go; with --lift, the root that receives results/")
     ap.add_argument("--voxel", type=float, default=None, help="edge of the voxel grid, in the scan's unit")
-    ap.add_argument("--scenes", default=None, help="text file with one scene name per line")
-    ap.add_argument("--force", action="store_true", help="overwrite existing thinned scans")
-    scans.add_workers_argument(ap)
-    ap.add_argument("--device", default=None)
+    scans.add_batch_arguments(ap, "overwrite existing thinned scans")
     ap.add_argument("-n", "--exp_name", default=None, help="--lift: name of the experiment")
     ap.add_argument("--stage", default="epoch_last", help="--lift: the export directory's name")
     ap.add_argument("--maps", default=None, help="--lift: the thinned scans (their <scene>.thin.npz hold the maps)")
@@ -204,11 +194,7 @@ def main(argv=None) -> int:
         ap.error("thinning needs --scans DIR and --voxel H")
     scans.check_workers(ap, a.workers)
     report, skipped = thin_scans(a.scans, a.out, a.voxel, scans.scene_list(a.scenes), a.force, a.workers, a.device)
-    for scene, e in report.items():
-        print("thinned", scene, e["V"], "->", e["M"])
-    for s in skipped:
-        print("skipped", s, "(thinned scan exists; --force overwrites)")
-    print(f"{len(report)} written, {len(skipped)} skipped")
+    scans.print_outcome(report, skipped, lambda scene, e: ("thinned", scene, e["V"], "->", e["M"]), "(thinned scan exists; --force overwrites)")
     return 0
 
 

@@ -216,6 +216,30 @@ def test_all_extents_has_a_size_limit_and_the_widest_sweep_runs():
     assert np.array_equal(best.cpu().numpy(), wb) and np.array_equal(ext.cpu().numpy(), we)
 
 
+def test_stage_timer_times_every_entry():
+    """hip.stage_timer("label") around one call of each entry point: the same bytes as untimed and four finite times above 0; after the
+    block an untimed call leaves the record as it was"""
+    from seggroup_amd import boxes, hip
+    xyz, lab = _cloud(5, 1025), _labels("interleaved", 1025)
+    frames = _frames(3, 1)
+
+    def calls():
+        idx = boxes.label_index(lab, device=DEV)
+        mom = boxes.label_moments(xyz, idx, device=DEV)
+        best, ext, _ = boxes.yaw_boxes(xyz, idx, 63, device=DEV)
+        fr = boxes.frame_extents(xyz, idx, frames, device=DEV)
+        return [v.cpu().numpy().tobytes() for v in (idx.order, idx.values, idx.start, mom.moments, mom.lo, mom.hi, best, ext, fr)]
+
+    plain = calls()
+    with hip.stage_timer("label") as t:
+        assert t.names == ["index", "moments", "yaw", "frame"]
+        assert calls() == plain
+        last = t.read()
+        assert len(last) == len(t.names) and all(np.isfinite(u) and u > 0.0 for u in last), last
+    assert calls() == plain
+    assert t.read() == last
+
+
 def _grid_cases():
     """(A, step a, cloud): 3 x 2 x 1 lattice cuboids turned by a * (pi/2)/A, two of them in one cloud with a third label on a half step"""
     for a_count, steps in ((90, (0, 1, 30, 45, 89)), (64, (7, 33)), (256, (100, 255)), (65, (13,))):

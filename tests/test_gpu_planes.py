@@ -85,11 +85,11 @@ def test_ransac_against_the_restatement(n, sg_lib):
             passed = planes.plane_ransac(xyz, 0.02, h, seed + 1, triples=G.triples_of(seed, h, n), device=DEV, **kw)
             assert passed[0].cpu().numpy().tobytes() == count.tobytes() and passed[1].cpu().numpy().tobytes() == plane.tobytes(), (n, h)
             assert passed[2:] == (free, best)
-            assert sg_lib.sg_plane_set_tuning(0, 0) == 0
+            assert sg_lib.sg_plane_set_tuning(0) == 0
             try:
                 walked = planes.plane_ransac(xyz, 0.02, h, seed, device=DEV, **kw)
             finally:
-                assert sg_lib.sg_plane_set_tuning(1, 0) == 0
+                assert sg_lib.sg_plane_set_tuning(1) == 0
             assert walked[0].cpu().numpy().tobytes() == count.tobytes() and walked[1].cpu().numpy().tobytes() == plane.tobytes(), (n, h)
             assert walked[2:] == (free, best)
     if n >= 63:
@@ -246,6 +246,42 @@ def test_assign_labels_the_reference_mask_and_returns_its_size():
     with pytest.raises(ValueError, match="id"):
         planes.plane_assign(xyz, start, pl, 0.004, -1, device=DEV)
     assert planes.plane_assign(np.zeros((0, 3), np.float32), np.zeros(0, np.int32), pl, 0.004, 1, device=DEV)[1] == 0
+
+
+def test_stage_timer_times_every_entry_and_the_tuning_knob_leaves_it_on(sg_lib):
+    """hip.stage_timer("plane") around one call of each entry point: the same bytes as untimed, five finite times with the stages that ran
+    above 0, and sg_plane_set_tuning inside the block does not switch the timer off.  A call on two points ends before its count (M < 3), so a
+    timed one leaves that stage at 0: the count of the call after the knob was turned is above 0 only if it was timed.  After the block an
+    untimed call leaves the record as it was."""
+    from seggroup_amd import hip, planes
+    xyz, two = _cloud(63, 63), _cloud(2, 2)
+    pl = np.array([-0.5, 0.0, 1.0, -0.25]) / np.sqrt(1.25)
+    free = np.full(63, -1, np.int32)
+
+    def calls(cloud=xyz):
+        count, plane, _, best = planes.plane_ransac(cloud, 0.02, 65, 7, min_edge=0.2, device=DEV)
+        m = planes.plane_moments(xyz, pl, 0.05, device=DEV)
+        lab, done = planes.plane_assign(xyz, free, pl, 0.05, 4, device=DEV)
+        return [count.cpu().numpy().tobytes(), plane.cpu().numpy().tobytes(), m.tobytes(), lab.cpu().numpy().tobytes()], best, done
+
+    plain = calls()
+    assert plain[1] >= 0 and plain[2] > 0, "nothing was kept or labelled: the case checks nothing"
+    with hip.stage_timer("plane") as t:
+        assert t.names == ["compact", "generate", "count", "moments", "assign"]
+        assert calls() == plain
+        us = t.read()
+        assert len(us) == len(t.names) and all(np.isfinite(u) and u > 0.0 for u in us), us
+        calls(two)
+        assert t.read()[t.names.index("count")] == 0.0
+        assert sg_lib.sg_plane_set_tuning(0) == 0
+        try:
+            assert calls() == plain
+        finally:
+            assert sg_lib.sg_plane_set_tuning(1) == 0
+        last = t.read()
+        assert all(np.isfinite(u) and u > 0.0 for u in last), last
+    assert calls(two)[0][2:] == plain[0][2:] and calls() == plain
+    assert t.read() == last
 
 
 # ---- the loop ---------------------------------------------------------------------------------------------------------------------------

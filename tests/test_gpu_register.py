@@ -236,11 +236,11 @@ def test_ransac_count_against_the_reference(c, sg_lib):
             passed = register.ransac_count(moving, fixed, ci, cj, h, 0.05, seed=seed + 1, triples=G.triples_of(seed, h, c), device=DEV,
                                            min_edge=0.3 if c > 3 else 0.01)
             assert passed.cpu().numpy().tobytes() == got.tobytes(), (c, h)
-            assert sg_lib.sg_ransac_set_tuning(1, 0) == 0                # a thread per survivor instead of a wave: the same bytes
+            assert sg_lib.sg_ransac_set_tuning(1) == 0                # a thread per survivor instead of a wave: the same bytes
             try:
                 alone = register.ransac_count(moving, fixed, ci, cj, h, 0.05, seed=seed, device=DEV, min_edge=0.3 if c > 3 else 0.01)
             finally:
-                assert sg_lib.sg_ransac_set_tuning(0, 0) == 0
+                assert sg_lib.sg_ransac_set_tuning(0) == 0
             assert alone.cpu().numpy().tobytes() == got.tobytes(), (c, h)
     assert kept > 0, "no hypothesis survived at any H: the case checks nothing"
 
@@ -281,6 +281,45 @@ def test_ransac_explicit_triples():
         register.ransac_count(moving, fixed, ci[:2], cj[:2], 4, 0.01, device=DEV)
     with pytest.raises(ValueError):
         register.ransac_count(moving, fixed, ci, cj, 4, 0.01, triples=far, device=DEV)
+
+
+def test_stage_timer_times_the_call_and_the_tuning_knob_leaves_it_on(sg_lib):
+    """hip.stage_timer("ransac") around sg_ransac_count: the same bytes as untimed, three finite times above 0, and sg_ransac_set_tuning
+    inside the block does not switch the timer off.  A call that is refused for a correspondence outside its cloud ends before its count, so
+    a timed one leaves that stage at 0: the count of the call after the knob was turned is above 0 only if it was timed.  After the block
+    an untimed call leaves the record as it was."""
+    from seggroup_amd import hip, register
+    rng = np.random.RandomState(64)
+    moving = _lattice(rng, 64)
+    fixed = A.apply(moving, QUARTER)
+    ci = rng.randint(0, 64, 64).astype(np.int32)
+    cj = np.where(rng.rand(64) < 0.34, ci, rng.randint(0, 64, 64)).astype(np.int32)
+    outside = cj.copy()
+    outside[5] = 64
+
+    def call(cj=cj):
+        count, survivors = register.ransac_count(moving, fixed, ci, cj, 4097, 0.05, seed=68097, device=DEV, min_edge=0.3, want_survivors=True)
+        return count.cpu().numpy().tobytes(), survivors
+
+    plain = call()
+    assert plain[1] > 0, "no hypothesis survived: the count stage has nothing to run"
+    with hip.stage_timer("ransac") as t:
+        assert t.names == ["gather", "filter", "count"]
+        assert call() == plain
+        us = t.read()
+        assert len(us) == len(t.names) and all(np.isfinite(u) and u > 0.0 for u in us), us
+        with pytest.raises(ValueError, match="a correspondence outside"):
+            call(outside)
+        assert t.read()[t.names.index("count")] == 0.0
+        assert sg_lib.sg_ransac_set_tuning(1) == 0
+        try:
+            assert call() == plain
+        finally:
+            assert sg_lib.sg_ransac_set_tuning(0) == 0
+        last = t.read()
+        assert all(np.isfinite(u) and u > 0.0 for u in last), last
+    assert call() == plain
+    assert t.read() == last
 
 
 # ---- the pipeline ---------------------------------------------------------------------------------------------------------------------------

@@ -140,7 +140,7 @@ def test_library_refuses_before_a_device_is_touched(sg_lib):
         assert sg_lib.sg_ransac_count(*args(10, 10, **kw)) == hip.SG_EINVAL, kw
     assert sg_lib.sg_ransac_ws_bytes(2, 10) == 0 and sg_lib.sg_ransac_ws_bytes(10, (1 << 24) + 1) == 0
     assert sg_lib.sg_ransac_ws_bytes(1 << 18, 1 << 24) >= 4 * (1 << 24) + 24 * (1 << 18)
-    assert sg_lib.sg_ransac_set_tuning(7, 0) == hip.SG_EINVAL and sg_lib.sg_ransac_set_tuning(0, 0) == hip.SG_OK
+    assert sg_lib.sg_ransac_set_tuning(7) == hip.SG_EINVAL and sg_lib.sg_ransac_set_tuning(0) == hip.SG_OK
     assert [sg_lib.sg_ransac_stage_name(i) for i in range(4)] == [b"gather", b"filter", b"count", None]
 
 

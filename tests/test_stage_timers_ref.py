@@ -20,6 +20,9 @@ FAMILIES = {
     "radius_grid": ("box", "cells", "sort", "table", "init", "search", "finish"),
     "segment_vote": ("check", "rank_sort", "rank_unique", "pair_sort", "pair_unique", "arg_max", "vertex_gather"),
     "segment_graph": ("keys", "sort", "unique", "emit"),
+    "ransac": ("gather", "filter", "count"),
+    "plane": ("compact", "generate", "count", "moments", "assign"),
+    "label": ("index", "moments", "yaw", "frame"),
 }
 
 

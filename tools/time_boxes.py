@@ -8,16 +8,14 @@ One process, one GPU, one stream.  The cloud is make_room_scan(400, 375) (150,00
 three label vectors: 1,500 labels (the scan's own seg_indices name three parts only, so a label here is a run of 100 consecutive lattice
 vertices: a strip of one lattice row), every point its own label, and one label for all.  The stages -- sg_label_index, sg_label_moments,
 sg_label_yaw_boxes at A = 90 and A = 256, sg_label_frame_extents -- are timed by the library's own events on the stream
-(sg_label_set_tuning), the median (min .. max) of the repeats after a warm-up; label_boxes (yaw, 90) by the host's clock stands beside
+(hip.stage_timer("label")), the median (min .. max) of the repeats after a warm-up; label_boxes (yaw, 90) by the host's clock stands beside
 them.  EXPECTED was written down before the first run.
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
 import time
-import types
 
 import numpy as np
 
@@ -49,17 +47,6 @@ def measure(repeats):
     room = np.ascontiguousarray(synthetic.make_room_scan(400, 375, 11, jitter=5e-4, name="scene0000_00").xyz, dtype=np.float32)
     d_xyz = torch.from_numpy(room).to(dev)
     n = int(room.shape[0])
-    lib = hip.lib()
-    names = []
-    while lib.sg_label_stage_name(len(names)) is not None:
-        names.append(lib.sg_label_stage_name(len(names)).decode())
-    buf = (C.c_float * len(names))()
-
-    def read():
-        hip.check(lib.sg_label_stage_times(buf, len(names)))
-        return list(buf)
-
-    timer = types.SimpleNamespace(names=names, read=read)
     vectors = {"1,500 labels": (np.arange(n) // 100).astype(np.int32), "every point its own": np.arange(n, dtype=np.int32),
                "one label": np.zeros(n, np.int32)}
     out = dict(points=n, clouds=[])
@@ -86,12 +73,9 @@ def measure(repeats):
 
         labels = int(np.unique(lab).size)
         state["frames"] = torch.eye(3, dtype=torch.float64, device=dev).repeat(labels, 1, 1)
-        try:
-            hip.check(lib.sg_label_set_tuning(1))
+        with hip.stage_timer("label") as timer:
             one_round()                                                       # the warm-up
             rows = [one_round(timer) for _ in range(repeats)]
-        finally:
-            hip.check(lib.sg_label_set_tuning(0))
         row = dict(name=name, labels=labels, stages_us={k: spread([r[k] for r in rows]) for k in rows[0]})
         boxes.label_boxes(d_xyz, d_lab, "yaw", 90, device=dev)
         torch.cuda.synchronize()

@@ -6,12 +6,11 @@
 
 One process, one GPU, one stream.  The cloud is make_room_scan(400, 375) (150,000 points on a 0.04 lattice with a jitter of 5e-4), every
 point free.  At H = 1,024 / 4,096 / 16,384 the stages of sg_plane_ransac (compact, generate, count), of sg_plane_moments and of
-sg_plane_assign on the winning plane are timed by the library's own events on the stream (sg_plane_set_tuning), the median (min .. max)
+sg_plane_assign on the winning plane are timed by the library's own events on the stream (hip.stage_timer("plane")), the median (min .. max)
 of the repeats after a warm-up; the count also with the kept hypotheses NOT compacted.  The whole of detect_planes by the host's clock and
 the planes it finds stand beside them.  EXPECTED was written down before the first run.
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -50,11 +49,7 @@ def measure(dist, min_points, repeats):
     d_xyz = torch.from_numpy(room).to(dev)
     n = int(room.shape[0])
     origin = 0.5 * (room.min(0).astype(np.float64) + room.max(0).astype(np.float64))
-    names = []
-    while lib.sg_plane_stage_name(len(names)) is not None:
-        names.append(lib.sg_plane_stage_name(len(names)).decode())
-    buf = (C.c_float * len(names))()
-    out = dict(points=n, dist=dist, min_points=min_points, min_edge=10.0 * dist, stages=names, rounds=[], whole_call=[])
+    out = dict(points=n, dist=dist, min_points=min_points, min_edge=10.0 * dist, stages=None, rounds=[], whole_call=[])
     free = torch.full((n,), -1, dtype=torch.int32, device=dev)
     for h in HYPOTHESES:
         row = dict(hypotheses=h)
@@ -68,16 +63,17 @@ def measure(dist, min_points, repeats):
 
         for compact in (1, 0):
             try:
-                hip.check(lib.sg_plane_set_tuning(compact, 1))
-                one_round()                                               # the warm-up
-                rows = []
-                for _ in range(repeats):
-                    one_round()
-                    hip.check(lib.sg_plane_stage_times(buf, len(names)))
-                    rows.append(list(buf))
+                hip.check(lib.sg_plane_set_tuning(compact))
+                with hip.stage_timer("plane") as t:
+                    one_round()                                           # the warm-up
+                    rows = []
+                    for _ in range(repeats):
+                        one_round()
+                        rows.append(t.read())
             finally:
-                hip.check(lib.sg_plane_set_tuning(1, 0))
-            row["stages_us" if compact else "stages_us_not_compacted"] = dict(zip(names, spread(rows)))
+                hip.check(lib.sg_plane_set_tuning(1))
+            out["stages"] = t.names
+            row["stages_us" if compact else "stages_us_not_compacted"] = dict(zip(t.names, spread(rows)))
             state["bytes_%d" % compact] = state["count"].cpu().numpy().tobytes()
         assert state["bytes_1"] == state["bytes_0"]
         kept = int((state["count"] >= 0).sum())

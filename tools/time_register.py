@@ -8,12 +8,11 @@ One process, one GPU, one stream.  The cloud is make_room_scan(400, 375) (150,00
 at --voxel, which leaves roughly 20,000 points; the moving cloud is the same scan under the inverse of 150 degrees and 1.5 m, thinned on
 its own.  Every device stage runs between two events on the stream after a warm-up, the median (min .. max) of the repeats: the radius
 lists and the normals of both clouds, sg_fpfh of both, sg_feature_nearest, sg_ransac_count at 2^18, 2^20 and 2^22 hypotheses -- its
-filter and its count by the library's own events (sg_ransac_set_tuning), the count with a wave and with a thread per survivor -- and the
+filter and its count by the library's own events (hip.stage_timer("ransac")), the count with a wave and with a thread per survivor -- and the
 16 verification searches (align.apply + prepare.nearest_point_grid each).  The survivor fraction and the whole global_registration call
 by the host's clock stand beside them.  EXPECTED was written down before the first run.
 """
 import argparse
-import ctypes as C
 import json
 import math
 import os
@@ -117,19 +116,18 @@ def measure(voxel, repeats):
                 state["count"], state["surv"] = register.ransac_count(d_mov, d_fix, ci, cj, h, max_dist, device=dev, want_survivors=True)
 
             try:
-                hip.check(lib.sg_ransac_set_tuning(lanes, 0))
+                hip.check(lib.sg_ransac_set_tuning(lanes))
                 row["call_ms_%d_lanes" % lanes] = timed(count, repeats)
-                hip.check(lib.sg_ransac_set_tuning(lanes, 1))             # the library's own events around its three stages
-                rows, buf = [], (C.c_float * 3)()
-                for _ in range(3):
-                    count()
-                    hip.check(lib.sg_ransac_stage_times(buf, 3))
-                    rows.append(list(buf))
+                with hip.stage_timer("ransac") as t:                      # the library's own events around its three stages
+                    rows = []
+                    for _ in range(3):
+                        count()
+                        rows.append(t.read())
                 us = np.median(np.asarray(rows), 0)
-                row["stages_us_%d_lanes" % lanes] = {lib.sg_ransac_stage_name(i).decode(): round(float(u), 1) for i, u in enumerate(us)}
+                row["stages_us_%d_lanes" % lanes] = {name: round(float(u), 1) for name, u in zip(t.names, us)}
                 state["bytes_%d" % lanes] = state["count"].cpu().numpy().tobytes()
             finally:
-                hip.check(lib.sg_ransac_set_tuning(0, 0))
+                hip.check(lib.sg_ransac_set_tuning(0))
         assert state["bytes_64"] == state["bytes_1"]
         row.update(survivors=int(state["surv"]), survivor_fraction=state["surv"] / float(h), best_count=int(state["count"].max()))
         out["ransac"].append(row)
