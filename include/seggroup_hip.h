@@ -1196,6 +1196,54 @@ int sg_label_set_timing(int on);
 int sg_label_stage_times(float* h_us, int cap);
 const char* sg_label_stage_name(int i);
 
+/* IoU of upright boxes: the consumer of the boxes above.  A BOX is 8 doubles, cx cy cz sx sy sz c s: the centre, the FULL
+ * size, and the footprint axes u = (c, s), v = (-s, c) about z, the convention of sg_label_yaw_boxes (u = c*x + s*y, v = c*y - s*x); c and
+ * s are host doubles -- the caller takes cos / sin, no device transcendental enters; an axis-aligned box has c = 1, s = 0.  z is up.
+ * Sets A [Ka,8] and B [Kb,8] are flat over `B` scenes; the host tables h_off_a [B+1] and h_off_b [B+1] delimit the scenes (ascending
+ * from 0 to Ka / Kb; a scene may be empty on either side) and only boxes of the same scene pair.  Double arithmetic, every operation
+ * rounded once, nothing contracted, no floating-point atomics, the caller's stream, one synchronisation per call; a _ws_bytes function
+ * returns 0 for a size the entry does not take.  At most 2^20 boxes a side and 2^16 scenes.
+ *
+ * IoU(a, b), THE OPERATION SEQUENCE (tests/boxap_ref.py restates it statement by statement; the device has one function for it):
+ *   dx = ax - bx, dy = ay - by;  hax = 0.5*asx, hay = 0.5*asy, hbx = 0.5*bsx, hby = 0.5*bsy
+ *   ex = hax*ac, ey = hax*as, fx = hay*as, fy = hay*ac
+ *   the corners of a about b's centre, k = 0..3 = (-,-), (+,-), (+,+), (-,+) along a's (u, v), counter-clockwise:
+ *     wx = (dx - ex) + fx, (dx + ex) + fx, (dx + ex) - fx, (dx - ex) - fx;   wy = (dy - ey) - fy, (dy + ey) - fy, (dy + ey) + fy, (dy - ey) + fy
+ *   into b's frame: u_k = bc*wx_k + bs*wy_k, v_k = bc*wy_k - bs*wx_k (two rounded products, one rounded sum or difference)
+ *   the polygon (n = 4) is clipped by b's sides in the order d = hbx - u, d = u + hbx, d = hby - v, d = v + hby; a vertex is inside when
+ *   d >= 0.  One side (Sutherland-Hodgman): for i = 0..n-1 with q = vertex i and p = the vertex before it (vertex n-1 for i = 0), in order:
+ *     if (dp >= 0) != (dq >= 0):  t = dp / (dp - dq)  -- taken only where the signs differ -- and the crossing is appended: on sides 0 / 1
+ *       (+hbx / -hbx, pv + t*(qv - pv)), on sides 2 / 3 (pu + t*(qu - pu), +hby / -hby): the clipped coordinate is the side itself, exactly;
+ *     if dq >= 0: q is appended.
+ *   The result has at most 8 vertices; an append past the eighth is dropped (rounding alone could ask for one).
+ *   area: the fan about vertex 0, acc = 0, for i = 1..n-2 in order: e = vertex i - vertex 0, g = vertex i+1 - vertex 0,
+ *     acc = acc + (e.u*g.v - e.v*g.u);  area = 0.5*acc, and 0 unless area > 0 (fewer than three vertices: 0)
+ *   h = min(az + 0.5*asz, bz + 0.5*bsz) - max(az - 0.5*asz, bz - 0.5*bsz), and 0 unless h > 0
+ *   inter = area*h;  va = (asx*asy)*asz, vb = (bsx*bsy)*bsz;  uni = (va + vb) - inter;  IoU = inter / uni if uni > 0, else 0
+ *   So touching boxes (a shared face: every vertex left lies on one side) give exactly 0, two single-point boxes give 0 (the union is
+ *   not positive), and an axis-aligned box inside another gives va / vb.  The sequence is NOT symmetric -- a's corners are carried into
+ *   b's frame --, so IoU(a, b) and IoU(b, a) agree to rounding (a few 1e-15: tests/test_boxap_ref.py measures it), not to the last bit.
+ *
+ * sg_box_iou: d_iou is flat; scene b holds a row-major [Ka_b, Kb_b] block and the blocks are stored in scene order; `pairs` is the
+ *   number of doubles d_iou holds and must be the sum of Ka_b * Kb_b, at most 2^24.
+ * sg_box_best: per box of A the best partner among the boxes of B of its scene: d_best [Ka] = the index WITHIN the scene's B boxes of
+ *   the highest IoU, the lowest index among equals, d_best_iou [Ka] that IoU -- the bits sg_box_iou writes for the pair; an IoU of 0 is
+ *   not a partner: -1 and 0.0.  d_cls_a [Ka] / d_cls_b [Kb] (int32; both or neither) restrict partners to the same class.  No Ka x Kb
+ *   table and no limit on the pairs.
+ *
+ * SG_EINVAL: offsets that do not start at 0, do not ascend or do not end at Ka / Kb (checked on the host, they are host tables, before
+ *   anything is read through them), one class vector without the other, `pairs` that is not the scenes' sum, a workspace below the
+ *   _ws_bytes function; and, through one flag word on the device that is read with the call's synchronisation (the outputs are then
+ *   undefined): a box with a value that is not finite, a negative size (0 is valid), |c*c + s*s - 1| > 1e-6.  Every message names its
+ *   entry and the set.  SG_EUNSUP: more than 2^20 boxes a side, 2^16 scenes or (sg_box_iou) 2^24 pairs.  These entries have no stage
+ *   timer: tools/time_boxap.py brackets them with events on the caller's stream. */
+size_t sg_box_iou_ws_bytes(int Ka, int Kb, int B);
+int sg_box_iou(const double* d_a, int Ka, const double* d_b, int Kb, const int32_t* h_off_a, const int32_t* h_off_b, int B, double* d_iou,
+               long long pairs, void* d_ws, size_t ws_bytes, void* stream);
+size_t sg_box_best_ws_bytes(int Ka, int Kb, int B);
+int sg_box_best(const double* d_a, int Ka, const double* d_b, int Kb, const int32_t* d_cls_a, const int32_t* d_cls_b, const int32_t* h_off_a,
+                const int32_t* h_off_b, int B, int32_t* d_best, double* d_best_iou, void* d_ws, size_t ws_bytes, void* stream);
+
 /* Connected components of a scan's graph.  Vertices 0..V-1, 1 <= V <= SG_MAX_CLOUD_POINTS; the undirected graph comes from
  * one of three sources:
  *   sg_components_edges  d_edges int32 [E,2], 0 <= E < 2^30: a row (a, a) is a no-op, duplicates and both orientations are allowed, no order

@@ -25,8 +25,8 @@ are the same on every run to the last bit; the sums are deterministic.
     no classes.  --detector-files: OUT/<scene>_bbox.npy, float64 [K,7] = centre (3), full size (3), class id -- axis-aligned from lo / hi
     whatever --kind is.  --ply: OUT/<scene>.boxes.ply, 8 vertices and 12 triangles per kept box in the label palette.
 
-Not here: exact minimum-area rectangles (rotating calipers on a hull), box IoU and detection mAP against ground-truth boxes, merging or
-splitting instances, an up axis other than z.
+Not here: exact minimum-area rectangles (rotating calipers on a hull), merging or splitting instances, an up axis other than z; box IoU
+and detection mAP against ground-truth boxes are `python -m seggroup_amd.boxap` (seggroup_amd/boxap.py).
 """
 from __future__ import annotations
 

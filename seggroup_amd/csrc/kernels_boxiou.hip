@@ -1,0 +1,310 @@
+// IoU of upright boxes, device side: the box consumer beside kernels_boxes.hip's producer.  A box is 8 doubles,
+// cx cy cz sx sy sz c s; include/seggroup_hip.h spells the operation sequence of one pair out, and pair_iou below follows it statement
+// by statement -- it is the ONE device function for a pair, so sg_box_iou and sg_box_best return the same bits for the same pair.
+//
+//   k_bi_check         one thread a box: a value that is not finite, a negative size, |c*c + s*s - 1| > 1e-6 -> a bit of the flag word
+//   k_bi_pairs         one thread a pair.  The pair's scene is bisected in the pair offsets (at most 16 steps of a table that sits in
+//                      L2), then (i, j) = divmod(pair - first pair of the scene, Kb of the scene).
+//   k_bb_best          one wave a box of A, lanes over the boxes of B of its scene in steps of 64; a lane keeps its best (iou, j) --
+//                      strictly greater only, so the lowest j among equals and never an IoU of 0 -- and a butterfly over the wave takes
+//                      the highest IoU, the lowest j among equals.  No Ka x Kb table.
+// The clipped footprint has at most 8 vertices.  It lives in two sets of eight NAMED slots (every index below is a compile-time constant
+// once the loops are unrolled): an append is a predicated move into the slot whose number equals the running count, so nothing is
+// indexed at run time and nothing goes to scratch.  Double arithmetic, nothing contracted (-ffp-contract=off), no floating-point atomics;
+// the only integer atomic is the OR into the flag word.
+#include <cmath>
+#include <vector>
+
+#include "sg_common.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWave = 64;
+constexpr int kWaves = kBlock / kWave;
+constexpr int kMaxBoxes = 1 << 20;            // per side
+constexpr int kMaxScenes = 1 << 16;
+constexpr long long kMaxPairs = 1ll << 24;    // sg_box_iou's d_iou
+constexpr int kSlots = 8;
+constexpr int kNotFinite = 1, kNegative = 2, kNotUnit = 4, kSetB = 3;   // the flag word: three bits for set A, the same three shifted for B
+constexpr double kUnitTol = 1e-6;
+
+struct Landing { int flag, pad[3]; };
+
+__device__ __forceinline__ bool finite_f64(double v) { return (__double2hiint(v) & 0x7ff00000) != 0x7ff00000; }
+
+__global__ __launch_bounds__(kBlock) void k_bi_check(const double* __restrict__ box, int K, int shift, int* __restrict__ flag) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= K) return;
+    const double* p = box + (size_t)i * 8;
+    int bad = 0;
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+        if (!finite_f64(p[r])) bad = kNotFinite;
+    if (!bad) {
+        if (p[3] < 0.0 || p[4] < 0.0 || p[5] < 0.0) bad |= kNegative;
+        const double n = p[6] * p[6] + p[7] * p[7];
+        if (fabs(n - 1.0) > kUnitTol) bad |= kNotUnit;
+    }
+    if (bad) atomicOr(flag, bad << shift);
+}
+
+// slot m of the polygon <- (x, y): eight predicated moves, no run-time index.  An append past slot 7 is dropped (the contract says so).
+__device__ __forceinline__ void put(double (&u)[kSlots], double (&v)[kSlots], int m, double x, double y) {
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j)
+        if (j == m) { u[j] = x; v[j] = y; }
+}
+
+// the signed distance of (u, v) to side SIDE of the rectangle |u| <= hu, |v| <= hv, >= 0 inside: hu - u, u + hu, hv - v, v + hv
+template <int SIDE>
+__device__ __forceinline__ double side_dist(double u, double v, double h) {
+    return SIDE == 0 ? h - u : SIDE == 1 ? u + h : SIDE == 2 ? h - v : v + h;
+}
+
+// One side of Sutherland-Hodgman.  The polygon (iu, iv)[0..n-1] has at most MAXIN vertices; (ou, ov)[0..m-1] is what is left of it.
+template <int SIDE, int MAXIN>
+__device__ __forceinline__ int clip_side(const double (&iu)[kSlots], const double (&iv)[kSlots], int n, double h, double (&ou)[kSlots],
+                                         double (&ov)[kSlots]) {
+    int m = 0;
+    double pu = iu[0], pv = iv[0];                       // the vertex before vertex 0 is vertex n - 1
+#pragma unroll
+    for (int j = 1; j < MAXIN; ++j)
+        if (j == n - 1) { pu = iu[j]; pv = iv[j]; }
+    double dp = side_dist<SIDE>(pu, pv, h);
+#pragma unroll
+    for (int i = 0; i < MAXIN; ++i) {
+        if (i < n) {
+            const double qu = iu[i], qv = iv[i];
+            const double dq = side_dist<SIDE>(qu, qv, h);
+            const bool in_p = dp >= 0.0, in_q = dq >= 0.0;
+            if (in_p != in_q) {
+                const double t = dp / (dp - dq);
+                double xu, xv;
+                if (SIDE < 2) {
+                    xu = SIDE == 0 ? h : -h;              // on the side itself, exactly
+                    xv = pv + t * (qv - pv);
+                } else {
+                    xu = pu + t * (qu - pu);
+                    xv = SIDE == 2 ? h : -h;
+                }
+                put(ou, ov, m, xu, xv);
+                ++m;
+            }
+            if (in_q) {
+                put(ou, ov, m, qu, qv);
+                ++m;
+            }
+            pu = qu;
+            pv = qv;
+            dp = dq;
+        }
+    }
+    return min(m, kSlots);
+}
+
+// IoU(a, b): include/seggroup_hip.h, statement by statement
+__device__ __forceinline__ double pair_iou(const double* __restrict__ a, const double* __restrict__ b) {
+    const double ax = a[0], ay = a[1], az = a[2], asx = a[3], asy = a[4], asz = a[5], ac = a[6], as = a[7];
+    const double bx = b[0], by = b[1], bz = b[2], bsx = b[3], bsy = b[4], bsz = b[5], bc = b[6], bs = b[7];
+    const double dx = ax - bx, dy = ay - by;
+    const double hax = 0.5 * asx, hay = 0.5 * asy, hbx = 0.5 * bsx, hby = 0.5 * bsy;
+    const double ex = hax * ac, ey = hax * as, fx = hay * as, fy = hay * ac;
+    // the corners of a about b's centre: (-,-), (+,-), (+,+), (-,+) along (u, v) of a, counter-clockwise
+    const double wx[4] = {(dx - ex) + fx, (dx + ex) + fx, (dx + ex) - fx, (dx - ex) - fx};
+    const double wy[4] = {(dy - ey) - fy, (dy + ey) - fy, (dy + ey) + fy, (dy - ey) + fy};
+    double pu[kSlots], pv[kSlots], qu[kSlots], qv[kSlots];
+#pragma unroll
+    for (int k = 0; k < kSlots; ++k) pu[k] = pv[k] = qu[k] = qv[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        pu[k] = bc * wx[k] + bs * wy[k];
+        pv[k] = bc * wy[k] - bs * wx[k];
+    }
+    int n = 4;
+    n = clip_side<0, 4>(pu, pv, n, hbx, qu, qv);
+    n = clip_side<1, 5>(qu, qv, n, hbx, pu, pv);
+    n = clip_side<2, 6>(pu, pv, n, hby, qu, qv);
+    n = clip_side<3, 7>(qu, qv, n, hby, pu, pv);
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 1; i + 1 < kSlots; ++i) {
+        if (i + 1 < n) {
+            const double e0 = pu[i] - pu[0], e1 = pv[i] - pv[0], g0 = pu[i + 1] - pu[0], g1 = pv[i + 1] - pv[0];
+            acc = acc + (e0 * g1 - e1 * g0);
+        }
+    }
+    double area = 0.5 * acc;
+    if (!(area > 0.0)) area = 0.0;
+    const double haz = 0.5 * asz, hbz = 0.5 * bsz;
+    const double top = fmin(az + haz, bz + hbz), bottom = fmax(az - haz, bz - hbz);
+    double h = top - bottom;
+    if (!(h > 0.0)) h = 0.0;
+    const double inter = area * h;
+    const double va = (asx * asy) * asz, vb = (bsx * bsy) * bsz;
+    const double uni = (va + vb) - inter;
+    return uni > 0.0 ? inter / uni : 0.0;
+}
+
+// the first s in 0..B-1 with off[s + 1] > x; the caller knows that x < off[B]
+__device__ __forceinline__ int scene_of(const int32_t* __restrict__ off, int B, int x) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (off[mid + 1] > x) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kBlock) void k_bi_pairs(const double* __restrict__ a, const double* __restrict__ b, const int32_t* __restrict__ off_a,
+                                                     const int32_t* __restrict__ off_b, const int32_t* __restrict__ poff, int B, int total,
+                                                     double* __restrict__ iou) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;         // total <= 2^24
+    if (p >= total) return;
+    const int s = scene_of(poff, B, p);
+    const int kb = off_b[s + 1] - off_b[s];                   // > 0: the scene has a pair
+    const int r = p - poff[s];
+    const int i = off_a[s] + r / kb, j = off_b[s] + r % kb;   // inside the sets: the host checked the offsets
+    iou[p] = pair_iou(a + (size_t)i * 8, b + (size_t)j * 8);
+}
+
+__global__ __launch_bounds__(kBlock) void k_bb_best(const double* __restrict__ a, const double* __restrict__ b, const int32_t* __restrict__ cls_a,
+                                                    const int32_t* __restrict__ cls_b, const int32_t* __restrict__ off_a,
+                                                    const int32_t* __restrict__ off_b, int B, int Ka, int32_t* __restrict__ best,
+                                                    double* __restrict__ best_iou) {
+    const int lane = threadIdx.x % kWave;
+    const int i = blockIdx.x * kWaves + threadIdx.x / kWave;  // uniform over the wave
+    if (i >= Ka) return;
+    const int s = scene_of(off_a, B, i);
+    const int j0 = off_b[s], j1 = off_b[s + 1];
+    const int ca = cls_a ? cls_a[i] : 0;
+    double top = 0.0;                                         // an IoU of 0 is not a partner
+    int at = 0x7fffffff;
+    for (int j = j0 + lane; j < j1; j += kWave) {
+        if (cls_a && cls_b[j] != ca) continue;
+        const double v = pair_iou(a + (size_t)i * 8, b + (size_t)j * 8);
+        if (v > top) { top = v; at = j; }                     // ascending j: the lowest among a lane's equals stays
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const double other = __shfl_xor(top, o);
+        const int other_at = __shfl_xor(at, o);
+        if (other > top || (other == top && other_at < at)) { top = other; at = other_at; }
+    }
+    if (lane == 0) {
+        best[i] = at == 0x7fffffff ? -1 : at - j0;
+        best_iou[i] = at == 0x7fffffff ? 0.0 : top;
+    }
+}
+
+bool sizes_ok(int Ka, int Kb, int B) { return Ka >= 0 && Ka <= kMaxBoxes && Kb >= 0 && Kb <= kMaxBoxes && B >= 0 && B <= kMaxScenes; }
+
+size_t table_bytes(int B) { return sg::align_up(sizeof(Landing)) + 3 * sg::align_up((size_t)(B + 1) * sizeof(int32_t)); }
+
+struct Tables {
+    Landing* land;
+    int32_t *off_a, *off_b, *poff;
+    std::vector<int32_t> host;            // off_a | off_b | poff as they were uploaded: alive until the call has synchronised
+    long long pairs;
+};
+
+// offsets ascend from 0 to K: checked on the host, before anything is read through them
+int check_offsets(const char* who, const char* set, const int32_t* h_off, int B, int K) {
+    SG_REQUIRE(h_off[0] == 0, "%s: the offsets of set %s do not start at 0 (%d)", who, set, h_off[0]);
+    for (int s = 0; s < B; ++s)
+        SG_REQUIRE(h_off[s + 1] >= h_off[s], "%s: the offsets of set %s do not ascend (scene %d: %d after %d)", who, set, s, h_off[s + 1], h_off[s]);
+    SG_REQUIRE(h_off[B] == K, "%s: the offsets of set %s end at %d, not at its %d boxes", who, set, h_off[B], K);
+    return SG_OK;
+}
+
+// what both entries do first: the sizes, the offsets (host), the tables on the device, the check of every box
+int prepare(const char* who, const double* d_a, int Ka, const double* d_b, int Kb, const int32_t* h_off_a, const int32_t* h_off_b, int B,
+            void* d_ws, size_t ws_bytes, hipStream_t st, Tables* t) {
+    SG_REQUIRE(Ka >= 0 && Kb >= 0 && B >= 0 && h_off_a && h_off_b, "%s: bad arguments (%d and %d boxes, %d scenes)", who, Ka, Kb, B);
+    if (!sizes_ok(Ka, Kb, B))
+        return sg::fail(SG_EUNSUP, "%s: %d and %d boxes in %d scenes; a call takes at most 2^20 boxes a side and 2^16 scenes", who, Ka, Kb, B);
+    if (int rc = check_offsets(who, "A", h_off_a, B, Ka)) return rc;
+    if (int rc = check_offsets(who, "B", h_off_b, B, Kb)) return rc;
+    SG_REQUIRE((d_a || !Ka) && (d_b || !Kb) && d_ws, "%s: bad arguments", who);
+    const size_t need = table_bytes(B);
+    SG_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    sg::Carver cv(d_ws, ws_bytes);
+    t->land = cv.take<Landing>(1);
+    t->off_a = cv.take<int32_t>((size_t)B + 1);
+    t->off_b = cv.take<int32_t>((size_t)B + 1);
+    t->poff = cv.take<int32_t>((size_t)B + 1);
+    SG_REQUIRE(cv.ok, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    const size_t n = (size_t)B + 1;
+    t->host.resize(3 * n);
+    t->pairs = 0;
+    for (int s = 0; s <= B; ++s) {
+        t->host[s] = h_off_a[s];
+        t->host[n + s] = h_off_b[s];
+        t->host[2 * n + s] = (int32_t)std::min(t->pairs, kMaxPairs + 1);        // used by sg_box_iou alone, which refuses more
+        if (s < B) t->pairs += (long long)(h_off_a[s + 1] - h_off_a[s]) * (h_off_b[s + 1] - h_off_b[s]);
+    }
+    SG_HIP(hipMemsetAsync(t->land, 0, sizeof(Landing), st));
+    SG_HIP(hipMemcpyAsync(t->off_a, t->host.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    SG_HIP(hipMemcpyAsync(t->off_b, t->host.data() + n, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    SG_HIP(hipMemcpyAsync(t->poff, t->host.data() + 2 * n, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (Ka) k_bi_check<<<sg::cdiv(Ka, kBlock), kBlock, 0, st>>>(d_a, Ka, 0, &t->land->flag);
+    if (Kb) k_bi_check<<<sg::cdiv(Kb, kBlock), kBlock, 0, st>>>(d_b, Kb, kSetB, &t->land->flag);
+    return SG_OK;
+}
+
+int land_flag(const char* who, const Tables& t, hipStream_t st) {
+    Landing land{};
+    SG_HIP(hipMemcpyAsync(&land, t.land, sizeof(Landing), hipMemcpyDeviceToHost, st));
+    SG_HIP(hipStreamSynchronize(st));
+    SG_LAUNCH_CHECK();
+    for (int set = 0; set < 2; ++set) {
+        const int f = land.flag >> (set * kSetB) & 7;
+        const char* name = set ? "B" : "A";
+        if (f & kNotFinite) return sg::fail(SG_EINVAL, "%s: a box of set %s has a value that is not finite", who, name);
+        if (f & kNegative) return sg::fail(SG_EINVAL, "%s: a box of set %s has a negative size", who, name);
+        if (f & kNotUnit) return sg::fail(SG_EINVAL, "%s: a box of set %s has (c, s) off the unit circle: |c*c + s*s - 1| > 1e-6", who, name);
+    }
+    return SG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sg_box_iou_ws_bytes(int Ka, int Kb, int B) { return sizes_ok(Ka, Kb, B) ? table_bytes(B) : 0; }
+
+int sg_box_iou(const double* d_a, int Ka, const double* d_b, int Kb, const int32_t* h_off_a, const int32_t* h_off_b, int B, double* d_iou,
+               long long pairs, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* who = "sg_box_iou";
+    hipStream_t st = sg::as_stream(stream);
+    Tables t;
+    if (int rc = prepare(who, d_a, Ka, d_b, Kb, h_off_a, h_off_b, B, d_ws, ws_bytes, st, &t)) return rc;
+    if (t.pairs > kMaxPairs) {
+        (void)hipStreamSynchronize(st);                                        // the uploads out of t.host end here
+        return sg::fail(SG_EUNSUP, "%s: %lld pairs; d_iou holds at most 2^24 (sg_box_best has no such limit)", who, t.pairs);
+    }
+    if (pairs != t.pairs || (t.pairs && !d_iou)) {
+        (void)hipStreamSynchronize(st);
+        return sg::fail(SG_EINVAL, "%s: d_iou holds %lld values and the scenes have %lld pairs", who, pairs, t.pairs);
+    }
+    if (t.pairs)
+        k_bi_pairs<<<sg::cdiv(t.pairs, kBlock), kBlock, 0, st>>>(d_a, d_b, t.off_a, t.off_b, t.poff, B, (int)t.pairs, d_iou);
+    return land_flag(who, t, st);
+}
+
+size_t sg_box_best_ws_bytes(int Ka, int Kb, int B) { return sizes_ok(Ka, Kb, B) ? table_bytes(B) : 0; }
+
+int sg_box_best(const double* d_a, int Ka, const double* d_b, int Kb, const int32_t* d_cls_a, const int32_t* d_cls_b, const int32_t* h_off_a,
+                const int32_t* h_off_b, int B, int32_t* d_best, double* d_best_iou, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* who = "sg_box_best";
+    SG_REQUIRE((d_cls_a == nullptr) == (d_cls_b == nullptr), "%s: classes are given for both sets or for neither", who);
+    SG_REQUIRE((d_best && d_best_iou) || Ka <= 0, "%s: bad arguments", who);
+    hipStream_t st = sg::as_stream(stream);
+    Tables t;
+    if (int rc = prepare(who, d_a, Ka, d_b, Kb, h_off_a, h_off_b, B, d_ws, ws_bytes, st, &t)) return rc;
+    if (Ka)
+        k_bb_best<<<sg::cdiv(Ka, kWaves), kBlock, 0, st>>>(d_a, d_b, d_cls_a, d_cls_b, t.off_a, t.off_b, B, Ka, d_best, d_best_iou);
+    return land_flag(who, t, st);
+}
+
+}  // extern "C"
