@@ -1244,6 +1244,40 @@ size_t sg_box_best_ws_bytes(int Ka, int Kb, int B);
 int sg_box_best(const double* d_a, int Ka, const double* d_b, int Kb, const int32_t* d_cls_a, const int32_t* d_cls_b, const int32_t* h_off_a,
                 const int32_t* h_off_b, int B, int32_t* d_best, double* d_best_iou, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Which boxes hold a point: the way back from boxes to points.  A BOX is 15 doubles, cx cy cz sx sy sz r00 r01 .. r22: the
+ * centre, the FULL size along the rows of R, and R row-major; the rows of R are the box axes (Boxes.center, Boxes.size, Boxes.R as they
+ * stand).  The test does not need an upright box: any orthonormal frame is taken.  Points are d_xyz rows of `stride` >= 3 floats.  Points
+ * [N] and boxes [K,15] are flat over `B` scenes; the host tables h_off_p [B+1] and h_off_b [B+1] delimit the scenes (ascending from 0 to
+ * N / K; a scene may be empty on either side) and only points and boxes of the same scene meet.  Double arithmetic on the widened fp32
+ * inputs, every operation rounded once, nothing contracted, no floating-point atomics, the caller's stream, one synchronisation per call;
+ * the _ws_bytes function returns 0 for a size the entry does not take.  At most 2^24 points, 2^20 boxes and 2^16 scenes.
+ *
+ * Point p against box b, THE OPERATION SEQUENCE (tests/boxlabels_ref.py restates it one statement per operation):
+ *   d_i = double(p_i) - c_i,                          i = 0, 1, 2
+ *   l_k = (r_k0*d_0 + r_k1*d_1) + r_k2*d_2,           k = 0, 1, 2
+ *   h_k = 0.5*s_k + margin
+ *   b holds p iff fabs(l_k) <= h_k for all three k: a face is inside.  vol = (s_0*s_1)*s_2; the margin does not enter it.
+ * Outputs, int32 [N] each, with indices counted WITHIN the scene's boxes:
+ *   d_count  the number of boxes of the point's scene that hold it
+ *   d_first  the lowest index of a box that holds it, -1 if none
+ *   d_inner  the box of smallest vol among those that hold it, the lowest index among equal volumes, -1 if none: the boxes are visited
+ *            in ascending index and a box replaces the one kept only when its vol is smaller (vol < kept)
+ *   d_held   (may be NULL) int32 [K]: per box the number of points it holds; integer sums, so the same on every run
+ * All are order-free (a sum of 0/1, a minimum index, a minimum of (vol, index)): no tiling shows, and equality with the restatement is
+ * the gate.  N = 0 or K = 0 is SG_OK; a point of a scene without boxes gets 0 / -1 / -1 whatever its coordinates are.
+ *
+ * SG_EINVAL: a null pointer, stride < 3, negative sizes, a margin that is negative or not finite, offsets that do not start at 0, do not
+ *   ascend or do not end at N / K (host tables, checked on the host before the first launch), a workspace below the _ws_bytes function;
+ *   and, through one flag word on the device that is read with the call's synchronisation (the outputs are then undefined): a point of a
+ *   scene that has boxes with a coordinate that is not finite, a box value that is not finite, a negative size (0 is valid: a sheet or a
+ *   point box holds what lies exactly on it), a row of R with |r.r - 1| > 1e-6 or two rows with |r_i.r_j| > 1e-6, the dot product taken
+ *   as l_k above.  Every message names the entry.  SG_EUNSUP: N > 2^24, K > 2^20, B > 2^16.  No stage timer: tools/time_boxlabels.py
+ *   brackets the entry with events on the caller's stream. */
+size_t sg_points_in_boxes_ws_bytes(int N, int K, int B);
+int sg_points_in_boxes(const float* d_xyz, int stride, int N, const double* d_box, int K, const int32_t* h_off_p, const int32_t* h_off_b, int B,
+                       double margin, int32_t* d_count, int32_t* d_first, int32_t* d_inner, int32_t* d_held, void* d_ws, size_t ws_bytes,
+                       void* stream);
+
 /* Connected components of a scan's graph.  Vertices 0..V-1, 1 <= V <= SG_MAX_CLOUD_POINTS; the undirected graph comes from
  * one of three sources:
  *   sg_components_edges  d_edges int32 [E,2], 0 <= E < 2^30: a row (a, a) is a no-op, duplicates and both orientations are allowed, no order

@@ -26,7 +26,8 @@ are the same on every run to the last bit; the sums are deterministic.
     whatever --kind is.  --ply: OUT/<scene>.boxes.ply, 8 vertices and 12 triangles per kept box in the label palette.
 
 Not here: exact minimum-area rectangles (rotating calipers on a hull), merging or splitting instances, an up axis other than z; box IoU
-and detection mAP against ground-truth boxes are `python -m seggroup_amd.boxap` (seggroup_amd/boxap.py).
+and detection mAP against ground-truth boxes are `python -m seggroup_amd.boxap` (seggroup_amd/boxap.py); which boxes hold a
+point, and weak labels from boxes, are `python -m seggroup_amd.boxlabels` (seggroup_amd/boxlabels.py).
 """
 from __future__ import annotations
 
