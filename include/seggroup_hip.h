@@ -1244,6 +1244,38 @@ size_t sg_box_best_ws_bytes(int Ka, int Kb, int B);
 int sg_box_best(const double* d_a, int Ka, const double* d_b, int Kb, const int32_t* d_cls_a, const int32_t* d_cls_b, const int32_t* h_off_a,
                 const int32_t* h_off_b, int B, int32_t* d_best, double* d_best_iou, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Non-maximum suppression of upright boxes: the duplicates of a box set removed, greedily by score.  A BOX is the 8
+ * doubles of the IoU entries above, cx cy cz sx sy sz c s; d_box [K,8], d_score [K] (doubles) and d_cls [K] (int32, or NULL for
+ * class-agnostic suppression) are flat over `B` scenes; the host table h_off [B+1] delimits the scenes (ascending from 0 to K; a scene may
+ * be empty) and only boxes of one scene meet.  Double arithmetic, every operation rounded once, nothing contracted, no floating-point
+ * atomics, the caller's stream, one synchronisation per call; the _ws_bytes function returns 0 for a size the entry does not take.
+ *
+ * THE RULE (tests/boxnms_ref.py restates it in plain loops):
+ *   ORDER: within a scene i comes BEFORE j iff s_i > s_j, or s_i == s_j and i < j -- a comparison of doubles, so -0.0 ties with 0.0.
+ *   The scene is visited in that order.  Box j is SUPPRESSED iff some box i before it is KEPT, has the class of j (when classes are
+ *   given) and IoU(a = box i, b = box j) > thresh, strictly (sg_box_best's partners and boxap's rule): the IoU is the operation sequence
+ *   above with the EARLIER box as a -- the sequence is not symmetric, so the argument order is part of the contract.  Otherwise j is KEPT.
+ *   The REPRESENTATIVE of a suppressed box is the FIRST such i in the order; a kept box represents itself.  So a box that only a
+ *   suppressed box overlaps is kept: that is the whole difference from "overlaps anything better".
+ * Outputs, int32 [K] each, addressed by the box's ORIGINAL position, indices counted WITHIN the scene (as sg_box_best's are):
+ *   d_rank  the box's place in its scene's order, 0 first
+ *   d_keep  1 or 0
+ *   d_rep   a kept box's own index; for a suppressed box the index of the box that suppressed it
+ * All are integers: equality with the restatement is the gate, and the same bytes come back on every run.
+ * `words` is the sum over the scenes of n_s * ceil(n_s / 64), the 64-bit words of the suppression bit matrix (row i of a scene in rank
+ * order holds the bits of the boxes after it); the caller passes it as sg_box_iou takes `pairs`, and sg_box_nms_ws_bytes(K, B, words)
+ * sizes the workspace from it.  K = 0 is SG_OK.
+ *
+ * SG_EINVAL: a null pointer, offsets that do not start at 0, do not ascend or do not end at K (a host table, checked on the host before
+ *   the first launch), thresh that is not finite or outside [0, 1), `words` that is not the scenes' sum, a workspace below the _ws_bytes
+ *   function; and, through one flag word on the device that is read with the call's synchronisation (the outputs are then undefined): a
+ *   box value or a score that is not finite, a negative size (0 is valid), |c*c + s*s - 1| > 1e-6.  Every message names the entry.
+ *   SG_EUNSUP: K > 2^20, B > 2^16, a scene of more than 2^14 boxes, words > 2^24 (128 MB of bits).  No stage timer: tools/time_boxnms.py
+ *   brackets the entry with events on the caller's stream. */
+size_t sg_box_nms_ws_bytes(int K, int B, long long words);
+int sg_box_nms(const double* d_box, const double* d_score, const int32_t* d_cls, int K, const int32_t* h_off, int B, double thresh,
+               int32_t* d_rank, int32_t* d_keep, int32_t* d_rep, long long words, void* d_ws, size_t ws_bytes, void* stream);
+
 /* Which boxes hold a point: the way back from boxes to points.  A BOX is 15 doubles, cx cy cz sx sy sz r00 r01 .. r22: the
  * centre, the FULL size along the rows of R, and R row-major; the rows of R are the box axes (Boxes.center, Boxes.size, Boxes.R as they
  * stand).  The test does not need an upright box: any orthonormal frame is taken.  Points are d_xyz rows of `stride` >= 3 floats.  Points

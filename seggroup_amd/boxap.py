@@ -35,8 +35,9 @@ is true positives / ground-truth boxes.
     OUT/<scene>.boxmatch.npz (best, iou, cls per prediction, and the ground truth's classes), one OUT/boxap_report.json (per class and
     threshold AP, recall, predictions, ground truth, true positives; mAP per threshold; the parameters), and the table on the terminal.
 
-Not here: exact 3D IoU of tilted (pca) boxes, non-maximum suppression, rotating calipers, an up axis other than z; which boxes hold a
-point (any kind, pca too) is seggroup_amd/boxlabels.py.
+Not here: exact 3D IoU of tilted (pca) boxes, rotating calipers, an up axis other than z; which boxes hold a point (any kind, pca too) is
+seggroup_amd/boxlabels.py; non-maximum suppression -- a prediction tree with duplicates counts each as a false positive
+-- is seggroup_amd/boxnms.py, whose filtered tree --pred reads as it is.
 """
 from __future__ import annotations
 

@@ -27,7 +27,8 @@ are the same on every run to the last bit; the sums are deterministic.
 
 Not here: exact minimum-area rectangles (rotating calipers on a hull), merging or splitting instances, an up axis other than z; box IoU
 and detection mAP against ground-truth boxes are `python -m seggroup_amd.boxap` (seggroup_amd/boxap.py); which boxes hold a
-point, and weak labels from boxes, are `python -m seggroup_amd.boxlabels` (seggroup_amd/boxlabels.py).
+point, and weak labels from boxes, are `python -m seggroup_amd.boxlabels` (seggroup_amd/boxlabels.py); removing stacked or
+duplicate boxes (non-maximum suppression) is `python -m seggroup_amd.boxnms` (seggroup_amd/boxnms.py).
 """
 from __future__ import annotations
 

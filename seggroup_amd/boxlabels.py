@@ -26,8 +26,9 @@ exactly one box almost surely belongs to that instance, and a segment whose vert
     table), ROOT/label/seg/<style-name>/boxlabels_report.json, and -- where ROOT/data/resampled/<s>/<s>.map.pth exists -- the resampled
     label.pth through labels.generate_weak_label_pth; `infer` and `train` then take --label_style <style-name>.
 
-Not here: a spatial index over the boxes (brute force), refining the labels inside a box, non-maximum suppression, IoU of tilted boxes,
-scene packs for a dataset without label/real.
+Not here: a spatial index over the boxes (brute force), refining the labels inside a box, IoU of tilted boxes, scene packs for a dataset
+without label/real; non-maximum suppression -- a detector's overlapping proposals leave every vertex "in several boxes" -- is
+seggroup_amd/boxnms.py, whose filtered tree --boxes reads as it is.
 """
 from __future__ import annotations
 

@@ -1,6 +1,7 @@
 // IoU of upright boxes, device side: the box consumer beside kernels_boxes.hip's producer.  A box is 8 doubles,
 // cx cy cz sx sy sz c s; include/seggroup_hip.h spells the operation sequence of one pair out, and pair_iou below follows it statement
-// by statement -- it is the ONE device function for a pair, so sg_box_iou and sg_box_best return the same bits for the same pair.
+// by statement -- it is the ONE device function for a pair (box_iou_device.h, shared with kernels_boxnms.hip), so sg_box_iou and
+// sg_box_best return the same bits for the same pair.
 //
 //   k_bi_check         one thread a box: a value that is not finite, a negative size, |c*c + s*s - 1| > 1e-6 -> a bit of the flag word
 //   k_bi_pairs         one thread a pair.  The pair's scene is bisected in the pair offsets (at most 16 steps of a table that sits in
@@ -8,16 +9,17 @@
 //   k_bb_best          one wave a box of A, lanes over the boxes of B of its scene in steps of 64; a lane keeps its best (iou, j) --
 //                      strictly greater only, so the lowest j among equals and never an IoU of 0 -- and a butterfly over the wave takes
 //                      the highest IoU, the lowest j among equals.  No Ka x Kb table.
-// The clipped footprint has at most 8 vertices.  It lives in two sets of eight NAMED slots (every index below is a compile-time constant
-// once the loops are unrolled): an append is a predicated move into the slot whose number equals the running count, so nothing is
-// indexed at run time and nothing goes to scratch.  Double arithmetic, nothing contracted (-ffp-contract=off), no floating-point atomics;
-// the only integer atomic is the OR into the flag word.
+// Double arithmetic, nothing contracted (-ffp-contract=off), no floating-point atomics; the only integer atomic is the OR into the flag
+// word.
 #include <cmath>
 #include <vector>
 
 #include "sg_common.h"
+#include "box_iou_device.h"
 
 namespace {
+
+using namespace sg_box;                       // put, side_dist, clip_side, pair_iou, finite_f64, scene_of: the one pair function
 
 constexpr int kBlock = 256;
 constexpr int kWave = 64;
@@ -25,13 +27,10 @@ constexpr int kWaves = kBlock / kWave;
 constexpr int kMaxBoxes = 1 << 20;            // per side
 constexpr int kMaxScenes = 1 << 16;
 constexpr long long kMaxPairs = 1ll << 24;    // sg_box_iou's d_iou
-constexpr int kSlots = 8;
 constexpr int kNotFinite = 1, kNegative = 2, kNotUnit = 4, kSetB = 3;   // the flag word: three bits for set A, the same three shifted for B
 constexpr double kUnitTol = 1e-6;
 
 struct Landing { int flag, pad[3]; };
-
-__device__ __forceinline__ bool finite_f64(double v) { return (__double2hiint(v) & 0x7ff00000) != 0x7ff00000; }
 
 __global__ __launch_bounds__(kBlock) void k_bi_check(const double* __restrict__ box, int K, int shift, int* __restrict__ flag) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -47,113 +46,6 @@ __global__ __launch_bounds__(kBlock) void k_bi_check(const double* __restrict__ 
         if (fabs(n - 1.0) > kUnitTol) bad |= kNotUnit;
     }
     if (bad) atomicOr(flag, bad << shift);
-}
-
-// slot m of the polygon <- (x, y): eight predicated moves, no run-time index.  An append past slot 7 is dropped (the contract says so).
-__device__ __forceinline__ void put(double (&u)[kSlots], double (&v)[kSlots], int m, double x, double y) {
-#pragma unroll
-    for (int j = 0; j < kSlots; ++j)
-        if (j == m) { u[j] = x; v[j] = y; }
-}
-
-// the signed distance of (u, v) to side SIDE of the rectangle |u| <= hu, |v| <= hv, >= 0 inside: hu - u, u + hu, hv - v, v + hv
-template <int SIDE>
-__device__ __forceinline__ double side_dist(double u, double v, double h) {
-    return SIDE == 0 ? h - u : SIDE == 1 ? u + h : SIDE == 2 ? h - v : v + h;
-}
-
-// One side of Sutherland-Hodgman.  The polygon (iu, iv)[0..n-1] has at most MAXIN vertices; (ou, ov)[0..m-1] is what is left of it.
-template <int SIDE, int MAXIN>
-__device__ __forceinline__ int clip_side(const double (&iu)[kSlots], const double (&iv)[kSlots], int n, double h, double (&ou)[kSlots],
-                                         double (&ov)[kSlots]) {
-    int m = 0;
-    double pu = iu[0], pv = iv[0];                       // the vertex before vertex 0 is vertex n - 1
-#pragma unroll
-    for (int j = 1; j < MAXIN; ++j)
-        if (j == n - 1) { pu = iu[j]; pv = iv[j]; }
-    double dp = side_dist<SIDE>(pu, pv, h);
-#pragma unroll
-    for (int i = 0; i < MAXIN; ++i) {
-        if (i < n) {
-            const double qu = iu[i], qv = iv[i];
-            const double dq = side_dist<SIDE>(qu, qv, h);
-            const bool in_p = dp >= 0.0, in_q = dq >= 0.0;
-            if (in_p != in_q) {
-                const double t = dp / (dp - dq);
-                double xu, xv;
-                if (SIDE < 2) {
-                    xu = SIDE == 0 ? h : -h;              // on the side itself, exactly
-                    xv = pv + t * (qv - pv);
-                } else {
-                    xu = pu + t * (qu - pu);
-                    xv = SIDE == 2 ? h : -h;
-                }
-                put(ou, ov, m, xu, xv);
-                ++m;
-            }
-            if (in_q) {
-                put(ou, ov, m, qu, qv);
-                ++m;
-            }
-            pu = qu;
-            pv = qv;
-            dp = dq;
-        }
-    }
-    return min(m, kSlots);
-}
-
-// IoU(a, b): include/seggroup_hip.h, statement by statement
-__device__ __forceinline__ double pair_iou(const double* __restrict__ a, const double* __restrict__ b) {
-    const double ax = a[0], ay = a[1], az = a[2], asx = a[3], asy = a[4], asz = a[5], ac = a[6], as = a[7];
-    const double bx = b[0], by = b[1], bz = b[2], bsx = b[3], bsy = b[4], bsz = b[5], bc = b[6], bs = b[7];
-    const double dx = ax - bx, dy = ay - by;
-    const double hax = 0.5 * asx, hay = 0.5 * asy, hbx = 0.5 * bsx, hby = 0.5 * bsy;
-    const double ex = hax * ac, ey = hax * as, fx = hay * as, fy = hay * ac;
-    // the corners of a about b's centre: (-,-), (+,-), (+,+), (-,+) along (u, v) of a, counter-clockwise
-    const double wx[4] = {(dx - ex) + fx, (dx + ex) + fx, (dx + ex) - fx, (dx - ex) - fx};
-    const double wy[4] = {(dy - ey) - fy, (dy + ey) - fy, (dy + ey) + fy, (dy - ey) + fy};
-    double pu[kSlots], pv[kSlots], qu[kSlots], qv[kSlots];
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) pu[k] = pv[k] = qu[k] = qv[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        pu[k] = bc * wx[k] + bs * wy[k];
-        pv[k] = bc * wy[k] - bs * wx[k];
-    }
-    int n = 4;
-    n = clip_side<0, 4>(pu, pv, n, hbx, qu, qv);
-    n = clip_side<1, 5>(qu, qv, n, hbx, pu, pv);
-    n = clip_side<2, 6>(pu, pv, n, hby, qu, qv);
-    n = clip_side<3, 7>(qu, qv, n, hby, pu, pv);
-    double acc = 0.0;
-#pragma unroll
-    for (int i = 1; i + 1 < kSlots; ++i) {
-        if (i + 1 < n) {
-            const double e0 = pu[i] - pu[0], e1 = pv[i] - pv[0], g0 = pu[i + 1] - pu[0], g1 = pv[i + 1] - pv[0];
-            acc = acc + (e0 * g1 - e1 * g0);
-        }
-    }
-    double area = 0.5 * acc;
-    if (!(area > 0.0)) area = 0.0;
-    const double haz = 0.5 * asz, hbz = 0.5 * bsz;
-    const double top = fmin(az + haz, bz + hbz), bottom = fmax(az - haz, bz - hbz);
-    double h = top - bottom;
-    if (!(h > 0.0)) h = 0.0;
-    const double inter = area * h;
-    const double va = (asx * asy) * asz, vb = (bsx * bsy) * bsz;
-    const double uni = (va + vb) - inter;
-    return uni > 0.0 ? inter / uni : 0.0;
-}
-
-// the first s in 0..B-1 with off[s + 1] > x; the caller knows that x < off[B]
-__device__ __forceinline__ int scene_of(const int32_t* __restrict__ off, int B, int x) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = lo + (hi - lo) / 2;
-        if (off[mid + 1] > x) hi = mid; else lo = mid + 1;
-    }
-    return lo;
 }
 
 __global__ __launch_bounds__(kBlock) void k_bi_pairs(const double* __restrict__ a, const double* __restrict__ b, const int32_t* __restrict__ off_a,

@@ -223,6 +223,8 @@ SIGNATURES = {
     "sg_box_iou": (_I, [vp, _I, vp, _I, vp, vp, _I, vp, C.c_longlong, vp, _Z, vp]),
     "sg_box_best_ws_bytes": (_Z, [_I, _I, _I]),
     "sg_box_best": (_I, [vp, _I, vp, _I, vp, vp, vp, vp, _I, vp, vp, vp, _Z, vp]),
+    "sg_box_nms_ws_bytes": (_Z, [_I, _I, C.c_longlong]),
+    "sg_box_nms": (_I, [vp, vp, vp, _I, vp, _I, C.c_double, vp, vp, vp, C.c_longlong, vp, _Z, vp]),
     "sg_points_in_boxes_ws_bytes": (_Z, [_I, _I, _I]),
     "sg_points_in_boxes": (_I, [vp, _I, _I, vp, _I, vp, vp, _I, C.c_double, vp, vp, vp, vp, vp, _Z, vp]),
     "sg_components_ws_bytes": (_Z, [_I]),
