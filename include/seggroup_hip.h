@@ -1340,6 +1340,46 @@ int sg_components_set_timing(int on);
 int sg_components_stage_times(float* h_us, int cap);
 const char* sg_components_stage_name(int i);
 
+/* Geodesic distances over a scan's graph: multi-source shortest paths along the edges, and which seed owns a vertex.
+ * Vertices 0..V-1, 1 <= V <= SG_MAX_CLOUD_POINTS.  d_edges int32 [E,2], 0 <= E <= 2^26, with sg_components_edges' rules: any order,
+ * duplicates and both orientations allowed, a row (a, a) is a no-op -- the rows of adj.pth.  The graph is undirected: a row gives two arcs.
+ * WEIGHTS, at most one of the two:
+ *   d_xyz     rows of `stride` >= 3 floats: the length of a row (a, b) in double, d = (double)p_a - (double)p_b,
+ *             w = sqrt((d0*d0 + d1*d1) + d2*d2), each operation rounded once, nothing contracted; symmetric by construction.
+ *   d_weight  double [E]: finite and >= 0; duplicate rows may carry different weights and all of them count.
+ *   neither   every arc weighs 1.0: distances are hop counts, exact integers.
+ * SEEDS: d_seed int32 [V]; v is a seed iff d_seed[v] >= 0 (a weak-label `ins` vector passes as it is).
+ *
+ * THE RULE for d_dist (double [V]): the unique greatest solution of D(s) = 0 for seeds and D(v) = min over arcs (u, v) of D(u) + w(u, v),
+ *   every addition rounded once -- what Dijkstra in double gives (tests/geodesic_ref.py).  A vertex no seed reaches has +inf.  fl(d + w) is
+ *   monotone in d and never below d, so the relaxation's fixed point from +inf is unique: the minimum over walks of the left-to-right
+ *   rounded sum, whatever the order of the updates.  max_dist is +inf for none, else finite and >= 0: a candidate ABOVE it is not taken,
+ *   and the result is the unlimited one with every D > max_dist replaced by +inf (prefixes of a best walk are never longer than it).
+ * THE RULE for d_owner (int32 [V]): an arc (u, v) is TIGHT iff D(v) is finite and D(u) + w(u, v) == D(v), the same double addition;
+ *   owner(v) is the lowest seed (its vertex index) from which v is reached over tight arcs: the least solution of O(s) <= s for seeds and
+ *   O(v) = min over tight arcs (u, v) of O(u).  An unreached vertex has -1.  Two phases on purpose: a pair (D, owner) relaxed together
+ *   depends on the order when two sums round to one value; integers and a minimum do not.  Zero weights and absorbed weights
+ *   (1.0 + 1e-20 == 1.0) make tight cycles; the rule covers them.
+ * The same bytes on every run and every stream.  E = 0 and "no seed" are SG_OK: with E = 0 a seed owns itself, all else is +inf / -1.
+ *
+ * sg_graph_geodesic_stats: the calling thread's last call, int64: h[0] arcs kept (two a row that is no self loop), h[1] distance launches,
+ *   h[2] owner launches, h[3] tight arcs, h[4] reached vertices; returns 5.  The launch counts are launches ENQUEUED: whole batches, so up to
+ *   a batch less one more than the launch that first changed nothing.  They are informative: they may differ from run
+ *   to run, the outputs may not.
+ * SG_EINVAL, on the host before the first HIP call: a null pointer where one is needed, V < 1, E < 0, stride < 3 with d_xyz, both d_xyz
+ *   and d_weight, max_dist that is NaN or negative, a workspace below the _ws_bytes function; through one flag word on the device, read
+ *   with the call's last synchronisation (the outputs are then undefined; such a row is dropped, never used): a vertex index outside
+ *   0..V-1, a weight that is negative or not finite, a coordinate of an edge's end that is not finite.  SG_EUNSUP: V above
+ *   SG_MAX_CLOUD_POINTS, E > 2^26.  SG_EINTERNAL: more than V + 1 launches of either phase, which no input can cause.  Every message names
+ *   the entry.  The stream is synchronised once per batch of relaxation launches.  No stage timer: tools/time_geodesic.py brackets the
+ *   entry with events on the caller's stream. */
+/* The workspace function does not know the metric, so it always holds room for one double weight per arc (16 E bytes, 1 GB at the limit),
+ * which a call by hops leaves unused. */
+size_t sg_graph_geodesic_ws_bytes(int V, long long E);      /* 0 outside the envelope */
+int sg_graph_geodesic(const int32_t* d_edges, long long E, int V, const float* d_xyz, int stride, const double* d_weight, const int32_t* d_seed,
+                      double max_dist, double* d_dist, int32_t* d_owner, void* d_ws, size_t ws_bytes, void* stream);
+int sg_graph_geodesic_stats(int64_t* h, int cap);           /* the calling thread's last call */
+
 /* The radius graph on the exact grid index: every pair of points i != j with d2 <= r2, where d = p_j - p_i,
  * d2 = (d0*d0 + d1*d1) + d2*d2 and r2 = radius * radius, fp32, each operation rounded once -- sg_components_knn's pair predicate over ALL
  * pairs of the cloud, not over a kNN table.  Coincident points are neighbours.  Points are rows of `stride` >= 3 floats,

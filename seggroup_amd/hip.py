@@ -234,6 +234,9 @@ SIGNATURES = {
     "sg_components_set_timing": (_I, [_I]),
     "sg_components_stage_times": (_I, [vp, _I]),
     "sg_components_stage_name": (C.c_char_p, [_I]),
+    "sg_graph_geodesic_ws_bytes": (_Z, [_I, C.c_longlong]),
+    "sg_graph_geodesic": (_I, [vp, C.c_longlong, _I, vp, _I, vp, vp, C.c_double, vp, vp, vp, _Z, vp]),
+    "sg_graph_geodesic_stats": (_I, [vp, _I]),
     "sg_radius_grid_ws_bytes": (_Z, [_I]),
     "sg_radius_count_grid": (_I, [vp, _I, _I, C.c_float, C.c_float, vp, vp, _Z, vp]),
     "sg_components_radius": (_I, [vp, _I, _I, C.c_float, C.c_float, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),

@@ -36,7 +36,10 @@ geometry, the distances in the report are those after alignment.
 Not here: a distance cut-off that un-labels far vertices (a lifted .sgl has no "no segment" for a vertex: the report says how far the
 vertices are -- after the alignment, when there is one -- and the decision is the user's), interpolation or distance-weighted votes,
 anything but a rigid transform between the two geometries (no scale, no deformation, no trimming or robust weights, no registration
-without a starting pose: align.py says what its ICP is and is not), and segs.json or clicks (rekey.py and thin.py own those).
+without a starting pose: align.py says what its ICP is and is not), and segs.json or clicks (rekey.py and thin.py own those).  Every
+search here is Euclidean: the nearest vertex THROUGH SPACE, which is right between two geometries of one room and wrong for spreading a
+click over its own scan (a chair's label reaches the table top 5 cm away).  Distances ALONG the scan's graph, the click nearest along the
+surface and the labels grown from clicks that way are seggroup_amd/geodesic.py.
 """
 from __future__ import annotations
 
