@@ -1380,6 +1380,62 @@ int sg_graph_geodesic(const int32_t* d_edges, long long E, int V, const float* d
                       double max_dist, double* d_dist, int32_t* d_owner, void* d_ws, size_t ws_bytes, void* stream);
 int sg_graph_geodesic_stats(int64_t* h, int cap);           /* the calling thread's last call */
 
+/* A scan and its labels as images: a z-buffer rasteriser of the scan's triangles, or of its points as square splats, into
+ * B views of W x H pixels in one call.  d_xyz rows of `stride` >= 3 floats, vertices 0..V-1; d_faces int32 [F,3] with F > 0 draws triangles,
+ * d_faces NULL with F == 0 draws every point as a splat of side `point_size` (odd, 1..15; ignored for triangles).  h_cam HOST double [B,16]:
+ * T, a row-major 3 x 4 world->camera matrix, then fx fy cx cy.  The camera looks along +z, x to the right, y down.  Outputs [B,H,W]:
+ * d_prim int32 (the winning face or point, -1 where empty), d_depth float (+inf where empty; may be NULL), d_vert int32 (a vertex index,
+ * -1 where empty; may be NULL), and d_hits int32 [V] or NULL: the pixels of all B views whose d_vert is v.
+ *
+ * THE RULE (tests/render_ref.py restates it).  Everything is in double unless said otherwise, each operation rounded once, nothing
+ * contracted; all integer work is int64.
+ *   CAMERA SPACE   c_k = ((T[k][0]*x + T[k][1]*y) + T[k][2]*z) + T[k][3], k = 0, 1, 2.
+ *   REJECTION      checked in this order.  A vertex with a coordinate that is not finite, with a c_k that is not finite, or with
+ *                  c_2 <= near (a NaN counts as such) is BEHIND.  Otherwise u, v are formed, and a vertex with |u| or |v| above 16384 (or
+ *                  NaN) is FAR.  A primitive with a behind or far vertex is dropped whole and counted once: as behind if any of its
+ *                  vertices is behind, otherwise as far.  Nothing is clipped.  Both projections count alike, and `near` applies to both.
+ *   SCREEN         perspective u = fx*(c_0/c_2) + cx, v = fy*(c_1/c_2) + cy; orthographic u = fx*c_0 + cx, v = fy*c_1 + cy.  Fixed point:
+ *                  X = (int)floor(u*256.0 + 0.5), Y likewise.  |X|, |Y| <= 2^22, so every edge function stays below 2^47 and converts to
+ *                  double exactly.
+ *   COVERAGE       the centre of pixel (px, py) is C = (256*px + 128, 256*py + 128).  With corners P_0, P_1, P_2 in the face's order,
+ *                  w_i = (X_k - X_j)*(C_y - Y_j) - (Y_k - Y_j)*(C_x - X_j) for (i, j, k) = (0, 1, 2), (1, 2, 0), (2, 0, 1): the edge
+ *                  function opposite corner i.  A = w_0 + w_1 + w_2, the same for every pixel.  A == 0 is DEGENERATE: dropped.  A < 0:
+ *                  all four are negated (two-sided).  The pixel is covered iff every w_i >= 0: a centre on an edge is inside, and since
+ *                  nothing is blended no fill rule is needed.
+ *   DEPTH          perspective s = ((double)w_0*(1.0/z_0) + (double)w_1*(1.0/z_1)) + (double)w_2*(1.0/z_2), zp = 1.0 / (s / (double)A);
+ *                  orthographic s over z_i in the same order, zp = s / (double)A.  z_i is c_2 of corner i.  depth = (float)zp: not
+ *                  negative, so its bits order as uint32.
+ *   WINNER         key = (bits(depth) << 32) | primitive index; a pixel keeps the least key of the primitives that cover it: the nearest,
+ *                  and at equal float depth the lower index.  An empty pixel has d_prim -1, d_depth +inf, d_vert -1.
+ *   d_vert         the corner of the winning face with the largest w_i at that pixel, a tie to the lower corner position, as its vertex index.
+ *   SPLATS         point i covers the square of side point_size centred on pixel (X >> 8, Y >> 8) (arithmetic shifts), clipped to the
+ *                  image; depth = (float)c_2; d_prim = d_vert = i.
+ *   d_hits[v]      the number of pixels over all B views whose d_vert is v: integer adds.
+ * The same bytes on every run and every stream.  No primitive in view is SG_OK and an empty image.
+ *
+ * sg_render_stats: the calling thread's last call, int64, summed over the views: h[0] primitives kept, h[1] behind, h[2] far,
+ *   h[3] degenerate, h[4] LARGE -- kept triangles whose clipped box (the pixels whose centres lie inside the corners' bounding box, clipped
+ *   to the image) is wider or higher than the small-primitive threshold, 8 --, h[5] covered pixels; returns 6.  None depends on the
+ *   schedule.  sg_render_set_tuning(1..32) sets that threshold for the whole PROCESS, 0 restores the build's: a knob of
+ *   tools/time_render.py, not part of the interface.  h[4] (LARGE) is counted against the threshold in force, so it depends on the knob;
+ *   the images and the other five counts do not.
+ * SG_EINVAL, on the host before the first HIP call: a null pointer where one is needed, V, B, W or H < 1, F < 0, stride < 3, faces without
+ *   F or F without faces, a point_size that is even or outside 1..15 (splats), near that is not finite or <= 0, a camera number that is
+ *   not finite, fx or fy == 0, a workspace below the _ws_bytes function; through one flag word on the device, read at the call's one
+ *   synchronisation (the outputs are then undefined): a face index outside 0..V-1; such a face is dropped and never dereferenced.
+ *   SG_EUNSUP: V above SG_MAX_CLOUD_POINTS, F > 2^26, B > 64, W or H > 4096, B*H*W > 2^26.  Every message names the entry.
+ * The workspace holds 16 bytes per (view, vertex), 8 per pixel and 4 per (view, face): sg_render_ws_bytes(V, F, B, W, H), F = 0 for splats. */
+size_t sg_render_ws_bytes(int V, long long P, int B, int W, int H);     /* 0 outside the envelope */
+int sg_render(const float* d_xyz, int stride, int V, const int32_t* d_faces, long long F, int point_size, int B, const double* h_cam, int ortho,
+              double near, int W, int H, int32_t* d_prim, float* d_depth, int32_t* d_vert, int32_t* d_hits, void* d_ws, size_t ws_bytes, void* stream);
+int sg_render_stats(int64_t* h, int cap);                   /* the calling thread's last call */
+int sg_render_set_tuning(int small);
+/* d_img uint8 [n,3]: pixel i takes h_background (3 bytes, host) where d_vert[i] is outside 0..V-1 (an empty pixel's -1), else the colour of
+ * its vertex: exactly one of d_cidx (uint8 [V], a palette index 0..40 as sg_colour_vector_apply leaves it) and d_rgb (uint8 [V,3]).
+ * 0 <= n <= 2^26.  No synchronisation. */
+int sg_render_colour(const int32_t* d_vert, long long n, const uint8_t* d_cidx, const uint8_t* d_rgb, int V, const uint8_t* h_background,
+                     uint8_t* d_img, void* stream);
+
 /* The radius graph on the exact grid index: every pair of points i != j with d2 <= r2, where d = p_j - p_i,
  * d2 = (d0*d0 + d1*d1) + d2*d2 and r2 = radius * radius, fp32, each operation rounded once -- sg_components_knn's pair predicate over ALL
  * pairs of the cloud, not over a kNN table.  Coincident points are neighbours.  Points are rows of `stride` >= 3 floats,

@@ -237,6 +237,11 @@ SIGNATURES = {
     "sg_graph_geodesic_ws_bytes": (_Z, [_I, C.c_longlong]),
     "sg_graph_geodesic": (_I, [vp, C.c_longlong, _I, vp, _I, vp, vp, C.c_double, vp, vp, vp, _Z, vp]),
     "sg_graph_geodesic_stats": (_I, [vp, _I]),
+    "sg_render_ws_bytes": (_Z, [_I, C.c_longlong, _I, _I, _I]),
+    "sg_render": (_I, [vp, _I, _I, vp, C.c_longlong, _I, _I, vp, _I, C.c_double, _I, _I, vp, vp, vp, vp, vp, _Z, vp]),
+    "sg_render_stats": (_I, [vp, _I]),
+    "sg_render_set_tuning": (_I, [_I]),
+    "sg_render_colour": (_I, [vp, C.c_longlong, vp, vp, _I, vp, vp, vp]),
     "sg_radius_grid_ws_bytes": (_Z, [_I]),
     "sg_radius_count_grid": (_I, [vp, _I, _I, C.c_float, C.c_float, vp, vp, _Z, vp]),
     "sg_components_radius": (_I, [vp, _I, _I, C.c_float, C.c_float, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),
