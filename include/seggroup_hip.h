@@ -186,8 +186,15 @@ int sg_cluster_knn_pruned(const float* d_xyzw, int N, const int32_t* d_cl_off,
  * to the host) fits a block's LDS (2048 points); segments beyond that take a second launch that buckets by the top 12
  * Morton bits in d_ws (sg_segment_sort_ws_bytes(N) = 16 N bytes; unused otherwise) and sorts every run of cells in LDS.
  * Outputs: d_segbox [S,8], d_sperm [N], d_chunk_box.  d_seg_sums (may be NULL): [S,3] double, the sum of every
- * segment's xyz -- layer-invariant, so the host can form any cluster's centroid from it. */
+ * segment's xyz -- layer-invariant, so the host can form any cluster's centroid from it.
+ * Segments of at most 256 points take a launch of their own in front of it: one wave per segment, four segments per block, box / keys /
+ * bitonic network / chunk boxes in registers (same outputs, same bits); the block launch is skipped when max_seg says that no larger
+ * segment exists.  sg_segment_sort_set_wave_max(64 | 128 | 256) sets that size for the whole PROCESS (this call and the scene engine),
+ * 0 sends every segment through the block kernel: a knob of the tests and of A/B timing, not part of the interface.  SG_EINVAL for
+ * any other value.  sg_segment_sort_get_wave_max returns the setting in force. */
 size_t sg_segment_sort_ws_bytes(int N);
+int sg_segment_sort_set_wave_max(int wave_max);
+int sg_segment_sort_get_wave_max(void);
 int sg_segment_sort_boxes(const float* d_data, int N, const int32_t* d_seg_points, const int32_t* d_seg_off,
                           const int32_t* d_seg_of_point, int S, const int32_t* d_seg_chunk_off, int max_seg, float* d_segbox,
                           int32_t* d_sperm, float* d_chunk_box, double* d_seg_sums, void* d_ws, size_t ws_bytes, void* stream);

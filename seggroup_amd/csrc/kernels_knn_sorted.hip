@@ -11,6 +11,7 @@
 //     share their neighbourhood, so after the queries' own segment almost every chunk is rejected by its box.
 // The 64-bit keys carry the MEMBER index, so ties resolve exactly as in the member-order scan ("lower member
 // index wins"), whatever order candidates arrive in.
+#include <atomic>
 #include <cstdlib>
 
 
@@ -72,7 +73,7 @@ constexpr int kSortCap = sg::kSegMidMax;      // = the boundary of the engine's 
 __device__ __forceinline__ void segment_sort_boxes_body(const float* __restrict__ data, const int32_t* __restrict__ seg_points,
                                                         const int32_t* __restrict__ seg_off, const int32_t* __restrict__ seg_chunk_off,
                                                         float* __restrict__ segbox, int32_t* __restrict__ sperm,
-                                                        float* __restrict__ chunk_box, double* __restrict__ seg_sums, int s) {
+                                                        float* __restrict__ chunk_box, double* __restrict__ seg_sums, int s, int wave_max) {
     __shared__ unsigned long long key[kSortCap];
     __shared__ float red[4][8];
     __shared__ double dred[4][3];
@@ -80,6 +81,7 @@ __device__ __forceinline__ void segment_sort_boxes_body(const float* __restrict_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lo = seg_off[s], n = seg_off[s + 1] - lo;
     if (n > kSortCap) return;                                  // k_bigseg_sort_boxes' share (block-uniform)
+    if (wave_max > 0 && n <= wave_max) return;                 // segment_sort_boxes_wave's share
     // 1. segment box {min xyz, max xyz, max |p|^2}
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY}, xx = 0.f;
     double sm[3] = {0.0, 0.0, 0.0};                          // coordinate sums: the host builds cluster centroids from them
@@ -158,13 +160,210 @@ __device__ __forceinline__ void segment_sort_boxes_body(const float* __restrict_
 __global__ __launch_bounds__(256) void k_segment_sort_boxes(const float* __restrict__ data, const int32_t* __restrict__ seg_points,
                                                             const int32_t* __restrict__ seg_off, const int32_t* __restrict__ seg_chunk_off,
                                                             float* __restrict__ segbox, int32_t* __restrict__ sperm,
-                                                            float* __restrict__ chunk_box, double* __restrict__ seg_sums) {
-    segment_sort_boxes_body(data, seg_points, seg_off, seg_chunk_off, segbox, sperm, chunk_box, seg_sums, blockIdx.x);
+                                                            float* __restrict__ chunk_box, double* __restrict__ seg_sums, int wave_max) {
+    segment_sort_boxes_body(data, seg_points, seg_off, seg_chunk_off, segbox, sperm, chunk_box, seg_sums, blockIdx.x, wave_max);
 }
-__global__ __launch_bounds__(256) void k_segment_sort_boxes_b(const sg::SlotCtx* __restrict__ cx) {
+__global__ __launch_bounds__(256) void k_segment_sort_boxes_b(const sg::SlotCtx* __restrict__ cx, int wave_max) {
     const sg::SlotCtx& c = cx[blockIdx.y];
     if ((int)blockIdx.x >= c.S) return;
-    segment_sort_boxes_body(c.data, c.seg_points, c.seg_off, c.seg_chunk_off, c.segbox, c.sperm, c.chunk_box, c.seg_sums, blockIdx.x);
+    segment_sort_boxes_body(c.data, c.seg_points, c.seg_off, c.seg_chunk_off, c.segbox, c.sperm, c.chunk_box, c.seg_sums, blockIdx.x, wave_max);
+}
+
+// The same four outputs, same bits, for segments of <= kWaveCap points -- nearly all of an over-segmentation (median ~100 points) -- on ONE WAVE
+// per segment: point i = lane + 64 u sits in register slot u (kU = 1, 2 or 4 slots), so the box, the keys, the bitonic network and the chunk boxes
+// need no LDS array, no barrier and one read of the rows.  The block kernel above gave such a segment four waves of which one or two held a point and
+// all four walked 21-36 passes with a barrier each.  A pass at lane distance j < 64 fetches the partner's key through the
+// cross-lane data paths (quad_perm at 1 and 2, row_ror at 8, ds_swizzle at 4 and 16, v_permlane32_swap at 32: no memory behind any of them) and
+// keeps the smaller or the larger of the two; at j >= 64 it exchanges two of the lane's own registers.  Keys are unique (the index is in the low bits), so the network's result is
+// the block kernel's order.
+constexpr int kWaveCap = 256;
+std::atomic<int> g_wave_max{kWaveCap};                          // sg_segment_sort_set_wave_max
+
+template <int J>
+__device__ __forceinline__ int lane_xor(int v) {               // v of lane ^ J, J = 1 .. 16
+    static_assert(J == 1 || J == 2 || J == 4 || J == 8 || J == 16, "lane distance");
+    if constexpr (J == 1) return sgw::dpp_i<sgw::kQuadXor1>(v, v);
+    else if constexpr (J == 2) return sgw::dpp_i<sgw::kQuadXor2>(v, v);
+    else if constexpr (J == 8) return sgw::dpp_i<sgw::kRowRor8>(v, v);           // half a row round is an exchange; a quarter (distance 4) is not
+    else return __builtin_amdgcn_ds_swizzle(v, 0x1F | (J << 10));               // bit mode: and 0x1f, or 0, xor J -- the crossbar, no memory
+}
+// lanes that keep the SMALLER key in pass (K, J) of slot u: the lower element of an ascending pair, the upper one of a descending pair
+constexpr unsigned long long take_min_mask(int K, int J, int u) {
+    unsigned long long m = 0;
+    for (int l = 0; l < 64; ++l) {
+        const int e = l | (u << 6);
+        if (((e & J) == 0) == ((e & K) == 0)) m |= 1ull << l;
+    }
+    return m;
+}
+__device__ __forceinline__ unsigned long long pack64(unsigned int hi, unsigned int lo) { return ((unsigned long long)hi << 32) | lo; }
+
+template <int kU, int K, int J>
+__device__ __forceinline__ void bitonic_pass(unsigned long long (&key)[kU]) {
+    if constexpr (J >= 64) {
+        constexpr int d = J >> 6;
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            if (u & d) continue;
+            const bool up = ((u << 6) & K) == 0;
+            const unsigned long long a = key[u], b = key[u | d];
+            const bool sw = (a > b) == up;
+            key[u] = sw ? b : a;
+            key[u | d] = sw ? a : b;
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const bool take_min = __builtin_amdgcn_inverse_ballot_w64(take_min_mask(K, J, u));     // a constant in two SGPRs: no lane arithmetic
+            const unsigned int hi = (unsigned int)(key[u] >> 32), lw = (unsigned int)key[u];
+            unsigned long long a, b;
+            if constexpr (J == 32) {
+                // {lower half of both | upper half of both}: one of the two is the lane's own key, the other its partner's, and min / max do not ask which
+                const auto sl = __builtin_amdgcn_permlane32_swap(lw, lw, false, false);
+                const auto sh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+                a = pack64(sh[0], sl[0]);
+                b = pack64(sh[1], sl[1]);
+            } else {
+                a = key[u];
+                b = pack64((unsigned int)lane_xor<J>((int)hi), (unsigned int)lane_xor<J>((int)lw));
+            }
+            key[u] = ((a < b) == take_min) ? a : b;
+        }
+    }
+}
+template <int kU, int K, int J>
+__device__ __forceinline__ void bitonic_merge(unsigned long long (&key)[kU]) {
+    bitonic_pass<kU, K, J>(key);
+    if constexpr (J > 1) bitonic_merge<kU, K, J / 2>(key);
+}
+template <int kU, int K>
+__device__ __forceinline__ void bitonic_sort(unsigned long long (&key)[kU]) {      // ascending over element lane + 64 u
+    if constexpr (K > 2) bitonic_sort<kU, K / 2>(key);
+    bitonic_merge<kU, K, K / 2>(key);
+}
+
+template <int kU>
+__device__ __forceinline__ void segment_sort_boxes_wave(const float* __restrict__ data, const int32_t* __restrict__ seg_points,
+                                                        const int32_t* __restrict__ seg_chunk_off, float* __restrict__ segbox,
+                                                        int32_t* __restrict__ sperm, float* __restrict__ chunk_box, double* __restrict__ seg_sums,
+                                                        int s, int lo, int n, int lane) {
+    // 1. the rows, once; segment box {min xyz, max xyz, max |p|^2}.  Minima and maxima are taken on the coordinates' order-preserving integer
+    // images (sgw::ford): the same bits fminf / fmaxf select, a third of the instructions per cross-lane step
+    float p[kU][3];
+    const int kPosInf = sgw::ford(INFINITY), kNegInf = sgw::ford(-INFINITY);
+    int omn[3] = {kPosInf, kPosInf, kPosInf}, omx[3] = {kNegInf, kNegInf, kNegInf}, oxx = 0;      // |p|^2 >= +0: its bits order as they are
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+        const int i = lane + 64 * u;
+        p[u][0] = p[u][1] = p[u][2] = 0.f;
+        if (i < n) {
+            const float* r = data + (size_t)seg_points[lo + i] * 6;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { p[u][k] = r[k]; const int o = sgw::ford(r[k]); omn[k] = min(omn[k], o); omx[k] = max(omx[k], o); }
+            oxx = max(oxx, __float_as_int((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]));
+        }
+    }
+    float mn[3], mx[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { mn[k] = sgw::ford_back(sgw::wave_min(omn[k])); mx[k] = sgw::ford_back(sgw::wave_max(omx[k])); }
+    const float xx = __int_as_float(sgw::wave_max(oxx));
+    if (seg_sums) {
+        // the block kernel's tree: slot u is its wave u (one point per thread at these sizes), the four wave sums are added in wave order
+        double d[4][3];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                d[u][k] = 0.0;
+                if (u < kU) {
+                    double t = 0.0;
+                    if (lane + 64 * u < n) t += (double)p[u < kU ? u : 0][k];
+                    d[u][k] = sgw::wave_sum(t);
+                }
+            }
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) seg_sums[(size_t)s * 3 + k] = ((d[0][k] + d[1][k]) + d[2][k]) + d[3][k];
+        }
+    }
+    if (lane == 0) {
+        float* b = segbox + (size_t)s * 8;
+        b[0] = mn[0]; b[1] = mn[1]; b[2] = mn[2]; b[3] = mx[0]; b[4] = mx[1]; b[5] = mx[2]; b[6] = xx; b[7] = 0.f;
+    }
+    if (n == 0) return;
+    // 2. keys (morton30 inside the box just computed); padding sorts last
+    const float bx[6] = {mn[0], mn[1], mn[2], mx[0], mx[1], mx[2]};
+    unsigned long long key[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+        const int i = lane + 64 * u;
+        const unsigned int m = morton30(p[u], bx);
+        key[u] = i < n ? pack64(m, (unsigned int)i) : ~0ull;
+    }
+    // 3. bitonic sort, ascending: sorted position r = lane + 64 u
+    bitonic_sort<kU, 64 * kU>(key);
+    // 4. sorted position -> index into the segment CSR
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+        const int r = lane + 64 * u;
+        if (r < n) sperm[lo + r] = lo + (int)(unsigned int)key[u];
+    }
+    // 5. boxes of the 32-point chunks, two per slot; the sorted points' coordinates come from the lanes that read them
+    const int c0 = seg_chunk_off[s], half = lane >> 5, l = lane & 31;
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+        if (64 * u >= n) break;                                  // wave-uniform
+        const int idx = (int)(unsigned int)key[u], src = (idx & 63) << 2, slot = idx >> 6;     // a padding key reads lane 63: masked below
+        float q[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            int g = __builtin_amdgcn_ds_bpermute(src, __float_as_int(p[0][k]));
+#pragma unroll
+            for (int v = 1; v < kU; ++v) {
+                const int t = __builtin_amdgcn_ds_bpermute(src, __float_as_int(p[v][k]));
+                g = slot == v ? t : g;
+            }
+            q[k] = __int_as_float(g);
+        }
+        const int j = 2 * u + half, t = j * kChunkPts + l;
+        int cmn[3] = {kPosInf, kPosInf, kPosInf}, cmx[3] = {kNegInf, kNegInf, kNegInf}, cxx = 0;
+        if (t < n) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { cmn[k] = sgw::ford(q[k]); cmx[k] = cmn[k]; }
+            cxx = __float_as_int((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { cmn[k] = sgw::ford(sgw::half_min_tail(cmn[k])); cmx[k] = sgw::ford(sgw::half_max_tail(cmx[k])); }
+        cxx = sgw::half_max_tail(cxx);
+        if (l == 31 && j * kChunkPts < n) {                       // the half's last lane holds its results
+            int* b = reinterpret_cast<int*>(chunk_box + (size_t)(c0 + j) * 8);
+            b[0] = cmn[0]; b[1] = cmn[1]; b[2] = cmn[2]; b[3] = cmx[0]; b[4] = cmx[1]; b[5] = cmx[2]; b[6] = cxx; b[7] = 0;
+        }
+    }
+}
+// wave w of block b takes segment 4 b + w; the waves of a block share nothing
+__device__ __forceinline__ void segment_sort_boxes_wave_body(const float* __restrict__ data, const int32_t* __restrict__ seg_points,
+                                                             const int32_t* __restrict__ seg_off, const int32_t* __restrict__ seg_chunk_off,
+                                                             float* __restrict__ segbox, int32_t* __restrict__ sperm,
+                                                             float* __restrict__ chunk_box, double* __restrict__ seg_sums, int S, int wave_max) {
+    const int lane = threadIdx.x & 63;
+    const int s = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (s >= S) return;
+    const int lo = seg_off[s], n = seg_off[s + 1] - lo;
+    if (n < 0 || n > wave_max) return;                           // the block kernel's, or the big-segment chain's
+    if (n <= 64) segment_sort_boxes_wave<1>(data, seg_points, seg_chunk_off, segbox, sperm, chunk_box, seg_sums, s, lo, n, lane);
+    else if (n <= 128) segment_sort_boxes_wave<2>(data, seg_points, seg_chunk_off, segbox, sperm, chunk_box, seg_sums, s, lo, n, lane);
+    else segment_sort_boxes_wave<4>(data, seg_points, seg_chunk_off, segbox, sperm, chunk_box, seg_sums, s, lo, n, lane);
+}
+__global__ __launch_bounds__(256) void k_segment_sort_boxes_wave(const float* __restrict__ data, const int32_t* __restrict__ seg_points,
+                                                                 const int32_t* __restrict__ seg_off, const int32_t* __restrict__ seg_chunk_off,
+                                                                 float* __restrict__ segbox, int32_t* __restrict__ sperm,
+                                                                 float* __restrict__ chunk_box, double* __restrict__ seg_sums, int S, int wave_max) {
+    segment_sort_boxes_wave_body(data, seg_points, seg_off, seg_chunk_off, segbox, sperm, chunk_box, seg_sums, S, wave_max);
+}
+__global__ __launch_bounds__(256) void k_segment_sort_boxes_wave_b(const sg::SlotCtx* __restrict__ cx, int wave_max) {
+    const sg::SlotCtx& c = cx[blockIdx.y];
+    segment_sort_boxes_wave_body(c.data, c.seg_points, c.seg_off, c.seg_chunk_off, c.segbox, c.sperm, c.chunk_box, c.seg_sums, c.S, wave_max);
 }
 
 // Segments of more than kSortCap points (floors, walls: 10k-40k points in ScanNet's over-segmentation) -- same outputs, same order
@@ -838,9 +1037,8 @@ __device__ __forceinline__ void cluster_knn_sorted_body(
         float fbound = score_bound(list_max(use_l, thr_l), ok);
         for (int i = 0; i < m; i += kQuadS) {
             // all kQuadS operand reads first: behind the first conditional store the scheduler would issue them one candidate
-            // at a time and every candidate would wait out its own LDS round trip (with the reads together the compiler also
-            // pairs the candidates' arithmetic into v_pk_mul / v_pk_fma_f32: same IEEE operations, fewer issue slots; a slab laid
-            // out in candidate pairs to drop the packing moves measured no faster)
+            // at a time and every candidate would wait out its own LDS round trip (the build switches packed fp32 arithmetic off, see the
+            // Makefile: the candidates' arithmetic is scalar per lane; a slab laid out in candidate pairs measured no faster)
             float4 c4[kQuadS];
 #pragma unroll
             for (int u = 0; u < kQuadS; ++u) c4[u] = cw[i + u];
@@ -1404,7 +1602,13 @@ bool sort_boxes_fits_lds(int max_seg) { return max_seg <= kSortCap; }
 // which: 1 = the segments of <= kSortCap points, 2 = the larger ones, 3 = both (the engine runs the two chains on two streams: engine.cpp, phase P0)
 int b_sort_boxes(const SlotCtx* d_ctx, const BatchDims& bd, hipStream_t st, int which) {
     if (bd.nslots == 0 || bd.max_S == 0) return SG_OK;
-    if (which & 1) k_segment_sort_boxes_b<<<dim3(bd.max_S, bd.nslots), 256, 0, st>>>(d_ctx);
+    if (which & 1) {
+        // one wave per segment up to wave_max points; the block kernel only when the batch holds a larger one (the host knows the batch's largest
+        // segment; whether one of 257-2,048 points hides behind a floor it does not, and then the block kernel's blocks find out and return)
+        const int wave_max = g_wave_max.load();
+        if (wave_max > 0) k_segment_sort_boxes_wave_b<<<dim3(sg::cdiv(bd.max_S, 4), bd.nslots), 256, 0, st>>>(d_ctx, wave_max);
+        if (bd.max_seg > wave_max) k_segment_sort_boxes_b<<<dim3(bd.max_S, bd.nslots), 256, 0, st>>>(d_ctx, wave_max);
+    }
     if ((which & 2) && bd.max_big > 0) {                                       // windows without a big segment exit at once
         const int wins = sg::cdiv(bd.max_N, kWin);
         k_bigseg_box_b<<<dim3(bd.max_big * kBigPieces, bd.nslots), kPieceBlock, 0, st>>>(d_ctx);
@@ -1480,6 +1684,16 @@ int sg_debug_knn_check(unsigned long long* h_out) {
 }
 #endif
 
+// Largest segment the one-wave kernel takes: 64, 128 or 256 points (the default), 0 = every segment of <= kSortCap points goes to the block
+// kernel.  For the WHOLE PROCESS, both entry points: a knob of the tests and of A/B timing, not part of the interface -- the outputs are the
+// same bits under every setting.
+int sg_segment_sort_set_wave_max(int wave_max) {
+    SG_REQUIRE(wave_max == 0 || wave_max == 64 || wave_max == 128 || wave_max == kWaveCap, "sg_segment_sort_set_wave_max: 0, 64, 128 or %d (%d)", kWaveCap, wave_max);
+    g_wave_max.store(wave_max);
+    return SG_OK;
+}
+int sg_segment_sort_get_wave_max(void) { return g_wave_max.load(); }
+
 // two N-key arrays + one BigScratch record per possible big segment (k_bigseg_box / keys / scatter)
 size_t sg_segment_sort_ws_bytes(int N) { return sg::align_up((size_t)std::max(N, 1) * 16, 64) + bigseg_scratch_slots(std::max(N, 1)) * sizeof(BigScratch) + 64; }
 
@@ -1502,8 +1716,13 @@ int sg_segment_sort_boxes(const float* d_data, int N, const int32_t* d_seg_point
                           int32_t* d_sperm, float* d_chunk_box, double* d_seg_sums, void* d_ws, size_t ws_bytes, void* stream) {
     SG_REQUIRE(N >= 0 && S >= 0 && max_seg >= 0 && d_segbox && d_sperm && d_chunk_box, "sg_segment_sort_boxes: bad arguments");
     if (N == 0 || S == 0) return SG_OK;
-    k_segment_sort_boxes<<<S, 256, 0, sg::as_stream(stream)>>>(d_data, d_seg_points, d_seg_off, d_seg_chunk_off, d_segbox, d_sperm, d_chunk_box,
-                                                               d_seg_sums);
+    const int wave_max = g_wave_max.load();
+    if (wave_max > 0)
+        k_segment_sort_boxes_wave<<<sg::cdiv(S, 4), 256, 0, sg::as_stream(stream)>>>(d_data, d_seg_points, d_seg_off, d_seg_chunk_off, d_segbox, d_sperm,
+                                                                                    d_chunk_box, d_seg_sums, S, wave_max);
+    if (max_seg > wave_max)                                    // a segment of wave_max + 1 .. kSortCap points may exist
+        k_segment_sort_boxes<<<S, 256, 0, sg::as_stream(stream)>>>(d_data, d_seg_points, d_seg_off, d_seg_chunk_off, d_segbox, d_sperm, d_chunk_box,
+                                                                   d_seg_sums, wave_max);
     if (max_seg > kSortCap) {                                  // segments beyond one block's LDS: cell-bucketed LDS sort, scratch = 2 x N keys
         if (!d_ws || ws_bytes < sg_segment_sort_ws_bytes(N)) return sg::fail(SG_ENOMEM, "sg_segment_sort_boxes: workspace too small (%zu < %zu)", ws_bytes, sg_segment_sort_ws_bytes(N));
         unsigned long long* keys = reinterpret_cast<unsigned long long*>(d_ws);

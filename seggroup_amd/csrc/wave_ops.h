@@ -115,6 +115,25 @@ __device__ __forceinline__ float half_min(float v, int lane) {
     return half_reduce_pick(v, lane);
 }
 
+// The same on integers (one v_min_i32_dpp / v_max_i32_dpp per step: a float step pays a move and a canonicalising v_max_f32 on top, because a
+// value that arrives through a lane exchange is not known to be quiet), and the map that lets float minima and maxima ride on them: `ford` is
+// monotonic from the floats' order (-inf < ... < -0 < +0 < ... < +inf, the order v_min_f32 / v_max_f32 use for the two zeros) to the ints', and its
+// own inverse, so min / max of mapped values map back to the bits fminf / fmaxf select.  Not for NaNs.
+__device__ __forceinline__ int ford(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
+__device__ __forceinline__ int ford(float f) { return ford(__float_as_int(f)); }
+__device__ __forceinline__ float ford_back(int o) { return __int_as_float(ford(o)); }
+// over the 32 lanes of each half; the result is valid in the half's LAST lane (31 / 63) only: for a caller whose last lanes do the writing
+__device__ __forceinline__ int half_max_tail(int v) {
+    v = max(v, dpp_i<kQuadXor1>(v, v)); v = max(v, dpp_i<kQuadXor2>(v, v));
+    v = max(v, dpp_i<kRowRor4>(v, v));  v = max(v, dpp_i<kRowRor8>(v, v));
+    return max(v, dpp_i<kRowBcast15, 0xA>(v, v));
+}
+__device__ __forceinline__ int half_min_tail(int v) {
+    v = min(v, dpp_i<kQuadXor1>(v, v)); v = min(v, dpp_i<kQuadXor2>(v, v));
+    v = min(v, dpp_i<kRowRor4>(v, v));  v = min(v, dpp_i<kRowRor8>(v, v));
+    return min(v, dpp_i<kRowBcast15, 0xA>(v, v));
+}
+
 // lane `j` (wave-uniform) of v for every lane: v_readlane_b32 instead of a ds_bpermute round trip
 __device__ __forceinline__ float bcast(float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); }
 __device__ __forceinline__ int bcast(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
