@@ -1443,6 +1443,41 @@ int sg_render_set_tuning(int small);
 int sg_render_colour(const int32_t* d_vert, long long n, const uint8_t* d_cidx, const uint8_t* d_rgb, int V, const uint8_t* h_background,
                      uint8_t* d_img, void* stream);
 
+/* 2D label images onto a scan's vertices: the way back from sg_render's images.  Every vertex is projected into every view,
+ * the view's depth image decides whether the view sees it, the label under it is a vote.  d_xyz rows of `stride` >= 3 floats, vertices
+ * 0..V-1; h_cam HOST double [B,16], `ortho` and `near` as sg_render takes them; d_label int32 [B,H,W] (negative: no label; every other value
+ * is below C); d_depth float [B,H,W], z-depth in the unit of the coordinates: what sg_render writes (+inf where empty) or what a sensor
+ * gives (0 or NaN where invalid); d_counts uint32 [V,C] and d_seen int32 [V].  The call ACCUMULATES into d_counts and d_seen -- the caller
+ * clears them --, so any number of views goes through in calls of at most 64.
+ *
+ * THE RULE (tests/lift_ref.py restates it).  For every (view b, vertex v), decided in this order:
+ *   PROJECTION     sg_render's CAMERA SPACE, REJECTION and SCREEN, the same function (csrc/render_project_device.h): the vertex is BEHIND, or
+ *                  FAR, or has X, Y in 1/256 pixel and its depth c_2, all in double.
+ *   PIXEL          px = X >> 8, py = Y >> 8 (arithmetic shifts): the pixel a splat of size 1 lands on.  Outside 0..W-1 x 0..H-1 the pair is
+ *                  OUTSIDE.
+ *   DEPTH          d = d_depth[b,py,px].  NODEPTH unless d is finite and d > 0.
+ *   OCCLUSION      OCCLUDED iff fabs(c_2 - (double)d) > tol, in double.  Equality is visible.
+ *   VISIBLE        otherwise.  l = d_label[b,py,px].  l >= C raises the flag word: the pair adds NOTHING (not to d_seen, not to d_counts),
+ *                  nothing is indexed by l, and the call returns SG_EINVAL.  Else d_seen[v] += 1, and l < 0 is UNLABELLED (seen, no vote),
+ *                  l >= 0 is LABELLED: d_counts[v*C + l] += 1.
+ * All additions are integer atomics, so the result is the same bytes under any schedule and on any stream.
+ * sg_lift_stats: the calling thread's last call, int64, summed over the views: h[0] behind, h[1] far, h[2] outside, h[3] nodepth,
+ *   h[4] occluded, h[5] visible WITHOUT a label (seen, no vote), h[6] labelled (seen, one vote); returns 7.  The seven are disjoint and sum
+ *   to B*V; h[5] + h[6] is what the call added to d_seen, h[6] what it added to d_counts.  After a refused call all are 0.
+ * SG_EINVAL, on the host before the first HIP call: a null pointer, V, B, W, H or C < 1, stride < 3, near that is not finite or <= 0, tol
+ *   that is not finite or < 0, a camera number that is not finite, fx or fy == 0, a workspace below sg_lift_ws_bytes(V, B); through the flag
+ *   word, read at the call's ONE stream synchronisation: a visible pixel's label >= C (the other pairs have been added as the rule says).
+ *   SG_EUNSUP: V above SG_MAX_CLOUD_POINTS, B > 64, W or H > 4096, B*H*W > 2^26, C > 4096, V*C > 2^31.  Every message names the entry.
+ *
+ * sg_lift_vote: per vertex, int32 [V] each: d_winner the class with the most votes, a tie to the LOWEST class, -1 where the row is all
+ *   zero; d_votes the winner's votes (0 with no winner); d_total the row's sum; d_tied 1 iff another class holds as many votes as the
+ *   winner, else 0.  The same limits on V and C.  No synchronisation. */
+size_t sg_lift_ws_bytes(int V, int B);                      /* 0 outside the envelope */
+int sg_lift(const float* d_xyz, int stride, int V, int B, const double* h_cam, int ortho, double near, int W, int H, const int32_t* d_label,
+            const float* d_depth, double tol, int C, uint32_t* d_counts, int32_t* d_seen, void* d_ws, size_t ws_bytes, void* stream);
+int sg_lift_stats(int64_t* h, int cap);                     /* the calling thread's last call */
+int sg_lift_vote(const uint32_t* d_counts, int V, int C, int32_t* d_winner, int32_t* d_votes, int32_t* d_total, int32_t* d_tied, void* stream);
+
 /* The radius graph on the exact grid index: every pair of points i != j with d2 <= r2, where d = p_j - p_i,
  * d2 = (d0*d0 + d1*d1) + d2*d2 and r2 = radius * radius, fp32, each operation rounded once -- sg_components_knn's pair predicate over ALL
  * pairs of the cloud, not over a kNN table.  Coincident points are neighbours.  Points are rows of `stride` >= 3 floats,

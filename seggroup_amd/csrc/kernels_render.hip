@@ -24,6 +24,7 @@
 #include "box_iou_device.h"
 #include "overseg_device.h"
 #include "palette_device.h"
+#include "render_project_device.h"
 
 namespace {
 
@@ -38,10 +39,9 @@ constexpr int kLargeGrid = 2048;               // workgroups of k_rd_large: 256 
 constexpr long long kMaxFaces = 1ll << 26;
 constexpr long long kMaxPixels = 1ll << 26;
 constexpr int kMaxViews = 64, kMaxSide = 4096, kMaxPointSize = 15;
-constexpr double kGuard = 16384.0;             // |u|, |v| above it: far
 constexpr int kPrimBits = 26;                  // a queue entry: view << 26 | face (F <= 2^26, B <= 64)
 enum { mFlag = 0, mCursor = 1, mKept = 2, mBehind = 3, mFar = 4, mDegenerate = 5, mLarge = 6, mCovered = 7, kMisc = 8 };
-constexpr int kCamDoubles = 16;
+constexpr int kCamDoubles = sgrd::kCamDoubles;
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -65,26 +65,7 @@ __global__ __launch_bounds__(kBlock) void k_rd_project(const float* __restrict__
     const double* c = cam + (size_t)b * kCamDoubles;
     const float* p = xyz + (size_t)v * stride;
     Proj out{0, 0, 0.0};
-    bool ok = sgos::finite_f32(p[0]) && sgos::finite_f32(p[1]) && sgos::finite_f32(p[2]);
-    if (ok) {
-        const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
-        const double c0 = ((c[0] * x + c[1] * y) + c[2] * z) + c[3];
-        const double c1 = ((c[4] * x + c[5] * y) + c[6] * z) + c[7];
-        const double c2 = ((c[8] * x + c[9] * y) + c[10] * z) + c[11];
-        ok = sg_box::finite_f64(c0) && sg_box::finite_f64(c1) && sg_box::finite_f64(c2) && c2 > vw.near;
-        if (ok) {
-            const double fx = c[12], fy = c[13], cx = c[14], cy = c[15];
-            const double u = vw.ortho ? fx * c0 + cx : fx * (c0 / c2) + cx;
-            const double w = vw.ortho ? fy * c1 + cy : fy * (c1 / c2) + cy;
-            if (fabs(u) <= kGuard && fabs(w) <= kGuard) {       // a NaN fails both: far
-                out.X = (int)floor(u * 256.0 + 0.5);
-                out.Y = (int)floor(w * 256.0 + 0.5);
-                out.z = c2;
-            } else {
-                out.z = -1.0;
-            }
-        }
-    }
+    if (sgrd::project(p, c, vw.ortho, vw.near, out.X, out.Y, out.z) == sgrd::kFar) out.z = -1.0;      // the rule itself: render_project_device.h
     proj[(size_t)b * V + v] = out;
 }
 

@@ -244,6 +244,10 @@ SIGNATURES = {
     "sg_render_stats": (_I, [vp, _I]),
     "sg_render_set_tuning": (_I, [_I]),
     "sg_render_colour": (_I, [vp, C.c_longlong, vp, vp, _I, vp, vp, vp]),
+    "sg_lift_ws_bytes": (_Z, [_I, _I]),
+    "sg_lift": (_I, [vp, _I, _I, _I, vp, _I, C.c_double, _I, _I, vp, vp, C.c_double, _I, vp, vp, vp, _Z, vp]),
+    "sg_lift_stats": (_I, [vp, _I]),
+    "sg_lift_vote": (_I, [vp, _I, _I, vp, vp, vp, vp, vp]),
     "sg_radius_grid_ws_bytes": (_Z, [_I]),
     "sg_radius_count_grid": (_I, [vp, _I, _I, C.c_float, C.c_float, vp, vp, _Z, vp]),
     "sg_components_radius": (_I, [vp, _I, _I, C.c_float, C.c_float, vp, vp, vp, C.POINTER(C.c_int), vp, _Z, vp]),

@@ -31,7 +31,7 @@ orbit_views, from_pose (ScanNet's camera-to-world pose and intrinsics).
     first image OUT holds already is skipped without --force.
 
 Not here: clipping against the near plane, shading, lighting, anti-aliasing, textures, a top-left fill rule, lifting 2D labels back onto
-vertices, reading .sens files.
+vertices (that is seggroup_amd/lift.py), reading .sens files.
 """
 from __future__ import annotations
 
