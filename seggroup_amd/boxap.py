@@ -1,8 +1,8 @@
 """Box IoU and detection AP for label boxes on the GPU: the consumer of what `boxes` makes.  How good are pseudo boxes,
 judged the way a 3D detector is judged -- by the IoU of BOXES, not of point masks?
 
-    rows      = box_rows(boxes)                          -- float64 [K,8] = cx cy cz sx sy sz c s of a Boxes of kind aabb or yaw: the
-                                                            centre, the full size, c = R[:,0,0], s = R[:,0,1] (the bits that made the box)
+    rows      = boxset.box_rows(boxes)                   -- float64 [K,8] = cx cy cz sx sy sz c s of a Boxes of kind aabb or yaw; the row
+                                                            layout, the box files and the limits of a call are seggroup_amd/boxset.py's
     blocks    = box_iou(a, b, off_a, off_b)              -- sg_box_iou: [Ka,Kb], or one block per scene when offsets delimit scenes
     best, iou = box_best(a, b, cls_a, cls_b, off_a, ..)  -- sg_box_best: per box of a the best partner of b in its scene (and class), the
                                                             lowest index among equals, -1 / 0.0 when every IoU is 0; no Ka x Kb table
@@ -48,69 +48,27 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import hip, scans
+from . import boxset, hip, scans
 from .device import device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
 
-MAX_BOXES = 1 << 20
-MAX_SCENES = 1 << 16
 MAX_PAIRS = 1 << 24
-KINDS = ("aabb", "yaw")
 MATCH_SUFFIX = ".boxmatch.npz"
 REPORT_NAME = "boxap_report.json"
 DEFAULT_THRESHOLDS = (0.25, 0.5)
 
 
-def box_rows(boxes) -> np.ndarray:
-    """Boxes of kind aabb or yaw -> float64 [K,8] = centre, full size, c = R[:,0,0], s = R[:,0,1].  Kind pca is a ValueError."""
-    kind = getattr(boxes, "kind", None)
-    if kind == "pca":
-        raise ValueError("box_rows: a box of kind pca is not upright (its axes are the label's principal frame), and the IoU here is of "
-                         "upright boxes: make the boxes with kind aabb or yaw")
-    if kind not in KINDS:
-        raise ValueError("box_rows: Boxes of kind %s are needed, not %r" % (" or ".join(KINDS), kind))
-    R = np.asarray(boxes.R, np.float64).reshape(-1, 3, 3)
-    return np.ascontiguousarray(np.concatenate([np.asarray(boxes.center, np.float64).reshape(-1, 3),
-                                                np.asarray(boxes.size, np.float64).reshape(-1, 3), R[:, 0, 0:1], R[:, 0, 1:2]], 1))
-
-
-def _rows(x, who: str) -> np.ndarray:
-    if hasattr(x, "R") and hasattr(x, "center"):
-        return box_rows(x)
-    r = np.asarray(x)
-    if r.ndim != 2 or r.shape[1] != 8 or not (np.issubdtype(r.dtype, np.floating) or np.issubdtype(r.dtype, np.integer)):
-        raise ValueError("%s: boxes are [K,8] rows cx cy cz sx sy sz c s (or Boxes), not %s %r" % (who, r.dtype, r.shape))
-    if r.shape[0] > MAX_BOXES:
-        raise hip.SgError(hip.SG_EUNSUP, "%s: %d boxes; a call takes at most 2^20 a side" % (who, r.shape[0]))
-    return np.ascontiguousarray(r, dtype=np.float64)
-
-
-def _offsets(off_a, off_b, ka: int, kb: int, who: str):
-    if (off_a is None) != (off_b is None):
-        raise ValueError("%s: off_a and off_b delimit the same scenes: both or neither" % who)
-    if off_a is None:
-        return np.array([0, ka], np.int32), np.array([0, kb], np.int32), False
-    out = []
-    for name, off, k in (("off_a", off_a, ka), ("off_b", off_b, kb)):
-        o = np.asarray(off)
-        if o.ndim != 1 or o.shape[0] < 1 or not np.issubdtype(o.dtype, np.integer):
-            raise ValueError("%s: %s is [B+1] whole numbers" % (who, name))
-        o = o.astype(np.int64)
-        if o[0] != 0 or o[-1] != k or (np.diff(o) < 0).any():
-            raise ValueError("%s: %s must ascend from 0 to the %d boxes of its set" % (who, name, k))
-        out.append(np.ascontiguousarray(o, dtype=np.int32))
-    if out[0].shape != out[1].shape:
-        raise ValueError("%s: off_a and off_b name %d and %d scenes" % (who, out[0].shape[0] - 1, out[1].shape[0] - 1))
-    if out[0].shape[0] - 1 > MAX_SCENES:
-        raise hip.SgError(hip.SG_EUNSUP, "%s: %d scenes; a call takes at most 2^16" % (who, out[0].shape[0] - 1))
-    return out[0], out[1], True
+def _sets(a, b, off_a, off_b, who: str):
+    """the two sets of an entry -> their rows [Ka,8], [Kb,8] and their scene offsets, int32 [B+1] each"""
+    ra, rb = boxset.box_rows(a, who), boxset.box_rows(b, who)
+    oa, ob = boxset.paired_offsets(who, (off_a, ra.shape[0], "off_a", "boxes of its set"), (off_b, rb.shape[0], "off_b", "boxes of its set"))
+    return ra, rb, oa, ob
 
 
 def box_iou(a, b, off_a=None, off_b=None, device=None, stream=None):
     """sg_box_iou: `a` [Ka,8] and `b` [Kb,8] rows (or Boxes) -> float64 [Ka,Kb]; with `off_a` / `off_b` ([B+1] each) the list of the B
     scenes' [Ka_b,Kb_b] blocks.  More than 2^24 pairs are refused (box_best has no such limit)."""
     import torch
-    ra, rb = _rows(a, "box_iou"), _rows(b, "box_iou")
-    oa, ob, batched = _offsets(off_a, off_b, ra.shape[0], rb.shape[0], "box_iou")
+    ra, rb, oa, ob = _sets(a, b, off_a, off_b, "box_iou")
     na, nb = np.diff(oa).astype(np.int64), np.diff(ob).astype(np.int64)
     pairs = int((na * nb).sum())
     if pairs > MAX_PAIRS:
@@ -128,7 +86,7 @@ def box_iou(a, b, off_a=None, off_b=None, device=None, stream=None):
         flat = d_iou[:pairs].cpu().numpy()
     ends = np.concatenate([[0], np.cumsum(na * nb)])
     blocks = [flat[ends[s]:ends[s + 1]].reshape(int(na[s]), int(nb[s])) for s in range(scenes)]
-    return blocks if batched else blocks[0]
+    return blocks if off_a is not None else blocks[0]
 
 
 def box_best(a, b, cls_a=None, cls_b=None, off_a=None, off_b=None, device=None, stream=None):
@@ -136,15 +94,11 @@ def box_best(a, b, cls_a=None, cls_b=None, off_a=None, off_b=None, device=None, 
     (the lowest index among equals) and that IoU -- the bits box_iou gives for the pair; -1 and 0.0 when every IoU is 0.  `cls_a` /
     `cls_b` (both or neither) restrict partners to the same class."""
     import torch
-    ra, rb = _rows(a, "box_best"), _rows(b, "box_best")
-    oa, ob, _ = _offsets(off_a, off_b, ra.shape[0], rb.shape[0], "box_best")
+    ra, rb, oa, ob = _sets(a, b, off_a, off_b, "box_best")
     if (cls_a is None) != (cls_b is None):
         raise ValueError("box_best: classes are given for both sets or for neither")
     if cls_a is not None:
-        cls_a, cls_b = np.asarray(cls_a), np.asarray(cls_b)
-        for name, c, k in (("cls_a", cls_a, ra.shape[0]), ("cls_b", cls_b, rb.shape[0])):
-            if c.shape != (k,) or not np.issubdtype(c.dtype, np.integer):
-                raise ValueError("box_best: %s is one whole number per box, [%d]" % (name, k))
+        cls_a, cls_b = boxset.class_vector(cls_a, ra.shape[0], "box_best", "cls_a"), boxset.class_vector(cls_b, rb.shape[0], "box_best", "cls_b")
     dev = torch_device(device)
     lib = hip.lib()
     scenes = int(oa.shape[0]) - 1
@@ -152,8 +106,7 @@ def box_best(a, b, cls_a=None, cls_b=None, off_a=None, off_b=None, device=None, 
         d_a, d_b = device_tensor(ra, torch.float64, dev), device_tensor(rb, torch.float64, dev)
         d_ca = d_cb = None
         if cls_a is not None:
-            d_ca = device_tensor(np.concatenate([cls_a, [0]]), torch.int32, dev)         # never empty: both or neither are pointers
-            d_cb = device_tensor(np.concatenate([cls_b, [0]]), torch.int32, dev)
+            d_ca, d_cb = device_tensor(cls_a, torch.int32, dev), device_tensor(cls_b, torch.int32, dev)     # [K+1]: both or neither are pointers
         best = torch.empty(max(ra.shape[0], 1), dtype=torch.int32, device=dev)
         top = torch.empty(max(ra.shape[0], 1), dtype=torch.float64, device=dev)
         ws = workspace(lib.sg_box_best_ws_bytes(ra.shape[0], rb.shape[0], scenes), dev)
@@ -292,7 +245,7 @@ def check_command(exp, stage, layer, root, label_style, pred, gt, kind, angles, 
     if (exp is None) == (pred is None and gt is None):
         raise ValueError("exactly one source of boxes is needed: -n EXP (with --stage) or --pred DIR with --gt DIR")
     if kind == "pca":
-        raise ValueError("--kind pca: such a box is not upright, and the IoU here is of upright boxes (aabb or yaw)")
+        boxset.check_upright(kind, "--kind")
     if classes not in (None, "scannet18", "all"):
         raise ValueError("--classes is scannet18 or all, not %r" % (classes,))
     thresholds = check_thresholds(thresholds)
@@ -346,63 +299,36 @@ def experiment_scene(scene_path: str, p: dict, device=None, stream=None) -> tupl
     truth = boxes.label_boxes(xyz, np.where(ids > 0, ids, -1).astype(np.int32), p["kind"], angles, 1, device=device, stream=stream)
     gcls = (truth.values // 1000).astype(np.int32)
     gkeep = _class_filter(gcls, p["classes"])
-    return SceneBoxes(box_rows(found)[keep], cls[keep], box_rows(truth)[gkeep], gcls[gkeep], None), n
+    return SceneBoxes(boxset.box_rows(found)[keep], cls[keep], boxset.box_rows(truth)[gkeep], gcls[gkeep], None), n
 
 
 def _file_boxes(path: str, score_key=None):
-    with np.load(path) as z:
-        if "sem" not in z.files:
-            raise ValueError("%s holds no `sem` (the class of every box): `boxes` writes it on its experiment route" % path)
-        kind = str(z["kind"]) if "kind" in z.files else None
-        if kind == "pca":
-            raise ValueError("%s holds boxes of kind pca: such a box is not upright, and the IoU here is of upright boxes" % path)
-        if kind not in KINDS:
-            raise ValueError("%s holds boxes of kind %r, not %s" % (path, kind, " or ".join(KINDS)))
-        R = np.asarray(z["R"], np.float64).reshape(-1, 3, 3)
-        rows = np.concatenate([np.asarray(z["center"], np.float64).reshape(-1, 3), np.asarray(z["size"], np.float64).reshape(-1, 3), R[:, 0, 0:1],
-                               R[:, 0, 1:2]], 1)
-        sem = np.asarray(z["sem"]).astype(np.int32)
-        score = None
-        if score_key is not None:
-            if score_key not in z.files:
-                raise ValueError("%s has no array %r (it has %s)" % (path, score_key, ", ".join(z.files)))
-            score = np.asarray(z[score_key], np.float64)
-            if score.shape != sem.shape:
-                raise ValueError("%s: %r holds %r values for %d boxes" % (path, score_key, score.shape, sem.shape[0]))
-    if sem.shape != (rows.shape[0],):
-        raise ValueError("%s: %d classes for %d boxes" % (path, sem.shape[0], rows.shape[0]))
-    return np.ascontiguousarray(rows), sem, score
+    """<scene>.boxes.npz -> (rows [K,8], classes int32 [K], scores float64 [K] or None): it needs `sem` and an upright kind"""
+    f = boxset.read_boxes(path)
+    sem = boxset.file_classes(f).astype(np.int32)
+    rows = boxset.box_rows(f, path)
+    score = None if score_key is None else boxset.file_scores(f, score_key).astype(np.float64)
+    return rows, sem, score
 
 
 def file_scene(scene: str, p: dict) -> SceneBoxes:
-    from .boxes import NPZ_SUFFIX
-    rows, cls, score = _file_boxes(os.path.join(p["pred"], scene + NPZ_SUFFIX), p["score_key"])
-    grows, gcls, _ = _file_boxes(os.path.join(p["gt"], scene + NPZ_SUFFIX))
+    rows, cls, score = _file_boxes(os.path.join(p["pred"], scene + boxset.NPZ_SUFFIX), p["score_key"])
+    grows, gcls, _ = _file_boxes(os.path.join(p["gt"], scene + boxset.NPZ_SUFFIX))
     keep, gkeep = _class_filter(cls, p["classes"]), _class_filter(gcls, p["classes"])
     return SceneBoxes(rows[keep], cls[keep], grows[gkeep], gcls[gkeep], None if score is None else score[keep])
 
 
 def file_scenes(pred: str, gt: str, scenes=None) -> list:
     """the scenes of the two trees; one that is on one side only is a ValueError that names it"""
-    from .boxes import NPZ_SUFFIX
-    sides = [{f[:-len(NPZ_SUFFIX)] for f in os.listdir(d) if f.endswith(NPZ_SUFFIX)} for d in (pred, gt)]
-    names = sorted(sides[0] | sides[1]) if scenes is None else list(scenes)
-    for s in names:
-        if (s in sides[0]) != (s in sides[1]) or (scenes is not None and s not in sides[0]):
-            missing = "--gt" if s in sides[0] else "--pred"
-            raise ValueError("scene %s has no %s%s under %s: every scene needs both sides" % (s, s, NPZ_SUFFIX, missing))
-    return names
+    return boxset.listed_scenes([("{}%s under %s" % (boxset.NPZ_SUFFIX, option), boxset.scene_files(d, boxset.NPZ_SUFFIX))
+                                 for option, d in (("--pred", pred), ("--gt", gt))], scenes)
 
 
 def match_batch(batch: list, device=None, stream=None):
     """[SceneBoxes] -> (best [K], iou [K], cls [K], scene_of_pred [K], n_gt {(scene, class): n}, score [K] or None): sg_box_best
     over all the scenes at once, in calls of at most 2^16 scenes and 2^20 boxes a side"""
-    best, top, at = [], [], 0
-    while at < len(batch):
-        end, ka, kb = at, 0, 0
-        while end < len(batch) and end - at < MAX_SCENES and (end == at or (ka + batch[end].pred.shape[0] <= MAX_BOXES and
-                                                                             kb + batch[end].gt.shape[0] <= MAX_BOXES)):
-            ka, kb, end = ka + batch[end].pred.shape[0], kb + batch[end].gt.shape[0], end + 1
+    best, top = [], []
+    for at, end in boxset.pack([(s.pred.shape[0], s.gt.shape[0]) for s in batch], (boxset.MAX_BOXES, boxset.MAX_BOXES), boxset.MAX_SCENES):
         part = batch[at:end]
         off_a = np.concatenate([[0], np.cumsum([s.pred.shape[0] for s in part])]).astype(np.int64)
         off_b = np.concatenate([[0], np.cumsum([s.gt.shape[0] for s in part])]).astype(np.int64)
@@ -411,7 +337,6 @@ def match_batch(batch: list, device=None, stream=None):
                         off_a, off_b, device=device, stream=stream)
         best.append(b)
         top.append(t)
-        at = end
     cls = np.concatenate([s.pred_cls for s in batch]).astype(np.int64) if batch else np.zeros(0, np.int64)
     scene = np.concatenate([np.full(s.pred.shape[0], k, np.int64) for k, s in enumerate(batch)]) if batch else np.zeros(0, np.int64)
     n_gt = {}

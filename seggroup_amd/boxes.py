@@ -43,13 +43,13 @@ from typing import NamedTuple
 import numpy as np
 
 from . import hip, scans
+from .boxset import NPY_SUFFIX, NPZ_SUFFIX                                     # the two files written here; boxset.py reads them
 from .device import device_rows, device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
 
 MAX_POINTS = 1 << 24
 MAX_ANGLES = 1024
 DEFAULT_ANGLES = 90
 KINDS = ("aabb", "yaw", "pca")
-NPZ_SUFFIX = ".boxes.npz"
 REPORT_NAME = "boxes_report.json"
 AP_MIN_POINTS = 100
 # the corners of a box, corner k at (+/-, +/-, +/-) half sizes with bit a of k the sign on axis a, and 12 triangles over them
@@ -425,7 +425,7 @@ def boxes_scan(scene_path: str, out_dir: str, exp=None, stage="epoch_last", laye
         arrays["sem"] = box_sem
     np.savez(npz, **arrays)
     if detector_files:
-        np.save(os.path.join(out_dir, scene + "_bbox.npy"), detector_rows(kept, box_sem))
+        np.save(os.path.join(out_dir, scene + NPY_SUFFIX), detector_rows(kept, box_sem))
     if ply:
         write_ply(os.path.join(out_dir, scene + ".boxes.ply"), *box_mesh(kept))
     return {"V": int(xyz.shape[0]), "instances": instances, "kept": int(kept.values.shape[0]), "ignored": int((labels < 0).sum())}

@@ -3,8 +3,8 @@ a detector's, an annotator's or the ground truth's own as a simulated annotator,
 exactly one box almost surely belongs to that instance, and a segment whose vertices all do is a click nobody had to make.
 
     rows  = box_frames(boxes)                              -- float64 [K,15] = cx cy cz sx sy sz r00 .. r22 of a Boxes of ANY kind (the
-                                                              test needs no upright box), of [K,15] rows, of boxap's [K,8] rows or of the
-                                                              [K,7] detector rows `boxes --detector-files` writes
+                                                              test needs no upright box), of [K,15], [K,8] or [K,7] rows; the row
+                                                              layouts, the box files and the limits of a call are seggroup_amd/boxset.py's
     pib   = points_in_boxes(xyz, boxes, margin)            -- sg_points_in_boxes: per point count (boxes that hold it), first (the lowest
                                                               such box) and inner (the one of smallest volume), -1 where none
     owner = vertex_owner(pib, K, overlap)                  -- one code per vertex: 0 no box, 1 + k box k only; in several boxes K + 1
@@ -40,14 +40,12 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import hip, scans
+from . import boxset, hip, scans
+from .boxset import box_frames                                                # the layout of every row this module sends to the device
 from .device import device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
 
 MAX_POINTS = 1 << 24
-MAX_BOXES = 1 << 20
-MAX_SCENES = 1 << 16
 OVERLAPS = ("skip", "inner")
-SUFFIXES = (".boxes.npz", "_bbox.npy")
 NPZ_SUFFIX = ".boxlabels.npz"
 REPORT_NAME = "boxlabels_report.json"
 DEFAULT_STYLE = "box"
@@ -71,40 +69,6 @@ class SegmentBoxes(NamedTuple):
     size: np.ndarray
 
 
-def box_frames(x, classes: bool = False):
-    """-> float64 [K,15] = centre, full size, R row-major.  `x`: a Boxes of any kind (center, size, R as they stand); [K,15] rows, taken
-    as they are; [K,8] rows of boxap (R = [[c,s,0],[-s,c,0],[0,0,1]]); [K,7] detector rows (identity frame).  With `classes` ->
-    (rows, the class column of [K,7] rows as int64 [K], None for every other input)."""
-    cls = None
-    if hasattr(x, "R") and hasattr(x, "center") and hasattr(x, "size"):
-        c, s = np.asarray(x.center, np.float64).reshape(-1, 3), np.asarray(x.size, np.float64).reshape(-1, 3)
-        R = np.asarray(x.R, np.float64).reshape(-1, 9)
-        if not c.shape[0] == s.shape[0] == R.shape[0]:
-            raise ValueError("box_frames: center, size and R of the Boxes hold %d, %d and %d boxes" % (c.shape[0], s.shape[0], R.shape[0]))
-        rows = np.concatenate([c, s, R], 1)
-    else:
-        r = np.asarray(x)
-        if r.ndim != 2 or r.shape[1] not in (7, 8, 15) or not (np.issubdtype(r.dtype, np.floating) or np.issubdtype(r.dtype, np.integer)):
-            raise ValueError("box_frames: boxes are a Boxes, or [K,15] (centre, size, R), [K,8] (centre, size, c, s) or [K,7] (centre, "
-                             "size, class) rows of numbers, not %s %r" % (r.dtype, r.shape))
-        r = r.astype(np.float64)
-        k = r.shape[0]
-        if r.shape[1] == 15:
-            rows = r
-        else:
-            R = np.zeros((k, 3, 3))
-            if r.shape[1] == 8:
-                R[:, 0, 0], R[:, 0, 1], R[:, 1, 0], R[:, 1, 1], R[:, 2, 2] = r[:, 6], r[:, 7], -r[:, 7], r[:, 6], 1.0
-            else:
-                R[:, 0, 0] = R[:, 1, 1] = R[:, 2, 2] = 1.0
-                cls = r[:, 6].astype(np.int64)
-                if not np.array_equal(cls.astype(np.float64), r[:, 6]):
-                    raise ValueError("box_frames: the class column of [K,7] rows holds whole numbers")
-            rows = np.concatenate([r[:, :6], R.reshape(k, 9)], 1)
-    rows = np.ascontiguousarray(rows, dtype=np.float64)
-    return (rows, cls) if classes else rows
-
-
 def check_margin(margin) -> float:
     if isinstance(margin, bool) or not isinstance(margin, (int, float, np.integer, np.floating)) or not math.isfinite(margin) or margin < 0:
         raise ValueError("margin (margin=, --margin) is a finite length >= 0, not %r" % (margin,))
@@ -123,27 +87,6 @@ def check_overlap(overlap) -> str:
     return overlap
 
 
-def _offsets(off_points, off_boxes, n: int, k: int):
-    if (off_points is None) != (off_boxes is None):
-        raise ValueError("points_in_boxes: off_points and off_boxes delimit the same scenes: both or neither")
-    if off_points is None:
-        return np.array([0, n], np.int32), np.array([0, k], np.int32)
-    out = []
-    for name, off, total, what in (("off_points", off_points, n, "points"), ("off_boxes", off_boxes, k, "boxes")):
-        o = np.asarray(off)
-        if o.ndim != 1 or o.shape[0] < 1 or not np.issubdtype(o.dtype, np.integer):
-            raise ValueError("points_in_boxes: %s is [B+1] whole numbers" % name)
-        o = o.astype(np.int64)
-        if o[0] != 0 or o[-1] != total or (np.diff(o) < 0).any():
-            raise ValueError("points_in_boxes: %s must ascend from 0 to the %d %s" % (name, total, what))
-        out.append(np.ascontiguousarray(o, dtype=np.int32))
-    if out[0].shape != out[1].shape:
-        raise ValueError("points_in_boxes: off_points and off_boxes name %d and %d scenes" % (out[0].shape[0] - 1, out[1].shape[0] - 1))
-    if out[0].shape[0] - 1 > MAX_SCENES:
-        raise hip.SgError(hip.SG_EUNSUP, "points_in_boxes: %d scenes; a call takes at most 2^16" % (out[0].shape[0] - 1))
-    return out[0], out[1]
-
-
 def points_in_boxes(xyz, boxes, margin=0.0, off_points=None, off_boxes=None, device=None, stream=None, held: bool = False) -> PointsInBoxes:
     """sg_points_in_boxes: `xyz` [N, >= 3] (array or tensor, float32 on the device), `boxes` anything box_frames takes -> PointsInBoxes of
     device tensors.  `off_points` / `off_boxes` ([B+1] each, both or neither) delimit scenes: only points and boxes of one scene meet,
@@ -155,9 +98,9 @@ def points_in_boxes(xyz, boxes, margin=0.0, off_points=None, off_boxes=None, dev
     if len(shape) != 2 or shape[1] < 3:
         raise ValueError("points_in_boxes: a cloud is [N, >= 3] rows with xyz first, not %r" % (shape,))
     n, k = int(shape[0]), int(rows.shape[0])
-    if n > MAX_POINTS or k > MAX_BOXES:
+    if n > MAX_POINTS or k > boxset.MAX_BOXES:
         raise hip.SgError(hip.SG_EUNSUP, "points_in_boxes: %d points and %d boxes; a call takes at most 2^24 points and 2^20 boxes" % (n, k))
-    op, ob = _offsets(off_points, off_boxes, n, k)
+    op, ob = boxset.paired_offsets("points_in_boxes", (off_points, n, "off_points", "points"), (off_boxes, k, "off_boxes", "boxes"))
     import torch
     dev = torch_device(device)
     lib = hip.lib()
@@ -268,45 +211,30 @@ def check_command(from_real, boxes_dir, suffix, kind, angles, min_points, margin
         return dict(p, from_real=True, kind=kind, angles=a, min_points=min_points)
     if kind is not None or angles is not None or min_points is not None:
         raise ValueError("--kind, --angles and --min-points belong to --from-real: the files of --boxes are made already")
-    suffix = SUFFIXES[0] if suffix is None else suffix
-    if suffix not in SUFFIXES:
-        raise ValueError("--suffix is %s, not %r" % (" or ".join(SUFFIXES), suffix))
+    suffix = boxset.SUFFIXES[0] if suffix is None else suffix
+    if suffix not in boxset.SUFFIXES:
+        raise ValueError("--suffix is %s, not %r" % (" or ".join(boxset.SUFFIXES), suffix))
     return dict(p, boxes=boxes_dir, suffix=suffix)
 
 
 def file_scenes(scans_dir: str, boxes_dir: str, suffix: str, scenes=None) -> list:
     """the scenes that have a scan and a box file; one that is on one side only is a ValueError that names it"""
-    sides = [set(scans.scan_names(scans_dir)), {f[:-len(suffix)] for f in os.listdir(boxes_dir) if f.endswith(suffix)}]
-    names = sorted(sides[0] | sides[1]) if scenes is None else list(scenes)
-    for s in names:
-        if s not in sides[0]:
-            raise ValueError("scene %s has %s%s under --boxes and no scan under --scans: every scene needs both sides" % (s, s, suffix))
-        if s not in sides[1]:
-            raise ValueError("scene %s has a scan and no %s%s under --boxes: every scene needs both sides" % (s, s, suffix))
-    return names
+    return boxset.listed_scenes([("scan under --scans", set(scans.scan_names(scans_dir))),
+                                 ("{}%s under --boxes" % suffix, boxset.scene_files(boxes_dir, suffix))], scenes)
 
 
 def file_boxes(path: str):
-    """<scene>.boxes.npz (it needs `sem`) or <scene>_bbox.npy ([K,7]) -> (rows float64 [K,15], ids int64 [K], sem int64 [K])"""
-    if path.endswith(".npy"):
-        r = np.load(path)
-        if r.ndim != 2 or r.shape[1] != 7:
-            raise ValueError("%s holds %r, not the [K,7] rows (centre, size, class) of `boxes --detector-files`: there is no class" % (path, r.shape))
-        rows, sem = box_frames(r, classes=True)
-        ids = 1 + np.arange(rows.shape[0], dtype=np.int64)
-    else:
-        with np.load(path) as z:
-            if "sem" not in z.files:
-                raise ValueError("%s holds no `sem` (the class of every box): `boxes` writes it on its experiment route" % path)
-            rows = np.concatenate([np.asarray(z["center"], np.float64).reshape(-1, 3), np.asarray(z["size"], np.float64).reshape(-1, 3),
-                                   np.asarray(z["R"], np.float64).reshape(-1, 9)], 1)
-            sem = np.asarray(z["sem"]).astype(np.int64)
-            ids = np.asarray(z["values"]).astype(np.int64) if "values" in z.files else 1 + np.arange(rows.shape[0], dtype=np.int64)
-    if sem.shape != (rows.shape[0],) or ids.shape != (rows.shape[0],):
-        raise ValueError("%s: %d classes and %d ids for %d boxes" % (path, sem.shape[0], ids.shape[0], rows.shape[0]))
+    """<scene>.boxes.npz (it needs `sem`; a box of kind pca is taken) or <scene>_bbox.npy ([K,7]) -> (rows float64 [K,15], ids int64 [K],
+    sem int64 [K]): ids are the file's `values`, 1 + k where it has none"""
+    f = boxset.read_boxes(path)
+    sem = boxset.file_classes(f).astype(np.int64)
+    rows = box_frames(f)
+    ids = 1 + np.arange(rows.shape[0], dtype=np.int64) if f.values is None else np.asarray(f.values).astype(np.int64)
+    if ids.shape != (rows.shape[0],):
+        raise ValueError("%s: %d ids for %d boxes" % (path, ids.size, rows.shape[0]))
     if rows.shape[0] and (int(sem.min()) < 1 or int(ids.min()) < 1):
         raise ValueError("%s: classes and ids must be >= 1 (the label files count from 1)" % path)
-    return np.ascontiguousarray(rows), ids, sem
+    return rows, ids, sem
 
 
 def boxlabels_scan(scene_path: str, root: str, p: dict, made=None, force: bool = False, device=None, stream=None):

@@ -10,7 +10,8 @@ THE RULE (include/seggroup_hip.h; tests/boxnms_ref.py restates it).  Within a sc
 equal and i < j.  The scene is visited in that order; a box is SUPPRESSED iff an earlier box that was KEPT, of its class (when classes
 are given), has IoU with it above `iou`, strictly -- the upright IoU of 8u with the earlier box as `a`.  Its representative `rep` is the
 first such box; a kept box represents itself.  A box that only a suppressed box overlaps is kept.  Boxes are upright (kind aabb or
-yaw, or [K,8] rows cx cy cz sx sy sz c s); kind pca is refused as `boxap` refuses it.
+yaw, or [K,8] rows cx cy cz sx sy sz c s); kind pca is refused.  The row layout, the two kinds of box file and the limits of a call are
+seggroup_amd/boxset.py's.
 
     python -m seggroup_amd.boxnms --boxes DIR --out DIR [--suffix .boxes.npz|_bbox.npy] --iou T [--score-key NAME] [--class-agnostic]
         [--min-score S] [--scenes FILE --workers W --device D --force]
@@ -35,14 +36,11 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import hip, scans
-from .boxap import KINDS, MAX_BOXES, MAX_SCENES, box_rows
+from . import boxset, hip, scans
 from .device import device_tensor, on_stream, stream_ptr, sync, torch_device, workspace
 
 MAX_SCENE_BOXES = 1 << 14
 MAX_WORDS = 1 << 24
-SUFFIXES = (".boxes.npz", "_bbox.npy")
-SCORE_SUFFIX = "_score.npy"
 NMS_SUFFIX = ".nms.npz"
 REPORT_NAME = "nms_report.json"
 
@@ -53,17 +51,6 @@ class Nms(NamedTuple):
     keep: np.ndarray
     rep: np.ndarray
     rank: np.ndarray
-
-
-def _rows(x, who: str) -> np.ndarray:
-    if hasattr(x, "R") and hasattr(x, "center"):
-        return box_rows(x)                                                   # kind pca is refused there, with 8u's reason
-    r = np.asarray(x)
-    if r.ndim != 2 or r.shape[1] != 8 or not (np.issubdtype(r.dtype, np.floating) or np.issubdtype(r.dtype, np.integer)):
-        raise ValueError("%s: boxes are [K,8] rows cx cy cz sx sy sz c s (or Boxes), not %s %r" % (who, r.dtype, r.shape))
-    if r.shape[0] > MAX_BOXES:
-        raise hip.SgError(hip.SG_EUNSUP, "%s: %d boxes; a call takes at most 2^20" % (who, r.shape[0]))
-    return np.ascontiguousarray(r, dtype=np.float64)
 
 
 def check_iou(iou) -> float:
@@ -82,24 +69,15 @@ def matrix_words(off) -> int:
 
 
 def _offsets(off, k: int, who: str) -> np.ndarray:
-    if off is None:
-        o = np.array([0, k], np.int64)
-    else:
-        o = np.asarray(off)
-        if o.ndim != 1 or o.shape[0] < 1 or not np.issubdtype(o.dtype, np.integer):
-            raise ValueError("%s: off is [B+1] whole numbers" % who)
-        o = o.astype(np.int64)
-        if o[0] != 0 or o[-1] != k or (np.diff(o) < 0).any():
-            raise ValueError("%s: off must ascend from 0 to the %d boxes" % (who, k))
-    if o.shape[0] - 1 > MAX_SCENES:
-        raise hip.SgError(hip.SG_EUNSUP, "%s: %d scenes; a call takes at most 2^16" % (who, o.shape[0] - 1))
+    """boxset.offsets (one scene without `off`), and on top what the bit matrix limits: the boxes of a scene and the words of a call"""
+    o = boxset.offsets([0, k] if off is None else off, k, who, "off", "boxes")
     n = np.diff(o)
     if n.size and int(n.max()) > MAX_SCENE_BOXES:
         raise hip.SgError(hip.SG_EUNSUP, "%s: a scene of %d boxes; a scene takes at most 2^14" % (who, int(n.max())))
     if matrix_words(o) > MAX_WORDS:
         raise hip.SgError(hip.SG_EUNSUP, "%s: the bit matrix has %d words; a call takes at most 2^24 (the sum over scenes of n * ceil(n / 64))"
                           % (who, matrix_words(o)))
-    return np.ascontiguousarray(o, dtype=np.int32)
+    return o
 
 
 def box_nms(boxes, scores, iou, cls=None, off=None, device=None, stream=None) -> Nms:
@@ -108,7 +86,7 @@ def box_nms(boxes, scores, iou, cls=None, off=None, device=None, stream=None) ->
     device call."""
     import torch
     who = "box_nms"
-    rows = _rows(boxes, who)
+    rows = boxset.box_rows(boxes, who)
     k = rows.shape[0]
     thresh = check_iou(iou)
     sc = np.asarray(scores)
@@ -116,9 +94,7 @@ def box_nms(boxes, scores, iou, cls=None, off=None, device=None, stream=None) ->
         raise ValueError("%s: scores hold one number per box, [%d], not %s %r" % (who, k, sc.dtype, sc.shape))
     sc = np.ascontiguousarray(sc, dtype=np.float64)
     if cls is not None:
-        cls = np.asarray(cls)
-        if cls.shape != (k,) or not np.issubdtype(cls.dtype, np.integer):
-            raise ValueError("%s: cls is one whole number per box, [%d]" % (who, k))
+        cls = boxset.class_vector(cls, k, who, "cls")
     o = _offsets(off, k, who)
     scenes, words = int(o.shape[0]) - 1, matrix_words(o)
     dev = torch_device(device)
@@ -126,7 +102,7 @@ def box_nms(boxes, scores, iou, cls=None, off=None, device=None, stream=None) ->
     with torch.cuda.device(dev), on_stream(stream):
         d_box = device_tensor(rows.reshape(-1) if k else np.zeros(8), torch.float64, dev)
         d_score = device_tensor(sc if k else np.zeros(1), torch.float64, dev)
-        d_cls = None if cls is None else device_tensor(np.concatenate([cls, [0]]), torch.int32, dev)
+        d_cls = None if cls is None else device_tensor(cls, torch.int32, dev)       # [K+1]
         out = torch.empty((3, max(k, 1)), dtype=torch.int32, device=dev)
         ws = workspace(lib.sg_box_nms_ws_bytes(k, scenes, words), dev)
         hip.check_arg(lib.sg_box_nms(d_box.data_ptr(), d_score.data_ptr(), hip.ptr(d_cls), k, o.ctypes.data, scenes, thresh, out[0].data_ptr(),
@@ -148,17 +124,17 @@ def cluster_sizes(nms: Nms, off=None) -> np.ndarray:
 # ---- files ------------------------------------------------------------------------------------------------------------------------------------
 def check_command(suffix, iou, score_key, class_agnostic, min_score) -> dict:
     """the combinations of the command's options that are refused before anything runs (ValueError) -> the parameters in force"""
-    suffix = SUFFIXES[0] if suffix is None else suffix
-    if suffix not in SUFFIXES:
-        raise ValueError("--suffix is %s, not %r" % (" or ".join(SUFFIXES), suffix))
+    suffix = boxset.SUFFIXES[0] if suffix is None else suffix
+    if suffix not in boxset.SUFFIXES:
+        raise ValueError("--suffix is %s, not %r" % (" or ".join(boxset.SUFFIXES), suffix))
     if iou is None:
         raise ValueError("--iou is needed: the IoU above which an earlier kept box suppresses a later one has no default")
     thresh = check_iou(iou)
-    if suffix == SUFFIXES[0] and not score_key:
+    if suffix == boxset.SUFFIXES[0] and not score_key:
         raise ValueError("--score-key is needed with --suffix .boxes.npz: the array of the file that holds the scores (`count` is the "
                          "natural score of pseudo boxes)")
-    if suffix == SUFFIXES[1] and score_key is not None:
-        raise ValueError("--score-key names an array of a .boxes.npz; the scores of <scene>_bbox.npy are <scene>%s beside it" % SCORE_SUFFIX)
+    if suffix == boxset.SUFFIXES[1] and score_key is not None:
+        raise ValueError("--score-key names an array of a .boxes.npz; the scores of <scene>_bbox.npy are <scene>%s beside it" % boxset.SCORE_SUFFIX)
     if min_score is not None and (isinstance(min_score, (bool, str)) or not math.isfinite(float(min_score))):
         raise ValueError("--min-score is a finite number, not %r" % (min_score,))
     return dict(suffix=suffix, iou=thresh, score_key=score_key, class_agnostic=bool(class_agnostic),
@@ -174,60 +150,24 @@ class SceneFile(NamedTuple):
 
 
 def read_scene(boxes_dir: str, scene: str, p: dict) -> SceneFile:
-    path = os.path.join(boxes_dir, scene + p["suffix"])
-    if p["suffix"] == SUFFIXES[1]:
-        r = np.load(path)
-        if r.ndim != 2 or r.shape[1] != 7:
-            raise ValueError("%s holds %r, not the [K,7] rows (centre, size, class) of `boxes --detector-files`" % (path, r.shape))
-        k = r.shape[0]
-        spath = os.path.join(boxes_dir, scene + SCORE_SUFFIX)
-        if not os.path.exists(spath):
-            raise ValueError("%s has no scores: %s must hold one per box" % (path, spath))
-        score = np.load(spath)
-        if score.shape != (k,):
-            raise ValueError("%s holds %r values for the %d boxes of %s" % (spath, score.shape, k, path))
-        cls = r[:, 6]
-        if (cls != np.round(cls)).any():
-            raise ValueError("%s: column 6 is the class, a whole number" % path)
-        rows = np.concatenate([r[:, :6].astype(np.float64), np.ones((k, 1)), np.zeros((k, 1))], 1)
-        return SceneFile(np.ascontiguousarray(rows), np.asarray(score, np.float64), None if p["class_agnostic"] else cls.astype(np.int32),
-                         {"rows": r, "score": score})
-    with np.load(path) as z:
-        arrays = {name: z[name] for name in z.files}
-    kind = str(arrays["kind"]) if "kind" in arrays else None
-    if kind == "pca":
-        raise ValueError("%s holds boxes of kind pca: such a box is not upright, and the IoU here is of upright boxes" % path)
-    if kind not in KINDS:
-        raise ValueError("%s holds boxes of kind %r, not %s" % (path, kind, " or ".join(KINDS)))
-    R = np.asarray(arrays["R"], np.float64).reshape(-1, 3, 3)
-    rows = np.concatenate([np.asarray(arrays["center"], np.float64).reshape(-1, 3), np.asarray(arrays["size"], np.float64).reshape(-1, 3),
-                           R[:, 0, 0:1], R[:, 0, 1:2]], 1)
-    k = rows.shape[0]
-    if p["score_key"] not in arrays:
-        raise ValueError("%s has no array %r (it has %s)" % (path, p["score_key"], ", ".join(sorted(arrays))))
-    score = np.asarray(arrays[p["score_key"]])
-    if score.shape != (k,) or not (np.issubdtype(score.dtype, np.floating) or np.issubdtype(score.dtype, np.integer)):
-        raise ValueError("%s: %r holds %s %r, not one number for each of the %d boxes" % (path, p["score_key"], score.dtype, score.shape, k))
-    cls = None
-    if not p["class_agnostic"]:
-        if "sem" not in arrays:
-            raise ValueError("%s holds no `sem` (the class of every box): `boxes` writes it on its experiment route; or pass --class-agnostic" % path)
-        cls = np.asarray(arrays["sem"]).astype(np.int32)
-        if cls.shape != (k,):
-            raise ValueError("%s: %d classes for %d boxes" % (path, cls.shape[0], k))
-    return SceneFile(np.ascontiguousarray(rows), score.astype(np.float64), cls, arrays)
+    f = boxset.read_boxes(os.path.join(boxes_dir, scene + p["suffix"]))
+    rows = boxset.box_rows(f, f.path)
+    score = boxset.file_scores(f, p["score_key"])
+    cls = None if p["class_agnostic"] else boxset.file_classes(f, "; or pass --class-agnostic").astype(np.int32)
+    arrays = dict(f.arrays, score=score) if p["suffix"] == boxset.NPY_SUFFIX else f.arrays       # the _score.npy travels with its _bbox.npy
+    return SceneFile(rows, score.astype(np.float64), cls, arrays)
 
 
 def write_scene(out_dir: str, scene: str, p: dict, f: SceneFile, nms: Nms) -> None:
     """the kept boxes as the same kind of file, and <scene>.nms.npz"""
     k = f.rows.shape[0]
     sel = np.flatnonzero(nms.keep == 1)
-    if p["suffix"] == SUFFIXES[1]:
-        np.save(os.path.join(out_dir, scene + SUFFIXES[1]), f.arrays["rows"][sel])
-        np.save(os.path.join(out_dir, scene + SCORE_SUFFIX), f.arrays["score"][sel])
+    if p["suffix"] == boxset.NPY_SUFFIX:
+        np.save(os.path.join(out_dir, scene + boxset.NPY_SUFFIX), f.arrays["rows"][sel])
+        np.save(os.path.join(out_dir, scene + boxset.SCORE_SUFFIX), f.arrays["score"][sel])
     else:
         cut = {n: (a[sel] if a.ndim >= 1 and a.shape[0] == k else a) for n, a in f.arrays.items()}
-        np.savez(os.path.join(out_dir, scene + SUFFIXES[0]), **cut)
+        np.savez(os.path.join(out_dir, scene + boxset.NPZ_SUFFIX), **cut)
     np.savez(os.path.join(out_dir, scene + NMS_SUFFIX), keep=nms.keep, rep=nms.rep, rank=nms.rank, score=f.score)
 
 
@@ -239,12 +179,8 @@ def nms_batch(batch: list, p: dict, device=None, stream=None) -> list:
     for f, m in zip(batch, n):
         if m > MAX_SCENE_BOXES:
             raise hip.SgError(hip.SG_EUNSUP, "boxnms: a scene of %d boxes; a scene takes at most 2^14" % m)
-    w = [m * ((m + 63) // 64) for m in n]
-    out, at = [], 0
-    while at < len(batch):
-        end, k, words = at, 0, 0
-        while end < len(batch) and end - at < MAX_SCENES and (end == at or (k + n[end] <= MAX_BOXES and words + w[end] <= MAX_WORDS)):
-            k, words, end = k + n[end], words + w[end], end + 1
+    out = []
+    for at, end in boxset.pack([(m, m * ((m + 63) // 64)) for m in n], (boxset.MAX_BOXES, MAX_WORDS), boxset.MAX_SCENES):
         part = range(at, end)
         off = np.concatenate([[0], np.cumsum([n[i] for i in part])]).astype(np.int64)
         cls = None if p["class_agnostic"] else np.concatenate([batch[i].cls[live[i]] for i in part]).astype(np.int32)
@@ -256,18 +192,11 @@ def nms_batch(batch: list, p: dict, device=None, stream=None) -> list:
             keep, rep, rank = (np.full(batch[i].rows.shape[0], v, np.int32) for v in (0, -1, -1))
             keep[back], rep[back], rank[back] = got.keep[a:b], back[got.rep[a:b]], got.rank[a:b]
             out.append(Nms(keep, rep, rank))
-        at = end
     return out
 
 
 def scene_names(boxes_dir: str, suffix: str, scenes=None) -> list:
-    have = sorted(f[:-len(suffix)] for f in os.listdir(boxes_dir) if f.endswith(suffix))
-    if scenes is None:
-        return have
-    for s in scenes:
-        if s not in have:
-            raise ValueError("scene %s has no %s%s under --boxes" % (s, s, suffix))
-    return list(scenes)
+    return boxset.listed_scenes([("{}%s under --boxes" % suffix, boxset.scene_files(boxes_dir, suffix))], scenes)
 
 
 def nms_scans(boxes_dir: str, out_dir: str, scenes=None, workers: int = 4, device=None, force: bool = False, **options):
@@ -280,10 +209,7 @@ def nms_scans(boxes_dir: str, out_dir: str, scenes=None, workers: int = 4, devic
         raise ValueError("--out is --boxes: the filtered tree is another directory")
     skipped = [s for s in names if os.path.exists(os.path.join(out_dir, s + p["suffix"])) and not force]
     todo = [s for s in names if s not in skipped]
-    files = [read_scene(boxes_dir, s, p) for s in todo]
-    for f in files:
-        if f.rows.shape[0] > MAX_BOXES:
-            raise hip.SgError(hip.SG_EUNSUP, "boxnms: %d boxes in one file; a call takes at most 2^20" % f.rows.shape[0])
+    files = [read_scene(boxes_dir, s, p) for s in todo]                      # a file of more than 2^20 boxes is refused there, by box_rows
     dev = torch_device(device)
     results = nms_batch(files, p, dev)
     os.makedirs(out_dir, exist_ok=True)

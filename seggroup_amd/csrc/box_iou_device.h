@@ -4,15 +4,48 @@
 // The clipped footprint has at most 8 vertices.  It lives in two sets of eight NAMED slots (every index below is a compile-time constant
 // once the loops are unrolled): an append is a predicated move into the slot whose number equals the running count, so nothing is
 // indexed at run time and nothing goes to scratch.  Double arithmetic, nothing contracted (-ffp-contract=off).
+//
+// Also here, for both files: the check of one box (upright_flags) and the refusal its flag bits become on the host (upright_refusal).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
+
+#include "sg_common.h"
 
 namespace sg_box {
 
-constexpr int kSlots = 8;
+using sg::finite_f64;
 
-__device__ __forceinline__ bool finite_f64(double v) { return (__double2hiint(v) & 0x7ff00000) != 0x7ff00000; }
+constexpr int kSlots = 8;
+constexpr int kNotFinite = 1, kNegative = 2, kNotUnit = 4;   // upright_flags' bits
+constexpr double kUnitTol = 1e-6;
+
+// the 8 doubles of one box -> its flag bits: a value that is not finite (nothing else is looked at then), a negative size,
+// |c*c + s*s - 1| > 1e-6.  A size of zero is valid.
+__device__ __forceinline__ int upright_flags(const double* __restrict__ p) {
+    int bad = 0;
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+        if (!finite_f64(p[r])) bad = kNotFinite;
+    if (!bad) {
+        if (p[3] < 0.0 || p[4] < 0.0 || p[5] < 0.0) bad |= kNegative;
+        const double n = p[6] * p[6] + p[7] * p[7];
+        if (fabs(n - 1.0) > kUnitTol) bad |= kNotUnit;
+    }
+    return bad;
+}
+
+// the refusal of a set whose boxes ORed these bits together, SG_OK for none: not finite before negative size before the unit circle.
+// `set` is "A" or "B", or null where the entry takes one set.
+inline int upright_refusal(const char* who, const char* set, int bits) {
+    const char* of = set ? " of set " : "";
+    if (!set) set = "";
+    if (bits & kNotFinite) return sg::fail(SG_EINVAL, "%s: a box%s%s has a value that is not finite", who, of, set);
+    if (bits & kNegative) return sg::fail(SG_EINVAL, "%s: a box%s%s has a negative size", who, of, set);
+    if (bits & kNotUnit) return sg::fail(SG_EINVAL, "%s: a box%s%s has (c, s) off the unit circle: |c*c + s*s - 1| > 1e-6", who, of, set);
+    return SG_OK;
+}
 
 // slot m of the polygon <- (x, y): eight predicated moves, no run-time index.  An append past slot 7 is dropped (the contract says so).
 __device__ __forceinline__ void put(double (&u)[kSlots], double (&v)[kSlots], int m, double x, double y) {

@@ -19,32 +19,20 @@
 
 namespace {
 
-using namespace sg_box;                       // put, side_dist, clip_side, pair_iou, finite_f64, scene_of: the one pair function
+using namespace sg_box;                       // put, side_dist, clip_side, pair_iou, scene_of: the one pair function; upright_flags
 
 constexpr int kBlock = 256;
 constexpr int kWave = 64;
 constexpr int kWaves = kBlock / kWave;
-constexpr int kMaxBoxes = 1 << 20;            // per side
-constexpr int kMaxScenes = 1 << 16;
 constexpr long long kMaxPairs = 1ll << 24;    // sg_box_iou's d_iou
-constexpr int kNotFinite = 1, kNegative = 2, kNotUnit = 4, kSetB = 3;   // the flag word: three bits for set A, the same three shifted for B
-constexpr double kUnitTol = 1e-6;
+constexpr int kSetB = 3;                      // the flag word: upright_flags' three bits for set A, the same three shifted for B
 
 struct Landing { int flag, pad[3]; };
 
 __global__ __launch_bounds__(kBlock) void k_bi_check(const double* __restrict__ box, int K, int shift, int* __restrict__ flag) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= K) return;
-    const double* p = box + (size_t)i * 8;
-    int bad = 0;
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-        if (!finite_f64(p[r])) bad = kNotFinite;
-    if (!bad) {
-        if (p[3] < 0.0 || p[4] < 0.0 || p[5] < 0.0) bad |= kNegative;
-        const double n = p[6] * p[6] + p[7] * p[7];
-        if (fabs(n - 1.0) > kUnitTol) bad |= kNotUnit;
-    }
+    const int bad = upright_flags(box + (size_t)i * 8);
     if (bad) atomicOr(flag, bad << shift);
 }
 
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(kBlock) void k_bb_best(const double* __restrict__ a
     }
 }
 
-bool sizes_ok(int Ka, int Kb, int B) { return Ka >= 0 && Ka <= kMaxBoxes && Kb >= 0 && Kb <= kMaxBoxes && B >= 0 && B <= kMaxScenes; }
+bool sizes_ok(int Ka, int Kb, int B) { return Ka >= 0 && Ka <= sg::kMaxBoxes && Kb >= 0 && Kb <= sg::kMaxBoxes && B >= 0 && B <= sg::kMaxScenes; }
 
 size_t table_bytes(int B) { return sg::align_up(sizeof(Landing)) + 3 * sg::align_up((size_t)(B + 1) * sizeof(int32_t)); }
 
@@ -100,23 +88,14 @@ struct Tables {
     long long pairs;
 };
 
-// offsets ascend from 0 to K: checked on the host, before anything is read through them
-int check_offsets(const char* who, const char* set, const int32_t* h_off, int B, int K) {
-    SG_REQUIRE(h_off[0] == 0, "%s: the offsets of set %s do not start at 0 (%d)", who, set, h_off[0]);
-    for (int s = 0; s < B; ++s)
-        SG_REQUIRE(h_off[s + 1] >= h_off[s], "%s: the offsets of set %s do not ascend (scene %d: %d after %d)", who, set, s, h_off[s + 1], h_off[s]);
-    SG_REQUIRE(h_off[B] == K, "%s: the offsets of set %s end at %d, not at its %d boxes", who, set, h_off[B], K);
-    return SG_OK;
-}
-
 // what both entries do first: the sizes, the offsets (host), the tables on the device, the check of every box
 int prepare(const char* who, const double* d_a, int Ka, const double* d_b, int Kb, const int32_t* h_off_a, const int32_t* h_off_b, int B,
             void* d_ws, size_t ws_bytes, hipStream_t st, Tables* t) {
     SG_REQUIRE(Ka >= 0 && Kb >= 0 && B >= 0 && h_off_a && h_off_b, "%s: bad arguments (%d and %d boxes, %d scenes)", who, Ka, Kb, B);
     if (!sizes_ok(Ka, Kb, B))
         return sg::fail(SG_EUNSUP, "%s: %d and %d boxes in %d scenes; a call takes at most 2^20 boxes a side and 2^16 scenes", who, Ka, Kb, B);
-    if (int rc = check_offsets(who, "A", h_off_a, B, Ka)) return rc;
-    if (int rc = check_offsets(who, "B", h_off_b, B, Kb)) return rc;
+    if (int rc = sg::check_offsets(who, "set A", h_off_a, B, Ka)) return rc;
+    if (int rc = sg::check_offsets(who, "set B", h_off_b, B, Kb)) return rc;
     SG_REQUIRE((d_a || !Ka) && (d_b || !Kb) && d_ws, "%s: bad arguments", who);
     const size_t need = table_bytes(B);
     SG_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
@@ -149,14 +128,8 @@ int land_flag(const char* who, const Tables& t, hipStream_t st) {
     SG_HIP(hipMemcpyAsync(&land, t.land, sizeof(Landing), hipMemcpyDeviceToHost, st));
     SG_HIP(hipStreamSynchronize(st));
     SG_LAUNCH_CHECK();
-    for (int set = 0; set < 2; ++set) {
-        const int f = land.flag >> (set * kSetB) & 7;
-        const char* name = set ? "B" : "A";
-        if (f & kNotFinite) return sg::fail(SG_EINVAL, "%s: a box of set %s has a value that is not finite", who, name);
-        if (f & kNegative) return sg::fail(SG_EINVAL, "%s: a box of set %s has a negative size", who, name);
-        if (f & kNotUnit) return sg::fail(SG_EINVAL, "%s: a box of set %s has (c, s) off the unit circle: |c*c + s*s - 1| > 1e-6", who, name);
-    }
-    return SG_OK;
+    if (int rc = upright_refusal(who, "A", land.flag & 7)) return rc;     // every refusal of set A before any of set B
+    return upright_refusal(who, "B", land.flag >> kSetB & 7);
 }
 
 }  // namespace

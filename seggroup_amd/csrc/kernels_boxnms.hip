@@ -34,15 +34,12 @@ using namespace sg_box;
 
 constexpr int kBlock = 256;
 constexpr int kWave = 64;
-constexpr int kMaxBoxes = 1 << 20;
-constexpr int kMaxScenes = 1 << 16;
 constexpr int kMaxScene = 1 << 14;            // boxes of one scene: 256 words a bit row, four a lane of the scan
 constexpr long long kMaxWords = 1ll << 24;    // the bit matrix: 128 MB
 constexpr int kRemWords = kMaxScene / 64 / kWave;   // words of `removed` a lane holds: 4
 constexpr int kMaskRows = kWave / (kBlock / kWave);   // rows of a tile a wave of k_nm_mask takes: 16
 constexpr int kAhead = 8;                     // independent row loads in flight in the scan
-constexpr int kNotFinite = 1, kNegative = 2, kNotUnit = 4, kScore = 8;
-constexpr double kUnitTol = 1e-6;
+constexpr int kScore = 8;                     // the flag word: upright_flags' three bits and this one
 constexpr int kPad = 64;                      // the sections of the upload start at multiples of 256 bytes
 
 typedef unsigned long long u64;
@@ -50,16 +47,7 @@ typedef unsigned long long u64;
 __global__ __launch_bounds__(kBlock) void k_nm_check(const double* __restrict__ box, const double* __restrict__ score, int K, int* __restrict__ flag) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= K) return;
-    const double* p = box + (size_t)i * 8;
-    int bad = 0;
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-        if (!finite_f64(p[r])) bad = kNotFinite;
-    if (!bad) {
-        if (p[3] < 0.0 || p[4] < 0.0 || p[5] < 0.0) bad |= kNegative;
-        const double n = p[6] * p[6] + p[7] * p[7];
-        if (fabs(n - 1.0) > kUnitTol) bad |= kNotUnit;
-    }
+    int bad = upright_flags(box + (size_t)i * 8);
     if (!finite_f64(score[i])) bad |= kScore;
     if (bad) atomicOr(flag, bad);
 }
@@ -235,7 +223,7 @@ __global__ __launch_bounds__(kWave) void k_nm_scan(const u64* __restrict__ mask,
     }
 }
 
-bool sizes_ok(int K, int B, long long words) { return K >= 0 && K <= kMaxBoxes && B >= 0 && B <= kMaxScenes && words >= 0 && words <= kMaxWords; }
+bool sizes_ok(int K, int B, long long words) { return K >= 0 && K <= sg::kMaxBoxes && B >= 0 && B <= sg::kMaxScenes && words >= 0 && words <= kMaxWords; }
 
 size_t pad(size_t ints) { return (ints + kPad - 1) / kPad * kPad; }
 size_t job_entries(int K, int B) { return (size_t)sg::cdiv(K, kBlock) + (size_t)B; }
@@ -257,12 +245,9 @@ int sg_box_nms(const double* d_box, const double* d_score, const int32_t* d_cls,
                int32_t* d_rank, int32_t* d_keep, int32_t* d_rep, long long words, void* d_ws, size_t ws_bytes, void* stream) {
     const char* who = "sg_box_nms";
     SG_REQUIRE(K >= 0 && B >= 0 && h_off, "%s: bad arguments (%d boxes, %d scenes, a null pointer for the offsets)", who, K, B);
-    if (K > kMaxBoxes || B > kMaxScenes)
+    if (K > sg::kMaxBoxes || B > sg::kMaxScenes)
         return sg::fail(SG_EUNSUP, "%s: %d boxes in %d scenes; a call takes at most 2^20 boxes and 2^16 scenes", who, K, B);
-    SG_REQUIRE(h_off[0] == 0, "%s: the offsets do not start at 0 (%d)", who, h_off[0]);
-    for (int s = 0; s < B; ++s)
-        SG_REQUIRE(h_off[s + 1] >= h_off[s], "%s: the offsets do not ascend (scene %d: %d after %d)", who, s, h_off[s + 1], h_off[s]);
-    SG_REQUIRE(h_off[B] == K, "%s: the offsets end at %d, not at the %d boxes", who, h_off[B], K);
+    if (int rc = sg::check_offsets(who, "the boxes", h_off, B, K)) return rc;
     SG_REQUIRE(std::isfinite(thresh) && thresh >= 0.0 && thresh < 1.0, "%s: the threshold is not finite or outside [0, 1) (%g)", who, thresh);
     long long sum = 0, tiles = 0, longest = 0;
     for (int s = 0; s < B; ++s) {
@@ -321,11 +306,9 @@ int sg_box_nms(const double* d_box, const double* d_score, const int32_t* d_cls,
     SG_HIP(hipStreamSynchronize(st));                         // whatever the copy said: the upload out of `host` ends here
     SG_HIP(copied);
     SG_LAUNCH_CHECK();
-    if (land[0] & kNotFinite) return sg::fail(SG_EINVAL, "%s: a box has a value that is not finite", who);
-    if (land[0] & kScore) return sg::fail(SG_EINVAL, "%s: a score is not finite", who);
-    if (land[0] & kNegative) return sg::fail(SG_EINVAL, "%s: a box has a negative size", who);
-    if (land[0] & kNotUnit) return sg::fail(SG_EINVAL, "%s: a box has (c, s) off the unit circle: |c*c + s*s - 1| > 1e-6", who);
-    return SG_OK;
+    // a value that is not finite comes first, then the score, then what upright_refusal lists after it
+    if (!(land[0] & kNotFinite) && (land[0] & kScore)) return sg::fail(SG_EINVAL, "%s: a score is not finite", who);
+    return upright_refusal(who, nullptr, land[0]);
 }
 
 }  // extern "C"

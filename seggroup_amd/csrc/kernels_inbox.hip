@@ -23,13 +23,9 @@ constexpr int kWave = 64;
 constexpr int kTile = 128;                    // boxes in LDS at a time
 constexpr int kPrep = 16;                     // doubles of a prepared box
 constexpr int kMaxPoints = 1 << 24;
-constexpr int kMaxBoxes = 1 << 20;
-constexpr int kMaxScenes = 1 << 16;
 constexpr int kBoxNotFinite = 1, kNegative = 2, kNotFrame = 4, kPointNotFinite = 8;
 constexpr double kFrameTol = 1e-6;
 
-__device__ __forceinline__ bool finite_f64(double v) { return (__double2hiint(v) & 0x7ff00000) != 0x7ff00000; }
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
 __global__ __launch_bounds__(kBlock) void k_pb_prepare(const double* __restrict__ box, int K, double margin, double* __restrict__ prep,
@@ -41,7 +37,7 @@ __global__ __launch_bounds__(kBlock) void k_pb_prepare(const double* __restrict_
 #pragma unroll
     for (int r = 0; r < 15; ++r) {
         v[r] = box[(size_t)i * 15 + r];
-        if (!finite_f64(v[r])) bad = kBoxNotFinite;
+        if (!sg::finite_f64(v[r])) bad = kBoxNotFinite;
     }
     if (!bad) {
         if (v[3] < 0.0 || v[4] < 0.0 || v[5] < 0.0) bad |= kNegative;
@@ -91,7 +87,7 @@ __global__ __launch_bounds__(kBlock) void k_pb_test(const float* __restrict__ xy
     if (live && job.w > job.z) {
         const float* q = xyz + (size_t)p * stride;
         const float fx = q[0], fy = q[1], fz = q[2];
-        if (!(finite_f32(fx) && finite_f32(fy) && finite_f32(fz))) atomicOr(flag, kPointNotFinite);
+        if (!(sg::finite_f32(fx) && sg::finite_f32(fy) && sg::finite_f32(fz))) atomicOr(flag, kPointNotFinite);
         x = (double)fx;
         y = (double)fy;
         z = (double)fz;
@@ -128,19 +124,11 @@ __global__ __launch_bounds__(kBlock) void k_pb_test(const float* __restrict__ xy
     }
 }
 
-bool sizes_ok(int N, int K, int B) { return N >= 0 && N <= kMaxPoints && K >= 0 && K <= kMaxBoxes && B >= 0 && B <= kMaxScenes; }
+bool sizes_ok(int N, int K, int B) { return N >= 0 && N <= kMaxPoints && K >= 0 && K <= sg::kMaxBoxes && B >= 0 && B <= sg::kMaxScenes; }
 
 // entry 0 is the flag word's landing; a scene of n points has cdiv(n, 256) workgroups, so there are at most cdiv(N, 256) + B of them
 size_t table_entries(int N, int B) { return 1 + (size_t)sg::cdiv(N, kBlock) + (size_t)B; }
 size_t need_bytes(int N, int K, int B) { return sg::align_up(table_entries(N, B) * sizeof(int4)) + sg::align_up((size_t)std::max(K, 1) * kPrep * sizeof(double)); }
-
-int check_offsets(const char* who, const char* what, const int32_t* h_off, int B, int total) {
-    SG_REQUIRE(h_off[0] == 0, "%s: the offsets of the %s do not start at 0 (%d)", who, what, h_off[0]);
-    for (int s = 0; s < B; ++s)
-        SG_REQUIRE(h_off[s + 1] >= h_off[s], "%s: the offsets of the %s do not ascend (scene %d: %d after %d)", who, what, s, h_off[s + 1], h_off[s]);
-    SG_REQUIRE(h_off[B] == total, "%s: the offsets of the %s end at %d, not at their number %d", who, what, h_off[B], total);
-    return SG_OK;
-}
 
 }  // namespace
 
@@ -157,8 +145,8 @@ int sg_points_in_boxes(const float* d_xyz, int stride, int N, const double* d_bo
     SG_REQUIRE(margin >= 0.0 && std::isfinite(margin), "%s: the margin is negative or not finite (%g)", who, margin);
     if (!sizes_ok(N, K, B))
         return sg::fail(SG_EUNSUP, "%s: %d points and %d boxes in %d scenes; a call takes at most 2^24 points, 2^20 boxes and 2^16 scenes", who, N, K, B);
-    if (int rc = check_offsets(who, "points", h_off_p, B, N)) return rc;
-    if (int rc = check_offsets(who, "boxes", h_off_b, B, K)) return rc;
+    if (int rc = sg::check_offsets(who, "the points", h_off_p, B, N)) return rc;
+    if (int rc = sg::check_offsets(who, "the boxes", h_off_b, B, K)) return rc;
     SG_REQUIRE((d_xyz && d_count && d_first && d_inner) || !N, "%s: bad arguments (a null pointer)", who);
     SG_REQUIRE((d_box || !K) && d_ws, "%s: bad arguments (a null pointer)", who);
     const size_t need = need_bytes(N, K, B);

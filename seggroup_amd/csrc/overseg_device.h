@@ -12,7 +12,7 @@
 
 namespace sgos {
 
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+using sg::finite_f32;
 
 // ascending as unsigned <=> ascending as fp32, negatives included (w may be slightly negative)
 __device__ __forceinline__ unsigned int weight_key(float w) {

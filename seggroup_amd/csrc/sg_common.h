@@ -29,6 +29,10 @@ template <class T>
 using gptr = SG_GLOBAL T*;
 template <class T>
 __host__ __device__ __forceinline__ gptr<T> as_global(T* p) { return (gptr<T>)p; }
+
+// neither an infinity nor a NaN: the exponent field is not all ones.  The one definition each; sgos:: and sg_box:: name them by `using`.
+__device__ __forceinline__ bool finite_f64(double v) { return (__double2hiint(v) & 0x7ff00000) != 0x7ff00000; }
+__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 #endif
 
 
@@ -146,5 +150,18 @@ struct Carver {
         return r;
     }
 };
+
+// What one call of a box entry takes (sg_box_iou, sg_box_best, sg_points_in_boxes, sg_box_nms): boxes in a set, scenes.
+constexpr int kMaxBoxes = 1 << 20, kMaxScenes = 1 << 16;
+
+// A host vector of B + 1 scene offsets ascends from 0 to `total`: checked before anything is read through it.  `what` names what the
+// offsets delimit in the message: "set A", "the points", "the boxes".
+inline int check_offsets(const char* who, const char* what, const int32_t* h_off, int B, int total) {
+    SG_REQUIRE(h_off[0] == 0, "%s: the offsets of %s do not start at 0 (%d)", who, what, h_off[0]);
+    for (int s = 0; s < B; ++s)
+        SG_REQUIRE(h_off[s + 1] >= h_off[s], "%s: the offsets of %s do not ascend (scene %d: %d after %d)", who, what, s, h_off[s + 1], h_off[s]);
+    SG_REQUIRE(h_off[B] == total, "%s: the offsets of %s end at %d, not at %d", who, what, h_off[B], total);
+    return SG_OK;
+}
 
 }  // namespace sg

@@ -201,19 +201,19 @@ def _boxes(kind, R3, center, size):
 
 
 def test_box_rows_on_each_kind():
-    from seggroup_amd import boxap
+    from seggroup_amd import boxset
     c, s = math.cos(0.3), math.sin(0.3)
     center = np.array([[1.0, 2.0, 3.0], [-4.0, 0.5, 0.0]])
     size = np.array([[2.0, 4.0, 6.0], [1.0, 0.5, 0.25]])
-    rows = boxap.box_rows(_boxes("aabb", np.tile(np.eye(3), (2, 1, 1)), center, size))
+    rows = boxset.box_rows(_boxes("aabb", np.tile(np.eye(3), (2, 1, 1)), center, size))
     assert rows.dtype == np.float64 and rows.tolist() == [[1, 2, 3, 2, 4, 6, 1, 0], [-4, 0.5, 0, 1, 0.5, 0.25, 1, 0]]
-    rows = boxap.box_rows(_boxes("yaw", np.array([np.eye(3), [[c, s, 0], [-s, c, 0], [0, 0, 1]]]), center, size))
+    rows = boxset.box_rows(_boxes("yaw", np.array([np.eye(3), [[c, s, 0], [-s, c, 0], [0, 0, 1]]]), center, size))
     assert rows[1].tolist() == [-4, 0.5, 0, 1, 0.5, 0.25, c, s] and rows[0, 6:].tolist() == [1, 0]     # the bits of R, no cos taken again
-    assert boxap.box_rows(_boxes("yaw", np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros((0, 3)))).shape == (0, 8)
+    assert boxset.box_rows(_boxes("yaw", np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros((0, 3)))).shape == (0, 8)
     with pytest.raises(ValueError, match="not upright"):
-        boxap.box_rows(_boxes("pca", np.tile(np.eye(3), (2, 1, 1)), center, size))
+        boxset.box_rows(_boxes("pca", np.tile(np.eye(3), (2, 1, 1)), center, size))
     with pytest.raises(ValueError, match="kind"):
-        boxap.box_rows(_boxes("obb", np.tile(np.eye(3), (2, 1, 1)), center, size))
+        boxset.box_rows(_boxes("obb", np.tile(np.eye(3), (2, 1, 1)), center, size))
 
 
 def _write_boxes(path, kind="yaw", sem=True, k=2, **more):

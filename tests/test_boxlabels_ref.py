@@ -121,28 +121,28 @@ def _boxes(kind, R3, center, size):
 
 
 def test_box_frames_on_each_input():
-    from seggroup_amd import boxlabels
+    from seggroup_amd import boxset
     c, s = math.cos(0.3), math.sin(0.3)
     center = np.array([[1.0, 2.0, 3.0], [-4.0, 0.5, 0.0]])
     size = np.array([[2.0, 4.0, 6.0], [1.0, 0.5, 0.25]])
     tilted, _ = np.linalg.qr(np.random.RandomState(3).normal(size=(3, 3)))
     frames = np.array([np.eye(3), tilted])
     for kind in ("aabb", "yaw", "pca"):                                      # a Boxes of any kind: center, size and R as they stand
-        rows = boxlabels.box_frames(_boxes(kind, frames, center, size))
+        rows = boxset.box_frames(_boxes(kind, frames, center, size))
         assert rows.dtype == np.float64 and rows.shape == (2, 15)
         assert rows[:, :3].tolist() == center.tolist() and rows[:, 3:6].tolist() == size.tolist() and rows[:, 6:].tolist() == frames.reshape(2, 9).tolist()
-    assert boxlabels.box_frames(rows) is not rows and boxlabels.box_frames(rows).tolist() == rows.tolist()     # [K,15]: as they are
+    assert boxset.box_frames(rows) is not rows and boxset.box_frames(rows).tolist() == rows.tolist()     # [K,15]: as they are
     eight = np.concatenate([center, size, [[1.0, 0.0], [c, s]]], 1)
-    got = boxlabels.box_frames(eight)
+    got = boxset.box_frames(eight)
     assert got[0].tolist() == R.row(1, 2, 3, 2, 4, 6).tolist() and got[1, 6:].tolist() == [c, s, 0, -s, c, 0, 0, 0, 1]
     seven = np.concatenate([center, size, [[5.0], [14.0]]], 1)
-    got, cls = boxlabels.box_frames(seven, classes=True)
+    got, cls = boxset.box_frames(seven, classes=True)
     assert got.tolist() == [R.row(1, 2, 3, 2, 4, 6).tolist(), R.row(-4, 0.5, 0, 1, 0.5, 0.25).tolist()] and cls.tolist() == [5, 14]
-    assert boxlabels.box_frames(seven).shape == (2, 15) and boxlabels.box_frames(eight, classes=True)[1] is None
-    assert boxlabels.box_frames(np.zeros((0, 15))).shape == (0, 15) and boxlabels.box_frames(np.zeros((0, 7))).shape == (0, 15)
+    assert boxset.box_frames(seven).shape == (2, 15) and boxset.box_frames(eight, classes=True)[1] is None
+    assert boxset.box_frames(np.zeros((0, 15))).shape == (0, 15) and boxset.box_frames(np.zeros((0, 7))).shape == (0, 15)
     for bad in (np.zeros((2, 9)), np.zeros(15), np.zeros((2, 15), str), np.concatenate([center, size, [[5.5], [14.0]]], 1)):
         with pytest.raises(ValueError, match="box_frames"):
-            boxlabels.box_frames(bad)
+            boxset.box_frames(bad)
 
 
 def _write_boxes(path, sem=True, k=2, **more):
